@@ -12,7 +12,11 @@ BASELINE.json configs[2] per GPU (num_envs 65 536, 128-segment wire grid,
 segment_len 0.625), fresh reset, constant quickstart action ->
 weak scaling.  ``--workload config2`` selects num_envs 4096 / 400 segments instead.
 
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the ``--steps`` steps and prints that line
+(headline, ``roofline``, ``check``).  ``--full`` adds the measurements that take runs of their own: the ``side`` lines and
+the ``cpu_baseline`` leg described below.  ``--dump-outputs DIR`` writes what the last timed step returned to its caller
+(observation, reward, terminated, truncated and the ``info`` tensors) as ``DIR/<name>.npy`` in float32 / float64; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 ``roofline`` names the resource that binds the dominant kernel.  The fused launches keep the wire
 on the chip for 1000 us (in the lanes' registers: wedm_step_regs, the kernel of the headline batch;
@@ -72,9 +76,13 @@ def parse_args():
     ap.add_argument("--num-envs", type=int, default=0, help="override environments per GPU")
     ap.add_argument("--kernel", type=int, default=0, help="0 auto, 1 global-memory, 2 LDS any-geometry (packed), 9 served packed, 10 LDS any-geometry cell by cell, 11 served any-geometry, 12 served registers, 3 LDS fused, 4 LDS fused + packed f32, 5 global-memory split, 6 stream (single microseconds), 7 registers (one or two lanes per environment), 8 wide registers (4 / 8 / 16 lanes per environment)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per environment in kernel 3 (0 auto)")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the cpu_baseline leg")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side measurements (1-us cadence, dense sparking, closed loop)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and the cpu_baseline leg (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the cpu_baseline leg (--full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
+    ap.add_argument("--no-side", action="store_true", help="--full without the side measurements (1-us cadence, dense sparking, closed loop)")
     ap.add_argument("--gap", type=float, default=None,
                     help="side measurement: start from this gap [um] instead of the reset state's 50 um (a 15 um gap "
                          "sparks about every 90 us per environment, so the general scalar path runs on most steps)")
@@ -475,6 +483,42 @@ def policy_in_the_loop_line(n_local, wire, device):
     return line
 
 
+DUMP_LIMIT_BYTES = 64 * 1024 * 1024
+
+
+def dump_outputs(out_dir, step_out, gathered_obs=None):
+    """Write what `step_many` returned to its caller in the last timed step (obs, reward, terminated, truncated and the
+    tensors of `info`) as `out_dir/<name>.npy`: floating arrays keep float32 / float64, booleans and small integers become
+    float32, 32- and 64-bit integers float64 (exact).  A batch whose arrays would pass 64 MB is cut to a fixed sample of
+    environments (numpy.default_rng(0), sorted; their indices in `env_index.npy`).  With several ranks, rank 0 also writes
+    the all-gathered observations as `obs_gathered[i, r]` = rank r's environment i."""
+    import numpy as np
+
+    obs, reward, terminated, truncated, info = step_out
+    n = obs.shape[0]
+    arrays = {"obs": obs, "reward": reward, "terminated": terminated, "truncated": truncated}
+    arrays.update({f"info_{k}": v for k, v in info.items()})
+    if gathered_obs is not None:
+        arrays["obs_gathered"] = gathered_obs.reshape(-1, obs.shape[1], n).permute(2, 0, 1)  # [world * obs_dim, n] -> [n, world, obs_dim]
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype.kind == "f":
+            a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        else:
+            a = a.astype(np.float64 if a.dtype.itemsize >= 4 else np.float32)
+        assert a.shape[0] == n, (name, a.shape)
+        host[name] = a
+    keep = DUMP_LIMIT_BYTES // (8 + sum(a.nbytes // n for a in host.values()))
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {name: a[idx] for name, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse_args()
     import torch
@@ -552,7 +596,7 @@ def main():
     for i in range(args.steps):
         if per_step_events:
             starts[i].record()
-        env.step_many(act, n_sub)
+        step_out = env.step_many(act, n_sub)
         if per_step_events:
             ends[i].record()
         if use_dist:
@@ -579,6 +623,8 @@ def main():
         km = [float(x[0].item()) for x in allr]
         per_rank = {"kernel_ms": km, "kernel_ms_min": min(km), "kernel_ms_max": max(km), "slowest_rank": km.index(max(km)),
                     "wall_ms_per_step": [float(x[1].item()) for x in allr]}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_out, gathered)
 
     done = int(env.state.done.sum().item())
     broken = int(env.state.is_wire_broken.sum().item())
@@ -616,13 +662,13 @@ def main():
                                   "and still counted in `value` (the kernel carries its lanes)"}
                          if args.workload == "config5" and done else {})},
         }
-        if world == 1 and not args.no_side and args.workload == "config3" and args.trace == "off" and args.gap is None \
-                and not args.num_envs and args.kernel == 0 and args.stencil_dtype == "float32":
+        if args.full and world == 1 and not args.no_side and args.workload == "config3" and args.trace == "off" \
+                and args.gap is None and not args.num_envs and args.kernel == 0 and args.stencil_dtype == "float32":
             out["side"] = side_measurements(n_local, wire, S, device)
             out["side"].append(policy_in_the_loop_line(n_local, wire, device))
             out["side"] += other_config_lines(device)
             out["side"] += other_config_lines(device, "float64")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wire, n_local, n_sub, args.cpu_seconds)
             out["cpu_baseline"]["reference_python"] = (
                 "1 209 env-steps/s, 1 core: the Python reference itself (Numba stubbed), measured in the build "

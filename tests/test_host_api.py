@@ -364,3 +364,29 @@ def test_wire_temperature_proxy_reads_gather_and_assignments_write_through():
     env.state.wire_temperature = np.full(n, 300.0, dtype=np.float32)
     env.step_many(env.make_action(), 3)                                 # and the kernels' view is the same memory
     assert abs(float(env.state.wire_temperature[0, 64]) - 300.0) < 1.0 and float(env.state.wire_temperature[0, 0]) == np.float32(293.15)
+
+
+def test_bench_dump_outputs_writes_the_step_returns(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs`: every array `step_many` hands its caller, as float32 / float64 .npy, exact; past the size
+    limit a fixed sample of environments (the same for every run) with its indices."""
+    import bench
+
+    env = make(16, wire_params=WireModuleParameters(segment_len=0.625))
+    env.reset(seed=1234)
+    act = env.make_action(0.1, 80.0, 5, 3.0, 80.0)
+    env.step_many(act, 1000)
+    out = env.step_many(act, 1000)
+    bench.dump_outputs(tmp_path / "all", out)
+    got = {p.stem: np.load(p) for p in (tmp_path / "all").glob("*.npy")}
+    assert set(got) == {"obs", "reward", "terminated", "truncated", "info_wire_broken", "info_target_reached",
+                        "info_spark_state", "info_time", "info_control_step"}
+    assert all(a.dtype in (np.float32, np.float64) and a.shape[0] == 16 for a in got.values())
+    assert np.array_equal(got["obs"], out[0].numpy()) and got["obs"].any()
+    assert got["info_time"].dtype == np.float64 and np.array_equal(got["info_time"], out[4]["time"].numpy())
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, out)
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert 0 < len(idx) < 16 and np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy"))
+    assert sum(p.stat().st_size - 128 for p in (tmp_path / "a").glob("*.npy")) <= 1000
+    assert np.array_equal(np.load(tmp_path / "a" / "obs.npy"), got["obs"][idx])

@@ -32,7 +32,7 @@ bench() {  # name, flags...
   grep '^{' $S/$name.json.tmp | tail -1 > $S/$name.json; rm -f $S/$name.json.tmp   # (an RCCL banner may precede the line)
   check_line $S/$name.json
 }
-bench_lines() {  # $1: extra flags of the headline run ("" = with the CPU baseline leg and the side lines)
+bench_lines() {  # $1: extra flags of the headline run ("--full" = with the CPU baseline leg and the side lines)
   bench bench_config3 --steps 20 --warmup 5 $1
   bench bench_config2 --steps 10 --warmup 2 --workload config2 --no-cpu-baseline
   bench bench_config4_shard --steps 10 --warmup 2 --workload config4 --no-cpu-baseline
@@ -92,7 +92,7 @@ python tools/make_traffic_json.py $S profiles/$R || exit 1
 cp profiles/traffic.json profiles/valu.json $S/
 
 echo "[profile] bench lines, final pass (roofline objects use the counters just recorded)"; date +%T
-bench_lines ""
+bench_lines "--full"
 bench bench_config3_f64_1us --steps 2000 --warmup 100 --substeps 1 --stencil-dtype float64 --no-cpu-baseline --no-side
 bench bench_config3_trace_voltage --steps 5 --warmup 1 --trace voltage --no-cpu-baseline
 bench bench_config3_trace_signals --steps 5 --warmup 1 --trace signals --no-cpu-baseline
