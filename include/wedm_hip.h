@@ -156,6 +156,25 @@ enum wedm_stat_field {
     WEDM_STAT_COUNT
 };
 
+/* ------------------------------------------------ pulse statistics (optional)
+ * The reference driver's "Sparks" / "Short pulses" (experiments/run_simulation.py:597-636) per control interval,
+ * counted inside the kernels.  A SAMPLE is the state after one physics step an environment ran (a frozen environment
+ * has none; the state right after a reset counts as a sample with current 0 and no short).  With I = state.current and
+ * threshold 0.1 A:  spark pulse = a sample where (I > 0.1) && !is_short_circuit holds and did not hold at the previous
+ * sample; short pulse = the same with is_short_circuit; short step = a sample with is_short_circuit.  The *_ACC rows
+ * accumulate sample by sample; at every control step (this step's sample included) the kernels publish them into the
+ * *_LAST rows and restart them from zero.  A reset (wedm_reset, the in-launch autoreset, either reset_semantics) clears
+ * all six rows.  Counts are per physics step: with dt_us = 2 short_steps counts steps, not microseconds.            */
+enum wedm_pulse_field {
+    WEDM_P_SPARK_ACC = 0,      /* spark pulses since the last control step          */
+    WEDM_P_SHORT_ACC,          /* short pulses since the last control step          */
+    WEDM_P_SHORT_STEPS_ACC,    /* short-circuit samples since the last control step */
+    WEDM_P_SPARK_LAST,         /* spark pulses of the last completed interval       */
+    WEDM_P_SHORT_LAST,         /* short pulses of the last completed interval       */
+    WEDM_P_SHORT_STEPS_LAST,   /* short-circuit samples of the last completed interval */
+    WEDM_PULSE_COUNT
+};
+
 /* -------------------------------------- per-environment geometry (optional)
  * BASELINE config 5: workpiece_height / wire_diameter differ per environment.
  * When bound, these rows override the uniform values in wedm_params.       */
@@ -380,6 +399,14 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
 /* binds (table != NULL) or removes (table == NULL) the variate table described at wedm_replay_slot; `n_steps`
  * physics steps are covered (an environment stepped beyond them gets its ERROR flag set).                 */
 int32_t wedm_bind_rng_replay(wedm_ctx* ctx, const double* table, int64_t n_steps);
+
+/* binds (rows != NULL) or removes (rows == NULL) the caller-owned pulse-statistics block
+ * int32 [WEDM_PULSE_COUNT][stride] described at wedm_pulse_field (same stride as the state blocks).  While it is bound,
+ * wedm_step runs the kernels' pulse-counting instantiations: kernels 7, 8 and 2 (float32 stencil, no trace sample in the
+ * launch) and kernel 1 for every other launch; wedm_set_kernel values without such a form make wedm_step return
+ * WEDM_ERR_UNSUPPORTED.  With wedm_params.obs_dim >= 11 the control steps also write the three published counts into
+ * obs columns 8, 9, 10 (float32).  Binding does not clear the block: wedm_reset does.                                */
+int32_t wedm_bind_pulse_stats(wedm_ctx* ctx, int32_t* rows);
 
 /* binds (desc != NULL) or removes (desc == NULL) the signal trace; resets the sample counter.
  * Terminated environments keep being sampled (their frozen state).                        */

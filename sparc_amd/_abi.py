@@ -123,6 +123,22 @@ class STAT(enum.IntEnum):
 STAT_COUNT = 4
 
 
+class PULSE(enum.IntEnum):
+    """Rows of the optional pulse-statistics block (``enum wedm_pulse_field``, int32)."""
+
+    SPARK_ACC = 0
+    SHORT_ACC = 1
+    SHORT_STEPS_ACC = 2
+    SPARK_LAST = 3
+    SHORT_LAST = 4
+    SHORT_STEPS_LAST = 5
+
+
+PULSE_COUNT = 6
+# obs columns 8-10 of an environment built with pulse_stats=True (the published rows, float32)
+PULSE_OBS_NAMES = ("spark_pulses", "short_pulses", "short_steps")
+
+
 class GF64(enum.IntEnum):
     """Rows of the per-environment geometry float64 block."""
 

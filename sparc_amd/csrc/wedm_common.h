@@ -91,11 +91,17 @@ struct KArgs {
     int32_t trace_slot;     // ring slot of that sample
     wedm_trace_desc trace;  // the bound trace (by value: one kernarg s_load, only in the TRACE instantiations)
     unsigned long long* dbg; // diagnostic builds only (WEDM_STAMPS): per-wave phase cycle sums
+    int32_t* pulse;          // wedm_bind_pulse_stats block or NULL (read by the PULSE instantiations only, via kernarg_pulse)
 };
 
 // The by-value `cold` member as the kernels read it: through the kernarg segment (wedm_device.h).
 __device__ __forceinline__ ColdRef kernarg_cold() {
     return ColdRef{(ColdPtr)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, cold))};
+}
+
+// The pulse block's pointer as the PULSE instantiations read it: through the kernarg segment (wedm_device.h, PulseRef).
+__device__ __forceinline__ PulseRef kernarg_pulse() {
+    return PulseRef{(PulseSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, pulse))};
 }
 
 // ------------------------------------------------------------ signal trace
@@ -209,9 +215,11 @@ __device__ __forceinline__ float stencil_pass(const TA& T, const Geom& g, const 
     return tmax;
 }
 
-template <bool TRACE, bool F64, bool REPLAY, class TA>
+template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false>
 __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
                                              uint32_t gid, Env& s, const TA& T) {
+    const PulseRef pulse = kernarg_pulse();
+    (void)pulse;
     Persist ps;
     init_persist(k.hot, cold, e, s, ps);
     StencilF64 f64c{0.0, 0.0, 0.0};
@@ -221,10 +229,12 @@ __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold,
     (void)trace_next; (void)trace_slot;
     for (int it = 0; it < k.n_substeps; ++it) {
         if (!s.done) {
+            const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
             Coef c = scalar_prelude<REPLAY>(k.hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
             float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, k.hot, f64c, s.h_base, s.h_zone);
             scalar_epilogue(k.hot, s, tmax);
+            pulse_tally<PULSE>(pulse, cold, e, s, pk, true);
             if (s.ctrl) control_step_outputs(cold, e, s, true);
         } else if (!tracing) {
             break;

@@ -1368,6 +1368,68 @@ __device__ __forceinline__ void control_step_outputs(const ColdRef cold, int64_t
     s.vacc = s.V;
 }
 
+// ------------------------------------------------- pulse statistics (wedm_bind_pulse_stats, enum wedm_pulse_field)
+// The block's pointer travels at the END of the kernel arguments (existing kernels keep their argument layout) and is read
+// through the kernel-argument segment at the point of use, like `Cold`: it costs SGPRs only inside the rare branch.
+typedef int32_t* const WEDM_AS4* PulseSlot;
+struct PulseRef {
+    PulseSlot slot;
+    __device__ __forceinline__ int32_t* get() const {
+        PulseSlot p = slot;
+        asm volatile("" : "+s"(p));
+        return *p;
+    }
+};
+
+// what the reference driver's summary looks at in one sample (experiments/run_simulation.py:604-627): 0 = no pulse
+// (I <= 0.1 A), 1 = a spark pulse (I > 0.1 A, no short), 2 = a short pulse (I > 0.1 A during a short)
+__device__ __forceinline__ int32_t pulse_kind(const Env& s) { return s.I > 0.1 ? (s.is_short ? 2 : 1) : 0; }
+
+// The tally of one sample, called by every kernel's PULSE instantiation right before control_step_outputs() for a step the
+// environment ran; `prev` = pulse_kind() of the previous sample (taken before the step's prelude).  A rising edge and a
+// short-circuit sample are rare per environment: the writer lane increments the accumulator row in memory with a
+// fire-and-forget atomic (no register carries a count through the microsecond loop, nothing waits), as crater_stats_update()
+// does at a fresh spark.  At a control step the accumulators are swapped out for zero (atomics to the same address from
+// one lane are performed in program order) and published, with the observation's columns 8-10 where obs_dim >= 11.
+template <bool PULSE>
+__device__ __forceinline__ void pulse_tally(const PulseRef pulse, const ColdRef cold, int64_t e, const Env& s, int32_t prev,
+                                            bool writer) {
+    if (!PULSE) return;
+    const int32_t kind = pulse_kind(s);
+    const bool edge = kind != 0 && kind != prev;
+    if (writer && (edge || s.is_short || s.ctrl)) {
+        int32_t* const rows = pulse.get();
+        const ColdPtr c = cold.get();
+        const int64_t stride = c->s.stride;
+        if (edge)
+            (void)__hip_atomic_fetch_add(WEDM_ROW(rows, kind == 1 ? WEDM_P_SPARK_ACC : WEDM_P_SHORT_ACC), 1, __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_AGENT);
+        if (s.is_short)
+            (void)__hip_atomic_fetch_add(WEDM_ROW(rows, WEDM_P_SHORT_STEPS_ACC), 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (s.ctrl) {
+            float* const obs = c->s.obs;
+            const bool to_obs = obs && opaque(c->p)->obs_dim >= 11;
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const int32_t n = __hip_atomic_exchange(WEDM_ROW(rows, WEDM_P_SPARK_ACC + q), 0, __ATOMIC_RELAXED,
+                                                        __HIP_MEMORY_SCOPE_AGENT);
+                *WEDM_ROW(rows, WEDM_P_SPARK_LAST + q) = n;
+                if (to_obs) obs[(int64_t)(8 + q) * stride + e] = (float)n;
+            }
+        }
+    }
+}
+
+// reinit_env()'s part for the pulse block (the in-launch autoreset): all six rows to zero, by the writer lane
+template <bool PULSE>
+__device__ __forceinline__ void pulse_reinit(const PulseRef pulse, const ColdRef cold, int64_t e, bool writer) {
+    if (!PULSE || !writer) return;
+    int32_t* const rows = pulse.get();
+    const int64_t stride = cold->s.stride;
+#pragma unroll
+    for (int q = 0; q < WEDM_PULSE_COUNT; ++q) __hip_atomic_store(WEDM_ROW(rows, q), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // wedm_params.autoreset: what wedm_reset_kernel(mask = DONE, reseed = 0) writes for one environment,
 // applied to the registers at the start of a launch (next-step autoreset).  `writer` also clears the
 // per-environment memory outside the register state (statistics, observation) and stores the rows

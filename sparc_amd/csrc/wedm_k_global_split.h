@@ -4,7 +4,9 @@
 // Included by wedm_kernels.hip (one translation unit per WEDM_PART; see the bottom of that file).
 #pragma once
 
-template <bool TRACE, bool F64, bool REPLAY>
+// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats): every launch with the block bound that the
+// fast kernels' PULSE forms do not take (a trace sample, stencil_mode 1, injected variates, forced kernel 1)
+template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false>
 __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     const ColdRef cold = kernarg_cold();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -20,13 +22,14 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     const GlobalT T = global_wire(cold->s.T, cold->s.stride, e);
     if (reinit) {  // next-step autoreset: wedm_reset for this environment, inside the launch
         reinit_env(cold, e, s, true);
+        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, true);
         for (int q = 0; q < WEDM_T_QUADS(k.n_seg_max); ++q) T.stq(q, f4v{k.hot.spool, k.hot.spool, k.hot.spool, k.hot.spool});
     }
     unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
     load_geom(k.hot, cold, e, g);
-    run_substeps<TRACE, F64, REPLAY>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
+    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
     if (WEDM_REWARD_ON(cold)) {
         if (!frozen) write_reward(cold, e, s);
         else cold->s.reward[e] = 0.0f;

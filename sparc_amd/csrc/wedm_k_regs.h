@@ -46,7 +46,8 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 // TRACE: the instantiation with the signal-trace point (a launch into which a sample falls: the reference's logger samples
 // after every step, utils/logger.py:110-160); launches without a sample run the instantiation without it.
 // F64: stencil_mode 1 -- the walk in the typing Numba gives wire.py:58-123 (cell_f64 above); everything else is the same kernel.
-template <int CELLS, int L, bool TRACE = false, bool F64 = false>
+// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+template <int CELLS, int L, bool TRACE = false, bool F64 = false, bool PULSE = false>
 __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     // L = 1: one environment per lane (H = 64 pairs, one wave per SIMD at a 512-register budget);
     // L = 2: two lanes per environment, each with half of the wire (H = 32 pairs, two waves per SIMD, the scalar physics
@@ -103,7 +104,10 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     }
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
     const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all lanes of the environment agree)
-    if (reinit) reinit_env(cold, e, s, writer);
+    if (reinit) {
+        reinit_env(cold, e, s, writer);
+        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, writer);
+    }
     if (__any(reinit)) {
 #pragma unroll
         for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];
@@ -156,6 +160,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
 
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
+        const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
         const bool was_quiet = quiet_prelude_t<WEDM_REGS_DENSE>(hv, cold, g, e, gid, s, qt, cf);
@@ -196,6 +201,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
         unfreeze_wire(hv, s);
         if (!s.done) {
             scalar_epilogue(hv, s, tmax);
+            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, writer);
             if (s.ctrl) control_step_outputs(cold, e, s, writer);
         }
         WEDM_TRACE_POINT(k, it, e, s, writer,
@@ -287,7 +293,8 @@ __device__ __forceinline__ float dpp_perm(float x) {
 // F64: stencil_mode 1 (the walk in Numba's typing of wire.py:58-123, as in wedm_step_regs)
 // MINB: blocks per CU the register budget admits (2: the float64 typing's instantiation for batches of more than one wave per
 // SIMD -- a lone wave issues a float64 operation every ~7 cycles, two share the pipe; 256 registers, nothing pinned)
-template <int H, int L, bool CUT, bool TRACE = false, bool F64 = false, int MINB = WEDM_WIDE_MIN_BLOCKS>
+// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+template <int H, int L, bool CUT, bool TRACE = false, bool F64 = false, int MINB = WEDM_WIDE_MIN_BLOCKS, bool PULSE = false>
 __global__ void __launch_bounds__(256, MINB) wedm_step_regs_wide(const KArgs k) {
     static_assert(H % 8 == 0 && H <= 32, "whole tiles");
     static_assert(L == 4 || L == 8 || L == 16, "the lanes of an environment lie in one DPP row");
@@ -333,7 +340,10 @@ __global__ void __launch_bounds__(256, MINB) wedm_step_regs_wide(const KArgs k) 
     }
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
     const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all lanes of the environment agree)
-    if (reinit) reinit_env(cold, e, s, writer);
+    if (reinit) {
+        reinit_env(cold, e, s, writer);
+        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, writer);
+    }
     if (__any(reinit)) {
 #pragma unroll
         for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];
@@ -392,6 +402,7 @@ __global__ void __launch_bounds__(256, MINB) wedm_step_regs_wide(const KArgs k) 
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
         WEDM_STAMP(st0);
+        const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
         const bool was_quiet = quiet_prelude_t<WEDM_WIDE_DENSE>(hv, cold, g, e, gid, s, qt, cf);
@@ -555,6 +566,7 @@ __global__ void __launch_bounds__(256, MINB) wedm_step_regs_wide(const KArgs k) 
         WEDM_STAMP(st3);
         if (!s.done) {
             scalar_epilogue(hv, s, tmax);
+            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, writer);
             if (s.ctrl) control_step_outputs(cold, e, s, writer);
         }
         WEDM_STAMP(st4);

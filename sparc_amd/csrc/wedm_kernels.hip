@@ -97,6 +97,16 @@ using namespace wedm;
 #define WEDM_INST_WIDE_F64(L, cut, tr, mb) template __global__ void wedm_step_regs_wide<16, L, cut, tr, true, mb>(const KArgs);
 #define WEDM_EXT_WIDE_F64(L, cut, tr, mb) extern template __global__ void wedm_step_regs_wide<16, L, cut, tr, true, mb>(const KArgs);
 #define WEDM_INST_SERVED(L, ex) template __global__ void wedm_step_served<L, ex>(const KArgs);
+// pulse statistics (wedm_bind_pulse_stats): the PULSE instantiations of kernels 7, 8 and 2 (float32 stencil, no trace sample)
+#define WEDM_REGS_PULSE_LIST(X) X(1) X(2)
+#define WEDM_INST_REGS_PULSE(L) template __global__ void wedm_step_regs<128, L, false, false, true>(const KArgs);
+#define WEDM_EXT_REGS_PULSE(L) extern template __global__ void wedm_step_regs<128, L, false, false, true>(const KArgs);
+#define WEDM_WIDE_PULSE_LIST(X) X(4, false) X(4, true) X(8, false) X(8, true) X(16, false) X(16, true)
+#define WEDM_INST_WIDE_PULSE(L, cut) template __global__ void wedm_step_regs_wide<16, L, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>(const KArgs);
+#define WEDM_EXT_WIDE_PULSE(L, cut) extern template __global__ void wedm_step_regs_wide<16, L, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>(const KArgs);
+#define WEDM_LANES_PK_PULSE_LIST(X) X(1) X(2) X(4) X(8) X(16)
+#define WEDM_INST_LANES_PK_PULSE(L) template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
+#define WEDM_EXT_LANES_PK_PULSE(L) extern template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
 #define WEDM_EXT_SERVED(L, ex) extern template __global__ void wedm_step_served<L, ex>(const KArgs);
 #if defined(WEDM_PART) && WEDM_PART == 1
 WEDM_PACKED_LIST(WEDM_INST_PACKED)
@@ -108,11 +118,14 @@ WEDM_SERVED_LIST(WEDM_INST_SERVED)
 WEDM_INST_REGS_SERVED
 WEDM_LANES_PK_LIST(WEDM_INST_LANES_PK)
 WEDM_LANES_SERVED_LIST(WEDM_INST_LANES_SERVED)
+WEDM_LANES_PK_PULSE_LIST(WEDM_INST_LANES_PK_PULSE)
 #elif defined(WEDM_PART) && WEDM_PART == 4
 WEDM_REGS_F64_LIST(WEDM_INST_REGS_F64)
 WEDM_WIDE_F64_LIST(WEDM_INST_WIDE_F64)
 WEDM_LANES_PK_LIST(WEDM_INST_LANES_PK_F64)
 WEDM_STREAM_F64_LIST(WEDM_INST_STREAM_F64)
+WEDM_REGS_PULSE_LIST(WEDM_INST_REGS_PULSE)
+WEDM_WIDE_PULSE_LIST(WEDM_INST_WIDE_PULSE)
 #else
 #if defined(WEDM_PART)
 WEDM_PACKED_LIST(WEDM_EXT_PACKED)
@@ -126,6 +139,9 @@ WEDM_LANES_PK_LIST(WEDM_EXT_LANES_PK)
 WEDM_LANES_PK_LIST(WEDM_EXT_LANES_PK_F64)
 WEDM_STREAM_F64_LIST(WEDM_EXT_STREAM_F64)
 WEDM_LANES_SERVED_LIST(WEDM_EXT_LANES_SERVED)
+WEDM_LANES_PK_PULSE_LIST(WEDM_EXT_LANES_PK_PULSE)
+WEDM_REGS_PULSE_LIST(WEDM_EXT_REGS_PULSE)
+WEDM_WIDE_PULSE_LIST(WEDM_EXT_WIDE_PULSE)
 #endif
 
 __global__ void __launch_bounds__(256)
@@ -184,6 +200,16 @@ wedm_reset_kernel(const wedm_params p, const wedm_state_ptrs s, int32_t num_envs
     if (s.obs)
         for (int c = 0; c < p.obs_dim; ++c) s.obs[(int64_t)c * stride + e] = 0.0f;
     if (s.reward) s.reward[e] = 0.0f;
+}
+
+// wedm_reset's part for the pulse-statistics block (wedm_bind_pulse_stats): its own launch, so that wedm_reset_kernel stays as
+// it is for handles without the block
+__global__ void __launch_bounds__(256)
+wedm_reset_pulse_kernel(int32_t* rows, int64_t stride, int32_t num_envs, const uint8_t* mask) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= num_envs) return;
+    if (mask && !mask[e]) return;
+    for (int q = 0; q < WEDM_PULSE_COUNT; ++q) *WEDM_ROW(rows, q) = 0;
 }
 
 // Probe of the device math the physics relies on (test hook; see wedm_debug_math).
@@ -260,6 +286,7 @@ struct wedm_ctx {
     bool trace_on = false;
     wedm_trace_desc trace{};
     int64_t trace_us = 0, trace_count = 0;
+    int32_t* pulse = nullptr;          // wedm_bind_pulse_stats: [WEDM_PULSE_COUNT][stride] or NULL
     std::string err;
     std::string last_kernel;
     LaunchPlan plans[2][2][2];         // [single microsecond][trace point][frozen-lane tile code]: cached launch decisions
@@ -407,13 +434,13 @@ template <bool TR, bool FZ> static const void* pick_packed(int L, bool extra) {
     return extra ? pick_packed<TR, FZ, true>(L) : pick_packed<TR, FZ, false>(L);
 }
 
-template <bool TR, bool F64 = false> static const void* pick_lanes_pk(int L) {
+template <bool TR, bool F64 = false, bool PULSE = false> static const void* pick_lanes_pk(int L) {
     switch (L) {
-        case 1: return (const void*)wedm_step_lanes_pk<1, TR, F64>;
-        case 2: return (const void*)wedm_step_lanes_pk<2, TR, F64>;
-        case 4: return (const void*)wedm_step_lanes_pk<4, TR, F64>;
-        case 8: return (const void*)wedm_step_lanes_pk<8, TR, F64>;
-        default: return (const void*)wedm_step_lanes_pk<16, TR, F64>;
+        case 1: return (const void*)wedm_step_lanes_pk<1, TR, F64, PULSE>;
+        case 2: return (const void*)wedm_step_lanes_pk<2, TR, F64, PULSE>;
+        case 4: return (const void*)wedm_step_lanes_pk<4, TR, F64, PULSE>;
+        case 8: return (const void*)wedm_step_lanes_pk<8, TR, F64, PULSE>;
+        default: return (const void*)wedm_step_lanes_pk<16, TR, F64, PULSE>;
     }
 }
 static const void* pick_served(int L, bool extra) {
@@ -569,6 +596,7 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates and stencil_mode 1 cannot be combined");
         variant = 1;
     }
+    const int32_t forced = variant;  // (the caller's choice; with the pulse block bound only it counts, see below)
     const bool f64 = P.stencil_mode != 0;
     // Numba's typing of the stencil: the register kernels (uniform geometry; at most 128 / 512 segments), the fused tile walk
     // (uniform geometry), the predicated LDS kernel (any geometry), or in place in global memory; no packed LDS form, no served
@@ -668,6 +696,24 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
         else if (fused_ok) variant = 3;
         else variant = (lanes_ok || use_pk) ? 2 : 1;
     }
+    // pulse statistics bound (wedm_bind_pulse_stats): only kernels with a PULSE instantiation.  The fused launches of the float32
+    // stencil without a trace sample take what the automatic choice above takes where that is kernel 8 or 7, else kernel 2's
+    // packed form; everything else -- a trace sample in the launch, stencil_mode 1, injected variates, single microseconds --
+    // runs kernel 1.  A name without a PULSE form is refused.
+    if (ctx->pulse) {
+        if (forced != 0 && forced != 1 && forced != 2 && forced != 7 && forced != 8)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
+        const bool fast = !tr && !f64 && !ctx->replay;
+        int v = fast ? forced : 1;
+        if (v == 0 && !single) {
+            if (wide_ok && ctx->lanes == 0 && (int64_t)ctx->num_envs * wl <= (int64_t)WEDM_WIDE_AUTO_MAX_LANES) v = 8;
+            else if (regs_ok && ctx->lanes == 0 && ctx->num_envs >= 20480) v = 7;
+            else if (use_pk) v = 2;
+        }
+        variant = v == 0 ? 1 : v;
+        if (variant == 2 && !use_pk)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+    }
     if (variant == 9 && !served_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: served kernel needs uniform geometry, the float32 stencil, lanes 4 or 8, two chunks that fit in LDS and freeze_terminated");
     if (variant == 9 && tr) variant = packed_ok ? 4 : fused_ok ? 3 : (lanes_ok || use_pk) ? 2 : 1;
@@ -690,7 +736,34 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     int grid = 0;
     size_t fl = 0;
     out.walk = nullptr;
-    if (variant == 1) {
+    const bool pulse = ctx->pulse != nullptr;
+    if (variant == 1 && pulse) {
+        grid = (ctx->num_envs + 255) / 256;
+        fn = ctx->replay ? (tr ? (const void*)wedm_step_global<true, false, true, true> : (const void*)wedm_step_global<false, false, true, true>)
+           : f64 ? (tr ? (const void*)wedm_step_global<true, true, false, true> : (const void*)wedm_step_global<false, true, false, true>)
+                 : (tr ? (const void*)wedm_step_global<true, false, false, true> : (const void*)wedm_step_global<false, false, false, true>);
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_global%s[pulse]<<<%d,256>>>", ctx->replay ? "[injected variates]" : f64 ? "[f64 stencil]" : "", grid);
+    } else if (variant == 7 && pulse) {
+        const int rl = ctx->lanes == 1 ? 1 : 2;
+        grid = (ctx->num_envs + 256 / rl - 1) / (256 / rl);
+        out.walk = ctx->walk_dev + (rl == 1 ? 10 : 11);
+        fn = rl == 1 ? (const void*)wedm_step_regs<128, 1, false, false, true> : (const void*)wedm_step_regs<128, 2, false, false, true>;
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs<%d>[pulse]<<<%d,256>>>", rl, grid);
+    } else if (variant == 8 && pulse) {
+        grid = (ctx->num_envs + 256 / wl - 1) / (256 / wl);
+        const bool cutw = (P.n_seg & 7) != 0;
+#define WEDM_PICK_WIDE_PULSE(cut) (wl == 4 ? (const void*)wedm_step_regs_wide<16, 4, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true> \
+                                  : wl == 8 ? (const void*)wedm_step_regs_wide<16, 8, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true> \
+                                            : (const void*)wedm_step_regs_wide<16, 16, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>)
+        fn = cutw ? WEDM_PICK_WIDE_PULSE(true) : WEDM_PICK_WIDE_PULSE(false);
+#undef WEDM_PICK_WIDE_PULSE
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs_wide<%d>[pulse]<<<%d,256>>>", wl, grid);
+    } else if (variant == 2 && pulse) {
+        grid = (ctx->num_envs + 256 / pklanes - 1) / (256 / pklanes);
+        fl = (2 * (size_t)((ctx->n_seg_max + 2 * pklanes - 1) / (2 * pklanes)) + 2) * 1024;
+        fn = pick_lanes_pk<false, false, true>(pklanes);
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_pk<%d>[pulse]<<<%d,256,%zuB>>>", pklanes, grid, fl);
+    } else if (variant == 1) {
         grid = (ctx->num_envs + 255) / 256;
         fn = ctx->replay ? (tr ? (const void*)wedm_step_global<true, false, true> : (const void*)wedm_step_global<false, false, true>)
            : f64 ? (tr ? (const void*)wedm_step_global<true, true, false> : (const void*)wedm_step_global<false, true, false>)
@@ -1014,6 +1087,13 @@ int32_t wedm_bind_rng_replay(wedm_ctx* ctx, const double* table, int64_t n_steps
     return WEDM_OK;
 }
 
+int32_t wedm_bind_pulse_stats(wedm_ctx* ctx, int32_t* rows) {
+    if (!ctx) return WEDM_ERR_BAD_ARG;
+    ctx->pulse = rows;
+    ctx->invalidate_plans();
+    return WEDM_OK;
+}
+
 int32_t wedm_set_kernel(wedm_ctx* ctx, int32_t variant) {
     if (!ctx) return WEDM_ERR_BAD_ARG;
     if (variant < 0 || variant > 12) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_set_kernel: variant must be 0..12");
@@ -1051,6 +1131,12 @@ int32_t wedm_reset(wedm_ctx* ctx, const uint8_t* mask, uint64_t seed, int32_t re
                        ctx->num_envs, ctx->n_seg_max, mask, (uint32_t)seed, (uint32_t)(seed >> 32), reseed);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(ctx, e, "wedm_reset launch");
+    if (ctx->pulse) {  // the pulse block is not module state of the reference: cleared by every reset, either semantics
+        hipLaunchKernelGGL(wedm_reset_pulse_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, ctx->pulse, ctx->s.stride,
+                           ctx->num_envs, mask);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(ctx, e, "wedm_reset launch (pulse statistics)");
+    }
     if (!mask && ctx->frozen_seen) *(volatile int32_t*)ctx->frozen_seen = 0;  // every environment reset: none is frozen
     return WEDM_OK;
 }
@@ -1103,6 +1189,7 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
     k.n_seg_max = ctx->n_seg_max;
     k.walk = nullptr;
     k.dbg = ctx->dbg;
+    k.pulse = ctx->pulse;
     k.trace = ctx->trace;
     k.trace_next = INT32_MAX;
     k.trace_slot = 0;

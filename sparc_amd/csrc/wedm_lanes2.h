@@ -179,7 +179,8 @@ __device__ __forceinline__ float lanes_pk_step(float* col, const LanesPkGeom& q,
     return tmax;
 }
 
-template <int L, bool TRACE, bool F64 = false>
+// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+template <int L, bool TRACE, bool F64 = false, bool PULSE = false>
 __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
@@ -213,6 +214,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all L lanes of the environment agree)
     if (reinit) {
         reinit_env(cold, e, s, c == 0);
+        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, c == 0);
         for (int row = 0; row < R; ++row) col[row * 256] = k.hot.spool;
     }
     unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
@@ -246,6 +248,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     (void)trace_next; (void)trace_slot;
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;
+        const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
         const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE>(hv, cold, g, e, gid, s, qt, cf);
@@ -258,6 +261,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
         unfreeze_wire(hv, s);
         if (!s.done) {
             scalar_epilogue(hv, s, tmax);
+            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, c == 0);
             if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
         }
         WEDM_TRACE_POINT(k, it, e, s, c == 0,

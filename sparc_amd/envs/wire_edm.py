@@ -138,6 +138,7 @@ class WireEDMEnv:
         crater_log_capacity: int = 0,
         reset_semantics: str = "full",
         freeze_terminated: bool = True,
+        pulse_stats: bool = False,
         backend: Optional[Callable] = None,
     ):
         """Beyond the reference's keywords (wire_edm.py:22-34):
@@ -162,7 +163,11 @@ class WireEDMEnv:
         keeps being stepped as the reference does when ``step()`` is called after ``terminated`` (wire_edm.py:116-157
         has no guard): after a wire break the wire module returns at once and the step returns before mechanics
         and clocks, after the cutting target everything goes on; ``terminated`` then repeats what the reference's
-        ``step()`` returns."""
+        ``step()`` returns.
+        ``pulse_stats``: count, inside the kernels, the reference driver's "Sparks" and "Short pulses"
+        (experiments/run_simulation.py:597-636) and the short-circuit steps of every control interval; the observation
+        gains three columns (``spark_pulses``, ``short_pulses``, ``short_steps`` of the last completed interval: ``obs_dim``
+        11) and `get_pulse_statistics` returns them.  Needs a backend with ``bind_pulse_stats`` (the HIP library)."""
         self.render_mode = render_mode
         if mechanics_control_mode not in ["position", "velocity"]:
             raise ValueError(f"mechanics_control_mode must be 'position' or 'velocity', got {mechanics_control_mode}")
@@ -201,6 +206,12 @@ class WireEDMEnv:
         if stencil_dtype not in ("float32", "float64"):
             raise ValueError("stencil_dtype must be 'float32' or 'float64'")
         self.stencil_dtype = stencil_dtype
+        self.pulse_stats = bool(pulse_stats)
+        if backend is not None and self.pulse_stats and not hasattr(backend, "bind_pulse_stats"):
+            raise ValueError(f"pulse_stats=True needs a backend that counts pulses inside its step (bind_pulse_stats); "
+                             f"{getattr(backend, '__name__', backend)!r} has none")
+        self.obs_dim = _abi.OBS_DIM + (len(_abi.PULSE_OBS_NAMES) if self.pulse_stats else 0)
+        self.obs_names = _abi.OBS_NAMES + (_abi.PULSE_OBS_NAMES if self.pulse_stats else ())
 
         # ---- geometry: uniform (reference behaviour) or one (h, d) pair per environment
         stride = (self.num_envs + 63) // 64 * 64
@@ -223,14 +234,14 @@ class WireEDMEnv:
         self.params = derive.build_params(
             self.config, mechanics_control_mode, self.ignition_params, self.wire_params, self.material_params,
             self.dielectric_params, self.mechanics_params, self.wire_material, geometry=self.geometry,
-            env_id_offset=self.env_id_offset, obs_dim=_abi.OBS_DIM, disable_ignition=disable_ignition,
+            env_id_offset=self.env_id_offset, obs_dim=self.obs_dim, disable_ignition=disable_ignition,
             autoreset=self.autoreset, reward_mode=1 if reward == "progress" else 0,
             reward_break_penalty=reward_break_penalty, stencil_mode=1 if stencil_dtype == "float64" else 0,
             reset_semantics=1 if reset_semantics == "reference" else 0, keep_stepping_terminated=not freeze_terminated)
 
         # ---- state (caller-owned memory) + backend
-        self.state = BatchedEDMState(self.num_envs, self.n_segments, _abi.OBS_DIM, self.device,
-                                     crater_log_capacity=int(crater_log_capacity))
+        self.state = BatchedEDMState(self.num_envs, self.n_segments, self.obs_dim, self.device,
+                                     crater_log_capacity=int(crater_log_capacity), pulse_stats=self.pulse_stats)
         from ..utils.logger import dielectric_flow_rate
 
         base_flow = float(self.dielectric_params.base_flow_rate)
@@ -245,6 +256,8 @@ class WireEDMEnv:
         self._backend.bind_state(self.state.pointers(with_obs=True))
         if self.per_env_geometry:
             self._backend.bind_geometry(_abi.GeomPtrs(self._geom_f64.data_ptr(), self._geom_i32.data_ptr()))
+        if self.pulse_stats:
+            self._backend.bind_pulse_stats(self.state.pulse.data_ptr())
 
         # what remains of the reference's module objects: parameters + read-only helpers
         from ..modules.views import DielectricView, IgnitionView, MaterialView, MechanicsView, WireView
@@ -267,7 +280,7 @@ class WireEDMEnv:
                 "OFF_time": Box(0.0, 100.0, (1,), np.float32),
             }),
         })
-        self.observation_space = Box(-np.inf, np.inf, (_abi.OBS_DIM,), np.float32)
+        self.observation_space = Box(-np.inf, np.inf, (self.obs_dim,), np.float32)
         self.single_action_space = self.action_space
         self.single_observation_space = self.observation_space
 
@@ -404,9 +417,10 @@ class WireEDMEnv:
             )
 
     def _get_obs(self) -> torch.Tensor:
-        """``float32[num_envs, 8]``: gap, wire_velocity, voltage, current, spark_state,
+        """``float32[num_envs, obs_dim]``: gap, wire_velocity, voltage, current, spark_state,
         debris_density, flow_rate, max wire temperature — as of each environment's last
-        control step (the reference's ``_get_obs`` is a TODO, wire_edm.py:181-183)."""
+        control step (the reference's ``_get_obs`` is a TODO, wire_edm.py:181-183) — and with
+        ``pulse_stats`` the interval's spark pulses, short pulses and short-circuit steps (``obs_names``)."""
         return self.state.obs[:, : self.num_envs].t()
 
     def check_errors(self) -> None:
@@ -494,7 +508,7 @@ class WireEDMEnv:
         fingerprint of the physics parameters (tensors, ints and strings only: loads with
         ``weights_only=True``)."""
         return {"abi_version": _abi.ABI_VERSION, "blocks": self.state.clone_blocks(), "seed": self._seed, "num_envs": self.num_envs,
-                "n_segments": self.n_segments, "env_id_offset": self.env_id_offset,
+                "n_segments": self.n_segments, "env_id_offset": self.env_id_offset, "pulse_stats": self.pulse_stats,
                 "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint()}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
@@ -503,6 +517,9 @@ class WireEDMEnv:
                              f"{_abi.ABI_VERSION} (rows and the wire-temperature layout differ): it cannot be continued here")
         if (sd["num_envs"], sd["n_segments"], sd["env_id_offset"]) != (self.num_envs, self.n_segments, self.env_id_offset):
             raise ValueError("checkpoint was taken from an environment of a different shape / shard")
+        if bool(sd.get("pulse_stats", False)) != self.pulse_stats:
+            raise ValueError(f"checkpoint was taken with pulse_stats={bool(sd.get('pulse_stats', False))}, this environment has "
+                             f"pulse_stats={self.pulse_stats}: the observation and the interval counts differ")
         if sd.get("physics") != self._physics_fingerprint():
             raise ValueError("checkpoint was taken with different physics (configuration, module parameters, control "
                              "mode or per-environment geometry): continuing would silently change the trajectory")
@@ -557,6 +574,20 @@ class WireEDMEnv:
         return {"total_craters": n, "mean_volume_um3": mean, "std_volume_um3": torch.sqrt(var),
                 "min_volume_um3": torch.where(none, zero, st[STAT.CRATER_MIN]),
                 "max_volume_um3": torch.where(none, zero, st[STAT.CRATER_MAX])}
+
+    def get_pulse_statistics(self) -> Dict[str, torch.Tensor]:
+        """The reference driver's "Sparks" and "Short pulses" (experiments/run_simulation.py:597-636) of the last completed
+        control interval, per environment, as the kernels published them at its control step: ``spark_pulses`` /
+        ``short_pulses`` = rising edges of ``current > 0.1`` A outside / inside a short circuit, ``short_steps`` = physics
+        steps with ``is_short_circuit`` (int32 views; zeros until the first control step after a reset).  Summing the
+        published counts of the last 200 intervals gives the driver's "Last 200ms" figures.  Needs ``pulse_stats=True``."""
+        rows = self.state.pulse
+        if rows is None:
+            raise RuntimeError("construct the environment with pulse_stats=True to count pulses")
+        P = _abi.PULSE
+        n = self.num_envs
+        return {"spark_pulses": rows[P.SPARK_LAST, :n], "short_pulses": rows[P.SHORT_LAST, :n],
+                "short_steps": rows[P.SHORT_STEPS_LAST, :n]}
 
     def get_crater_volumes(self, env_index: int) -> torch.Tensor:
         """`MaterialRemovalModule.crater_volumes_um3` (material.py:133) of one environment since its reset, oldest

@@ -17,7 +17,6 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _abi
 from .envs.wire_edm import DeviceAction, WireEDMEnv
 
 
@@ -59,7 +58,8 @@ class ShardedWireEDMEnv:
         self.device = self.env.device
         self.state = self.env.state
         # outputs are the rank-major concatenation of the inputs (the layout every backend accepts)
-        self._obs_all = torch.empty((self.world_size * _abi.OBS_DIM, self.num_envs), dtype=torch.float32,
+        self.obs_dim = self.env.obs_dim  # (11 with pulse_stats=True)
+        self._obs_all = torch.empty((self.world_size * self.obs_dim, self.num_envs), dtype=torch.float32,
                                     device=self.device)
         self._done_all = torch.empty((self.world_size * self.num_envs,), dtype=torch.uint8, device=self.device)
 
@@ -94,11 +94,11 @@ class ShardedWireEDMEnv:
 
     # ------------------------------------------------------------------ the one collective
     def gather_obs(self) -> torch.Tensor:
-        """``float32[global_num_envs, 8]`` on every rank (all-gather over xGMI)."""
+        """``float32[global_num_envs, obs_dim]`` on every rank (all-gather over xGMI)."""
         local = self.env.state.obs[:, : self.num_envs].contiguous()
         dist.all_gather_into_tensor(self._obs_all, local, group=self.group)
-        return self._obs_all.view(self.world_size, _abi.OBS_DIM, self.num_envs).permute(0, 2, 1).reshape(
-            self.global_num_envs, _abi.OBS_DIM)
+        return self._obs_all.view(self.world_size, self.obs_dim, self.num_envs).permute(0, 2, 1).reshape(
+            self.global_num_envs, self.obs_dim)
 
     def gather_done(self) -> torch.Tensor:
         local = self.env.state.done.to(torch.uint8).contiguous()

@@ -13,7 +13,6 @@ from typing import Any, Dict, Optional
 
 import torch
 
-from . import _abi
 from .envs.wire_edm import WireEDMEnv
 
 
@@ -104,4 +103,4 @@ class WireEDMVectorEnv:
 
     @property
     def obs_names(self):
-        return _abi.OBS_NAMES
+        return self.env.obs_names
