@@ -175,6 +175,33 @@ enum wedm_pulse_field {
     WEDM_PULSE_COUNT
 };
 
+/* ------------------------------------ per-environment physics parameters (optional)
+ * Domain randomisation: one value per environment of each row below, float64, overriding the uniform value of the same
+ * name in wedm_params (derived rows hold what the host derives, exactly as for wedm_params: damping_coeff =
+ * -2 zeta omega_n, stiffness_coeff = -(omega_n ** 2), max_jerk_dt = max_jerk * dt_s, debris_removal_per_us =
+ * efficiency * base_flow_rate * 1e-6).  Not in the set, on purpose: the random-short parameters (has_random_short is a
+ * wave-uniform switch), the crater and current tables, material properties and tcrit / tbreak (the served kernels'
+ * no-break proof relies on them) and geometry (wedm_geom_*_field).  Nothing of the reset reads any of these rows.   */
+enum wedm_envp_field {
+    WEDM_EP_BASE_CRITICAL_DENSITY = 0,
+    WEDM_EP_GAP_COEFFICIENT,
+    WEDM_EP_MAX_CRITICAL_DENSITY,
+    WEDM_EP_HARD_SHORT_GAP,
+    WEDM_EP_SIGMOID_STEEPNESS,
+    WEDM_EP_SPARK_VOLTAGE_FACTOR,
+    WEDM_EP_DEBRIS_REMOVAL_PER_US,     /* dielectric.py:64-66, 150-158                       */
+    WEDM_EP_DIELECTRIC_TEMPERATURE,    /* the float32 stencil rounds it to float32           */
+    WEDM_EP_PLASMA_EFFICIENCY,         /* wire.py:298                                       */
+    WEDM_EP_BASE_CONVECTION,           /* wire.py:349-374                                   */
+    WEDM_EP_DAMPING_COEFF,             /* mechanics.py:52                                   */
+    WEDM_EP_STIFFNESS_COEFF,           /* mechanics.py:53                                   */
+    WEDM_EP_OMEGA_N,                   /* velocity control                                  */
+    WEDM_EP_MAX_ACCELERATION,
+    WEDM_EP_MAX_JERK_DT,               /* mechanics.py:57                                   */
+    WEDM_EP_MAX_SPEED,
+    WEDM_ENVP_COUNT
+};
+
 /* -------------------------------------- per-environment geometry (optional)
  * BASELINE config 5: workpiece_height / wire_diameter differ per environment.
  * When bound, these rows override the uniform values in wedm_params.       */
@@ -407,6 +434,14 @@ int32_t wedm_bind_rng_replay(wedm_ctx* ctx, const double* table, int64_t n_steps
  * WEDM_ERR_UNSUPPORTED.  With wedm_params.obs_dim >= 11 the control steps also write the three published counts into
  * obs columns 8, 9, 10 (float32).  Binding does not clear the block: wedm_reset does.                                */
 int32_t wedm_bind_pulse_stats(wedm_ctx* ctx, int32_t* rows);
+
+/* binds (rows != NULL) or removes (rows == NULL) the caller-owned per-environment physics parameters:
+ * float64 [WEDM_ENVP_COUNT][stride] described at wedm_envp_field (same stride as the state blocks), read at the start of
+ * every wedm_step (the caller may rewrite them between launches, stream-ordered).  While they are bound, wedm_step runs
+ * the kernels' ENVP instantiations: kernel 2's packed form (float32 stencil, no trace sample, no pulse statistics) and
+ * kernel 1 for every other launch; wedm_set_kernel values other than 0, 1 and 2 make wedm_step return
+ * WEDM_ERR_UNSUPPORTED.  wedm_reset reads none of the rows.                                                            */
+int32_t wedm_bind_env_params(wedm_ctx* ctx, const double* rows);
 
 /* binds (desc != NULL) or removes (desc == NULL) the signal trace; resets the sample counter.
  * Terminated environments keep being sampled (their frozen state).                        */

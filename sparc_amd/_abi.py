@@ -139,6 +139,30 @@ PULSE_COUNT = 6
 PULSE_OBS_NAMES = ("spark_pulses", "short_pulses", "short_steps")
 
 
+class ENVP(enum.IntEnum):
+    """Rows of the optional per-environment physics block (``enum wedm_envp_field``, float64)."""
+
+    BASE_CRITICAL_DENSITY = 0
+    GAP_COEFFICIENT = 1
+    MAX_CRITICAL_DENSITY = 2
+    HARD_SHORT_GAP = 3
+    SIGMOID_STEEPNESS = 4
+    SPARK_VOLTAGE_FACTOR = 5
+    DEBRIS_REMOVAL_PER_US = 6
+    DIELECTRIC_TEMPERATURE = 7
+    PLASMA_EFFICIENCY = 8
+    BASE_CONVECTION = 9
+    DAMPING_COEFF = 10
+    STIFFNESS_COEFF = 11
+    OMEGA_N = 12
+    MAX_ACCELERATION = 13
+    MAX_JERK_DT = 14
+    MAX_SPEED = 15
+
+
+ENVP_COUNT = 16
+
+
 class GF64(enum.IntEnum):
     """Rows of the per-environment geometry float64 block."""
 

@@ -92,6 +92,7 @@ struct KArgs {
     wedm_trace_desc trace;  // the bound trace (by value: one kernarg s_load, only in the TRACE instantiations)
     unsigned long long* dbg; // diagnostic builds only (WEDM_STAMPS): per-wave phase cycle sums
     int32_t* pulse;          // wedm_bind_pulse_stats block or NULL (read by the PULSE instantiations only, via kernarg_pulse)
+    const double* envp;      // wedm_bind_env_params rows or NULL (read by the ENVP instantiations only, via kernarg_envp)
 };
 
 // The by-value `cold` member as the kernels read it: through the kernarg segment (wedm_device.h).
@@ -102,6 +103,14 @@ __device__ __forceinline__ ColdRef kernarg_cold() {
 // The pulse block's pointer as the PULSE instantiations read it: through the kernarg segment (wedm_device.h, PulseRef).
 __device__ __forceinline__ PulseRef kernarg_pulse() {
     return PulseRef{(PulseSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, pulse))};
+}
+
+// The per-environment physics rows as the ENVP instantiations read them: through the kernarg segment (wedm_device.h)
+__device__ __forceinline__ const double* wedm::kernarg_envp() {
+    typedef const double* const WEDM_AS4* EnvpSlot;
+    EnvpSlot p = (EnvpSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, envp));
+    asm volatile("" : "+s"(p));
+    return *p;
 }
 
 // ------------------------------------------------------------ signal trace
@@ -215,25 +224,30 @@ __device__ __forceinline__ float stencil_pass(const TA& T, const Geom& g, const 
     return tmax;
 }
 
-template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false>
-__device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
-                                             uint32_t gid, Env& s, const TA& T) {
+// `hot`: k.hot, or (ENVP) the lane's copy with its environment's rows (envp_apply)
+template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE, bool ENVP>
+__device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, const ColdRef cold, const Geom& g, int64_t e,
+                                               uint32_t gid, Env& s, const TA& T) {
     const PulseRef pulse = kernarg_pulse();
     (void)pulse;
     Persist ps;
-    init_persist(k.hot, cold, e, s, ps);
+    init_persist(hot, cold, e, s, ps);
     StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) { const wedm_params* pp = cold->p; f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature}; }
+    if (F64) {
+        const wedm_params* pp = cold->p;
+        f64c = StencilF64{pp->temp_ref, pp->alpha_rho,
+                          ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_DIELECTRIC_TEMPERATURE, cold->s.stride) : pp->dielectric_temperature};
+    }
     const bool tracing = WEDM_TRACING(k);
     int trace_next = k.trace_next, trace_slot = k.trace_slot;
     (void)trace_next; (void)trace_slot;
     for (int it = 0; it < k.n_substeps; ++it) {
         if (!s.done) {
             const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
-            Coef c = scalar_prelude<REPLAY>(k.hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
+            Coef c = scalar_prelude<REPLAY, false, ENVP>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
-            float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, k.hot, f64c, s.h_base, s.h_zone);
-            scalar_epilogue(k.hot, s, tmax);
+            float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, hot, f64c, s.h_base, s.h_zone);
+            scalar_epilogue(hot, s, tmax);
             pulse_tally<PULSE>(pulse, cold, e, s, pk, true);
             if (s.ctrl) control_step_outputs(cold, e, s, true);
         } else if (!tracing) {
@@ -241,6 +255,19 @@ __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold,
         }
         WEDM_TRACE_POINT(k, it, e, s, true,
                          for (int i = 0; i < g.n_seg; ++i) tT[(int64_t)i * tcnt] = T.ld(i));
+    }
+}
+
+// ENVP: the every-step constants of environment e's rows (wedm_bind_env_params) instead of the uniform ones
+template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false, bool ENVP = false>
+__device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
+                                             uint32_t gid, Env& s, const TA& T) {
+    if (ENVP) {
+        Hot hv = k.hot;
+        envp_apply(hv, cold->s.stride, e);
+        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, true>(k, hv, cold, g, e, gid, s, T);
+    } else {
+        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, false>(k, k.hot, cold, g, e, gid, s, T);
     }
 }
 

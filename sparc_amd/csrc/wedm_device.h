@@ -224,6 +224,35 @@ __device__ __forceinline__ void pin_hot_in_vgprs(Hot& h) {
 #undef WEDM_PIN
 }
 
+// per-environment physics rows (wedm_bind_env_params, enum wedm_envp_field): the pointer travels at the END of the kernel
+// arguments and is read through the kernel-argument segment (kernarg_envp, wedm_common.h) by the ENVP instantiations only.
+// The rows that the kernels read as `Hot` fields are copied into the lane's `Hot` once per launch (envp_apply); the two that
+// live in the cold parameters (plasma efficiency, base convection) are read at their point of use, in the style of
+// WEDM_COLD_GEOM_F64.
+__device__ __forceinline__ const double* kernarg_envp();
+#define WEDM_ENVP_ROW(rows, row, stride) ((rows)[(int64_t)(row) * (stride) + e])
+
+// The ENVP instantiations' copy of `Hot`: environment e's rows (wedm_envp_field) replace the uniform values, bit for bit
+// (`tdiel` is rounded to float32 as wedm_step rounds the uniform value).  Called once per launch by every lane, before the
+// kernel pins its constants in VGPRs; `e` must be a real environment (the rows hold `stride` columns).
+__device__ __forceinline__ void envp_apply(Hot& h, int64_t stride, int64_t e) {
+    const double* const r = kernarg_envp();
+    h.base_critical_density = WEDM_ENVP_ROW(r, WEDM_EP_BASE_CRITICAL_DENSITY, stride);
+    h.gap_coefficient = WEDM_ENVP_ROW(r, WEDM_EP_GAP_COEFFICIENT, stride);
+    h.max_critical_density = WEDM_ENVP_ROW(r, WEDM_EP_MAX_CRITICAL_DENSITY, stride);
+    h.hard_short_gap = WEDM_ENVP_ROW(r, WEDM_EP_HARD_SHORT_GAP, stride);
+    h.sigmoid_steepness = WEDM_ENVP_ROW(r, WEDM_EP_SIGMOID_STEEPNESS, stride);
+    h.spark_voltage_factor = WEDM_ENVP_ROW(r, WEDM_EP_SPARK_VOLTAGE_FACTOR, stride);
+    h.debris_removal_per_us = WEDM_ENVP_ROW(r, WEDM_EP_DEBRIS_REMOVAL_PER_US, stride);
+    h.tdiel = (float)WEDM_ENVP_ROW(r, WEDM_EP_DIELECTRIC_TEMPERATURE, stride);
+    h.damping_coeff = WEDM_ENVP_ROW(r, WEDM_EP_DAMPING_COEFF, stride);
+    h.stiffness_coeff = WEDM_ENVP_ROW(r, WEDM_EP_STIFFNESS_COEFF, stride);
+    h.omega_n = WEDM_ENVP_ROW(r, WEDM_EP_OMEGA_N, stride);
+    h.max_acceleration = WEDM_ENVP_ROW(r, WEDM_EP_MAX_ACCELERATION, stride);
+    h.max_jerk_dt = WEDM_ENVP_ROW(r, WEDM_EP_MAX_JERK_DT, stride);
+    h.max_speed = WEDM_ENVP_ROW(r, WEDM_EP_MAX_SPEED, stride);
+}
+
 __device__ __forceinline__ void pin_mechanics_in_vgprs(Hot& h) {  // the epilogue's constants only
 #define WEDM_PIN(x) asm volatile("" : "+v"(h.x))
     WEDM_PIN(dt_s); WEDM_PIN(damping_coeff); WEDM_PIN(stiffness_coeff); WEDM_PIN(omega_n);
@@ -807,7 +836,9 @@ struct QuietTry {  // what a failed quiet_prelude() hands on: the step's Philox 
 // draws, so that a native-seed run of the reference can be followed on the device (validation mode, global kernel).
 // SCOLD / lt: the single-microsecond stream kernel's flavour -- cold parameters by scalar loads, crater tables from the
 // lanes' registers (ColdParams, LaneTables): no vector load on the path a fresh spark takes.
-template <bool REPLAY = false, bool SCOLD = false>
+// ENVP: plasma efficiency and base convection come from the environment's rows (wedm_bind_env_params) where they are used;
+// the caller has put the rows of the `Hot` fields into `p` (envp_apply).
+template <bool REPLAY = false, bool SCOLD = false, bool ENVP = false>
 __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, Persist& ps, bool writer,
                                                const QuietTry& qt = QuietTry{W4{0u, 0u, 0u, 0u}, false},
@@ -1033,8 +1064,10 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
             const auto c = c0;
             double ve = c->convection_velocity_factor * s.unwind;
             ve = ve > -0.9 ? ve : -0.9;
-            double hb = c->base_convection * (1.0 + ve);
-            double fl = 0.1 * c->base_convection;
+            const double base_convection = ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_BASE_CONVECTION, cc0->s.stride)
+                                                : c->base_convection;
+            double hb = base_convection * (1.0 + ve);
+            double fl = 0.1 * base_convection;
             hb = fl > hb ? fl : hb;
             double he = hb * (1.0 + c->convection_flow_enhancement * s.flow);
             s.h_base = (float)hb;
@@ -1050,7 +1083,7 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
             int idx = seg != 0 ? zone_start + spark_cell_offset(s.y, seg) : zone_start;
             if (idx >= 0 && idx < g.n_seg) {
                 cf.pidx = idx;
-                cf.q64 = eff * s.V * I;
+                cf.q64 = (ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_PLASMA_EFFICIENCY, cc0->s.stride) : eff) * s.V * I;
                 cf.q = (float)cf.q64;
             }
         }
@@ -1082,7 +1115,8 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
 // lane scalar_prelude() computes exactly these assignments.  Only an igniting lane (fresh spark: crater, debris, cache
 // refresh), a short, or a control-step latch still sends the wave through the general path.  Bit-identical; it costs
 // registers, so batches that spark rarely run the instantiation without it.
-template <bool DENSE>
+// ENVP: the plasma efficiency comes from the environment's row (wedm_bind_env_params), as in scalar_prelude.
+template <bool DENSE, bool ENVP = false>
 __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold, const Geom& g, int64_t e, uint32_t gid,
                                                 Env& s, QuietTry& qt, Coef& cf) {
     qt.have_w = false;
@@ -1155,7 +1189,7 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
             const int idx = seg != 0 ? zone_start + spark_cell_offset(s.y, seg) : zone_start;
             if (idx >= 0 && idx < g.n_seg) {
                 cf.pidx = idx;
-                cf.q64 = eff * s.V * s.I;
+                cf.q64 = (ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_PLASMA_EFFICIENCY, cc0->s.stride) : eff) * s.V * s.I;
                 cf.q = (float)cf.q64;
             }
         }

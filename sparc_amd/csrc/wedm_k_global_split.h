@@ -6,7 +6,10 @@
 
 // PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats): every launch with the block bound that the
 // fast kernels' PULSE forms do not take (a trace sample, stencil_mode 1, injected variates, forced kernel 1)
-template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false>
+// ENVP: the instantiation with per-environment physics rows (wedm_bind_env_params): every launch with the rows bound that
+// kernel 2's ENVP form does not take (a trace sample, stencil_mode 1, injected variates, pulse statistics, single
+// microseconds, forced kernel 1)
+template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false, bool ENVP = false>
 __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     const ColdRef cold = kernarg_cold();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -29,7 +32,7 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
     load_geom(k.hot, cold, e, g);
-    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
+    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE, ENVP>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
     if (WEDM_REWARD_ON(cold)) {
         if (!frozen) write_reward(cold, e, s);
         else cold->s.reward[e] = 0.0f;

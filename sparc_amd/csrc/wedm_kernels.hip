@@ -107,6 +107,11 @@ using namespace wedm;
 #define WEDM_LANES_PK_PULSE_LIST(X) X(1) X(2) X(4) X(8) X(16)
 #define WEDM_INST_LANES_PK_PULSE(L) template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
 #define WEDM_EXT_LANES_PK_PULSE(L) extern template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
+// per-environment physics rows (wedm_bind_env_params): the ENVP instantiations of kernel 2 (float32 stencil, no trace sample,
+// no pulse statistics); kernel 1's ENVP forms are instantiated by plan_launch (pick_global_envp)
+#define WEDM_LANES_PK_ENVP_LIST(X) X(1) X(2) X(4) X(8) X(16)
+#define WEDM_INST_LANES_PK_ENVP(L) template __global__ void wedm_step_lanes_pk<L, false, false, false, true>(const KArgs);
+#define WEDM_EXT_LANES_PK_ENVP(L) extern template __global__ void wedm_step_lanes_pk<L, false, false, false, true>(const KArgs);
 #define WEDM_EXT_SERVED(L, ex) extern template __global__ void wedm_step_served<L, ex>(const KArgs);
 #if defined(WEDM_PART) && WEDM_PART == 1
 WEDM_PACKED_LIST(WEDM_INST_PACKED)
@@ -119,6 +124,7 @@ WEDM_INST_REGS_SERVED
 WEDM_LANES_PK_LIST(WEDM_INST_LANES_PK)
 WEDM_LANES_SERVED_LIST(WEDM_INST_LANES_SERVED)
 WEDM_LANES_PK_PULSE_LIST(WEDM_INST_LANES_PK_PULSE)
+WEDM_LANES_PK_ENVP_LIST(WEDM_INST_LANES_PK_ENVP)
 #elif defined(WEDM_PART) && WEDM_PART == 4
 WEDM_REGS_F64_LIST(WEDM_INST_REGS_F64)
 WEDM_WIDE_F64_LIST(WEDM_INST_WIDE_F64)
@@ -142,6 +148,7 @@ WEDM_LANES_SERVED_LIST(WEDM_EXT_LANES_SERVED)
 WEDM_LANES_PK_PULSE_LIST(WEDM_EXT_LANES_PK_PULSE)
 WEDM_REGS_PULSE_LIST(WEDM_EXT_REGS_PULSE)
 WEDM_WIDE_PULSE_LIST(WEDM_EXT_WIDE_PULSE)
+WEDM_LANES_PK_ENVP_LIST(WEDM_EXT_LANES_PK_ENVP)
 #endif
 
 __global__ void __launch_bounds__(256)
@@ -287,6 +294,7 @@ struct wedm_ctx {
     wedm_trace_desc trace{};
     int64_t trace_us = 0, trace_count = 0;
     int32_t* pulse = nullptr;          // wedm_bind_pulse_stats: [WEDM_PULSE_COUNT][stride] or NULL
+    const double* envp = nullptr;      // wedm_bind_env_params: [WEDM_ENVP_COUNT][stride] or NULL
     std::string err;
     std::string last_kernel;
     LaunchPlan plans[2][2][2];         // [single microsecond][trace point][frozen-lane tile code]: cached launch decisions
@@ -434,14 +442,21 @@ template <bool TR, bool FZ> static const void* pick_packed(int L, bool extra) {
     return extra ? pick_packed<TR, FZ, true>(L) : pick_packed<TR, FZ, false>(L);
 }
 
-template <bool TR, bool F64 = false, bool PULSE = false> static const void* pick_lanes_pk(int L) {
+template <bool TR, bool F64 = false, bool PULSE = false, bool ENVP = false> static const void* pick_lanes_pk(int L) {
     switch (L) {
-        case 1: return (const void*)wedm_step_lanes_pk<1, TR, F64, PULSE>;
-        case 2: return (const void*)wedm_step_lanes_pk<2, TR, F64, PULSE>;
-        case 4: return (const void*)wedm_step_lanes_pk<4, TR, F64, PULSE>;
-        case 8: return (const void*)wedm_step_lanes_pk<8, TR, F64, PULSE>;
-        default: return (const void*)wedm_step_lanes_pk<16, TR, F64, PULSE>;
+        case 1: return (const void*)wedm_step_lanes_pk<1, TR, F64, PULSE, ENVP>;
+        case 2: return (const void*)wedm_step_lanes_pk<2, TR, F64, PULSE, ENVP>;
+        case 4: return (const void*)wedm_step_lanes_pk<4, TR, F64, PULSE, ENVP>;
+        case 8: return (const void*)wedm_step_lanes_pk<8, TR, F64, PULSE, ENVP>;
+        default: return (const void*)wedm_step_lanes_pk<16, TR, F64, PULSE, ENVP>;
     }
+}
+// kernel 1 with per-environment physics rows (wedm_bind_env_params): injected variates / stencil_mode 1 / the float32 stencil,
+// with or without a trace sample and pulse statistics
+template <bool PU> static const void* pick_global_envp(bool replay, bool f64, bool tr) {
+    if (replay) return tr ? (const void*)wedm_step_global<true, false, true, PU, true> : (const void*)wedm_step_global<false, false, true, PU, true>;
+    if (f64) return tr ? (const void*)wedm_step_global<true, true, false, PU, true> : (const void*)wedm_step_global<false, true, false, PU, true>;
+    return tr ? (const void*)wedm_step_global<true, false, false, PU, true> : (const void*)wedm_step_global<false, false, false, PU, true>;
 }
 static const void* pick_served(int L, bool extra) {
     switch (L) {
@@ -597,6 +612,8 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
         variant = 1;
     }
     const int32_t forced = variant;  // (the caller's choice; with the pulse block bound only it counts, see below)
+    if (ctx->envp && forced != 0 && forced != 1 && forced != 2)
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound (wedm_bind_env_params) only kernels 0 (auto), 1 and 2 run");
     const bool f64 = P.stencil_mode != 0;
     // Numba's typing of the stencil: the register kernels (uniform geometry; at most 128 / 512 segments), the fused tile walk
     // (uniform geometry), the predicated LDS kernel (any geometry), or in place in global memory; no packed LDS form, no served
@@ -714,6 +731,16 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
         if (variant == 2 && !use_pk)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
     }
+    // per-environment physics rows bound (wedm_bind_env_params): only kernels with an ENVP instantiation.  Fused launches of the
+    // float32 stencil without a trace sample or pulse statistics run kernel 2's packed form (uniform or per-environment
+    // geometry); everything else -- a trace sample in the launch, stencil_mode 1, injected variates, pulse statistics, single
+    // microseconds, forced kernel 1 -- runs kernel 1.  A name without an ENVP form is refused.
+    if (ctx->envp) {  // (a forced kernel without an ENVP form was refused above)
+        const bool fast = !tr && !f64 && !ctx->replay && !ctx->pulse;
+        variant = (fast && (forced == 2 || (forced == 0 && !single && use_pk))) ? 2 : 1;
+        if (variant == 2 && !use_pk)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+    }
     if (variant == 9 && !served_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: served kernel needs uniform geometry, the float32 stencil, lanes 4 or 8, two chunks that fit in LDS and freeze_terminated");
     if (variant == 9 && tr) variant = packed_ok ? 4 : fused_ok ? 3 : (lanes_ok || use_pk) ? 2 : 1;
@@ -737,7 +764,17 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     size_t fl = 0;
     out.walk = nullptr;
     const bool pulse = ctx->pulse != nullptr;
-    if (variant == 1 && pulse) {
+    if (variant == 1 && ctx->envp) {
+        grid = (ctx->num_envs + 255) / 256;
+        fn = pulse ? pick_global_envp<true>(ctx->replay != nullptr, f64, tr) : pick_global_envp<false>(ctx->replay != nullptr, f64, tr);
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_global%s%s[envp]<<<%d,256>>>", ctx->replay ? "[injected variates]" : f64 ? "[f64 stencil]" : "",
+                      pulse ? "[pulse]" : "", grid);
+    } else if (variant == 2 && ctx->envp) {
+        grid = (ctx->num_envs + 256 / pklanes - 1) / (256 / pklanes);
+        fl = (2 * (size_t)((ctx->n_seg_max + 2 * pklanes - 1) / (2 * pklanes)) + 2) * 1024;
+        fn = pick_lanes_pk<false, false, false, true>(pklanes);
+        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_pk<%d>[envp]<<<%d,256,%zuB>>>", pklanes, grid, fl);
+    } else if (variant == 1 && pulse) {
         grid = (ctx->num_envs + 255) / 256;
         fn = ctx->replay ? (tr ? (const void*)wedm_step_global<true, false, true, true> : (const void*)wedm_step_global<false, false, true, true>)
            : f64 ? (tr ? (const void*)wedm_step_global<true, true, false, true> : (const void*)wedm_step_global<false, true, false, true>)
@@ -1094,6 +1131,13 @@ int32_t wedm_bind_pulse_stats(wedm_ctx* ctx, int32_t* rows) {
     return WEDM_OK;
 }
 
+int32_t wedm_bind_env_params(wedm_ctx* ctx, const double* rows) {
+    if (!ctx) return WEDM_ERR_BAD_ARG;
+    ctx->envp = rows;
+    ctx->invalidate_plans();
+    return WEDM_OK;
+}
+
 int32_t wedm_set_kernel(wedm_ctx* ctx, int32_t variant) {
     if (!ctx) return WEDM_ERR_BAD_ARG;
     if (variant < 0 || variant > 12) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_set_kernel: variant must be 0..12");
@@ -1190,6 +1234,7 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
     k.walk = nullptr;
     k.dbg = ctx->dbg;
     k.pulse = ctx->pulse;
+    k.envp = ctx->envp;
     k.trace = ctx->trace;
     k.trace_next = INT32_MAX;
     k.trace_slot = 0;

@@ -22,13 +22,14 @@ Documented deviations from the single-environment reference:
 from __future__ import annotations
 
 import os
-from typing import Any, Callable, Dict, Optional
+from typing import Any, Callable, Dict, Optional, Tuple
 
 import numpy as np
 import torch
 
 from .. import _abi
 from ..core import derive
+from ..core import env_params as envp
 from ..core.env_config import EnvironmentConfig
 from ..core.material_db import get_material_db
 from ..core.state import BatchedEDMState
@@ -139,6 +140,7 @@ class WireEDMEnv:
         reset_semantics: str = "full",
         freeze_terminated: bool = True,
         pulse_stats: bool = False,
+        env_params: Optional[Dict[str, Any]] = None,
         backend: Optional[Callable] = None,
     ):
         """Beyond the reference's keywords (wire_edm.py:22-34):
@@ -167,7 +169,14 @@ class WireEDMEnv:
         ``pulse_stats``: count, inside the kernels, the reference driver's "Sparks" and "Short pulses"
         (experiments/run_simulation.py:597-636) and the short-circuit steps of every control interval; the observation
         gains three columns (``spark_pulses``, ``short_pulses``, ``short_steps`` of the last completed interval: ``obs_dim``
-        11) and `get_pulse_statistics` returns them.  Needs a backend with ``bind_pulse_stats`` (the HIP library)."""
+        11) and `get_pulse_statistics` returns them.  Needs a backend with ``bind_pulse_stats`` (the HIP library).
+        ``env_params``: domain randomisation -- a dict from physics-parameter names (the dataclass field names listed in
+        `sparc_amd.core.env_params`: ignition thresholds, flushing efficiency, dielectric temperature, plasma heat share,
+        convection, servo dynamics) to a scalar or one value per environment (sequence, NumPy array or tensor).  Names
+        not given keep the uniform dataclass value.  The named set is fixed for the environment's life; the values can
+        be changed between launches with `set_env_params` and read with `get_env_params`.  The random-short
+        parameters, crater / current tables, material properties and geometry are not in the set (geometry has its own
+        per-environment keywords).  Needs a backend with ``bind_env_params`` (the HIP library)."""
         self.render_mode = render_mode
         if mechanics_control_mode not in ["position", "velocity"]:
             raise ValueError(f"mechanics_control_mode must be 'position' or 'velocity', got {mechanics_control_mode}")
@@ -212,6 +221,12 @@ class WireEDMEnv:
                              f"{getattr(backend, '__name__', backend)!r} has none")
         self.obs_dim = _abi.OBS_DIM + (len(_abi.PULSE_OBS_NAMES) if self.pulse_stats else 0)
         self.obs_names = _abi.OBS_NAMES + (_abi.PULSE_OBS_NAMES if self.pulse_stats else ())
+        if env_params is not None:
+            if backend is not None and not hasattr(backend, "bind_env_params"):
+                raise ValueError(f"env_params needs a backend that reads per-environment physics rows (bind_env_params); "
+                                 f"{getattr(backend, '__name__', backend)!r} has none")
+            env_params = dict(env_params)
+            envp.check_names(env_params)
 
         # ---- geometry: uniform (reference behaviour) or one (h, d) pair per environment
         stride = (self.num_envs + 63) // 64 * 64
@@ -258,6 +273,12 @@ class WireEDMEnv:
             self._backend.bind_geometry(_abi.GeomPtrs(self._geom_f64.data_ptr(), self._geom_i32.data_ptr()))
         if self.pulse_stats:
             self._backend.bind_pulse_stats(self.state.pulse.data_ptr())
+        # ---- per-environment physics parameters (include/wedm_hip.h, enum wedm_envp_field), optional
+        self.env_param_names: Tuple[str, ...] = ()
+        self._envp_src = self._envp_rows = None  # float64 [len(envp.NAMES), stride] user-facing / [ENVP_COUNT, stride] device
+        if env_params is not None:
+            self._init_env_params(env_params, stride)
+            self._backend.bind_env_params(self._envp_rows.data_ptr())
 
         # what remains of the reference's module objects: parameters + read-only helpers
         from ..modules.views import DielectricView, IgnitionView, MaterialView, MechanicsView, WireView
@@ -488,6 +509,75 @@ class WireEDMEnv:
         self._backend.bind_trace(None)
         self._trace = None
 
+    # ---- per-environment physics parameters (domain randomisation) ---------------------------------
+    def _envp_consts(self) -> Dict[str, float]:
+        return {"base_flow_rate": float(self.dielectric_params.base_flow_rate), "dt_s": float(self.params.dt_s)}
+
+    def _init_env_params(self, values: Dict[str, Any], stride: int) -> None:
+        n = self.num_envs
+        uni = envp.uniform_values(self)
+        cols = {name: np.full(stride, uni[name], dtype=np.float64) for name in envp.NAMES}
+        for name, v in values.items():
+            a = envp.host_column(name, v, n)
+            cols[name][:n] = a
+            cols[name][n:] = a[-1]  # padding columns repeat the last environment
+        self.env_param_names = tuple(name for name in envp.NAMES if name in values)
+        self._envp_src = torch.from_numpy(np.stack([cols[name] for name in envp.NAMES])).to(self.device)
+        self._envp_rows = torch.from_numpy(envp.derive_rows(cols, self._envp_consts())).to(self.device)
+
+    def set_env_params(self, values: Dict[str, Any], mask=None) -> None:
+        """New values of randomised physics parameters (names given at construction), taking effect at the next launch.
+        A value is a scalar or one value per environment; `mask` (bool per environment) limits the change to the
+        environments where it is set.  Device tensors are applied on the device with no host synchronisation (and are not
+        checked for finiteness); host values are checked and derived in Python floats (see `sparc_amd.core.env_params`)."""
+        if self._envp_rows is None:
+            raise RuntimeError("construct the environment with env_params={...} to randomise physics parameters")
+        values = dict(values)
+        envp.check_names(values)
+        outside = sorted(set(values) - set(self.env_param_names))
+        if outside:
+            raise ValueError(f"{outside} not randomised in this environment (env_params named {list(self.env_param_names)})")
+        n = self.num_envs
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device).reshape(-1).to(torch.bool)
+            if m.shape != (n,):
+                raise ValueError(f"mask must have one entry per environment ({n})")
+        src = {name: self._envp_src[envp.INDEX[name], :n] for name in envp.NAMES}
+        host = {}
+        new = {}
+        for name, v in values.items():
+            if torch.is_tensor(v) and v.device.type != "cpu":
+                col = v.detach().to(device=self.device, dtype=torch.float64).reshape(-1)
+                if col.numel() == 1:
+                    col = col.expand(n)
+                if col.shape != (n,):
+                    raise ValueError(f"env_params[{name!r}] must be a scalar or have one value per environment ({n})")
+            else:
+                host[name] = envp.host_column(name, v, n)
+                col = torch.from_numpy(host[name]).to(self.device)
+            new[name] = col
+        src.update(new)
+        consts = self._envp_consts()
+        rows = sorted({r for name in new for r in envp.AFFECTS[name]})
+        for r in rows:
+            if r == _abi.ENVP.STIFFNESS_COEFF and "omega_n" in host:  # C pow, element by element (module docstring)
+                val = torch.from_numpy(envp.derive_row(r, host, consts)).to(self.device)
+            else:
+                val = envp.derive_row(r, src, consts)
+            dst = self._envp_rows[r, :n]
+            dst.copy_(val if m is None else torch.where(m, val, dst))
+        for name, col in new.items():
+            dst = self._envp_src[envp.INDEX[name], :n]
+            dst.copy_(col if m is None else torch.where(m, col, dst))
+
+    def get_env_params(self) -> Dict[str, torch.Tensor]:
+        """Every randomisable physics parameter per environment (float64 [num_envs] copies, in the dataclass units): the
+        environment's own values for the randomised names, the uniform dataclass value for the others."""
+        if self._envp_src is None:
+            raise RuntimeError("construct the environment with env_params={...} to randomise physics parameters")
+        return {name: self._envp_src[envp.INDEX[name], : self.num_envs].clone() for name in envp.NAMES}
+
     # ---- checkpoint / resume (SURVEY.md §5: the reference has none for simulation state) ---------
     def _physics_fingerprint(self) -> str:
         """sha256 over everything that determines the physics of a continuation: the whole
@@ -509,7 +599,14 @@ class WireEDMEnv:
         ``weights_only=True``)."""
         return {"abi_version": _abi.ABI_VERSION, "blocks": self.state.clone_blocks(), "seed": self._seed, "num_envs": self.num_envs,
                 "n_segments": self.n_segments, "env_id_offset": self.env_id_offset, "pulse_stats": self.pulse_stats,
-                "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint()}
+                "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint(),
+                **self._env_params_state()}
+
+    def _env_params_state(self) -> Dict[str, Any]:
+        if self._envp_rows is None:
+            return {"env_param_names": None}
+        return {"env_param_names": list(self.env_param_names), "env_params_src": self._envp_src.detach().cpu().clone(),
+                "env_params_rows": self._envp_rows.detach().cpu().clone()}
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         if sd.get("abi_version") != _abi.ABI_VERSION:
@@ -520,10 +617,23 @@ class WireEDMEnv:
         if bool(sd.get("pulse_stats", False)) != self.pulse_stats:
             raise ValueError(f"checkpoint was taken with pulse_stats={bool(sd.get('pulse_stats', False))}, this environment has "
                              f"pulse_stats={self.pulse_stats}: the observation and the interval counts differ")
+        mine = list(self.env_param_names) if self._envp_rows is not None else None
+        theirs = sd.get("env_param_names")
+        if (list(theirs) if theirs is not None else None) != mine:
+            raise ValueError(f"checkpoint was taken with per-environment physics parameters {theirs}, this environment "
+                             f"randomises {mine}")
         if sd.get("physics") != self._physics_fingerprint():
             raise ValueError("checkpoint was taken with different physics (configuration, module parameters, control "
                              "mode or per-environment geometry): continuing would silently change the trajectory")
+        if mine is not None:
+            for key, dst in (("env_params_src", self._envp_src), ("env_params_rows", self._envp_rows)):
+                if tuple(sd[key].shape) != tuple(dst.shape):
+                    raise ValueError(f"checkpoint block {key!r} has shape {tuple(sd[key].shape)}, this environment's is "
+                                     f"{tuple(dst.shape)}")
         self.state.load_blocks(sd["blocks"])
+        if mine is not None:
+            self._envp_src.copy_(sd["env_params_src"])
+            self._envp_rows.copy_(sd["env_params_rows"])
         self._seed = int(sd["seed"])
         self.steps_since_reset = int(sd["steps_since_reset"])
 

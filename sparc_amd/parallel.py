@@ -39,7 +39,7 @@ class ShardedWireEDMEnv:
     """
 
     def __init__(self, global_num_envs: int, *, process_group: Optional[Any] = None, device: Any = None,
-                 workpiece_height=None, wire_diameter=None, **env_kwargs):
+                 workpiece_height=None, wire_diameter=None, env_params=None, **env_kwargs):
         if not dist.is_initialized():
             raise RuntimeError("ShardedWireEDMEnv needs torch.distributed.init_process_group first")
         self.group = process_group
@@ -54,6 +54,8 @@ class ShardedWireEDMEnv:
             num_envs=self.num_envs, device=device, env_id_offset=self.lo,
             workpiece_height=_slice_leaf(workpiece_height, self.lo, self.hi, self.global_num_envs),
             wire_diameter=_slice_leaf(wire_diameter, self.lo, self.hi, self.global_num_envs),
+            env_params=None if env_params is None else
+            {k: _slice_leaf(v, self.lo, self.hi, self.global_num_envs) for k, v in env_params.items()},
             **env_kwargs)
         self.device = self.env.device
         self.state = self.env.state
@@ -68,6 +70,11 @@ class ShardedWireEDMEnv:
         if options and options.get("mask") is not None:
             options = dict(options, mask=_slice_leaf(options["mask"], self.lo, self.hi, self.global_num_envs))
         return self.env.reset(seed=seed, options=options)
+
+    def set_env_params(self, values, mask=None) -> None:
+        """`WireEDMEnv.set_env_params` with values / mask given for the GLOBAL batch (or scalars)."""
+        cut = lambda x: _slice_leaf(x, self.lo, self.hi, self.global_num_envs)  # noqa: E731
+        self.env.set_env_params({k: cut(v) for k, v in values.items()}, mask=cut(mask))
 
     def make_action(self, servo=0.0, target_voltage=80.0, current_mode=5, ON_time=3.0, OFF_time=80.0) -> DeviceAction:
         cut = lambda x: _slice_leaf(x, self.lo, self.hi, self.global_num_envs)  # noqa: E731

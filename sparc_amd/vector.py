@@ -9,7 +9,7 @@ fresh Philox episode stream.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, Optional
+from typing import Any, Callable, Dict, Optional, Tuple
 
 import torch
 
@@ -25,6 +25,28 @@ def progress_reward(env: WireEDMEnv, prev: Dict[str, torch.Tensor]) -> torch.Ten
     return cut - 10.0 * st.is_wire_broken.to(torch.float32)
 
 
+def uniform_param_sampler(ranges: Dict[str, Tuple[float, float]], generator: Optional[torch.Generator] = None):
+    """A `param_sampler` for `WireEDMVectorEnv`: every named physics parameter uniform in ``[low, high)``, drawn on the
+    environment's device (``generator`` must live there when given).  ``omega_n`` draws keep 26 significant bits, so that
+    the stiffness row derived on the device equals Python's ``omega_n ** 2`` (`sparc_amd.core.env_params`)."""
+    spec = {name: (float(lo), float(hi)) for name, (lo, hi) in ranges.items()}
+    for name, (lo, hi) in spec.items():
+        if not (lo <= hi):
+            raise ValueError(f"range of {name!r} must have low <= high, got ({lo}, {hi})")
+
+    def sample(env: WireEDMEnv, reset_mask: torch.Tensor) -> Dict[str, torch.Tensor]:
+        out = {}
+        for name, (lo, hi) in spec.items():
+            u = torch.rand(env.num_envs, generator=generator, device=env.device, dtype=torch.float64)
+            x = lo + (hi - lo) * u
+            if name == "omega_n":  # clear the low 27 of 52 mantissa bits
+                x = (x.view(torch.int64) & ~((1 << 27) - 1)).view(torch.float64)
+            out[name] = x
+        return out
+
+    return sample
+
+
 class WireEDMVectorEnv:
     """Next-step autoreset (Gymnasium's ``AutoresetMode.NEXT_STEP``): the `step()` after the one that
     reported ``terminated`` / ``truncated`` for an environment starts a new episode for it.
@@ -37,12 +59,17 @@ class WireEDMVectorEnv:
     a torch expression."""
 
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
-                 reward=None):
+                 reward=None, param_sampler: Optional[Callable] = None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
         it); a callable ``f(env, prev) -> float32[N]`` receives the environment after the control
-        interval and ``prev = {"workpiece_position": ...}`` snapshotted before it (all on the device)."""
+        interval and ``prev = {"workpiece_position": ...}`` snapshotted before it (all on the device).
+        ``param_sampler``: domain randomisation -- ``f(env, reset_mask) -> {name: float64[N] device tensor}`` is called at
+        every `step()` before the launch (and at `reset()` with every environment marked); the values are applied
+        (`WireEDMEnv.set_env_params`) only where ``reset_mask`` is set, so each new episode starts with freshly drawn
+        physics.  The environment must have been built with ``env_params`` naming the sampled parameters
+        (see `uniform_param_sampler`)."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
@@ -60,16 +87,29 @@ class WireEDMVectorEnv:
         self._reward_fn = progress_reward if reward == "progress" else reward
         if self._reward_fn is not None and not callable(self._reward_fn):
             raise ValueError("reward must be None, 'progress' or a callable")
+        self._param_sampler = param_sampler
+        if param_sampler is not None and getattr(env, "_envp_rows", None) is None:
+            raise ValueError("param_sampler needs an environment built with env_params={...} naming the sampled parameters")
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
+        if self._param_sampler is not None:
+            mask = (options or {}).get("mask")
+            mask = torch.ones(self.num_envs, dtype=torch.bool, device=self.env.device) if mask is None else \
+                torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
+            self._apply_sampler(mask)
         obs, info = self.env.reset(seed=seed, options=options)
         self._need_reset.zero_()
         return obs.clone(), info
 
+    def _apply_sampler(self, reset_mask: torch.Tensor) -> None:
+        self.env.set_env_params(self._param_sampler(self.env, reset_mask), mask=reset_mask)
+
     def step(self, action):
         """One control interval for every environment (1000 us by default)."""
+        if self._param_sampler is not None and self.autoreset:
+            self._apply_sampler(self._need_reset)  # environments about to start a new episode draw their physics
         if self.autoreset:
             if self._in_kernel_reset:
                 # terminated environments are reset by the launch itself; a truncated one is handed to it
