@@ -183,6 +183,8 @@ def lib() -> C.CDLL:
                                          C.POINTER(_abi.GeomPtrs), C.POINTER(_abi.ActionPtrs),
                                          _i, _i, _i, _i, _i, _i]
     L.wedm_oracle_step_batch.restype = _i
+    L.wedm_oracle_step_batch_ex.argtypes = L.wedm_oracle_step_batch.argtypes + [C.c_void_p, C.c_void_p]
+    L.wedm_oracle_step_batch_ex.restype = _i
     L.wedm_oracle_max_threads.restype = _i
     _lib = L
     return L

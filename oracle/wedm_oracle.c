@@ -1149,9 +1149,70 @@ int32_t wedm_oracle_reset_batch(const wedm_params* p, const wedm_state_ptrs* s, 
     return WEDM_OK;
 }
 
+/* wedm_bind_env_params (include/wedm_hip.h, enum wedm_envp_field): environment e's rows replace the uniform constants of
+ * the same name, as given (the host derived them; nothing is re-derived here).  The kernels copy the same set into their
+ * `Hot` (envp_apply) and read plasma efficiency and base convection where they are used. */
+static void apply_env_params(const double* rows, int64_t stride, int64_t e, wedm_oracle_consts* c) {
+#define EP(row) rows[(int64_t)(row) * stride + e]
+    c->base_critical_density = EP(WEDM_EP_BASE_CRITICAL_DENSITY);
+    c->gap_coefficient = EP(WEDM_EP_GAP_COEFFICIENT);
+    c->max_critical_density = EP(WEDM_EP_MAX_CRITICAL_DENSITY);
+    c->hard_short_gap = EP(WEDM_EP_HARD_SHORT_GAP);
+    c->sigmoid_steepness = EP(WEDM_EP_SIGMOID_STEEPNESS);
+    c->spark_voltage_factor = EP(WEDM_EP_SPARK_VOLTAGE_FACTOR);
+    c->debris_removal_per_us = EP(WEDM_EP_DEBRIS_REMOVAL_PER_US);
+    c->dielectric_temperature = EP(WEDM_EP_DIELECTRIC_TEMPERATURE);
+    c->plasma_efficiency = EP(WEDM_EP_PLASMA_EFFICIENCY);
+    c->base_convection = EP(WEDM_EP_BASE_CONVECTION);
+    c->damping_coeff = EP(WEDM_EP_DAMPING_COEFF);
+    c->stiffness_coeff = EP(WEDM_EP_STIFFNESS_COEFF);
+    c->omega_n = EP(WEDM_EP_OMEGA_N);
+    c->max_acceleration = EP(WEDM_EP_MAX_ACCELERATION);
+    c->max_jerk_dt = EP(WEDM_EP_MAX_JERK_DT);
+    c->max_speed = EP(WEDM_EP_MAX_SPEED);
+#undef EP
+}
+
+/* What the reference driver's summary looks at in one sample (experiments/run_simulation.py:604-627): 0 = no pulse
+ * (I <= 0.1 A), 1 = a spark pulse (I > 0.1 A, no short), 2 = a short pulse (I > 0.1 A during a short). */
+static int32_t pulse_kind(const wedm_oracle_env* v) {
+    return v->current > 0.1 ? (v->is_short_circuit ? 2 : 1) : 0;
+}
+
+#define PULSE(row) pulse[(int64_t)(row) * stride + e]
+
+/* wedm_bind_pulse_stats (include/wedm_hip.h, enum wedm_pulse_field; the driver's "Sparks" / "Short pulses" of
+ * experiments/run_simulation.py:597-636 per control interval): the tally of one sample -- the state after a physics
+ * step the environment ran -- with `prev` the kind of the sample before it.  Rising edges of I > 0.1 A outside / inside a
+ * short and short-circuit samples accumulate; a control step (its own sample included) publishes the accumulators into
+ * the *_LAST rows (and obs columns 8-10 when obs_dim >= 11) and restarts them from zero. */
+static void pulse_tally(const wedm_params* p, const wedm_state_ptrs* s, int32_t* pulse, int64_t e,
+                        const wedm_oracle_env* v, int32_t prev) {
+    const int64_t stride = s->stride;
+    const int32_t kind = pulse_kind(v);
+    if (kind != 0 && kind != prev) PULSE(kind == 1 ? WEDM_P_SPARK_ACC : WEDM_P_SHORT_ACC) += 1;
+    if (v->is_short_circuit) PULSE(WEDM_P_SHORT_STEPS_ACC) += 1;
+    if (v->last_ctrl_step) {
+        for (int q = 0; q < 3; ++q) {
+            const int32_t n = PULSE(WEDM_P_SPARK_ACC + q);
+            PULSE(WEDM_P_SPARK_ACC + q) = 0;
+            PULSE(WEDM_P_SPARK_LAST + q) = n;
+            if (s->obs && p->obs_dim >= 11) s->obs[(int64_t)(8 + q) * stride + e] = (float)n;
+        }
+    }
+}
+
 int32_t wedm_oracle_step_batch(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
                                const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                int32_t math_mode, int32_t stencil_mode, int32_t n_threads) {
+    return wedm_oracle_step_batch_ex(p, s, g, a, num_envs, n_seg_max, n_substeps, math_mode, stencil_mode, n_threads,
+                                     NULL, NULL);
+}
+
+int32_t wedm_oracle_step_batch_ex(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                  const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                  int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                  int32_t* pulse) {
     if (!p || !s || !a || num_envs <= 0 || n_substeps < 0 || n_seg_max < 1) return WEDM_ERR_BAD_ARG;
     if (n_substeps == 0) return WEDM_OK;
     if (p->per_env_geometry && (!g || !g->f64 || !g->i32)) return WEDM_ERR_BAD_ARG;
@@ -1186,8 +1247,11 @@ int32_t wedm_oracle_step_batch(const wedm_params* p, const wedm_state_ptrs* s, c
                 for (int i = 0; i < 4 * WEDM_T_QUADS(n_seg_max); ++i) s->T[WEDM_T_INDEX(i, stride, e)] = (float)p->spool_T;
                 if (s->obs)
                     for (int q = 0; q < p->obs_dim; ++q) s->obs[(int64_t)q * stride + e] = 0.0f;
+                if (pulse)
+                    for (int q = 0; q < WEDM_PULSE_COUNT; ++q) PULSE(q) = 0;
             }
             if (p->per_env_geometry) apply_geometry(g, stride, e, &v->c);
+            if (envp_rows) apply_env_params(envp_rows, stride, e, &v->c);
             if (v->c.n_seg > WEDM_ORACLE_MAX_SEG || v->c.n_seg < 1) { bad = 1; continue; }
             gather_env(s, e, v);
             v->crater_log = s->crater_log ? s->crater_log + e : NULL;
@@ -1202,7 +1266,9 @@ int32_t wedm_oracle_step_batch(const wedm_params* p, const wedm_state_ptrs* s, c
             /* a terminated environment is frozen; with wedm_params.keep_stepping_terminated it is stepped on as the
              * reference's step() would be (wire_edm.py:116-157 has no guard), DONE = `terminated` of the last step */
             for (int k = 0; k < n_substeps && (!done || p->keep_stepping_terminated); ++k) {
+                const int32_t prev = pulse ? pulse_kind(v) : 0; /* the previous sample: the state before the step */
                 done = wedm_oracle_step(v, &act);
+                if (pulse) pulse_tally(p, s, pulse, e, v, prev);
                 if (v->last_ctrl_step) write_obs(p, s, e, v);
             }
             /* wedm_params.reward_mode 1: the launch's progress reward (the reference's is a TODO, wire_edm.py:185-187) */

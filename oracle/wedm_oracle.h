@@ -208,6 +208,18 @@ int32_t wedm_oracle_reset_batch(const wedm_params* p, const wedm_state_ptrs* s, 
 int32_t wedm_oracle_step_batch(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
                                const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                int32_t math_mode, int32_t stencil_mode, int32_t n_threads);
+/* The same launch with the two optional blocks of the C-ABI (HOST pointers, either may be NULL; NULL for both is exactly
+ * wedm_oracle_step_batch):
+ *   envp_rows  float64 [WEDM_ENVP_COUNT][stride], wedm_bind_env_params: environment e's rows replace the uniform
+ *              constants of the same name, as given (after the per-environment geometry; the reset reads none of them);
+ *   pulse      int32 [WEDM_PULSE_COUNT][stride], wedm_bind_pulse_stats: the per-interval pulse tally of enum
+ *              wedm_pulse_field (one sample per physics step an environment ran; published at control steps, into obs
+ *              columns 8-10 too when obs_dim >= 11; the in-launch autoreset clears all six rows).  wedm_reset's share
+ *              (clearing the rows of the reset environments) is the caller's. */
+int32_t wedm_oracle_step_batch_ex(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                  const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                  int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                  int32_t* pulse);
 int32_t wedm_oracle_max_threads(void);
 int64_t wedm_oracle_sizeof(int32_t which);
 

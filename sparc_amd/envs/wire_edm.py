@@ -93,6 +93,18 @@ class StepInfo(dict):
     def copy(self):
         return StepInfo({k: dict.__getitem__(self, k) for k in self}, self._state)
 
+    # CPython copies a dict subclass's stored values directly (`dict(info)`, `{**info}`, `dict.update`) unless the class
+    # overrides `__iter__`; it then goes through `keys()` and `__getitem__`, which composes the clock.
+    def __iter__(self):
+        return dict.__iter__(self)
+
+    # `copy.copy`, `copy.deepcopy` and `pickle`: a plain dict with the clock materialised (no reference to the live state)
+    def __reduce__(self):
+        return dict, (dict(self.items()),)
+
+    def __repr__(self):
+        return repr(dict(self.items()))
+
 
 class DeviceAction:
     """An action already laid out for the kernel: five contiguous length-N device

@@ -134,7 +134,7 @@ class WireEDMVectorEnv:
         else:
             truncated = truncated.clone()
         self._need_reset = terminated | truncated
-        info = dict(info)
+        info = dict(info)  # (StepInfo: the copy composes the exact int64 clock)
         info["episode"] = self.episode_count
         return obs.clone(), reward, terminated, truncated, info
 

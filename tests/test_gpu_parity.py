@@ -1505,6 +1505,7 @@ def test_vector_env_step_is_one_launch_without_host_sync():
     torch.cuda.synchronize()
     assert "wedm_step_" in env._backend.last_kernel()
     assert bool(term.any() | (env.state.episode > 0).any()) and reward.dtype == torch.float32
+    assert info["time"].dtype == torch.int64 and torch.equal(info["time"], env.state.time)  # the exact clock, not a placeholder
     # ... and with what a policy really hands over (wire_edm.py:116-121,162-170): a FRESH dict of device tensors per control
     # step -- the servo command a torch function of the observation, the generator settings drawn on the device.  The
     # current modes are validated on the device (sticky ERROR row, `check_errors()`), not read back.

@@ -51,6 +51,33 @@ def test_env_step_with_sampled_action():
     assert info["time"].tolist() == [2**31 + 5] * 4 and info.get("time").dtype == torch.int64
 
 
+def test_step_info_copies_carry_the_exact_clock():
+    """`dict(info)`, `{**info}`, `copy.deepcopy`, `pickle` and the vector adapter's `info` hold the int64 clock, never the
+    placeholder of the lazy read."""
+    import copy
+    import pickle
+
+    from sparc_amd import WireEDMVectorEnv
+
+    env = make()
+    env.reset(seed=0)
+    *_, info = env.step_many(env.make_action(), 3)
+    env.state.time = torch.tensor([3, 2**33 + 7, 2**31 + 1, 9], dtype=torch.int64)
+    for copied in (dict(info), {**info}, copy.copy(info), copy.deepcopy(info), pickle.loads(pickle.dumps(info))):
+        assert copied["time"] is not None and copied["time"].dtype == torch.int64
+        assert torch.equal(copied["time"], env.state.time), type(copied)
+        assert list(copied) == ["wire_broken", "target_reached", "spark_state", "time", "control_step"]
+    snap = copy.deepcopy(info)
+    env.state.time = 5
+    assert snap["time"].tolist() == [3, 2**33 + 7, 2**31 + 1, 9]  # a deep copy is a snapshot
+    assert info["time"].tolist() == [5] * 4                          # the step's own info still reads the live clock
+    vec = WireEDMVectorEnv(make())
+    vec.reset(seed=1)
+    vinfo = vec.step(vec.env.make_action())[4]
+    assert vinfo["time"] is not None and vinfo["time"].dtype == torch.int64
+    assert torch.equal(vinfo["time"], vec.env.state.time) and int(vinfo["time"][0]) == 1000
+
+
 def test_custom_config():
     cfg = EnvironmentConfig(workpiece_height=20.0, wire_diameter=0.3, target_cutting_distance=1000.0)
     env = make(config=cfg)
