@@ -52,103 +52,63 @@ using namespace wedm;
 #include "wedm_lanes2.h"
 
 // ------------------------------------------------------------ translation-unit parts (build time only)
-// The packed and fused kernels exist in 32 and 40 instantiations and take hipcc two minutes in one translation unit.
-// __graft_entry__.build_hip() compiles this file three times in parallel: -DWEDM_PART=1 emits the packed instantiations
-// only, -DWEDM_PART=2 the fused ones, -DWEDM_PART=0 everything else (host code, the other kernels) with the two families
-// declared `extern template`; the three objects link into the one shared library.  Without -DWEDM_PART the file is one
-// self-contained translation unit (the diagnostic builds of tools/ use it that way).
-#define WEDM_BOOLS3(X, L) X(L, false, false, false) X(L, false, false, true) X(L, false, true, false) X(L, false, true, true) \
-                          X(L, true, false, false) X(L, true, false, true) X(L, true, true, false) X(L, true, true, true)
-#define WEDM_PACKED_LIST(X) WEDM_BOOLS3(X, 1) WEDM_BOOLS3(X, 2) WEDM_BOOLS3(X, 4) WEDM_BOOLS3(X, 8)
-#define WEDM_FUSED_LIST(X) WEDM_BOOLS3(X, 1) WEDM_BOOLS3(X, 2) WEDM_BOOLS3(X, 4) WEDM_BOOLS3(X, 8) WEDM_BOOLS3(X, 16)
-#define WEDM_INST_PACKED(L, a, b, c) template __global__ void wedm_step_packed<L, a, b, c>(const KArgs);
-#define WEDM_INST_FUSED(L, a, b, c) template __global__ void wedm_step_fused<L, a, b, c>(const KArgs);
-// stencil_mode 1 on the tile walk: <L, TRACE, FROZEN_OK = true, N1 = false, F64 = true>
-#define WEDM_FUSED_F64_LIST(X) X(1, false) X(1, true) X(2, false) X(2, true) X(4, false) X(4, true) X(8, false) X(8, true) X(16, false) X(16, true)
-#define WEDM_INST_FUSED_F64(L, tr) template __global__ void wedm_step_fused<L, tr, true, false, true>(const KArgs);
-#define WEDM_EXT_FUSED_F64(L, tr) extern template __global__ void wedm_step_fused<L, tr, true, false, true>(const KArgs);
-#define WEDM_EXT_PACKED(L, a, b, c) extern template __global__ void wedm_step_packed<L, a, b, c>(const KArgs);
-#define WEDM_EXT_FUSED(L, a, b, c) extern template __global__ void wedm_step_fused<L, a, b, c>(const KArgs);
-// the served kernels (wedm_served.h): <L, EXTRA>
-#define WEDM_SERVED_LIST(X) X(4, false) X(4, true) X(8, false) X(8, true)
-#define WEDM_LANES_PK_LIST(X) X(1, false) X(1, true) X(2, false) X(2, true) X(4, false) X(4, true) X(8, false) X(8, true) X(16, false) X(16, true)
-#define WEDM_INST_LANES_PK(L, tr) template __global__ void wedm_step_lanes_pk<L, tr>(const KArgs);
-#define WEDM_EXT_LANES_PK(L, tr) extern template __global__ void wedm_step_lanes_pk<L, tr>(const KArgs);
-#define WEDM_INST_LANES_PK_F64(L, tr) template __global__ void wedm_step_lanes_pk<L, tr, true>(const KArgs);
-#define WEDM_EXT_LANES_PK_F64(L, tr) extern template __global__ void wedm_step_lanes_pk<L, tr, true>(const KArgs);
-// stencil_mode 1 on the stream kernel: the single-microsecond instantiation <L, false, 64, ONE = true, F64 = true>
-#define WEDM_STREAM_F64_LIST(X) X(1) X(2) X(4) X(8) X(16)
-#define WEDM_INST_STREAM_F64(L) template __global__ void wedm_step_stream<L, false, 64, true, true>(const KArgs);
-#define WEDM_EXT_STREAM_F64(L) extern template __global__ void wedm_step_stream<L, false, 64, true, true>(const KArgs);
-#define WEDM_LANES_SERVED_LIST(X) X(4) X(8) X(16)
-#define WEDM_INST_LANES_SERVED(L) template __global__ void wedm_step_lanes_served<L>(const KArgs);
-#define WEDM_EXT_LANES_SERVED(L) extern template __global__ void wedm_step_lanes_served<L>(const KArgs);
-#define WEDM_INST_REGS_SERVED template __global__ void wedm_step_regs_served<128>(const KArgs);
-#define WEDM_EXT_REGS_SERVED extern template __global__ void wedm_step_regs_served<128>(const KArgs);
-// stencil_mode 1 on the register kernel: <128, L, TRACE, F64 = true>
-#define WEDM_REGS_F64_LIST(X) X(1, false) X(1, true) X(2, false) X(2, true)
-#define WEDM_INST_REGS_F64(L, tr) template __global__ void wedm_step_regs<128, L, tr, true>(const KArgs);
-#define WEDM_EXT_REGS_F64(L, tr) extern template __global__ void wedm_step_regs<128, L, tr, true>(const KArgs);
-// stencil_mode 1 on the wide register kernel: <16, L, CUT, TRACE, F64 = true, MINB> (a traced launch runs the CUT form, as in
-// float32; MINB = 1 for a batch of one wave per SIMD, 2 beyond)
-#define WEDM_WIDE_F64_LIST1(X, mb) X(4, false, false, mb) X(4, true, false, mb) X(4, true, true, mb) X(8, false, false, mb) X(8, true, false, mb) \
-                                   X(8, true, true, mb) X(16, false, false, mb) X(16, true, false, mb) X(16, true, true, mb)
-#define WEDM_WIDE_F64_LIST(X) WEDM_WIDE_F64_LIST1(X, 1) WEDM_WIDE_F64_LIST1(X, 2)
-#define WEDM_INST_WIDE_F64(L, cut, tr, mb) template __global__ void wedm_step_regs_wide<16, L, cut, tr, true, mb>(const KArgs);
-#define WEDM_EXT_WIDE_F64(L, cut, tr, mb) extern template __global__ void wedm_step_regs_wide<16, L, cut, tr, true, mb>(const KArgs);
-#define WEDM_INST_SERVED(L, ex) template __global__ void wedm_step_served<L, ex>(const KArgs);
-// pulse statistics (wedm_bind_pulse_stats): the PULSE instantiations of kernels 7, 8 and 2 (float32 stencil, no trace sample)
-#define WEDM_REGS_PULSE_LIST(X) X(1) X(2)
-#define WEDM_INST_REGS_PULSE(L) template __global__ void wedm_step_regs<128, L, false, false, true>(const KArgs);
-#define WEDM_EXT_REGS_PULSE(L) extern template __global__ void wedm_step_regs<128, L, false, false, true>(const KArgs);
-#define WEDM_WIDE_PULSE_LIST(X) X(4, false) X(4, true) X(8, false) X(8, true) X(16, false) X(16, true)
-#define WEDM_INST_WIDE_PULSE(L, cut) template __global__ void wedm_step_regs_wide<16, L, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>(const KArgs);
-#define WEDM_EXT_WIDE_PULSE(L, cut) extern template __global__ void wedm_step_regs_wide<16, L, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>(const KArgs);
-#define WEDM_LANES_PK_PULSE_LIST(X) X(1) X(2) X(4) X(8) X(16)
-#define WEDM_INST_LANES_PK_PULSE(L) template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
-#define WEDM_EXT_LANES_PK_PULSE(L) extern template __global__ void wedm_step_lanes_pk<L, false, false, true>(const KArgs);
-// per-environment physics rows (wedm_bind_env_params): the ENVP instantiations of kernel 2 (float32 stencil, no trace sample,
-// no pulse statistics); kernel 1's ENVP forms are instantiated by plan_launch (pick_global_envp)
-#define WEDM_LANES_PK_ENVP_LIST(X) X(1) X(2) X(4) X(8) X(16)
-#define WEDM_INST_LANES_PK_ENVP(L) template __global__ void wedm_step_lanes_pk<L, false, false, false, true>(const KArgs);
-#define WEDM_EXT_LANES_PK_ENVP(L) extern template __global__ void wedm_step_lanes_pk<L, false, false, false, true>(const KArgs);
-#define WEDM_EXT_SERVED(L, ex) extern template __global__ void wedm_step_served<L, ex>(const KArgs);
+// The kernels exist in about 240 instantiations, which take hipcc minutes in one translation unit.
+// __graft_entry__.build_hip() compiles this file five times in parallel: -DWEDM_PART=1 ... 4 each emit the explicit
+// instantiations of one list below (1: packed, 2: fused, 3: served and packed-LDS, 4: the float64-typed and PULSE register
+// forms), -DWEDM_PART=0 holds the host code, the reset and debug kernels and every instantiation no list names (made where
+// plan_launch() refers to it), with the four lists declared `extern template`; the five objects link into the one shared
+// library.  Without -DWEDM_PART the file is one self-contained translation unit (the diagnostic builds of tools/ use it
+// that way).
+#define WEDM_BOOLS3(X, K, L) X(K<L, false, false, false>) X(K<L, false, false, true>) X(K<L, false, true, false>) \
+                             X(K<L, false, true, true>) X(K<L, true, false, false>) X(K<L, true, false, true>)   \
+                             X(K<L, true, true, false>) X(K<L, true, true, true>)
+#define WEDM_L4(G, X) G(X, 1) G(X, 2) G(X, 4) G(X, 8)
+#define WEDM_L5(G, X) WEDM_L4(G, X) G(X, 16)
+// part 1: wedm_step_packed<L, TRACE, FROZEN_OK, EXTRA>
+#define WEDM_P1(X, L) WEDM_BOOLS3(X, wedm_step_packed, L)
+// part 2: wedm_step_fused<L, TRACE, FROZEN_OK, N1>, and stencil_mode 1 on the tile walk: <L, TRACE, FROZEN_OK = true, N1 = false, F64 = true>
+#define WEDM_P2(X, L) WEDM_BOOLS3(X, wedm_step_fused, L) \
+                      X(wedm_step_fused<L, false, true, false, true>) X(wedm_step_fused<L, true, true, false, true>)
+// part 3: wedm_step_lanes_pk<L, TRACE>, its PULSE and ENVP forms (float32 stencil, no trace sample); the served kernels
+// (wedm_served.h) <L, EXTRA>, wedm_step_lanes_served<L>, wedm_step_regs_served
+#define WEDM_P3(X, L) X(wedm_step_lanes_pk<L, false>) X(wedm_step_lanes_pk<L, true>) \
+                      X(wedm_step_lanes_pk<L, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true>)
+// part 4: stencil_mode 1 on kernel 2 <L, TRACE, F64 = true> and on the stream kernel's single-microsecond instantiation
+// <L, false, 64, ONE = true, F64 = true>; the register kernel <128, L, TRACE, F64 = true> and its PULSE form; the wide
+// register kernel <16, L, CUT, TRACE, F64 = true, MINB> (a traced launch runs the CUT form, as in float32; MINB = 1 for a
+// batch of one wave per SIMD, 2 beyond) and its PULSE forms
+#define WEDM_P4(X, L) X(wedm_step_lanes_pk<L, false, true>) X(wedm_step_lanes_pk<L, true, true>) \
+                      X(wedm_step_stream<L, false, 64, true, true>)
+#define WEDM_P4_REGS(X, L) X(wedm_step_regs<128, L, false, true>) X(wedm_step_regs<128, L, true, true>) \
+                           X(wedm_step_regs<128, L, false, false, true>)
+#define WEDM_P4_WIDE_F64(X, L, mb) X(wedm_step_regs_wide<16, L, false, false, true, mb>) \
+                                   X(wedm_step_regs_wide<16, L, true, false, true, mb>) X(wedm_step_regs_wide<16, L, true, true, true, mb>)
+#define WEDM_P4_WIDE(X, L) WEDM_P4_WIDE_F64(X, L, 1) WEDM_P4_WIDE_F64(X, L, 2)                                \
+                           X(wedm_step_regs_wide<16, L, false, false, false, WEDM_WIDE_MIN_BLOCKS, true>) \
+                           X(wedm_step_regs_wide<16, L, true, false, false, WEDM_WIDE_MIN_BLOCKS, true>)
+#define WEDM_PART1_LIST(X) WEDM_L4(WEDM_P1, X)
+#define WEDM_PART2_LIST(X) WEDM_L5(WEDM_P2, X)
+#define WEDM_PART3_LIST(X) WEDM_L5(WEDM_P3, X) X(wedm_step_served<4, false>) X(wedm_step_served<4, true>)     \
+                           X(wedm_step_served<8, false>) X(wedm_step_served<8, true>) X(wedm_step_lanes_served<4>) \
+                           X(wedm_step_lanes_served<8>) X(wedm_step_lanes_served<16>) X(wedm_step_regs_served<128>)
+#define WEDM_PART4_LIST(X) WEDM_L5(WEDM_P4, X) WEDM_P4_REGS(X, 1) WEDM_P4_REGS(X, 2) \
+                           WEDM_P4_WIDE(X, 4) WEDM_P4_WIDE(X, 8) WEDM_P4_WIDE(X, 16)
+#define WEDM_INST(...) template __global__ void __VA_ARGS__(const KArgs);
+#define WEDM_EXT(...) extern template __global__ void __VA_ARGS__(const KArgs);
 #if defined(WEDM_PART) && WEDM_PART == 1
-WEDM_PACKED_LIST(WEDM_INST_PACKED)
+WEDM_PART1_LIST(WEDM_INST)
 #elif defined(WEDM_PART) && WEDM_PART == 2
-WEDM_FUSED_LIST(WEDM_INST_FUSED)
-WEDM_FUSED_F64_LIST(WEDM_INST_FUSED_F64)
+WEDM_PART2_LIST(WEDM_INST)
 #elif defined(WEDM_PART) && WEDM_PART == 3
-WEDM_SERVED_LIST(WEDM_INST_SERVED)
-WEDM_INST_REGS_SERVED
-WEDM_LANES_PK_LIST(WEDM_INST_LANES_PK)
-WEDM_LANES_SERVED_LIST(WEDM_INST_LANES_SERVED)
-WEDM_LANES_PK_PULSE_LIST(WEDM_INST_LANES_PK_PULSE)
-WEDM_LANES_PK_ENVP_LIST(WEDM_INST_LANES_PK_ENVP)
+WEDM_PART3_LIST(WEDM_INST)
 #elif defined(WEDM_PART) && WEDM_PART == 4
-WEDM_REGS_F64_LIST(WEDM_INST_REGS_F64)
-WEDM_WIDE_F64_LIST(WEDM_INST_WIDE_F64)
-WEDM_LANES_PK_LIST(WEDM_INST_LANES_PK_F64)
-WEDM_STREAM_F64_LIST(WEDM_INST_STREAM_F64)
-WEDM_REGS_PULSE_LIST(WEDM_INST_REGS_PULSE)
-WEDM_WIDE_PULSE_LIST(WEDM_INST_WIDE_PULSE)
+WEDM_PART4_LIST(WEDM_INST)
 #else
 #if defined(WEDM_PART)
-WEDM_PACKED_LIST(WEDM_EXT_PACKED)
-WEDM_FUSED_LIST(WEDM_EXT_FUSED)
-WEDM_FUSED_F64_LIST(WEDM_EXT_FUSED_F64)
-WEDM_SERVED_LIST(WEDM_EXT_SERVED)
-WEDM_EXT_REGS_SERVED
-WEDM_REGS_F64_LIST(WEDM_EXT_REGS_F64)
-WEDM_WIDE_F64_LIST(WEDM_EXT_WIDE_F64)
-WEDM_LANES_PK_LIST(WEDM_EXT_LANES_PK)
-WEDM_LANES_PK_LIST(WEDM_EXT_LANES_PK_F64)
-WEDM_STREAM_F64_LIST(WEDM_EXT_STREAM_F64)
-WEDM_LANES_SERVED_LIST(WEDM_EXT_LANES_SERVED)
-WEDM_LANES_PK_PULSE_LIST(WEDM_EXT_LANES_PK_PULSE)
-WEDM_REGS_PULSE_LIST(WEDM_EXT_REGS_PULSE)
-WEDM_WIDE_PULSE_LIST(WEDM_EXT_WIDE_PULSE)
-WEDM_LANES_PK_ENVP_LIST(WEDM_EXT_LANES_PK_ENVP)
+WEDM_PART1_LIST(WEDM_EXT)
+WEDM_PART2_LIST(WEDM_EXT)
+WEDM_PART3_LIST(WEDM_EXT)
+WEDM_PART4_LIST(WEDM_EXT)
 #endif
 
 __global__ void __launch_bounds__(256)
@@ -264,6 +224,23 @@ struct LaunchPlan {
     char name[160] = {0};
 };
 
+// kernel numbers of wedm_set_kernel (include/wedm_hip.h; the ABI carries them as int32_t)
+enum Kernel : int32_t {
+    K_AUTO = 0, K_GLOBAL = 1, K_LANES_PK = 2, K_FUSED = 3, K_PACKED = 4, K_SPLIT = 5, K_STREAM = 6, K_REGS = 7, K_WIDE = 8,
+    K_SERVED = 9, K_LANES = 10, K_LANES_SERVED = 11, K_REGS_SERVED = 12
+};
+
+// What the planner knows of a walk table (wedm_create builds them; wedm_ctx::walk_dev holds the tables, same index).
+struct WalkInfo {
+    bool ok = false;      // built: the chunk and its halo row fit WEDM_MAX_C
+    int32_t C = 0;        // cells per chunk
+    uint32_t kind_s = 0;  // tiles with several flag changes (the stream kernel's register walk has no code for them)
+    bool n1z = false;     // a one-change tile with a zone change (see WalkTable::kind_n1_mask)
+};
+// walk table indices: L = 1, 2, 4, 8, 16 chunks (LDS kernels) from W_LDS, the same with chunks of whole 16-byte words (stream
+// kernel) from W_STREAM, two chunks of exactly 64 cells and four of 32 (register kernels)
+enum : int { W_LDS = 0, W_STREAM = 5, W_REGS2 = 10, W_REGS4 = 11, W_COUNT = 12 };
+
 struct wedm_ctx {
     wedm_params p;
     int32_t num_envs = 0, n_seg_max = 0;
@@ -276,17 +253,10 @@ struct wedm_ctx {
     Tables tb{};
     int32_t variant = 0;
     int32_t lanes = 0;                 // lanes per environment for the fused kernel (0 = auto)
-    bool auto_prefers_packed = true;
     unsigned long long* dbg = nullptr; // diagnostic builds: phase stamp buffer
     int lds_limit = 0;
-    WalkTable* walk_dev = nullptr;     // [11] tables for L = 1, 2, 4, 8, 16; the same with chunks of whole 16-byte words (stream kernel); two chunks of 64 cells (register kernel)
-    bool walk_ok[5] = {false, false, false, false, false};
-    int32_t walk_C[5] = {0, 0, 0, 0, 0};
-    bool walk4_ok[5] = {false, false, false, false, false};
-    bool walk_regs_ok = false;
-    int32_t walk4_C[5] = {0, 0, 0, 0, 0};
-    uint32_t walk4_kind_s[5] = {0u, 0u, 0u, 0u, 0u};  // tiles with several flag changes (the stream kernel's register walk has no code for them)
-    uint32_t walk_n1z = 0;             // bit i: table i has a one-change tile with a zone change (see WalkTable::kind_n1_mask)
+    WalkTable* walk_dev = nullptr;     // [W_COUNT] walk tables (uniform geometry only)
+    WalkInfo walk[W_COUNT];
     // signal trace (wedm_bind_trace): descriptor, microseconds stepped and samples written since the bind
     const double* replay = nullptr;    // wedm_bind_rng_replay
     int64_t replay_steps = 0;
@@ -390,81 +360,6 @@ static bool build_walk(const wedm_params& p, int L, WalkTable& t, int align = 1)
     return true;
 }
 
-template <bool TR, bool F64> static const void* pick_lanes(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_lanes<1, TR, F64>;
-        case 2: return (const void*)wedm_step_lanes<2, TR, F64>;
-        case 4: return (const void*)wedm_step_lanes<4, TR, F64>;
-        case 8: return (const void*)wedm_step_lanes<8, TR, F64>;
-        default: return (const void*)wedm_step_lanes<16, TR, F64>;
-    }
-}
-template <bool TR, bool FZ, bool N1> static const void* pick_fused(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_fused<1, TR, FZ, N1>;
-        case 2: return (const void*)wedm_step_fused<2, TR, FZ, N1>;
-        case 4: return (const void*)wedm_step_fused<4, TR, FZ, N1>;
-        case 8: return (const void*)wedm_step_fused<8, TR, FZ, N1>;
-        default: return (const void*)wedm_step_fused<16, TR, FZ, N1>;
-    }
-}
-template <bool TR, bool FZ> static const void* pick_fused(int L, bool n1) {
-    return n1 ? pick_fused<TR, FZ, true>(L) : pick_fused<TR, FZ, false>(L);
-}
-template <bool TR> static const void* pick_fused_f64(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_fused<1, TR, true, false, true>;
-        case 2: return (const void*)wedm_step_fused<2, TR, true, false, true>;
-        case 4: return (const void*)wedm_step_fused<4, TR, true, false, true>;
-        case 8: return (const void*)wedm_step_fused<8, TR, true, false, true>;
-        default: return (const void*)wedm_step_fused<16, TR, true, false, true>;
-    }
-}
-// rows a lane of the stream kernel holds in registers: 64 (128 segments over 2 lanes, 400 over 8) or 104 (400 over 4)
-template <bool TR, int CMAX, bool ONE = false, bool F64 = false> static const void* pick_stream(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_stream<1, TR, CMAX, ONE, F64>;
-        case 2: return (const void*)wedm_step_stream<2, TR, CMAX, ONE, F64>;
-        case 4: return (const void*)wedm_step_stream<4, TR, CMAX, ONE, F64>;
-        case 8: return (const void*)wedm_step_stream<8, TR, CMAX, ONE, F64>;
-        default: return (const void*)wedm_step_stream<16, TR, CMAX, ONE, F64>;
-    }
-}
-template <bool TR, bool FZ, bool EX> static const void* pick_packed(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_packed<1, TR, FZ, EX>;
-        case 2: return (const void*)wedm_step_packed<2, TR, FZ, EX>;
-        case 4: return (const void*)wedm_step_packed<4, TR, FZ, EX>;
-        default: return (const void*)wedm_step_packed<8, TR, FZ, EX>;
-    }
-}
-template <bool TR, bool FZ> static const void* pick_packed(int L, bool extra) {
-    return extra ? pick_packed<TR, FZ, true>(L) : pick_packed<TR, FZ, false>(L);
-}
-
-template <bool TR, bool F64 = false, bool PULSE = false, bool ENVP = false> static const void* pick_lanes_pk(int L) {
-    switch (L) {
-        case 1: return (const void*)wedm_step_lanes_pk<1, TR, F64, PULSE, ENVP>;
-        case 2: return (const void*)wedm_step_lanes_pk<2, TR, F64, PULSE, ENVP>;
-        case 4: return (const void*)wedm_step_lanes_pk<4, TR, F64, PULSE, ENVP>;
-        case 8: return (const void*)wedm_step_lanes_pk<8, TR, F64, PULSE, ENVP>;
-        default: return (const void*)wedm_step_lanes_pk<16, TR, F64, PULSE, ENVP>;
-    }
-}
-// kernel 1 with per-environment physics rows (wedm_bind_env_params): injected variates / stencil_mode 1 / the float32 stencil,
-// with or without a trace sample and pulse statistics
-template <bool PU> static const void* pick_global_envp(bool replay, bool f64, bool tr) {
-    if (replay) return tr ? (const void*)wedm_step_global<true, false, true, PU, true> : (const void*)wedm_step_global<false, false, true, PU, true>;
-    if (f64) return tr ? (const void*)wedm_step_global<true, true, false, PU, true> : (const void*)wedm_step_global<false, true, false, PU, true>;
-    return tr ? (const void*)wedm_step_global<true, false, false, PU, true> : (const void*)wedm_step_global<false, false, false, PU, true>;
-}
-static const void* pick_served(int L, bool extra) {
-    switch (L) {
-        case 4: return extra ? (const void*)wedm_step_served<4, true> : (const void*)wedm_step_served<4, false>;
-        default: return extra ? (const void*)wedm_step_served<8, true> : (const void*)wedm_step_served<8, false>;
-    }
-}
-
 // A handle belongs to the device that was current in wedm_create: its parameter / table / walk buffers
 // live there and its launches must go to a stream of that device.  Launching with another device
 // current would hand hipLaunchKernel a foreign stream (hipErrorInvalidResourceHandle at best).
@@ -480,423 +375,443 @@ static int32_t check_device(wedm_ctx* ctx, const char* who) {
 
 static int lanes_index(int L) { return L == 1 ? 0 : L == 2 ? 1 : L == 4 ? 2 : L == 8 ? 3 : L == 16 ? 4 : -1; }
 
-// What wedm_step launches for (single microsecond?, trace point?) under the handle's current settings: decided once
-// and cached (the decision walks a cost model over five lane counts; on the one-launch-per-microsecond path that and
-// a hipFuncSetAttribute per call were a measurable part of the host time per launch).
-static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, LaunchPlan& out) {
+// blocks of `per_block` environments that cover the batch
+static int blocks(int64_t num_envs, int per_block) { return (int)((num_envs + per_block - 1) / per_block); }
+
+// ------------------------------------------------------------ per-family fits: the LDS image in bytes (0: it does not fit)
+// and the lanes per environment, each written once for the choice and the launch
+static size_t fits(const wedm_ctx* c, size_t bytes) { return bytes <= (size_t)c->lds_limit ? bytes : 0; }
+// a walk table of L chunks from `base` (W_LDS, W_STREAM), or nullptr
+static const WalkInfo* walk_of(const wedm_ctx* c, int base, int L) {
+    const int i = lanes_index(L);
+    return i >= 0 && c->walk[base + i].ok ? &c->walk[base + i] : nullptr;
+}
+// kernel 3 (fused): one chunk of the L-chunk table per lane, + the halo row
+static size_t fused_lds(const wedm_ctx* c, int L) {
+    const WalkInfo* w = walk_of(c, W_LDS, L);
+    return w ? fits(c, ((size_t)w->C + 1) * 1024) : 0;
+}
+// kernel 4 (packed): two chunks per lane, the table of 2L chunks
+static size_t packed_lds(const wedm_ctx* c, int L) {
+    const WalkInfo* w = walk_of(c, W_LDS, 2 * L);
+    return w ? fits(c, (2 * (size_t)w->C + 2) * 1024) : 0;
+}
+// tables with a one-change boundary tile or a 1- / 2-cell tail: the EXTRA instantiation of kernels 4 and 9
+static bool walk_extra(const WalkInfo* w) { return w->n1z || (w->C > 8 && (w->C & 7) >= 1 && (w->C & 7) <= 2); }
+// kernel 9 (served): kernel 4's image staged by three walker waves, + the scalar wave's box of 48 / 24 environments
+static size_t served_lds(const wedm_ctx* c, int L) {
+    const WalkInfo* w = walk_of(c, W_LDS, 2 * L);
+    return w ? fits(c, (2 * (size_t)w->C + 2) * 768 + (L == 8 ? sizeof(ServedBox<24>) : sizeof(ServedBox<48>))) : 0;
+}
+// kernel 6 (stream): the table of L chunks of whole 16-byte words, + the halo row
+static size_t stream_lds(const wedm_ctx* c, int L) {
+    const WalkInfo* w = walk_of(c, W_STREAM, L);
+    return w ? fits(c, ((size_t)w->C + 1) * 1024) : 0;
+}
+// kernel 10 (lanes, any geometry): a chunk of ceil(n_seg_max / L) cells per lane
+static size_t lanes_lds(const wedm_ctx* c, int L) { return fits(c, (size_t)((c->n_seg_max + L - 1) / L) * 1024); }
+// kernel 2 (lanes_pk, either typing of the stencil): two virtual chunks of ceil(n_seg_max / 2L) cells per lane
+static size_t lanes_pk_rows(const wedm_ctx* c, int L) { return 2 * (size_t)((c->n_seg_max + 2 * L - 1) / (2 * L)) + 2; }
+static size_t lanes_pk_lds(const wedm_ctx* c, int L) { return fits(c, lanes_pk_rows(c, L) * 1024); }
+// kernel 11 (lanes_served): those rows staged by three walker waves, + the scalar wave's box of 192 / L environments (the
+// lane choice sizes the box for 48 whatever L)
+static size_t lanes_served_lds(const wedm_ctx* c, int L, bool choice = false) {
+    const size_t box = (L == 4 || choice) ? sizeof(ServedBox<48>) : L == 8 ? sizeof(ServedBox<24>) : sizeof(ServedBox<12>);
+    return fits(c, lanes_pk_rows(c, L) * 768 + box);
+}
+
+// The lanes per environment of kernels 2, 10 and 11: the caller's count if its image fits, else the smallest L of `Ls`
+// whose image fits, raised until `fills(c, L, image)` says the launch fills the chip; 0 if none fits.
+template <class Image, class Fills>
+static int fit_lanes(const wedm_ctx* c, std::initializer_list<int> Ls, Image image, Fills fills) {
+    int lanes = 0;
+    for (const int L : Ls) {
+        const size_t b = image(c, L);
+        if (!b) continue;
+        if (c->lanes) { if (L == c->lanes) lanes = L; continue; }
+        lanes = L;
+        if (fills(c, L, b)) break;
+    }
+    return lanes;
+}
+// ~2 waves per SIMD (blocks of 256 lanes)
+static bool fills_waves(const wedm_ctx* c, int L, size_t) { return (long)blocks(c->num_envs, 256 / L) * 4 >= 2048; }
+
+static bool uniform_geometry(const wedm_ctx* c) { return !c->p.per_env_geometry && c->walk_dev; }
+
+// kernel 6 (stream, single microseconds, uniform geometry): the caller's lane count, else -- among the L whose chunk
+// has at most 64 cells (the registers a lane holds its chunk in) -- the largest one whose blocks are all resident at
+// once (2 048 waves): a launch of one microsecond is one dependent chain per wave, and a shorter chunk is a shorter
+// chain (4 096 x 400: 26.3 / 18.8 / 14.4 us with 4 / 8 / 16 lanes); a batch too large for one round takes the
+// smallest such L (65 536 x 128: 2 lanes); failing all that a chunk of at most 104 cells
+static int stream_lanes(const wedm_ctx* c) {
+    if (!uniform_geometry(c) || (uint64_t)WEDM_T_QUADS(c->n_seg_max) * (uint64_t)c->s.stride * 16ull >= (1ull << 32)) return 0;
+    for (const int cmax : {64, 104}) {
+        int lanes = 0;
+        for (const int L : {1, 2, 4, 8, 16}) {
+            if (!stream_lds(c, L) || walk_of(c, W_STREAM, L)->C > cmax) continue;
+            if (c->lanes && L != c->lanes) continue;
+            if (lanes && (cmax > 64 || (long)blocks(c->num_envs, 256 / L) * 4 > 2048)) break;
+            lanes = L;
+        }
+        if (lanes) return lanes;
+    }
+    return 0;
+}
+
+// kernel 8 (wide register kernel): 4, 8 or 16 lanes per environment (the fewest that hold the wire, or the caller's if they
+// do), 32 cells each in registers; uniform geometry, 9 to 512 segments; 0 where it cannot run
+static int wide_lanes(const wedm_ctx* c) {
+    const wedm_params& P = c->p;
+    const int wl_min = P.n_seg <= 128 ? 4 : P.n_seg <= 256 ? 8 : 16;
+    const int wl = (c->lanes == 4 || c->lanes == 8 || c->lanes == 16) ? c->lanes : wl_min;
+    const bool ok = uniform_geometry(c) && P.n_seg >= 9 && P.n_seg <= 512 && !c->replay && (c->lanes == 0 || (wl == c->lanes && wl >= wl_min));
+    return ok ? wl : 0;
+}
+
+// kernel 7 (register kernel): one or two lanes per environment (default 2: two waves per SIMD) with the wire in their
+// registers; wires of at most 128 segments, uniform geometry; 0 where it cannot run
+static int regs_lanes(const wedm_ctx* c) {
+    const bool ok = uniform_geometry(c) && c->walk[W_REGS2].ok && c->walk[W_REGS4].ok && c->n_seg_max <= 128 && !c->replay;
+    return ok ? (c->lanes == 1 ? 1 : 2) : 0;
+}
+
+// tiles a chunk of C cells costs: its full tiles, a whole tile for a partial one, a quarter for a 1- / 2-cell tail
+// (computed with the patched cells) -- 32 768 x 400: fused<8> 3.60e9, packed<8> 3.75e9 measured
+static double eff_tiles(int C) {
+    const int rest = C & 7;
+    return (double)(C / 8) + (rest == 0 ? 0.0 : (C > 8 && rest <= 2) ? 0.25 : 1.0);
+}
+
+// kernel 9 (served packed kernel, wedm_served.h): the packed walk on three waves of a block, the scalar physics on the fourth;
+// 4 or 8 lanes per environment.  Cost model (cycles per microsecond of the whole batch, same unit as the model of kernels
+// 3 / 4; fitted to profiles/r4/plan_sweep.txt): a block's chain c = 1300 + 950 x tiles per lane; j blocks resident together
+// on a CU take c x f(j), f = 1, 1.49, 1.80 (three fit the 168-register budget, fewer where the LDS image is large); blocks
+// are dispatched as CUs free up, so the busiest CU runs b = ceil(blocks / 256) of them in groups of at most `rb`.
+static double served_cost(const wedm_ctx* c, int L) {
+    const size_t lds = served_lds(c, L);
+    if (!lds) return 1e300;
+    const long rb = std::min<long>(3, (long)(160 * 1024 / lds));
+    const long b = (blocks(c->num_envs, 192 / L) + 255) / 256;
+    static const double f[4] = {0.0, 1.0, 1.49, 1.80};
+    // (a partial tile of 3 ... 7 cells runs the boundary-tile code for every lane: two tiles' worth -- 16 384 x 200 over 8 lanes,
+    // chunks of 13 cells: 5.3 ms against 3.4 ms over 4 lanes)
+    const int Cv = walk_of(c, W_LDS, 2 * L)->C, rest = Cv & 7;
+    const double tiles = eff_tiles(Cv) + ((rest >= 3 || (rest && Cv < 8)) ? 1.0 : 0.0);
+    const double cc = 1300.0 + 950.0 * tiles;
+    return (double)(b / rb) * cc * f[rb] + ((b % rb) ? cc * f[b % rb] : 0.0);
+}
+// the served kernel's lanes: the caller's 4 or 8, else the cheaper by the model; 0 where it cannot run
+static int served_lanes(const wedm_ctx* c) {
+    const int L = (c->lanes == 4 || c->lanes == 8) ? c->lanes : (served_cost(c, 4) < served_cost(c, 8) ? 4 : 8);
+    const bool ok = uniform_geometry(c) && c->p.stencil_mode == 0 && !c->replay && !c->p.keep_stepping_terminated &&
+                    (c->lanes == 0 || c->lanes == L) && served_lds(c, L);
+    return ok ? L : 0;
+}
+
+// forms of a family beyond the float32 stencil: the kernels with a float64-typed (stencil_mode 1), a pulse-counting
+// (wedm_bind_pulse_stats) and a per-environment-rows (wedm_bind_env_params) instantiation
+static constexpr uint32_t kernels(std::initializer_list<Kernel> ks) {
+    uint32_t m = 0;
+    for (const Kernel k : ks) m |= 1u << k;
+    return m;
+}
+static constexpr uint32_t F64_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_FUSED, K_STREAM, K_REGS, K_WIDE, K_LANES});
+static constexpr uint32_t PULSE_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_REGS, K_WIDE});
+static constexpr uint32_t ENVP_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK});
+
+struct Choice {
+    Kernel kernel = K_AUTO;
+    int lanes = 0;  // lanes per environment (0: the family has no such choice)
+};
+
+// The kernel wedm_step launches for (single microsecond?, trace point?) under the handle's settings, and its lanes per
+// environment; every refusal of a forced kernel or of a binding it has no form for.
+static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     const wedm_params& P = ctx->p;
+    const bool uniform = uniform_geometry(ctx), f64 = P.stencil_mode != 0, replay = ctx->replay != nullptr;
+    const bool pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
     // kernel 3 (one chunk per lane) and kernel 4 (two packed chunks per lane, table of 2L chunks).
     // Auto-selection by a small cost model fitted to measurements:
-    //   cycles per step ~ rounds * (4500 + tiles_per_lane * 8 * cell_cost),  tiles_per_lane: see eff_tiles below,
+    //   cycles per step ~ rounds * (4500 + tiles_per_lane * 8 * cell_cost),  tiles_per_lane: see eff_tiles,
     //   rounds = ceil(blocks / (256 CUs * resident blocks per CU)), resident = min(2 [VGPRs], LDS fit),
     //   cell_cost = 90 per cell, a packed pair = 2 * 90 * 0.93.
-    const bool uniform = !ctx->p.per_env_geometry && ctx->walk_dev;
-    int lanes = ctx->lanes, planes = ctx->lanes;
-    // tiles a chunk of C cells costs: its full tiles, a whole tile for a partial one, a quarter for a 1- / 2-cell tail
-    // (computed with the patched cells) -- 32 768 x 400: fused<8> 3.60e9, packed<8> 3.75e9 measured
-    auto eff_tiles = [](int C) -> double {
-        const int rest = C & 7;
-        return (double)(C / 8) + (rest == 0 ? 0.0 : (C > 8 && rest <= 2) ? 0.25 : 1.0);
-    };
-    double best_lds_cost = 1e300;  // cycles per microsecond of the whole batch on the better of kernels 3 / 4, by the model above
-    {
-        double best3 = 1e300, best4 = 1e300;
-        int l3 = 0, l4 = 0;
-        const int Ls[5] = {1, 2, 4, 8, 16};
-        for (int i = 0; i < 5 && uniform; ++i) {
-            const int Lc = Ls[i];
-            const long blocks = (ctx->num_envs + (256 / Lc) - 1) / (256 / Lc);
-            if (ctx->walk_ok[i]) {  // kernel 3 with Lc lanes: table i
-                const size_t lds = ((size_t)ctx->walk_C[i] + 1) * 1024;
-                if (lds <= (size_t)ctx->lds_limit) {
-                    const long rb = std::min<long>(2, (long)(160 * 1024 / lds));
-                    const long rounds = (blocks + 256 * rb - 1) / (256 * rb);
-                    const double cost = rounds * (4500.0 + eff_tiles(ctx->walk_C[i]) * 8 * 90.0);
-                    if (cost < best3) { best3 = cost; l3 = Lc; }
-                }
-            }
-            if (Lc <= 8 && ctx->walk_ok[lanes_index(2 * Lc)]) {  // kernel 4 with Lc lanes: table of 2*Lc chunks
-                const int ti = lanes_index(2 * Lc);
-                const size_t lds = (2 * (size_t)ctx->walk_C[ti] + 2) * 1024;
-                if (lds <= (size_t)ctx->lds_limit) {
-                    const long rb = std::min<long>(2, (long)(160 * 1024 / lds));
-                    const long rounds = (blocks + 256 * rb - 1) / (256 * rb);
-                    const double cost = rounds * (4500.0 + eff_tiles(ctx->walk_C[ti]) * 8 * 2 * 90.0 * 0.93);
-                    if (cost < best4) { best4 = cost; l4 = Lc; }
-                }
-            }
+    double best3 = 1e300, best4 = 1e300;  // cycles per microsecond of the whole batch, by the model above
+    int l3 = 0, l4 = 0;
+    for (const int L : {1, 2, 4, 8, 16}) {
+        if (!uniform) break;
+        const long nb = blocks(ctx->num_envs, 256 / L);
+        auto rounds = [&](size_t lds) {
+            const long rb = std::min<long>(2, (long)(160 * 1024 / lds));
+            return (nb + 256 * rb - 1) / (256 * rb);
+        };
+        if (const size_t lds = fused_lds(ctx, L)) {
+            const double cost = rounds(lds) * (4500.0 + eff_tiles(walk_of(ctx, W_LDS, L)->C) * 8 * 90.0);
+            if (cost < best3) { best3 = cost; l3 = L; }
         }
-        if (!lanes) lanes = l3;
-        if (!planes) planes = l4;
-        ctx->auto_prefers_packed = best4 <= best3;
-        best_lds_cost = std::min(best3, best4);
-    }
-    const int li = lanes_index(lanes);
-    const bool fused_ok = uniform && li >= 0 && ctx->walk_ok[li] &&
-                          ((size_t)ctx->walk_C[li] + 1) * 1024 <= (size_t)ctx->lds_limit;
-    const int pli = (planes >= 1 && planes <= 8) ? lanes_index(2 * planes) : -1;
-    const bool packed_ok = uniform && pli >= 0 && ctx->walk_ok[pli] &&
-                           (2 * (size_t)ctx->walk_C[pli] + 2) * 1024 <= (size_t)ctx->lds_limit;
-    // kernel 2 (any geometry): lanes per environment = the caller's choice, else the smallest L whose
-    // chunk fits in LDS, raised until the launch has ~2 waves per SIMD
-    int glanes = 0;
-    {
-        const int Ls[5] = {1, 2, 4, 8, 16};
-        for (int i = 0; i < 5; ++i) {
-            const size_t b = (size_t)((ctx->n_seg_max + Ls[i] - 1) / Ls[i]) * 1024;
-            if (b > (size_t)ctx->lds_limit) continue;
-            if (ctx->lanes) { if (Ls[i] == ctx->lanes) glanes = Ls[i]; continue; }
-            glanes = Ls[i];
-            const long waves = (long)((ctx->num_envs + (256 / Ls[i]) - 1) / (256 / Ls[i])) * 4;
-            if (waves >= 2048) break;
+        if (const size_t lds = packed_lds(ctx, L)) {
+            const double cost = rounds(lds) * (4500.0 + eff_tiles(walk_of(ctx, W_LDS, 2 * L)->C) * 8 * 2 * 90.0 * 0.93);
+            if (cost < best4) { best4 = cost; l4 = L; }
         }
     }
+    const int lanes = ctx->lanes ? ctx->lanes : l3, planes = ctx->lanes ? ctx->lanes : l4;
+    const bool fused_ok = uniform && fused_lds(ctx, lanes), packed_ok = uniform && packed_lds(ctx, planes);
+    // kernel 10 (any geometry) and kernel 2, its packed form: the smallest L whose chunk fits in LDS, raised until the
+    // launch has ~2 waves per SIMD
+    const int glanes = fit_lanes(ctx, {1, 2, 4, 8, 16}, lanes_lds, fills_waves);
+    const int pklanes = fit_lanes(ctx, {1, 2, 4, 8, 16}, lanes_pk_lds, fills_waves);
     const bool lanes_ok = glanes > 0;
-    // ... and its packed form (wedm_step_lanes_pk, either typing of the stencil): two virtual chunks of ceil(n_seg_max / 2L) cells per lane
-    int pklanes = 0;
-    {
-        const int Ls[5] = {1, 2, 4, 8, 16};
-        for (int i = 0; i < 5; ++i) {
-            const size_t b = (2 * (size_t)((ctx->n_seg_max + 2 * Ls[i] - 1) / (2 * Ls[i])) + 2) * 1024;
-            if (b > (size_t)ctx->lds_limit) continue;
-            if (ctx->lanes) { if (Ls[i] == ctx->lanes) pklanes = Ls[i]; continue; }
-            pklanes = Ls[i];
-            const long waves = (long)((ctx->num_envs + (256 / Ls[i]) - 1) / (256 / Ls[i])) * 4;
-            if (waves >= 2048) break;
-        }
-    }
-    const bool lanes_pk_ok = pklanes > 0;
-    // ... and the served form of that (wedm_step_lanes_served: 4, 8 or 16 lanes per environment, three walker waves + the scalar
-    // wave per block, three blocks per CU where the LDS image allows): the caller's lane count, else the fewest lanes whose
-    // blocks fill the chip at three per CU
-    int svgl = 0;
-    {
-        const int Ls[3] = {4, 8, 16};
-        for (int i = 0; i < 3; ++i) {
-            const size_t b = (2 * (size_t)((ctx->n_seg_max + 2 * Ls[i] - 1) / (2 * Ls[i])) + 2) * 768 + sizeof(ServedBox<48>);
-            if (b > (size_t)ctx->lds_limit) continue;
-            if (ctx->lanes) { if (Ls[i] == ctx->lanes) svgl = Ls[i]; continue; }
-            svgl = Ls[i];
-            const long blocks = (ctx->num_envs + (192 / Ls[i]) - 1) / (192 / Ls[i]);
-            if (blocks >= 768 && 3 * b <= 160 * 1024) break;
-        }
-    }
-    const bool lanes_sv_ok = svgl > 0 && !ctx->replay && P.stencil_mode == 0 && !P.keep_stepping_terminated;
-    // kernel 6 (stream, single microseconds, uniform geometry): the caller's lane count, else -- among the L whose chunk
-    // has at most 64 cells (the registers a lane holds its chunk in) -- the largest one whose blocks are all resident at
-    // once (2 048 waves): a launch of one microsecond is one dependent chain per wave, and a shorter chunk is a shorter
-    // chain (4 096 x 400: 26.3 / 18.8 / 14.4 us with 4 / 8 / 16 lanes); a batch too large for one round takes the
-    // smallest such L (65 536 x 128: 2 lanes); failing all that a chunk of at most 104 cells
-    int slanes = 0;
-    if (uniform && (uint64_t)WEDM_T_QUADS(ctx->n_seg_max) * (uint64_t)ctx->s.stride * 16ull < (1ull << 32)) {
-        const int Ls[5] = {1, 2, 4, 8, 16};
-        for (int pass = 0; pass < 2 && !slanes; ++pass)
-            for (int i = 0; i < 5; ++i) {
-                if (!ctx->walk4_ok[i] || ctx->walk4_C[i] > (pass ? 104 : 64) ||
-                    ((size_t)ctx->walk4_C[i] + 1) * 1024 > (size_t)ctx->lds_limit) continue;
-                if (ctx->lanes && Ls[i] != ctx->lanes) continue;
-                const long waves = (long)((ctx->num_envs + (256 / Ls[i]) - 1) / (256 / Ls[i])) * 4;
-                if (slanes && (pass || waves > 2048)) break;
-                slanes = Ls[i];
-            }
-    }
-    const bool stream_ok = slanes > 0;
-    const bool stream_auto = stream_ok && ctx->walk4_C[lanes_index(slanes)] <= 64 &&
-                             (long)((ctx->num_envs + (256 / slanes) - 1) / (256 / slanes)) * 4 <= 2048;
-    int variant = ctx->variant;
-    if (ctx->replay) {
-        if (variant != 0 && variant != 1)
+    const bool use_pk = !replay && pklanes > 0;  // (kernel 2 is the packed form where it applies, both typings of the stencil)
+    // kernel 11 (wedm_step_lanes_served: 4, 8 or 16 lanes per environment, three walker waves + the scalar wave per block, three
+    // blocks per CU where the LDS image allows): the fewest lanes whose blocks fill the chip at three per CU
+    const int svgl = fit_lanes(ctx, {4, 8, 16}, [](const wedm_ctx* c, int L) { return lanes_served_lds(c, L, true); },
+                               [](const wedm_ctx* c, int L, size_t b) { return blocks(c->num_envs, 192 / L) >= 768 && 3 * b <= 160 * 1024; });
+    const bool lanes_sv_ok = svgl > 0 && !replay && !f64 && !P.keep_stepping_terminated;
+    const int slanes = stream_lanes(ctx), wl = wide_lanes(ctx), rl = regs_lanes(ctx), svl = served_lanes(ctx);
+    const int stream_C = slanes ? walk_of(ctx, W_STREAM, slanes)->C : 0;
+    const bool stream_auto = slanes && stream_C <= 64 && (long)blocks(ctx->num_envs, 256 / slanes) * 4 <= 2048;
+    // the stream kernel under stencil_mode 1: its single-microsecond instantiation only (chunks of at most 64 cells, no trace sample)
+    const bool stream_f64_ok = slanes && single && !tr && WEDM_STREAM_REGWALK && stream_C <= 64;
+    // kernel 8 by itself for a batch that one round of blocks covers at one wave per SIMD: such a launch is one wave's
+    // dependent chain per microsecond whatever the kernel, and this one's is the shortest (measured, 4 096 x 400 and
+    // 16 384 x 128: DESIGN.md 4.1b).  (stencil_mode 1, a short wire in a tiny batch: 256 waves of this kernel over 4 lanes
+    // against 1 024 of the tile walk over 16 -- 2.81 against 2.47 ms at 4 096 x 128, profiles/r4/plan_sweep_f64.txt)
+    const bool f64_tiny = f64 && P.n_seg <= 128 && ctx->num_envs <= 4096;
+    const bool wide_auto = !single && wl && !f64_tiny && ctx->lanes == 0 && (int64_t)ctx->num_envs * wl <= (int64_t)WEDM_WIDE_AUTO_MAX_LANES;
+    // kernel 7 for fused launches of a batch that gives most CUs a block of the register kernel (measured, 128 segments, two
+    // lanes per environment against the best LDS kernel: 8 192 environments 2.8e9 vs 3.5e9, 16 384: 5.5e9 vs 6.1e9,
+    // 24 576: 8.3e9 vs 7.4e9, 32 768: 1.10e10 vs 9.9e9, 65 536: 1.67e10 vs 1.44e10, 131 072: 1.76e10 vs 1.50e10;
+    // up to 16 384 environments the wide register kernel has taken the launch: 8.1e9 there)
+    // (stencil_mode 1: single microseconds too -- 34 us against the cell-by-cell LDS kernel's 44 at 65 536 x 128)
+    const bool regs_auto = (!single || f64) && rl && ctx->lanes == 0 && ctx->num_envs >= 20480;
+
+    // the caller's kernel, and what refuses it outright
+    int32_t forced = ctx->variant;
+    if (replay) {
+        if (forced != K_AUTO && forced != K_GLOBAL)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) run on kernel 1 only");
-        if (P.stencil_mode != 0)
-            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates and stencil_mode 1 cannot be combined");
-        variant = 1;
+        if (f64) return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates and stencil_mode 1 cannot be combined");
+        forced = K_GLOBAL;
     }
-    const int32_t forced = variant;  // (the caller's choice; with the pulse block bound only it counts, see below)
-    if (ctx->envp && forced != 0 && forced != 1 && forced != 2)
+    if (envp && !((ENVP_FORMS >> forced) & 1u))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound (wedm_bind_env_params) only kernels 0 (auto), 1 and 2 run");
-    const bool f64 = P.stencil_mode != 0;
     // Numba's typing of the stencil: the register kernels (uniform geometry; at most 128 / 512 segments), the fused tile walk
     // (uniform geometry), the predicated LDS kernel (any geometry), or in place in global memory; no packed LDS form, no served
     // form, no stream / split kernel
-    if (f64 && variant != 0 && variant != 1 && variant != 2 && variant != 3 && variant != 6 && variant != 7 && variant != 8 && variant != 10)
+    if (f64 && !((F64_FORMS >> forced) & 1u))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: stencil_mode 1 (float64 stencil expressions) runs on kernels 1, 2 (10), 3, 6 (single microseconds without a trace sample), 7 and 8 only");
-    // the stream kernel in that typing: its single-microsecond instantiation only (chunks of at most 64 cells, no trace sample)
-    const bool stream_f64_ok = stream_ok && single && !tr && WEDM_STREAM_REGWALK && ctx->walk4_C[lanes_index(slanes)] <= 64;
-    if (f64 && variant == 6 && !stream_f64_ok)
+    if (f64 && forced == K_STREAM && !stream_f64_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: under stencil_mode 1 the stream kernel runs launches of one microsecond without a trace sample, chunks of at most 64 cells");
-    // (by itself where the float32 launch takes it too and every tile of the table has register-walk code)
-    if (f64 && variant == 0 && stream_f64_ok && stream_auto && ctx->walk4_kind_s[lanes_index(slanes)] == 0u) variant = 6;
-    // kernel 2 is the packed form where it applies (no injected variates; under stencil_mode 1 the same walk with float64-typed
-    // cells); kernel 10 names the cell-by-cell form explicitly (A/B timing, tests)
-    const bool use_pk = !ctx->replay && lanes_pk_ok;  // (both typings of the stencil)
-    // kernel 8 (wide register kernel): 4, 8 or 16 lanes per environment (the fewest that hold the wire), 32 cells each in
-    // registers; uniform geometry, either typing of the stencil, at most 512 segments.  Chosen by itself for a batch
-    // that one round of blocks covers at one wave per
-    // SIMD: such a launch is one wave's dependent chain per microsecond whatever the kernel, and this one's is the
-    // shortest (measured, 4 096 x 400 and 16 384 x 128: DESIGN.md 4.1b)
-    const int wl_min = P.n_seg <= 128 ? 4 : P.n_seg <= 256 ? 8 : 16;
-    const int wl = (ctx->lanes == 4 || ctx->lanes == 8 || ctx->lanes == 16) ? ctx->lanes : wl_min;
-    const bool wide_ok = uniform && P.n_seg >= 9 && P.n_seg <= 512 && !ctx->replay &&
-                         (ctx->lanes == 0 || (wl == ctx->lanes && wl >= wl_min));
-    // (stencil_mode 1, a short wire in a tiny batch: 256 waves of this kernel over 4 lanes against 1 024 of the tile walk over 16 --
-    // 2.81 against 2.47 ms at 4 096 x 128, profiles/r4/plan_sweep_f64.txt)
-    const bool f64_tiny = f64 && P.n_seg <= 128 && ctx->num_envs <= 4096;
-    if (variant == 0 && !single && wide_ok && !f64_tiny && ctx->lanes == 0 &&
-        (int64_t)ctx->num_envs * wl <= (int64_t)WEDM_WIDE_AUTO_MAX_LANES)
-        variant = 8;
-    if (variant == 8 && !wide_ok)
+    if (forced == K_WIDE && !wl)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: wide register kernel needs uniform geometry, 9 to 512 segments and lanes 0, 4, 8 or 16 with 32 cells per lane covering the wire");
-    // kernel 7 (register kernel): one or two lanes per environment with the wire in their registers; wires of at most 128
-    // segments, uniform geometry, either typing of the stencil; a launch with a trace sample runs its TRACE instantiation
-    const bool regs_ok = uniform && ctx->walk_regs_ok && ctx->n_seg_max <= 128 && !ctx->replay;
-    if (variant == 0) {
-        // fused launches of a batch that gives most CUs a block of the register kernel (measured, 128 segments, two lanes
-        // per environment against the best LDS kernel: 8 192 environments 2.8e9 vs 3.5e9, 16 384: 5.5e9 vs 6.1e9,
-        // 24 576: 8.3e9 vs 7.4e9, 32 768: 1.10e10 vs 9.9e9, 65 536: 1.67e10 vs 1.44e10, 131 072: 1.76e10 vs 1.50e10;
-        // up to 16 384 environments the wide register kernel above has taken the launch: 8.1e9 there)
-        // (stencil_mode 1: single microseconds too -- 34 us against the cell-by-cell LDS kernel's 44 at 65 536 x 128)
-        if ((!single || f64) && regs_ok && ctx->lanes == 0 && ctx->num_envs >= 20480) variant = 7;
+    if (pulse && !((PULSE_FORMS >> forced) & 1u))
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
+
+    int32_t v = forced;
+    if (pulse || envp) {
+        // bound rows: the float32 stencil without a trace sample or injected variates runs the caller's kernel, and a fused
+        // launch under auto what the automatic choice takes among the forms there are (pulse: 8 or 7, else kernel 2's packed
+        // form; envp: kernel 2's packed form); every other launch runs kernel 1, and so does every launch with both bound
+        // (kernel 2's ENVP form counts no pulses)
+        const bool fast = !tr && !f64 && !replay;
+        v = fast ? forced : K_GLOBAL;
+        if (v == K_AUTO && !single) v = pulse && wide_auto ? K_WIDE : pulse && regs_auto ? K_REGS : use_pk ? K_LANES_PK : K_GLOBAL;
+        if (v == K_AUTO) v = K_GLOBAL;
+        if (v == K_LANES_PK && !use_pk && pulse)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+        if (v == K_LANES_PK && !use_pk)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+        if (envp && pulse) v = K_GLOBAL;
+    } else if (v == K_AUTO) {
+        // (stencil_mode 1, single microseconds: the stream kernel where the float32 launch takes it too and every tile of
+        // the table has register-walk code)
+        if (f64 && stream_f64_ok && stream_auto && walk_of(ctx, W_STREAM, slanes)->kind_s == 0u) v = K_STREAM;
+        else if (wide_auto) v = K_WIDE;
+        else if (regs_auto) v = K_REGS;
         // stencil_mode 1, longer wires, any batch: the wide register kernel (two blocks per CU beyond one wave per SIMD) -- 18 - 20
         // float64 operations per cell leave the LDS round trips of the tile walk nothing to hide behind (32 768 x 400: 1.93e9
         // against the fused kernel's 1.49e9; 8 192 x 400: 1.5e9 against 1.2e9 already at one block per CU)
-        if (variant == 0 && f64 && !single && wide_ok && !f64_tiny && ctx->lanes == 0) variant = 8;
-    }
-    // kernel 9 (served packed kernel, wedm_served.h): the packed walk on three waves of a block, the scalar physics on the fourth;
-    // 4 or 8 lanes per environment; no trace point and no keep_stepping_terminated (such launches stay on kernel 4).
-    // Cost model (cycles per microsecond of the whole batch, same unit as the model of kernels 3 / 4; fitted to
-    // profiles/r4/plan_sweep.txt): a block's chain c = 1300 + 950 x tiles per lane; j blocks resident together on a CU take
-    // c x f(j), f = 1, 1.49, 1.80 (three fit the 168-register budget, fewer where the LDS image is large); blocks are
-    // dispatched as CUs free up, so the busiest CU runs b = ceil(blocks / 256) of them in groups of at most `rb`.
-    auto served_cost = [&](int L) -> double {
-        const int ti = lanes_index(2 * L);
-        if (ti < 0 || !ctx->walk_ok[ti]) return 1e300;
-        const size_t lds = (2 * (size_t)ctx->walk_C[ti] + 2) * 768 + (L == 8 ? sizeof(ServedBox<24>) : sizeof(ServedBox<48>));
-        if (lds > (size_t)ctx->lds_limit) return 1e300;
-        const long rb = std::min<long>(3, (long)(160 * 1024 / lds));
-        const long blocks = (ctx->num_envs + (192 / L) - 1) / (192 / L);
-        const long b = (blocks + 255) / 256;
-        static const double f[4] = {0.0, 1.0, 1.49, 1.80};
-        // (a partial tile of 3 ... 7 cells runs the boundary-tile code for every lane: two tiles' worth -- 16 384 x 200 over 8 lanes,
-        // chunks of 13 cells: 5.3 ms against 3.4 ms over 4 lanes)
-        const int Cv = ctx->walk_C[ti], rest = Cv & 7;
-        const double tiles = eff_tiles(Cv) + ((rest >= 3 || (rest && Cv < 8)) ? 1.0 : 0.0);
-        const double c = 1300.0 + 950.0 * tiles;
-        return (double)(b / rb) * c * f[rb] + ((b % rb) ? c * f[b % rb] : 0.0);
-    };
-    const double sv_cost4 = served_cost(4), sv_cost8 = served_cost(8);
-    const int svl = (ctx->lanes == 4 || ctx->lanes == 8) ? ctx->lanes : (sv_cost4 < sv_cost8 ? 4 : 8);
-    const int svi = lanes_index(2 * svl);
-    const size_t sv_box = svl == 8 ? sizeof(ServedBox<24>) : sizeof(ServedBox<48>);  // three walker waves: 24 / 48 environments per block
-    const bool served_ok = uniform && !f64 && !ctx->replay && !P.keep_stepping_terminated && (ctx->lanes == 0 || ctx->lanes == svl) &&
-                           svi >= 0 && ctx->walk_ok[svi] &&
-                           (2 * (size_t)ctx->walk_C[svi] + 2) * 768 + sv_box <= (size_t)ctx->lds_limit;
-    // the served kernel where its model beats what the choice so far would take (measured over 2 048 ... 131 072 environments x
-    // 128 ... 512 segments, profiles/r4/plan_sweep.txt: blocks of 24 / 48 environments, three to a CU, fill the chip where
-    // blocks of 32 ... 128 leave a ragged second round, and a sixth fewer instructions)
-    if (!single && !tr && served_ok && ctx->lanes == 0 && P.n_seg <= 512 /* the range the model was fitted on */ &&
-        (variant == 0 || (variant == 7 && ctx->variant == 0))) {
-        const double sv = std::min(sv_cost4, sv_cost8);
-        double other = best_lds_cost;
-        if (variant == 7) {  // the two-lane register kernel: 128 environments per block, two blocks per CU (6 050 / 7 800 cycles)
-            const long b = ((ctx->num_envs + 127) / 128 + 255) / 256;
-            other = (double)(b / 2) * 7800.0 + (double)(b % 2) * 6050.0;
+        else if (f64 && !single && wl && !f64_tiny && ctx->lanes == 0) v = K_WIDE;
+        // the served kernel where its model beats what the choice so far would take (measured over 2 048 ... 131 072 environments x
+        // 128 ... 512 segments, profiles/r4/plan_sweep.txt: blocks of 24 / 48 environments, three to a CU, fill the chip where
+        // blocks of 32 ... 128 leave a ragged second round, and a sixth fewer instructions)
+        if (!single && !tr && svl && ctx->lanes == 0 && P.n_seg <= 512 /* the range the model was fitted on */ &&
+            (v == K_AUTO || v == K_REGS)) {
+            double other = std::min(best3, best4);
+            if (v == K_REGS) {  // the two-lane register kernel: 128 environments per block, two blocks per CU (6 050 / 7 800 cycles)
+                const long b = (blocks(ctx->num_envs, 128) + 255) / 256;
+                other = (double)(b / 2) * 7800.0 + (double)(b % 2) * 6050.0;
+            }
+            if (served_cost(ctx, svl) < other) v = K_SERVED;
         }
-        if (sv < other) variant = 9;
-    }
-    if (variant == 0) {
         // single-microsecond launches: the stream kernel where one round of blocks covers the batch with chunks of
         // at most 64 cells (measured: 27.5 vs 30.3 us at 65 536 x 128, 20.5 vs 24.9 us at 4 096 x 400), else the
         // split global-memory kernel (32.7 vs 48.9 us at 32 768 x 400, where the stream kernel needs two rounds)
-        if (f64) variant = (!single && fused_ok) ? 3 : ((lanes_ok || use_pk) ? 2 : 1);
-        else if (single) variant = (stream_ok && stream_auto) ? 6 : 5;
-        else if (packed_ok && (ctx->auto_prefers_packed || !fused_ok)) variant = 4;
-        else if (fused_ok) variant = 3;
-        else variant = (lanes_ok || use_pk) ? 2 : 1;
-    }
-    // pulse statistics bound (wedm_bind_pulse_stats): only kernels with a PULSE instantiation.  The fused launches of the float32
-    // stencil without a trace sample take what the automatic choice above takes where that is kernel 8 or 7, else kernel 2's
-    // packed form; everything else -- a trace sample in the launch, stencil_mode 1, injected variates, single microseconds --
-    // runs kernel 1.  A name without a PULSE form is refused.
-    if (ctx->pulse) {
-        if (forced != 0 && forced != 1 && forced != 2 && forced != 7 && forced != 8)
-            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
-        const bool fast = !tr && !f64 && !ctx->replay;
-        int v = fast ? forced : 1;
-        if (v == 0 && !single) {
-            if (wide_ok && ctx->lanes == 0 && (int64_t)ctx->num_envs * wl <= (int64_t)WEDM_WIDE_AUTO_MAX_LANES) v = 8;
-            else if (regs_ok && ctx->lanes == 0 && ctx->num_envs >= 20480) v = 7;
-            else if (use_pk) v = 2;
+        if (v == K_AUTO) {
+            if (f64) v = (!single && fused_ok) ? K_FUSED : (lanes_ok || use_pk) ? K_LANES_PK : K_GLOBAL;
+            else if (single) v = stream_auto ? K_STREAM : K_SPLIT;
+            else if (packed_ok && (best4 <= best3 || !fused_ok)) v = K_PACKED;
+            else if (fused_ok) v = K_FUSED;
+            else v = (lanes_ok || use_pk) ? K_LANES_PK : K_GLOBAL;
         }
-        variant = v == 0 ? 1 : v;
-        if (variant == 2 && !use_pk)
-            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
     }
-    // per-environment physics rows bound (wedm_bind_env_params): only kernels with an ENVP instantiation.  Fused launches of the
-    // float32 stencil without a trace sample or pulse statistics run kernel 2's packed form (uniform or per-environment
-    // geometry); everything else -- a trace sample in the launch, stencil_mode 1, injected variates, pulse statistics, single
-    // microseconds, forced kernel 1 -- runs kernel 1.  A name without an ENVP form is refused.
-    if (ctx->envp) {  // (a forced kernel without an ENVP form was refused above)
-        const bool fast = !tr && !f64 && !ctx->replay && !ctx->pulse;
-        variant = (fast && (forced == 2 || (forced == 0 && !single && use_pk))) ? 2 : 1;
-        if (variant == 2 && !use_pk)
-            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
-    }
-    if (variant == 9 && !served_ok)
+    if (v == K_SERVED && !svl)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: served kernel needs uniform geometry, the float32 stencil, lanes 4 or 8, two chunks that fit in LDS and freeze_terminated");
-    if (variant == 9 && tr) variant = packed_ok ? 4 : fused_ok ? 3 : (lanes_ok || use_pk) ? 2 : 1;
+    // (no trace point in the served kernel)
+    if (v == K_SERVED && tr) v = packed_ok ? K_PACKED : fused_ok ? K_FUSED : (lanes_ok || use_pk) ? K_LANES_PK : K_GLOBAL;
     // kernel 12 (served register kernel): the register kernel's conditions + what the served scalar wave does not do
-    if (variant == 12 && (!regs_ok || f64 || tr || P.keep_stepping_terminated))
+    if (v == K_REGS_SERVED && (!rl || f64 || tr || P.keep_stepping_terminated))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: served register kernel needs uniform geometry, at most 128 segments, the float32 stencil, no trace sample in the launch and freeze_terminated");
-    if (variant == 7 && !regs_ok)
+    if (v == K_REGS && !rl)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: register kernel needs uniform geometry and at most 128 segments");
-    if (variant == 3 && !fused_ok)
+    if (v == K_FUSED && !fused_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: fused kernel needs uniform geometry and a chunk that fits in LDS");
-    if (variant == 4 && !packed_ok)
+    if (v == K_PACKED && !packed_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: packed kernel needs uniform geometry, lanes in {1,2,4,8} and two chunks that fit in LDS");
-    if (variant == 11 && (!lanes_sv_ok || tr)) variant = 2;  // (a trace sample, stencil_mode 1, keep-stepping: the unserved forms)
-    if ((variant == 2 && !use_pk && !lanes_ok) || (variant == 10 && !lanes_ok))
+    // (kernel 11 by name only: at 16 384 environments x <= 450 segments it measures 2.39e9 against the packed form's 2.48e9 -
+    // 2.62e9; a trace sample, stencil_mode 1, keep-stepping: the unserved forms)
+    if (v == K_LANES_SERVED && (!lanes_sv_ok || tr)) v = K_LANES_PK;
+    if ((v == K_LANES_PK && !use_pk && !lanes_ok) || (v == K_LANES && !lanes_ok))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: no lane count puts a chunk of the wire in LDS");
-    if (variant == 6 && !stream_ok)
+    if (v == K_STREAM && !slanes)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: stream kernel needs uniform geometry and lanes in {1,2,4,8,16} with a chunk of at most 104 cells");
+    if (v == K_LANES_PK && !use_pk) v = K_LANES;  // kernel 2 without a packed fit: its cell-by-cell form
+    out.kernel = (Kernel)v;
+    switch (out.kernel) {
+        case K_LANES_PK: out.lanes = pklanes; break;
+        case K_FUSED: out.lanes = lanes; break;
+        case K_PACKED: out.lanes = planes; break;
+        case K_STREAM: out.lanes = slanes; break;
+        case K_REGS: out.lanes = rl; break;
+        case K_WIDE: out.lanes = wl; break;
+        case K_SERVED: out.lanes = svl; break;
+        case K_LANES: out.lanes = glanes; break;
+        case K_LANES_SERVED: out.lanes = svgl; break;
+        default: out.lanes = 0; break;
+    }
+    return WEDM_OK;
+}
 
+// f(std::bool_constant<b>...) for the runtime flags: instantiates every combination of them, so pass only flags whose every
+// combination exists
+template <class F> static const void* with_flags(F f) { return f(); }
+template <class F, class... B> static const void* with_flags(F f, bool b, B... rest) {
+    if (b) return with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
+    return with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
+}
+// f(std::integral_constant<int, L>, flags...) for the runtime L among `Ls`: only the lane counts the family is instantiated for
+template <int... Ls, class F, class... B> static const void* by_lanes(int L, F f, B... flags) {
     const void* fn = nullptr;
-    int grid = 0;
+    ((L == Ls ? (void)(fn = with_flags([&](auto... t) { return f(std::integral_constant<int, Ls>{}, t...); }, flags...)) : (void)0), ...);
+    return fn;
+}
+
+static const char* const kernel_names[] = {"", "wedm_step_global", "wedm_step_lanes_pk", "wedm_step_fused", "wedm_step_packed",
+                                           "wedm_step_split", "wedm_step_stream", "wedm_step_regs", "wedm_step_regs_wide",
+                                           "wedm_step_served", "wedm_step_lanes", "wedm_step_lanes_served", "wedm_step_regs_served"};
+
+// What wedm_step launches for (single microsecond?, trace point?) under the handle's current settings: decided once
+// and cached (the decision walks a cost model over five lane counts; on the one-launch-per-microsecond path that and
+// a hipFuncSetAttribute per call were a measurable part of the host time per launch).  The choice, then one branch per
+// family from its flags to the instantiation, grid, block, LDS image and walk table.
+static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, LaunchPlan& out) {
+    Choice ch;
+    if (int32_t rc = choose_kernel(ctx, single, tr, ch)) return rc;
+    const int L = ch.lanes, n = ctx->num_envs;
+    const bool f64 = ctx->p.stencil_mode != 0, replay = ctx->replay != nullptr, pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
+    const WalkInfo* w = nullptr;  // the walk table the launch reads
+    bool fz = false;              // the FROZEN_OK instantiation (named in the kernel string)
+    const void* fn = nullptr;
+    int grid = blocks(n, 256 / std::max(L, 1)), block = 256;
     size_t fl = 0;
-    out.walk = nullptr;
-    const bool pulse = ctx->pulse != nullptr;
-    if (variant == 1 && ctx->envp) {
-        grid = (ctx->num_envs + 255) / 256;
-        fn = pulse ? pick_global_envp<true>(ctx->replay != nullptr, f64, tr) : pick_global_envp<false>(ctx->replay != nullptr, f64, tr);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_global%s%s[envp]<<<%d,256>>>", ctx->replay ? "[injected variates]" : f64 ? "[f64 stencil]" : "",
-                      pulse ? "[pulse]" : "", grid);
-    } else if (variant == 2 && ctx->envp) {
-        grid = (ctx->num_envs + 256 / pklanes - 1) / (256 / pklanes);
-        fl = (2 * (size_t)((ctx->n_seg_max + 2 * pklanes - 1) / (2 * pklanes)) + 2) * 1024;
-        fn = pick_lanes_pk<false, false, false, true>(pklanes);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_pk<%d>[envp]<<<%d,256,%zuB>>>", pklanes, grid, fl);
-    } else if (variant == 1 && pulse) {
-        grid = (ctx->num_envs + 255) / 256;
-        fn = ctx->replay ? (tr ? (const void*)wedm_step_global<true, false, true, true> : (const void*)wedm_step_global<false, false, true, true>)
-           : f64 ? (tr ? (const void*)wedm_step_global<true, true, false, true> : (const void*)wedm_step_global<false, true, false, true>)
-                 : (tr ? (const void*)wedm_step_global<true, false, false, true> : (const void*)wedm_step_global<false, false, false, true>);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_global%s[pulse]<<<%d,256>>>", ctx->replay ? "[injected variates]" : f64 ? "[f64 stencil]" : "", grid);
-    } else if (variant == 7 && pulse) {
-        const int rl = ctx->lanes == 1 ? 1 : 2;
-        grid = (ctx->num_envs + 256 / rl - 1) / (256 / rl);
-        out.walk = ctx->walk_dev + (rl == 1 ? 10 : 11);
-        fn = rl == 1 ? (const void*)wedm_step_regs<128, 1, false, false, true> : (const void*)wedm_step_regs<128, 2, false, false, true>;
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs<%d>[pulse]<<<%d,256>>>", rl, grid);
-    } else if (variant == 8 && pulse) {
-        grid = (ctx->num_envs + 256 / wl - 1) / (256 / wl);
-        const bool cutw = (P.n_seg & 7) != 0;
-#define WEDM_PICK_WIDE_PULSE(cut) (wl == 4 ? (const void*)wedm_step_regs_wide<16, 4, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true> \
-                                  : wl == 8 ? (const void*)wedm_step_regs_wide<16, 8, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true> \
-                                            : (const void*)wedm_step_regs_wide<16, 16, cut, false, false, WEDM_WIDE_MIN_BLOCKS, true>)
-        fn = cutw ? WEDM_PICK_WIDE_PULSE(true) : WEDM_PICK_WIDE_PULSE(false);
-#undef WEDM_PICK_WIDE_PULSE
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs_wide<%d>[pulse]<<<%d,256>>>", wl, grid);
-    } else if (variant == 2 && pulse) {
-        grid = (ctx->num_envs + 256 / pklanes - 1) / (256 / pklanes);
-        fl = (2 * (size_t)((ctx->n_seg_max + 2 * pklanes - 1) / (2 * pklanes)) + 2) * 1024;
-        fn = pick_lanes_pk<false, false, true>(pklanes);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_pk<%d>[pulse]<<<%d,256,%zuB>>>", pklanes, grid, fl);
-    } else if (variant == 1) {
-        grid = (ctx->num_envs + 255) / 256;
-        fn = ctx->replay ? (tr ? (const void*)wedm_step_global<true, false, true> : (const void*)wedm_step_global<false, false, true>)
-           : f64 ? (tr ? (const void*)wedm_step_global<true, true, false> : (const void*)wedm_step_global<false, true, false>)
-                 : (tr ? (const void*)wedm_step_global<true, false, false> : (const void*)wedm_step_global<false, false, false>);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_global%s<<<%d,256>>>", ctx->replay ? "[injected variates]" : f64 ? "[f64 stencil]" : "", grid);
-    } else if (variant == 7) {
-        const int rl = ctx->lanes == 1 ? 1 : 2;  // lanes per environment (default 2: two waves per SIMD)
-        grid = (ctx->num_envs + 256 / rl - 1) / (256 / rl);
-        out.walk = ctx->walk_dev + (rl == 1 ? 10 : 11);  // two chunks of 64 cells / four of 32
-        fn = f64 ? (tr ? (rl == 1 ? (const void*)wedm_step_regs<128, 1, true, true> : (const void*)wedm_step_regs<128, 2, true, true>)
-                       : (rl == 1 ? (const void*)wedm_step_regs<128, 1, false, true> : (const void*)wedm_step_regs<128, 2, false, true>))
-           : tr ? (rl == 1 ? (const void*)wedm_step_regs<128, 1, true> : (const void*)wedm_step_regs<128, 2, true>)
-                : (rl == 1 ? (const void*)wedm_step_regs<128, 1> : (const void*)wedm_step_regs<128, 2>);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs<%d>%s<<<%d,256>>>", rl, f64 ? "[f64 stencil]" : "", grid);
-    } else if (variant == 8) {
-        grid = (ctx->num_envs + 256 / wl - 1) / (256 / wl);
-#define WEDM_PICK_WIDE(...) (wl == 4 ? (const void*)wedm_step_regs_wide<16, 4, __VA_ARGS__> : wl == 8 ? (const void*)wedm_step_regs_wide<16, 8, __VA_ARGS__> \
-                                                                                                  : (const void*)wedm_step_regs_wide<16, 16, __VA_ARGS__>)
-        const bool cutw = (P.n_seg & 7) != 0;
-        // (stencil_mode 1: a batch of more than one wave per SIMD runs the two-blocks-per-CU instantiation -- 32 768 x 400: 1.93e9
-        // against 1.52e9; 4 096 x 400: 1.33e9 against 1.45e9)
-        const bool two = (int64_t)ctx->num_envs * wl > (int64_t)WEDM_WIDE_AUTO_MAX_LANES;
-        fn = f64 ? (two ? (tr ? WEDM_PICK_WIDE(true, true, true, 2) : cutw ? WEDM_PICK_WIDE(true, false, true, 2) : WEDM_PICK_WIDE(false, false, true, 2))
-                        : (tr ? WEDM_PICK_WIDE(true, true, true, 1) : cutw ? WEDM_PICK_WIDE(true, false, true, 1) : WEDM_PICK_WIDE(false, false, true, 1)))
-                 : (tr ? WEDM_PICK_WIDE(true, true) : cutw ? WEDM_PICK_WIDE(true) : WEDM_PICK_WIDE(false));
-#undef WEDM_PICK_WIDE
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs_wide<%d>%s<<<%d,256>>>", wl, f64 ? "[f64 stencil]" : "", grid);
-    } else if (variant == 5) {
-        grid = (ctx->num_envs + 63) / 64;
-        fn = tr ? (const void*)wedm_step_split<true> : (const void*)wedm_step_split<false>;
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_split<<<%d,256>>>", grid);
-    } else if (variant == 6) {
-        const int sli = lanes_index(slanes);
-        grid = (ctx->num_envs + 256 / slanes - 1) / (256 / slanes);
-        fl = ((size_t)ctx->walk4_C[sli] + 1) * 1024;
-        out.walk = ctx->walk_dev + 5 + sli;
-        // launches of one microsecond without a trace sample, chunks of at most 64 cells: the instantiation without the loop
-        const bool one = WEDM_STREAM_REGWALK && single && !tr && ctx->walk4_C[sli] <= 64;
-        fn = f64 ? pick_stream<false, 64, true, true>(slanes)
-           : one ? pick_stream<false, 64, true>(slanes)
-           : ctx->walk4_C[sli] <= 64 ? (tr ? pick_stream<true, 64>(slanes) : pick_stream<false, 64>(slanes))
-                                     : (tr ? pick_stream<true, 104>(slanes) : pick_stream<false, 104>(slanes));
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_stream<%d>%s<<<%d,256,%zuB>>>", slanes, f64 ? "[f64 stencil]" : "", grid, fl);
-    } else if (lanes_sv_ok && variant == 11) {  // (by name only: at 16 384 environments x <= 450 segments it measures 2.39e9 against the packed form's 2.48e9 - 2.62e9)
-        grid = (ctx->num_envs + 192 / svgl - 1) / (192 / svgl);
-        fl = (2 * (size_t)((ctx->n_seg_max + 2 * svgl - 1) / (2 * svgl)) + 2) * 768 + (svgl == 4 ? sizeof(ServedBox<48>) : svgl == 8 ? sizeof(ServedBox<24>) : sizeof(ServedBox<12>));
-        fn = svgl == 4 ? (const void*)wedm_step_lanes_served<4> : svgl == 8 ? (const void*)wedm_step_lanes_served<8> : (const void*)wedm_step_lanes_served<16>;
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_served<%d><<<%d,256,%zuB>>>", svgl, grid, fl);
-    } else if ((variant == 2 || variant == 11) && use_pk) {
-        grid = (ctx->num_envs + 256 / pklanes - 1) / (256 / pklanes);
-        fl = (2 * (size_t)((ctx->n_seg_max + 2 * pklanes - 1) / (2 * pklanes)) + 2) * 1024;
-        fn = f64 ? (tr ? pick_lanes_pk<true, true>(pklanes) : pick_lanes_pk<false, true>(pklanes))
-                 : (tr ? pick_lanes_pk<true>(pklanes) : pick_lanes_pk<false>(pklanes));
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes_pk<%d>%s<<<%d,256,%zuB>>>", pklanes, f64 ? "[f64 stencil]" : "", grid, fl);
-    } else if (variant == 2 || variant == 10) {
-        grid = (ctx->num_envs + 256 / glanes - 1) / (256 / glanes);
-        fl = (size_t)((ctx->n_seg_max + glanes - 1) / glanes) * 1024;
-        fn = f64 ? (tr ? pick_lanes<true, true>(glanes) : pick_lanes<false, true>(glanes))
-                 : (tr ? pick_lanes<true, false>(glanes) : pick_lanes<false, false>(glanes));
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_lanes<%d>%s<<<%d,256,%zuB>>>", glanes, f64 ? "[f64 stencil]" : "", grid, fl);
-    } else if (variant == 12) {
-        grid = (ctx->num_envs + 63) / 64;
-        fl = sizeof(ServedBox<64>);
-        out.walk = ctx->walk_dev + 11;  // four chunks of 32 cells
-        out.block = 192;                // two walker waves + the scalar wave
-        fn = (const void*)wedm_step_regs_served<128>;
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_regs_served<<<%d,192,%zuB>>>", grid, fl);
-    } else if (variant == 9) {
-        grid = (ctx->num_envs + 192 / svl - 1) / (192 / svl);
-        fl = (2 * (size_t)ctx->walk_C[svi] + 2) * 768 + sv_box;
-        out.walk = ctx->walk_dev + svi;
-        out.block = 256;  // three walker waves + the scalar wave
-        const bool extra = ((ctx->walk_n1z >> svi) & 1u) || ((ctx->walk_C[svi] > 8) && (ctx->walk_C[svi] & 7) >= 1 && (ctx->walk_C[svi] & 7) <= 2);
-        fn = pick_served(svl, extra);
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_served<%d><<<%d,256,%zuB>>>", svl, grid, fl);
-    } else if (variant == 4) {
-        grid = (ctx->num_envs + 256 / planes - 1) / (256 / planes);
-        fl = (2 * (size_t)ctx->walk_C[pli] + 2) * 1024;
-        out.walk = ctx->walk_dev + pli;
-        // handles with in-launch autoreset expect terminations, and so do handles whose kernels have reported a frozen
-        // environment (wedm_ctx::frozen_seen): the instantiation that tolerates frozen lanes
-        // tables with a one-change boundary tile or a 1- / 2-cell tail: the instantiation that handles them
-        const bool extra = ((ctx->walk_n1z >> pli) & 1u) || ((ctx->walk_C[pli] > 8) && (ctx->walk_C[pli] & 7) >= 1 && (ctx->walk_C[pli] & 7) <= 2);
-        fn = frozen_ok ? (tr ? pick_packed<true, true>(planes, extra) : pick_packed<false, true>(planes, extra))
-                       : (tr ? pick_packed<true, false>(planes, extra) : pick_packed<false, false>(planes, extra));
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_packed<%d>%s<<<%d,256,%zuB>>>", planes, frozen_ok ? "[frozen lanes ok]" : "", grid, fl);
-    } else {
-        grid = (ctx->num_envs + 256 / lanes - 1) / (256 / lanes);
-        fl = ((size_t)ctx->walk_C[li] + 1) * 1024;
-        out.walk = ctx->walk_dev + li;
-        const bool n1 = (ctx->walk_n1z >> li) & 1u;  // the table has a one-change tile that is a boundary tile in every microsecond
-        fn = f64 ? (tr ? pick_fused_f64<true>(lanes) : pick_fused_f64<false>(lanes))
-           : frozen_ok ? (tr ? pick_fused<true, true>(lanes, n1) : pick_fused<false, true>(lanes, n1))
-                       : (tr ? pick_fused<true, false>(lanes, n1) : pick_fused<false, false>(lanes, n1));
-        std::snprintf(out.name, sizeof(out.name), "wedm_step_fused<%d>%s<<<%d,256,%zuB>>>", lanes,
-                      f64 ? "[f64 stencil]" : frozen_ok ? "[frozen lanes ok]" : "", grid, fl);
+    switch (ch.kernel) {
+        case K_GLOBAL:  // injected variates / stencil_mode 1 / the float32 stencil, each with PULSE and ENVP forms
+            fn = replay ? with_flags([](auto t, auto p, auto e) { return (const void*)wedm_step_global<t, false, true, p, e>; }, tr, pulse, envp)
+                        : with_flags([](auto t, auto d, auto p, auto e) { return (const void*)wedm_step_global<t, d, false, p, e>; }, tr, f64, pulse, envp);
+            break;
+        case K_LANES_PK:
+            fl = lanes_pk_lds(ctx, L);
+            fn = pulse ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, true>; })
+               : envp  ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, false, true>; })
+                       : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_lanes_pk<l, t, d>; }, tr, f64);
+            break;
+        case K_LANES:
+            fl = lanes_lds(ctx, L);
+            fn = by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_lanes<l, t, d>; }, tr, f64);
+            break;
+        case K_FUSED:
+            // handles with in-launch autoreset expect terminations, and so do handles whose kernels have reported a frozen
+            // environment (wedm_ctx::frozen_seen): the instantiation that tolerates frozen lanes; N1: the table has a
+            // one-change tile that is a boundary tile in every microsecond
+            w = walk_of(ctx, W_LDS, L);
+            fl = fused_lds(ctx, L);
+            fz = frozen_ok;
+            fn = f64 ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t) { return (const void*)wedm_step_fused<l, t, true, false, true>; }, tr)
+                     : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto z, auto n1) { return (const void*)wedm_step_fused<l, t, z, n1>; },
+                                                tr, frozen_ok, w->n1z);
+            break;
+        case K_PACKED:
+            w = walk_of(ctx, W_LDS, 2 * L);
+            fl = packed_lds(ctx, L);
+            fz = frozen_ok;
+            fn = by_lanes<1, 2, 4, 8>(L, [](auto l, auto t, auto z, auto x) { return (const void*)wedm_step_packed<l, t, z, x>; },
+                                      tr, frozen_ok, walk_extra(w));
+            break;
+        case K_SERVED:  // three walker waves + the scalar wave
+            w = walk_of(ctx, W_LDS, 2 * L);
+            fl = served_lds(ctx, L);
+            grid = blocks(n, 192 / L);
+            fn = by_lanes<4, 8>(L, [](auto l, auto x) { return (const void*)wedm_step_served<l, x>; }, walk_extra(w));
+            break;
+        case K_LANES_SERVED:
+            fl = lanes_served_lds(ctx, L);
+            grid = blocks(n, 192 / L);
+            fn = by_lanes<4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_served<l>; });
+            break;
+        case K_STREAM: {
+            // launches of one microsecond without a trace sample, chunks of at most 64 cells: the instantiation without the
+            // loop (stencil_mode 1: the only one); else the rows a lane holds in registers: 64 (128 segments over 2 lanes, 400
+            // over 8) or 104 (400 over 4)
+            w = walk_of(ctx, W_STREAM, L);
+            fl = stream_lds(ctx, L);
+            const bool one = WEDM_STREAM_REGWALK && single && !tr && w->C <= 64;
+            fn = (one || f64) ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto d) { return (const void*)wedm_step_stream<l, false, 64, true, d>; }, f64)
+                              : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto c64) { return (const void*)wedm_step_stream<l, t, c64 ? 64 : 104>; },
+                                                         tr, w->C <= 64);
+            break;
+        }
+        case K_SPLIT:
+            grid = blocks(n, 64);
+            fn = with_flags([](auto t) { return (const void*)wedm_step_split<t>; }, tr);
+            break;
+        case K_REGS:  // the table of two chunks of 64 cells (one lane) / four of 32 (two lanes)
+            w = &ctx->walk[L == 1 ? W_REGS2 : W_REGS4];
+            fn = pulse ? by_lanes<1, 2>(L, [](auto l) { return (const void*)wedm_step_regs<128, l, false, false, true>; })
+                       : by_lanes<1, 2>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_regs<128, l, t, d>; }, tr, f64);
+            break;
+        case K_WIDE: {
+            // CUT: wires whose length is not a multiple of 8, and every traced launch.  (stencil_mode 1: a batch of more than
+            // one wave per SIMD runs the two-blocks-per-CU instantiation -- 32 768 x 400: 1.93e9 against 1.52e9; 4 096 x 400:
+            // 1.33e9 against 1.45e9)
+            const bool cut = (ctx->p.n_seg & 7) != 0, two = (int64_t)n * L > (int64_t)WEDM_WIDE_AUTO_MAX_LANES;
+            if (f64)
+                fn = tr ? by_lanes<4, 8, 16>(L, [](auto l, auto m) { return (const void*)wedm_step_regs_wide<16, l, true, true, true, m ? 2 : 1>; }, two)
+                        : by_lanes<4, 8, 16>(L, [](auto l, auto c, auto m) { return (const void*)wedm_step_regs_wide<16, l, c, false, true, m ? 2 : 1>; },
+                                             cut, two);
+            else
+                fn = tr ? by_lanes<4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_regs_wide<16, l, true, true>; })
+                        : by_lanes<4, 8, 16>(L, [](auto l, auto c, auto p) {
+                              return (const void*)wedm_step_regs_wide<16, l, c, false, false, WEDM_WIDE_MIN_BLOCKS, p>; }, cut, pulse);
+            break;
+        }
+        case K_REGS_SERVED:  // two walker waves + the scalar wave; the table of four chunks of 32 cells
+            w = &ctx->walk[W_REGS4];
+            fl = sizeof(ServedBox<64>);
+            grid = blocks(n, 64);
+            block = 192;
+            fn = (const void*)wedm_step_regs_served<128>;
+            break;
+        case K_AUTO: break;
     }
     if (fl) {
         // The attribute belongs to the kernel FUNCTION, not to this handle or plan: two live handles with different wire
@@ -905,10 +820,17 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
         hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, ctx->lds_limit);
         if (ea != hipSuccess) return hip_fail(ctx, ea, "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     }
+    char lanes_s[16] = "", lds_s[32] = "";
+    if (L) std::snprintf(lanes_s, sizeof(lanes_s), "<%d>", L);
+    if (fl) std::snprintf(lds_s, sizeof(lds_s), ",%zuB", fl);
+    std::snprintf(out.name, sizeof(out.name), "%s%s%s%s%s<<<%d,%d%s>>>", kernel_names[ch.kernel], lanes_s,
+                  replay ? "[injected variates]" : f64 ? "[f64 stencil]" : fz ? "[frozen lanes ok]" : "", pulse ? "[pulse]" : "",
+                  envp ? "[envp]" : "", grid, block, lds_s);
     out.fn = fn;
     out.grid = grid;
-    if (variant != 9 && variant != 12) out.block = 256;
+    out.block = block;
     out.lds = fl;
+    out.walk = w ? ctx->walk_dev + (w - ctx->walk) : nullptr;
     out.valid = true;
     return WEDM_OK;
 }
@@ -974,6 +896,12 @@ int32_t wedm_create(const wedm_params* params, int32_t num_envs, int32_t n_seg_m
     }
     wedm_ctx* ctx = new (std::nothrow) wedm_ctx();
     if (!ctx) return WEDM_ERR_BAD_ARG;
+    // a failure from here on frees what has been allocated (wedm_destroy frees the non-null members)
+    auto hip_error = [&](const char* what) {
+        g_create_error = std::string(what) + ": " + hipGetErrorString(e);
+        (void)wedm_destroy(ctx);
+        return WEDM_ERR_HIP;
+    };
     ctx->p = *params;
     ctx->num_envs = num_envs;
     ctx->n_seg_max = n_seg_max;
@@ -985,23 +913,14 @@ int32_t wedm_create(const wedm_params* params, int32_t num_envs, int32_t n_seg_m
     // per-mode tables -> one small device buffer (per-lane indexed loads)
     const size_t n = WEDM_MAX_MODE + 1;
     const size_t bytes = 4 * n * sizeof(double) + n * sizeof(int32_t);
-    if ((e = hipMalloc(&ctx->tables_dev, bytes)) != hipSuccess) {
-        g_create_error = std::string("hipMalloc(tables): ") + hipGetErrorString(e);
-        delete ctx;
-        return WEDM_ERR_HIP;
-    }
+    if ((e = hipMalloc(&ctx->tables_dev, bytes)) != hipSuccess) return hip_error("hipMalloc(tables)");
     char host[4 * 20 * 8 + 20 * 4];
     std::memcpy(host + 0 * n * 8, params->mode_current, n * 8);
     std::memcpy(host + 1 * n * 8, params->crater_mean, n * 8);
     std::memcpy(host + 2 * n * 8, params->crater_std, n * 8);
     std::memcpy(host + 3 * n * 8, params->crater_depth, n * 8);
     std::memcpy(host + 4 * n * 8, params->crater_valid, n * 4);
-    if ((e = hipMemcpy(ctx->tables_dev, host, bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-        g_create_error = std::string("hipMemcpy(tables): ") + hipGetErrorString(e);
-        (void)hipFree(ctx->tables_dev);
-        delete ctx;
-        return WEDM_ERR_HIP;
-    }
+    if ((e = hipMemcpy(ctx->tables_dev, host, bytes, hipMemcpyHostToDevice)) != hipSuccess) return hip_error("hipMemcpy(tables)");
     const double* d = (const double*)ctx->tables_dev;
     ctx->tb.mode_current = d;
     ctx->tb.crater_mean = d + n;
@@ -1009,36 +928,32 @@ int32_t wedm_create(const wedm_params* params, int32_t num_envs, int32_t n_seg_m
     ctx->tb.crater_depth = d + 3 * n;
     ctx->tb.crater_valid = (const int32_t*)(d + 4 * n);
     if ((e = hipMalloc((void**)&ctx->params_dev, sizeof(wedm_params))) != hipSuccess ||
-        (e = hipMemcpy(ctx->params_dev, params, sizeof(wedm_params), hipMemcpyHostToDevice)) != hipSuccess) {
-        g_create_error = std::string("params copy: ") + hipGetErrorString(e);
-        if (ctx->params_dev) (void)hipFree(ctx->params_dev);
-        (void)hipFree(ctx->tables_dev);
-        delete ctx;
-        return WEDM_ERR_HIP;
-    }
+        (e = hipMemcpy(ctx->params_dev, params, sizeof(wedm_params), hipMemcpyHostToDevice)) != hipSuccess)
+        return hip_error("params copy");
     if (!params->per_env_geometry) {
-        std::vector<WalkTable> host_tabs(12);  // [10], [11]: two chunks of exactly 64 cells, four of 32 (register kernel)
+        std::vector<WalkTable> host_tabs(W_COUNT);
+        auto build = [&](int w, int L, int align) {
+            WalkInfo& info = ctx->walk[w];
+            info.ok = build_walk(*params, L, host_tabs[w], align);
+            info.C = host_tabs[w].C;
+            info.kind_s = host_tabs[w].kind_s_mask;
+            info.n1z = info.ok && (host_tabs[w].kind_n1_mask & 0x80000000u);
+        };
         const int Ls[5] = {1, 2, 4, 8, 16};
         for (int i = 0; i < 5; ++i) {
-            ctx->walk_ok[i] = build_walk(*params, Ls[i], host_tabs[i]);
-            ctx->walk_C[i] = host_tabs[i].C;
-            if (ctx->walk_ok[i] && (host_tabs[i].kind_n1_mask & 0x80000000u)) ctx->walk_n1z |= 1u << i;
-            ctx->walk4_ok[i] = build_walk(*params, Ls[i], host_tabs[5 + i], 4);
-            ctx->walk4_C[i] = host_tabs[5 + i].C;
-            ctx->walk4_kind_s[i] = host_tabs[5 + i].kind_s_mask;
-            if (i == 0) ctx->walk_regs_ok = params->n_seg <= 128 && build_walk(*params, 2, host_tabs[10], 64) && host_tabs[10].C == 64 &&
-                                            build_walk(*params, 4, host_tabs[11], 32) && host_tabs[11].C == 32;
+            build(W_LDS + i, Ls[i], 1);
+            build(W_STREAM + i, Ls[i], 4);
         }
+        if (params->n_seg <= 128)  // the register kernels' tables: two chunks of exactly 64 cells, four of 32
+            for (const int w : {W_REGS2, W_REGS4}) {
+                const int L = w == W_REGS2 ? 2 : 4;
+                build(w, L, 128 / L);
+                ctx->walk[w].ok = ctx->walk[w].ok && ctx->walk[w].C == 128 / L;
+            }
         const size_t tab_bytes = host_tabs.size() * sizeof(WalkTable);
         if ((e = hipMalloc((void**)&ctx->walk_dev, tab_bytes)) != hipSuccess ||
-            (e = hipMemcpy(ctx->walk_dev, host_tabs.data(), tab_bytes, hipMemcpyHostToDevice)) != hipSuccess) {
-            g_create_error = std::string("walk tables: ") + hipGetErrorString(e);
-            if (ctx->walk_dev) (void)hipFree(ctx->walk_dev);
-            (void)hipFree(ctx->params_dev);
-            (void)hipFree(ctx->tables_dev);
-            delete ctx;
-            return WEDM_ERR_HIP;
-        }
+            (e = hipMemcpy(ctx->walk_dev, host_tabs.data(), tab_bytes, hipMemcpyHostToDevice)) != hipSuccess)
+            return hip_error("walk tables");
     }
     // (optional: without it every handle without autoreset simply keeps the instantiation without the frozen-lane code)
     if (hipHostMalloc((void**)&ctx->frozen_seen, sizeof(int32_t), hipHostMallocMapped) == hipSuccess) {
