@@ -202,6 +202,21 @@ enum wedm_envp_field {
     WEDM_ENVP_COUNT
 };
 
+/* ------------------------------------------------ per-environment wire material (optional)
+ * One wire material per environment: float64, one value per environment of each row below, overriding the uniform value
+ * of the same quantity in wedm_params, bit for bit as the host derives it for wedm_params (rho_c = density *
+ * specific_heat, critical temperature = melting_point * critical_temp_threshold).  The material's conductivity and heat
+ * capacity also enter WEDM_G_K_COND and WEDM_G_TUF of the geometry rows, so the block needs per-environment geometry.
+ * Nothing of the reset reads any of these rows.                                                                      */
+enum wedm_wmat_field {
+    WEDM_WM_RHO_ELEC = 0,          /* electrical_resistivity                     (wire.py:186)            */
+    WEDM_WM_ALPHA_RHO,             /* temperature_coefficient                    (wire.py:187)            */
+    WEDM_WM_RHO_C,                 /* density * specific_heat                    (wire.py:305-310 prefix) */
+    WEDM_WM_CRITICAL_TEMPERATURE,  /* melting_point * critical_temp_threshold    (wire.py:216-218)        */
+    WEDM_WM_BREAKING_TEMPERATURE,  /* breaking_temperature                       (wire.py:220)            */
+    WEDM_WMAT_COUNT
+};
+
 /* -------------------------------------- per-environment geometry (optional)
  * BASELINE config 5: workpiece_height / wire_diameter differ per environment.
  * When bound, these rows override the uniform values in wedm_params.       */
@@ -442,6 +457,17 @@ int32_t wedm_bind_pulse_stats(wedm_ctx* ctx, int32_t* rows);
  * kernel 1 for every other launch; wedm_set_kernel values other than 0, 1 and 2 make wedm_step return
  * WEDM_ERR_UNSUPPORTED.  wedm_reset reads none of the rows.                                                            */
 int32_t wedm_bind_env_params(wedm_ctx* ctx, const double* rows);
+
+/* binds (rows != NULL) or removes (rows == NULL) the caller-owned per-environment wire material:
+ * float64 [WEDM_WMAT_COUNT][stride] described at wedm_wmat_field (same stride as the state blocks), read at the start of
+ * every wedm_step (the caller may rewrite them between launches, stream-ordered, together with the material's
+ * WEDM_G_K_COND / WEDM_G_TUF geometry rows).  Binding needs per-environment geometry (wedm_params.per_env_geometry and
+ * wedm_bind_geometry): WEDM_ERR_NOT_BOUND otherwise.  While they are bound, wedm_step runs the kernels' MAT
+ * instantiations: kernel 2's packed form (float32 stencil, no trace sample, no pulse statistics; with or without
+ * per-environment physics parameters) and kernel 1 for every other launch; wedm_set_kernel values other than 0, 1 and 2,
+ * and injected variates (wedm_bind_rng_replay), make wedm_step return WEDM_ERR_UNSUPPORTED.  wedm_reset reads none of
+ * the rows.                                                                                                            */
+int32_t wedm_bind_wire_material(wedm_ctx* ctx, const double* rows);
 
 /* binds (desc != NULL) or removes (desc == NULL) the signal trace; resets the sample counter.
  * Terminated environments keep being sampled (their frozen state).                        */

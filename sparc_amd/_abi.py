@@ -163,6 +163,19 @@ class ENVP(enum.IntEnum):
 ENVP_COUNT = 16
 
 
+class WMAT(enum.IntEnum):
+    """Rows of the optional per-environment wire-material block (``enum wedm_wmat_field``, float64)."""
+
+    RHO_ELEC = 0
+    ALPHA_RHO = 1
+    RHO_C = 2
+    CRITICAL_TEMPERATURE = 3
+    BREAKING_TEMPERATURE = 4
+
+
+WMAT_COUNT = 5
+
+
 class GF64(enum.IntEnum):
     """Rows of the per-environment geometry float64 block."""
 

@@ -64,6 +64,8 @@ def load() -> C.CDLL:
     L.wedm_bind_pulse_stats.restype = C.c_int32
     L.wedm_bind_env_params.argtypes = [ctx, C.c_void_p]
     L.wedm_bind_env_params.restype = C.c_int32
+    L.wedm_bind_wire_material.argtypes = [ctx, C.c_void_p]
+    L.wedm_bind_wire_material.restype = C.c_int32
     L.wedm_trace_samples.argtypes = [ctx]
     L.wedm_trace_samples.restype = C.c_int64
     L.wedm_set_kernel.argtypes = [ctx, C.c_int32]
@@ -88,7 +90,7 @@ def load() -> C.CDLL:
 
 EXPORTS = (
     "wedm_abi_version", "wedm_create", "wedm_destroy", "wedm_bind_state", "wedm_bind_geometry",
-    "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
+    "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
 )
 
@@ -184,6 +186,11 @@ class HipBackend:
     def bind_env_params(self, rows_ptr) -> None:
         """`rows_ptr`: device address of a float64 [ENVP_COUNT][stride] block, or None (unbind)."""
         self._check(self._L.wedm_bind_env_params(self._ctx, rows_ptr))
+
+    def bind_wire_material(self, rows_ptr) -> None:
+        """`rows_ptr`: device address of a float64 [WMAT_COUNT][stride] block, or None (unbind).  Needs bound
+        per-environment geometry."""
+        self._check(self._L.wedm_bind_wire_material(self._ctx, rows_ptr))
 
     def trace_samples(self) -> int:
         return int(self._L.wedm_trace_samples(self._ctx))

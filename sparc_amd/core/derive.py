@@ -178,27 +178,32 @@ def build_params(config: EnvironmentConfig, control_mode: str, ignition: Ignitio
 
 
 def geometry_rows(heights: Sequence[float], diameters: Sequence[float], wire: WireModuleParameters,
-                  material: WireMaterial, material_params: MaterialModuleParameters, stride: int):
+                  material, material_params: MaterialModuleParameters, stride: int):
     """Per-environment geometry blocks (BASELINE config 5).  Returns
     ``(f64[GEOM_F64_COUNT, stride], i32[GEOM_I32_COUNT, stride], n_seg_max)`` as NumPy
-    arrays; padding environments repeat the last real one."""
+    arrays; padding environments repeat the last real one.  ``material``: one `WireMaterial`
+    for every environment, or a sequence of one per environment (K_COND and TUF hold the
+    material's conductivity and heat capacity)."""
     heights = np.asarray(heights, dtype=np.float64).reshape(-1)
     diameters = np.asarray(diameters, dtype=np.float64).reshape(-1)
     if heights.shape != diameters.shape:
         raise ValueError("workpiece_height and wire_diameter must have one value per environment")
     n = heights.shape[0]
+    materials = [material] * n if isinstance(material, WireMaterial) else list(material)
+    if len(materials) != n:
+        raise ValueError(f"wire material must be one WireMaterial or one per environment ({n}), got {len(materials)}")
     f64 = np.zeros((_abi.GEOM_F64_COUNT, stride), dtype=np.float64)
     i32 = np.zeros((_abi.GEOM_I32_COUNT, stride), dtype=np.int32)
     cache = {}
     for e in range(n):
-        key = (float(heights[e]), float(diameters[e]))
+        key = (float(heights[e]), float(diameters[e]), id(materials[e]))  # (`materials` holds the objects for the call)
         g = cache.get(key)
         if g is None:
             if key[0] <= 0:
                 raise ValueError("workpiece_height must be positive")
             if key[1] <= 0:
                 raise ValueError("wire_diameter must be positive")
-            g = cache[key] = derive_geometry(key[0], key[1], wire, material, material_params)
+            g = cache[key] = derive_geometry(key[0], key[1], wire, materials[e], material_params)
         f64[:, e] = (g.workpiece_height, g.kerf_base, g.cavity_coeff, g.k_cond, g.tuf, g.a_surf, g.s_area,
                      g.joule_geom)
         i32[:, e] = (g.n_seg, g.zone_start, g.az_start, g.az_end, g.contact_bottom, g.contact_top)
@@ -206,3 +211,29 @@ def geometry_rows(heights: Sequence[float], diameters: Sequence[float], wire: Wi
         f64[:, n:] = f64[:, n - 1: n]
         i32[:, n:] = i32[:, n - 1: n]
     return f64, i32, int(i32[_abi.GI32.N_SEG, :n].max())
+
+
+def material_rows(materials: Sequence[WireMaterial], index, wire: WireModuleParameters, stride: int) -> np.ndarray:
+    """Per-environment wire-material block (``enum wedm_wmat_field``): ``f64[WMAT_COUNT, stride]``, environment e holding
+    ``materials[index[e]]``.  Each value is the expression `build_params` writes into ``wedm_params`` for that material, in
+    Python floats and the same operand order; padding environments repeat the last real one."""
+    index = np.asarray(index).reshape(-1)
+    n = index.shape[0]
+    if n == 0 or n > stride:
+        raise ValueError(f"material index must have between 1 and stride={stride} entries, got {n}")
+    if not np.issubdtype(index.dtype, np.integer):
+        raise ValueError("material index must be integers")
+    if index.min() < 0 or index.max() >= len(materials):
+        raise ValueError(f"material index out of range [0, {len(materials)})")
+    W = _abi.WMAT
+    per = np.zeros((len(materials), _abi.WMAT_COUNT), dtype=np.float64)
+    for k, m in enumerate(materials):
+        per[k, W.RHO_ELEC] = float(m.electrical_resistivity)
+        per[k, W.ALPHA_RHO] = float(m.temperature_coefficient)
+        per[k, W.RHO_C] = float(m.density * m.specific_heat)  # wire.py:305-310 prefix
+        per[k, W.CRITICAL_TEMPERATURE] = float(m.melting_point * wire.critical_temp_threshold)  # wire.py:216-218
+        per[k, W.BREAKING_TEMPERATURE] = float(m.breaking_temperature)  # wire.py:220
+    rows = np.empty((_abi.WMAT_COUNT, stride), dtype=np.float64)
+    rows[:, :n] = per[index].T
+    rows[:, n:] = rows[:, n - 1: n]
+    return rows

@@ -48,6 +48,12 @@ class MaterialDatabase:
         for key, constants in table.items():
             self._wire_materials[key] = WireMaterial(name=key, **constants)
 
+    def add_wire_material(self, material: WireMaterial) -> None:
+        """Register (or replace) `material` under its name."""
+        if not isinstance(material, WireMaterial):
+            raise TypeError(f"expected a WireMaterial, got {type(material).__name__}")
+        self._wire_materials[material.name] = material
+
     def names(self):
         return sorted(self._wire_materials)
 

@@ -93,6 +93,7 @@ struct KArgs {
     unsigned long long* dbg; // diagnostic builds only (WEDM_STAMPS): per-wave phase cycle sums
     int32_t* pulse;          // wedm_bind_pulse_stats block or NULL (read by the PULSE instantiations only, via kernarg_pulse)
     const double* envp;      // wedm_bind_env_params rows or NULL (read by the ENVP instantiations only, via kernarg_envp)
+    const double* wmat;      // wedm_bind_wire_material rows or NULL (read by the MAT instantiations only, via kernarg_wmat)
 };
 
 // The by-value `cold` member as the kernels read it: through the kernarg segment (wedm_device.h).
@@ -109,6 +110,14 @@ __device__ __forceinline__ PulseRef kernarg_pulse() {
 __device__ __forceinline__ const double* wedm::kernarg_envp() {
     typedef const double* const WEDM_AS4* EnvpSlot;
     EnvpSlot p = (EnvpSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, envp));
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+
+// The per-environment wire-material rows as the MAT instantiations read them: through the kernarg segment (wedm_device.h)
+__device__ __forceinline__ const double* wedm::kernarg_wmat() {
+    typedef const double* const WEDM_AS4* WmatSlot;
+    WmatSlot p = (WmatSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, wmat));
     asm volatile("" : "+s"(p));
     return *p;
 }
@@ -224,18 +233,18 @@ __device__ __forceinline__ float stencil_pass(const TA& T, const Geom& g, const 
     return tmax;
 }
 
-// `hot`: k.hot, or (ENVP) the lane's copy with its environment's rows (envp_apply)
-template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE, bool ENVP>
+// `hot`: k.hot, or (ENVP / MAT) the lane's copy with its environment's rows (envp_apply, wmat_apply)
+template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE, bool ENVP, bool MAT = false>
 __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, const TA& T) {
     const PulseRef pulse = kernarg_pulse();
     (void)pulse;
     Persist ps;
-    init_persist(hot, cold, e, s, ps);
+    init_persist<false, MAT>(hot, cold, e, s, ps);
     StencilF64 f64c{0.0, 0.0, 0.0};
     if (F64) {
         const wedm_params* pp = cold->p;
-        f64c = StencilF64{pp->temp_ref, pp->alpha_rho,
+        f64c = StencilF64{pp->temp_ref, MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_ALPHA_RHO, cold->s.stride) : pp->alpha_rho,
                           ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_DIELECTRIC_TEMPERATURE, cold->s.stride) : pp->dielectric_temperature};
     }
     const bool tracing = WEDM_TRACING(k);
@@ -244,7 +253,7 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
     for (int it = 0; it < k.n_substeps; ++it) {
         if (!s.done) {
             const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
-            Coef c = scalar_prelude<REPLAY, false, ENVP>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
+            Coef c = scalar_prelude<REPLAY, false, ENVP, MAT>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
             float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, hot, f64c, s.h_base, s.h_zone);
             scalar_epilogue(hot, s, tmax);
@@ -259,10 +268,16 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
 }
 
 // ENVP: the every-step constants of environment e's rows (wedm_bind_env_params) instead of the uniform ones
-template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false, bool ENVP = false>
+// MAT: those of environment e's wire material (wedm_bind_wire_material), applied after the ENVP rows
+template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false, bool ENVP = false, bool MAT = false>
 __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
                                              uint32_t gid, Env& s, const TA& T) {
-    if (ENVP) {
+    if (MAT) {
+        Hot hv = k.hot;
+        if (ENVP) envp_apply(hv, cold->s.stride, e);
+        wmat_apply(hv, cold->s.stride, e);
+        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, ENVP, true>(k, hv, cold, g, e, gid, s, T);
+    } else if (ENVP) {
         Hot hv = k.hot;
         envp_apply(hv, cold->s.stride, e);
         run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, true>(k, hv, cold, g, e, gid, s, T);

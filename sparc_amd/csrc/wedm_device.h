@@ -253,6 +253,25 @@ __device__ __forceinline__ void envp_apply(Hot& h, int64_t stride, int64_t e) {
     h.max_speed = WEDM_ENVP_ROW(r, WEDM_EP_MAX_SPEED, stride);
 }
 
+// per-environment wire material (wedm_bind_wire_material, enum wedm_wmat_field): the pointer travels at the END of the
+// kernel arguments, after the ENVP pointer, and is read through the kernel-argument segment (kernarg_wmat, wedm_common.h)
+// by the MAT instantiations only.  The three rows the kernels read as `Hot` fields are copied into the lane's `Hot` once
+// per launch (wmat_apply); the three that live in the cold parameters (rho_elec, rho_c, and alpha_rho of the float64
+// stencil) are read at their point of use, in the style of WEDM_COLD_GEOM_F64.  The material's conductivity and heat
+// capacity come with the geometry rows (WEDM_G_K_COND, WEDM_G_TUF), which the any-geometry kernels read per environment.
+__device__ __forceinline__ const double* kernarg_wmat();
+#define WEDM_WMAT_ROW(rows, row, stride) ((rows)[(int64_t)(row) * (stride) + e])
+
+// The MAT instantiations' copy of `Hot`: environment e's material rows replace the uniform values, rounded to float32
+// exactly as wedm_step rounds the uniform ones.  Called once per launch by every lane, after envp_apply and before the
+// kernel pins its constants in VGPRs; `e` must be a real environment (the rows hold `stride` columns).
+__device__ __forceinline__ void wmat_apply(Hot& h, int64_t stride, int64_t e) {
+    const double* const r = kernarg_wmat();
+    h.alpha = (float)WEDM_WMAT_ROW(r, WEDM_WM_ALPHA_RHO, stride);
+    h.tcrit = (float)WEDM_WMAT_ROW(r, WEDM_WM_CRITICAL_TEMPERATURE, stride);
+    h.tbreak = (float)WEDM_WMAT_ROW(r, WEDM_WM_BREAKING_TEMPERATURE, stride);
+}
+
 __device__ __forceinline__ void pin_mechanics_in_vgprs(Hot& h) {  // the epilogue's constants only
 #define WEDM_PIN(x) asm volatile("" : "+v"(h.x))
     WEDM_PIN(dt_s); WEDM_PIN(damping_coeff); WEDM_PIN(stiffness_coeff); WEDM_PIN(omega_n);
@@ -784,17 +803,20 @@ __device__ __forceinline__ void refresh_convection(const Hot& hot, const ColdRef
 
 // once per launch: coefficients whose inputs no module changes (wire.py:304-312)
 // SCALAR_LOADS (the single-microsecond stream kernel): the uniform constants through the constant address space
-template <bool SCALAR_LOADS = false>
+// MAT: rho_c comes from the environment's wire-material row (wedm_bind_wire_material)
+template <bool SCALAR_LOADS = false, bool MAT = false>
 __device__ __forceinline__ void init_persist(const Hot& hot, const ColdRef cold, int64_t e, const Env& s, Persist& ps) {
     double adv = 0.0;
     if (__builtin_fabs(s.unwind) > 1e-6) {
         if (SCALAR_LOADS) {
             const auto pc = opaque_const(cold->p);
             const double s_area = hot.per_env_geometry ? cold->g.f64[(int64_t)WEDM_G_S_AREA * cold->s.stride + e] : pc->s_area;
-            adv = pc->rho_c * __builtin_fabs(s.unwind) * s_area;
+            const double rho_c = MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_RHO_C, cold->s.stride) : pc->rho_c;
+            adv = rho_c * __builtin_fabs(s.unwind) * s_area;
         } else {
             const double s_area = WEDM_COLD_GEOM_F64(cold, hot, WEDM_G_S_AREA, s_area);
-            adv = cold->p->rho_c * __builtin_fabs(s.unwind) * s_area;
+            const double rho_c = MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_RHO_C, cold->s.stride) : cold->p->rho_c;
+            adv = rho_c * __builtin_fabs(s.unwind) * s_area;
         }
     }
     ps.adv_on = __builtin_fabs(adv) > 1e-9;  // wire.py:115
@@ -838,7 +860,9 @@ struct QuietTry {  // what a failed quiet_prelude() hands on: the step's Philox 
 // lanes' registers (ColdParams, LaneTables): no vector load on the path a fresh spark takes.
 // ENVP: plasma efficiency and base convection come from the environment's rows (wedm_bind_env_params) where they are used;
 // the caller has put the rows of the `Hot` fields into `p` (envp_apply).
-template <bool REPLAY = false, bool SCOLD = false, bool ENVP = false>
+// MAT: the electrical resistivity of the Joule factor comes from the environment's wire-material row
+// (wedm_bind_wire_material); the caller has put the material's `Hot` fields into `p` (wmat_apply).
+template <bool REPLAY = false, bool SCOLD = false, bool ENVP = false, bool MAT = false>
 __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, Persist& ps, bool writer,
                                                const QuietTry& qt = QuietTry{W4{0u, 0u, 0u, 0u}, false},
@@ -1092,7 +1116,7 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
         cf.jf64 = 0.0;
         if (cf.joule_on) {
             const double joule_geom = p.per_env_geometry ? cc0->g.f64[(int64_t)WEDM_G_JOULE_GEOM * cc0->s.stride + e] : jg_u;
-            cf.jf64 = joule_geom * I2 * rho_elec;
+            cf.jf64 = joule_geom * I2 * (MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_RHO_ELEC, cc0->s.stride) : rho_elec);
             cf.jf = (float)cf.jf64;
         }
     }
@@ -1116,7 +1140,9 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
 // refresh), a short, or a control-step latch still sends the wave through the general path.  Bit-identical; it costs
 // registers, so batches that spark rarely run the instantiation without it.
 // ENVP: the plasma efficiency comes from the environment's row (wedm_bind_env_params), as in scalar_prelude.
-template <bool DENSE, bool ENVP = false>
+// MAT: the electrical resistivity comes from the environment's wire-material row (wedm_bind_wire_material), as in
+// scalar_prelude.
+template <bool DENSE, bool ENVP = false, bool MAT = false>
 __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold, const Geom& g, int64_t e, uint32_t gid,
                                                 Env& s, QuietTry& qt, Coef& cf) {
     qt.have_w = false;
@@ -1197,7 +1223,7 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
             const double I2 = s.I * s.I;
             cf.joule_on = I2 > 1e-6;
             if (cf.joule_on) {
-                cf.jf64 = joule_geom * I2 * rho_elec;
+                cf.jf64 = joule_geom * I2 * (MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_RHO_ELEC, cc0->s.stride) : rho_elec);
                 cf.jf = (float)cf.jf64;
             }
         }

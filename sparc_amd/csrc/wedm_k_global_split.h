@@ -9,7 +9,10 @@
 // ENVP: the instantiation with per-environment physics rows (wedm_bind_env_params): every launch with the rows bound that
 // kernel 2's ENVP form does not take (a trace sample, stencil_mode 1, injected variates, pulse statistics, single
 // microseconds, forced kernel 1)
-template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false, bool ENVP = false>
+// MAT: the instantiation with per-environment wire material (wedm_bind_wire_material), with or without ENVP: every launch
+// with the rows bound that kernel 2's MAT form does not take (a trace sample, stencil_mode 1, pulse statistics, single
+// microseconds, forced kernel 1); never with injected variates
+template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false, bool ENVP = false, bool MAT = false>
 __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     const ColdRef cold = kernarg_cold();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -32,7 +35,7 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
     load_geom(k.hot, cold, e, g);
-    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE, ENVP>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
+    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE, ENVP, MAT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
     if (WEDM_REWARD_ON(cold)) {
         if (!frozen) write_reward(cold, e, s);
         else cold->s.reward[e] = 0.0f;

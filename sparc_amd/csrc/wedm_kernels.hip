@@ -69,10 +69,11 @@ using namespace wedm;
 // part 2: wedm_step_fused<L, TRACE, FROZEN_OK, N1>, and stencil_mode 1 on the tile walk: <L, TRACE, FROZEN_OK = true, N1 = false, F64 = true>
 #define WEDM_P2(X, L) WEDM_BOOLS3(X, wedm_step_fused, L) \
                       X(wedm_step_fused<L, false, true, false, true>) X(wedm_step_fused<L, true, true, false, true>)
-// part 3: wedm_step_lanes_pk<L, TRACE>, its PULSE and ENVP forms (float32 stencil, no trace sample); the served kernels
+// part 3: wedm_step_lanes_pk<L, TRACE>, its PULSE, ENVP and MAT forms (float32 stencil, no trace sample); the served kernels
 // (wedm_served.h) <L, EXTRA>, wedm_step_lanes_served<L>, wedm_step_regs_served
 #define WEDM_P3(X, L) X(wedm_step_lanes_pk<L, false>) X(wedm_step_lanes_pk<L, true>) \
-                      X(wedm_step_lanes_pk<L, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true>)
+                      X(wedm_step_lanes_pk<L, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true>) \
+                      X(wedm_step_lanes_pk<L, false, false, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true, true>)
 // part 4: stencil_mode 1 on kernel 2 <L, TRACE, F64 = true> and on the stream kernel's single-microsecond instantiation
 // <L, false, 64, ONE = true, F64 = true>; the register kernel <128, L, TRACE, F64 = true> and its PULSE form; the wide
 // register kernel <16, L, CUT, TRACE, F64 = true, MINB> (a traced launch runs the CUT form, as in float32; MINB = 1 for a
@@ -265,6 +266,7 @@ struct wedm_ctx {
     int64_t trace_us = 0, trace_count = 0;
     int32_t* pulse = nullptr;          // wedm_bind_pulse_stats: [WEDM_PULSE_COUNT][stride] or NULL
     const double* envp = nullptr;      // wedm_bind_env_params: [WEDM_ENVP_COUNT][stride] or NULL
+    const double* wmat = nullptr;      // wedm_bind_wire_material: [WEDM_WMAT_COUNT][stride] or NULL
     std::string err;
     std::string last_kernel;
     LaunchPlan plans[2][2][2];         // [single microsecond][trace point][frozen-lane tile code]: cached launch decisions
@@ -510,7 +512,8 @@ static int served_lanes(const wedm_ctx* c) {
 }
 
 // forms of a family beyond the float32 stencil: the kernels with a float64-typed (stencil_mode 1), a pulse-counting
-// (wedm_bind_pulse_stats) and a per-environment-rows (wedm_bind_env_params) instantiation
+// (wedm_bind_pulse_stats), a per-environment-rows (wedm_bind_env_params) and a per-environment-material
+// (wedm_bind_wire_material) instantiation
 static constexpr uint32_t kernels(std::initializer_list<Kernel> ks) {
     uint32_t m = 0;
     for (const Kernel k : ks) m |= 1u << k;
@@ -519,6 +522,7 @@ static constexpr uint32_t kernels(std::initializer_list<Kernel> ks) {
 static constexpr uint32_t F64_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_FUSED, K_STREAM, K_REGS, K_WIDE, K_LANES});
 static constexpr uint32_t PULSE_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_REGS, K_WIDE});
 static constexpr uint32_t ENVP_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK});
+static constexpr uint32_t MAT_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK});
 
 struct Choice {
     Kernel kernel = K_AUTO;
@@ -530,7 +534,7 @@ struct Choice {
 static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     const wedm_params& P = ctx->p;
     const bool uniform = uniform_geometry(ctx), f64 = P.stencil_mode != 0, replay = ctx->replay != nullptr;
-    const bool pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
+    const bool pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr, mat = ctx->wmat != nullptr;
     // kernel 3 (one chunk per lane) and kernel 4 (two packed chunks per lane, table of 2L chunks).
     // Auto-selection by a small cost model fitted to measurements:
     //   cycles per step ~ rounds * (4500 + tiles_per_lane * 8 * cell_cost),  tiles_per_lane: see eff_tiles,
@@ -587,6 +591,12 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
 
     // the caller's kernel, and what refuses it outright
     int32_t forced = ctx->variant;
+    // per-environment wire material: kernels 1 and 2 only (the other families take uniform geometry, or have no MAT form),
+    // and no injected variates
+    if (mat && replay)
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) and a per-environment wire material (wedm_bind_wire_material) cannot be combined");
+    if (mat && !((MAT_FORMS >> forced) & 1u))
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with a per-environment wire material bound (wedm_bind_wire_material) only kernels 0 (auto), 1 and 2 run");
     if (replay) {
         if (forced != K_AUTO && forced != K_GLOBAL)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) run on kernel 1 only");
@@ -608,20 +618,22 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
 
     int32_t v = forced;
-    if (pulse || envp) {
+    if (pulse || envp || mat) {
         // bound rows: the float32 stencil without a trace sample or injected variates runs the caller's kernel, and a fused
         // launch under auto what the automatic choice takes among the forms there are (pulse: 8 or 7, else kernel 2's packed
-        // form; envp: kernel 2's packed form); every other launch runs kernel 1, and so does every launch with both bound
-        // (kernel 2's ENVP form counts no pulses)
+        // form; envp, mat: kernel 2's packed form); every other launch runs kernel 1, and so does every launch with pulse
+        // statistics and rows bound (kernel 2's ENVP and MAT forms count no pulses)
         const bool fast = !tr && !f64 && !replay;
         v = fast ? forced : K_GLOBAL;
         if (v == K_AUTO && !single) v = pulse && wide_auto ? K_WIDE : pulse && regs_auto ? K_REGS : use_pk ? K_LANES_PK : K_GLOBAL;
         if (v == K_AUTO) v = K_GLOBAL;
         if (v == K_LANES_PK && !use_pk && pulse)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
-        if (v == K_LANES_PK && !use_pk)
+        if (v == K_LANES_PK && !use_pk && envp)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
-        if (envp && pulse) v = K_GLOBAL;
+        if (v == K_LANES_PK && !use_pk)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with a per-environment wire material bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+        if ((envp || mat) && pulse) v = K_GLOBAL;
     } else if (v == K_AUTO) {
         // (stencil_mode 1, single microseconds: the stream kernel where the float32 launch takes it too and every tile of
         // the table has register-walk code)
@@ -719,19 +731,22 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     if (int32_t rc = choose_kernel(ctx, single, tr, ch)) return rc;
     const int L = ch.lanes, n = ctx->num_envs;
     const bool f64 = ctx->p.stencil_mode != 0, replay = ctx->replay != nullptr, pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
+    const bool mat = ctx->wmat != nullptr;  // (never with injected variates, never with pulse statistics on kernel 2: choose_kernel)
     const WalkInfo* w = nullptr;  // the walk table the launch reads
     bool fz = false;              // the FROZEN_OK instantiation (named in the kernel string)
     const void* fn = nullptr;
     int grid = blocks(n, 256 / std::max(L, 1)), block = 256;
     size_t fl = 0;
     switch (ch.kernel) {
-        case K_GLOBAL:  // injected variates / stencil_mode 1 / the float32 stencil, each with PULSE and ENVP forms
+        case K_GLOBAL:  // injected variates / stencil_mode 1 / the float32 stencil, each with PULSE and ENVP forms; MAT forms
             fn = replay ? with_flags([](auto t, auto p, auto e) { return (const void*)wedm_step_global<t, false, true, p, e>; }, tr, pulse, envp)
+               : mat    ? with_flags([](auto t, auto d, auto p, auto e) { return (const void*)wedm_step_global<t, d, false, p, e, true>; }, tr, f64, pulse, envp)
                         : with_flags([](auto t, auto d, auto p, auto e) { return (const void*)wedm_step_global<t, d, false, p, e>; }, tr, f64, pulse, envp);
             break;
         case K_LANES_PK:
             fl = lanes_pk_lds(ctx, L);
-            fn = pulse ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, true>; })
+            fn = mat   ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto e) { return (const void*)wedm_step_lanes_pk<l, false, false, false, e, true>; }, envp)
+               : pulse ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, true>; })
                : envp  ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, false, true>; })
                        : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_lanes_pk<l, t, d>; }, tr, f64);
             break;
@@ -823,9 +838,9 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     char lanes_s[16] = "", lds_s[32] = "";
     if (L) std::snprintf(lanes_s, sizeof(lanes_s), "<%d>", L);
     if (fl) std::snprintf(lds_s, sizeof(lds_s), ",%zuB", fl);
-    std::snprintf(out.name, sizeof(out.name), "%s%s%s%s%s<<<%d,%d%s>>>", kernel_names[ch.kernel], lanes_s,
+    std::snprintf(out.name, sizeof(out.name), "%s%s%s%s%s%s<<<%d,%d%s>>>", kernel_names[ch.kernel], lanes_s,
                   replay ? "[injected variates]" : f64 ? "[f64 stencil]" : fz ? "[frozen lanes ok]" : "", pulse ? "[pulse]" : "",
-                  envp ? "[envp]" : "", grid, block, lds_s);
+                  envp ? "[envp]" : "", mat ? "[wmat]" : "", grid, block, lds_s);
     out.fn = fn;
     out.grid = grid;
     out.block = block;
@@ -1053,6 +1068,16 @@ int32_t wedm_bind_env_params(wedm_ctx* ctx, const double* rows) {
     return WEDM_OK;
 }
 
+int32_t wedm_bind_wire_material(wedm_ctx* ctx, const double* rows) {
+    if (!ctx) return WEDM_ERR_BAD_ARG;
+    // the material's conductivity and heat capacity live in the geometry rows (WEDM_G_K_COND, WEDM_G_TUF)
+    if (rows && !(ctx->p.per_env_geometry && ctx->geom_bound))
+        return fail(ctx, WEDM_ERR_NOT_BOUND, "wedm_bind_wire_material: needs per-environment geometry (per_env_geometry and wedm_bind_geometry): the geometry rows hold the material's conductivity and heat capacity");
+    ctx->wmat = rows;
+    ctx->invalidate_plans();
+    return WEDM_OK;
+}
+
 int32_t wedm_set_kernel(wedm_ctx* ctx, int32_t variant) {
     if (!ctx) return WEDM_ERR_BAD_ARG;
     if (variant < 0 || variant > 12) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_set_kernel: variant must be 0..12");
@@ -1150,6 +1175,7 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
     k.dbg = ctx->dbg;
     k.pulse = ctx->pulse;
     k.envp = ctx->envp;
+    k.wmat = ctx->wmat;
     k.trace = ctx->trace;
     k.trace_next = INT32_MAX;
     k.trace_slot = 0;

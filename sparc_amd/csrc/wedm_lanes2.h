@@ -182,13 +182,18 @@ __device__ __forceinline__ float lanes_pk_step(float* col, const LanesPkGeom& q,
 // PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
 // ENVP: the instantiation with per-environment physics rows (wedm_bind_env_params; float32 stencil, no trace sample): each
 // lane's `hv` takes its environment's rows once per launch, the pinned constants become per-lane VGPR values.
-template <int L, bool TRACE, bool F64 = false, bool PULSE = false, bool ENVP = false>
+// MAT: the instantiation with per-environment wire material (wedm_bind_wire_material; float32 stencil, no trace sample, no
+// pulse statistics), with or without ENVP: `hv` takes the material's alpha / tcrit / tbreak after the ENVP rows, rho_c and
+// rho_elec are read from the rows where they are used.
+template <int L, bool TRACE, bool F64 = false, bool PULSE = false, bool ENVP = false, bool MAT = false>
 __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
-    if (ENVP) {
+    if (ENVP || MAT) {
         const int64_t ee = (int64_t)blockIdx.x * (256 / L) + threadIdx.x / L;
-        envp_apply(hv, cold->s.stride, ee < k.num_envs ? ee : 0);  // (a lane past the batch reads environment 0's rows)
+        const int64_t er = ee < k.num_envs ? ee : 0;  // (a lane past the batch reads environment 0's rows)
+        if (ENVP) envp_apply(hv, cold->s.stride, er);
+        if (MAT) wmat_apply(hv, cold->s.stride, er);
     }
     pin_mechanics_in_vgprs(hv);
     pin_quiet_in_vgprs(hv);
@@ -227,12 +232,12 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     const bool frozen0 = s.done;
     if (!s.done) {
         s.ipk = peak_current(cold, s.mode, e);
-        init_persist(k.hot, cold, e, s, ps);
+        init_persist<false, MAT>(k.hot, cold, e, s, ps);
     }
     const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
     const int baseA = 2 * c * Cv, baseB = baseA + Cv;  // first wire cell of each virtual chunk
     const int n = g.n_seg;                              // this lane's environment
-    const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = ENVP ? hv.tdiel : k.hot.tdiel;
+    const float spool = k.hot.spool, tref = k.hot.tref, alpha = MAT ? hv.alpha : k.hot.alpha, tdiel = ENVP ? hv.tdiel : k.hot.tdiel;
     if (c == 0) col[0] = spool;  // wire cell 0 (row 0 of lane 0's chunk A) is held at the spool temperature
 
     // which of this lane's virtual chunks holds wire cell i (0: none, 1: A, 2: B)
@@ -257,8 +262,8 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE, ENVP>(hv, cold, g, e, gid, s, qt, cf);
-        if (!was_quiet && !s.done) cf = scalar_prelude<false, false, ENVP>(hv, cold, g, e, gid, s, ps, c == 0, qt);
+        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE, ENVP, MAT>(hv, cold, g, e, gid, s, qt, cf);
+        if (!was_quiet && !s.done) cf = scalar_prelude<false, false, ENVP, MAT>(hv, cold, g, e, gid, s, ps, c == 0, qt);
         freeze_wire(s);
         const bool keep = !s.done;
 

@@ -279,6 +279,9 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
         }
         WEDM_SV_PHASE(pb);  // wait for and apply the previous step's monitor
         // ---- can this step break the wire?
+        // (the proof reads the uniform tbreak / alpha and the uniform kf / tuf: the served kernels take uniform geometry only,
+        // so with a per-environment wire material bound -- which needs per-environment geometry -- they are never reached;
+        // choose_kernel refuses them by name)
         const float Mb = fmaxf(M, tdiel);
         const float conv_max = fmaxf(ps.conv_base, ps.conv_zone);
         const bool scheme_ok = kf >= 0.0f && tuf > 0.0f && alpha >= 0.0f && ps.conv_base >= 0.0f && ps.conv_zone >= 0.0f &&

@@ -21,6 +21,7 @@ Documented deviations from the single-environment reference:
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 from typing import Any, Callable, Dict, Optional, Tuple
 
@@ -153,6 +154,8 @@ class WireEDMEnv:
         freeze_terminated: bool = True,
         pulse_stats: bool = False,
         env_params: Optional[Dict[str, Any]] = None,
+        wire_material=None,
+        wire_material_table=None,
         backend: Optional[Callable] = None,
     ):
         """Beyond the reference's keywords (wire_edm.py:22-34):
@@ -187,8 +190,22 @@ class WireEDMEnv:
         convection, servo dynamics) to a scalar or one value per environment (sequence, NumPy array or tensor).  Names
         not given keep the uniform dataclass value.  The named set is fixed for the environment's life; the values can
         be changed between launches with `set_env_params` and read with `get_env_params`.  The random-short
-        parameters, crater / current tables, material properties and geometry are not in the set (geometry has its own
-        per-environment keywords).  Needs a backend with ``bind_env_params`` (the HIP library)."""
+        parameters, crater / current tables, material properties and geometry are not in the set (geometry and the wire
+        material have their own per-environment keywords).  Needs a backend with ``bind_env_params`` (the HIP library).
+        ``wire_material``: one wire material per environment -- a sequence of ``num_envs`` material names (looked up in
+        `get_material_db()`) or `WireMaterial` objects.  The distinct materials, in order of first appearance, form
+        ``env.wire_materials``, fixed for the environment's life; `set_wire_material` moves environments between them
+        between launches (mid-episode too: the next launch steps the same wire temperatures with the new material), and
+        `get_wire_material_index` reads the current choice.  ``config.wire_material`` stays the material of the uniform
+        parameters, and ``env.wire_material`` (and ``env.wire.wire_material``) keep reporting it: the per-environment
+        materials are ``env.wire_materials[env.get_wire_material_index()]``.  Implies per-environment geometry (the
+        geometry rows carry the material's conductivity and heat capacity), even with uniform height and diameter: as for
+        any per-environment geometry, ``zone_mean_temperature()`` and the ``wire_average_temperature`` signal are then not
+        available.  Combines with ``workpiece_height`` / ``wire_diameter``, ``env_params``, ``pulse_stats``,
+        ``stencil_dtype``, ``autoreset`` and ``reward``.  Needs a backend with ``bind_wire_material`` (the HIP library).
+        ``wire_material_table``: the materials of ``env.wire_materials`` in a fixed order (names or `WireMaterial`
+        objects), so that indices mean the same materials in several environments (the shards of one batch); every
+        entry of ``wire_material`` must be one of them."""
         self.render_mode = render_mode
         if mechanics_control_mode not in ["position", "velocity"]:
             raise ValueError(f"mechanics_control_mode must be 'position' or 'velocity', got {mechanics_control_mode}")
@@ -239,10 +256,20 @@ class WireEDMEnv:
                                  f"{getattr(backend, '__name__', backend)!r} has none")
             env_params = dict(env_params)
             envp.check_names(env_params)
+        if wire_material is not None:
+            if backend is not None and not hasattr(backend, "bind_wire_material"):
+                raise ValueError(f"wire_material needs a backend that reads per-environment wire-material rows "
+                                 f"(bind_wire_material); {getattr(backend, '__name__', backend)!r} has none")
+            self.wire_materials, mat_index = _material_table(wire_material, self.num_envs, wire_material_table)
+        elif wire_material_table is not None:
+            raise ValueError("wire_material_table needs wire_material=[...]")
+        else:
+            self.wire_materials, mat_index = (), None
+        self._wmat_rows = None  # float64 [WMAT_COUNT, stride] device rows of the current materials (wire_material=)
 
         # ---- geometry: uniform (reference behaviour) or one (h, d) pair per environment
         stride = (self.num_envs + 63) // 64 * 64
-        self.per_env_geometry = workpiece_height is not None or wire_diameter is not None
+        self.per_env_geometry = workpiece_height is not None or wire_diameter is not None or mat_index is not None
         if self.per_env_geometry:
             h = np.broadcast_to(np.asarray(self.config.workpiece_height if workpiece_height is None
                                            else _to_numpy(workpiece_height), dtype=np.float64), (self.num_envs,))
@@ -254,6 +281,8 @@ class WireEDMEnv:
             self._geom_f64 = torch.from_numpy(gf).to(self.device)
             self._geom_i32 = torch.from_numpy(gi).to(self.device)
             self.n_segments = n_seg_max
+            if mat_index is not None:
+                self._init_wire_material(h, d, mat_index, stride)
         else:
             self.geometry = derive.derive_geometry(self.config.workpiece_height, self.config.wire_diameter,
                                                    self.wire_params, self.wire_material, self.material_params)
@@ -291,6 +320,8 @@ class WireEDMEnv:
         if env_params is not None:
             self._init_env_params(env_params, stride)
             self._backend.bind_env_params(self._envp_rows.data_ptr())
+        if mat_index is not None:
+            self._backend.bind_wire_material(self._wmat_rows.data_ptr())
 
         # what remains of the reference's module objects: parameters + read-only helpers
         from ..modules.views import DielectricView, IgnitionView, MaterialView, MechanicsView, WireView
@@ -590,18 +621,90 @@ class WireEDMEnv:
             raise RuntimeError("construct the environment with env_params={...} to randomise physics parameters")
         return {name: self._envp_src[envp.INDEX[name], : self.num_envs].clone() for name in envp.NAMES}
 
+    # ---- per-environment wire material (domain randomisation) --------------------------------------
+    def _init_wire_material(self, h, d, index: np.ndarray, stride: int) -> None:
+        """Every material's full row set, built once: the float64 geometry rows with that material's K_COND / TUF
+        ([M, GEOM_F64_COUNT, stride]) and its five material rows ([M, WMAT_COUNT, stride]).  A switch is a device-side
+        column select from these tables (`set_wire_material`): exact by construction, no arithmetic."""
+        M = len(self.wire_materials)
+        geom = [derive.geometry_rows(h, d, self.wire_params, m, self.material_params, stride)[0] for m in self.wire_materials]
+        mats = [derive.material_rows(self.wire_materials, np.full(self.num_envs, k), self.wire_params, stride) for k in range(M)]
+        self._wmat_geom_table = torch.from_numpy(np.stack(geom)).to(self.device)
+        self._wmat_table = torch.from_numpy(np.stack(mats)).to(self.device)
+        self._wmat_index = torch.zeros(stride, dtype=torch.int64, device=self.device)
+        self._wmat_rows = torch.empty((_abi.WMAT_COUNT, stride), dtype=torch.float64, device=self.device)
+        self.set_wire_material(index)
+
+    def set_wire_material(self, index, mask=None) -> None:
+        """Move environments to other materials of ``env.wire_materials``, taking effect at the next launch.  ``index`` is a
+        scalar or one index per environment (host values or a device tensor); ``mask`` (bool per environment) limits the
+        change to the environments where it is set.  The wire temperatures, and every other state, carry over: a switch
+        in mid-episode steps on from the current state with the new material's constants.  Host indices are checked;
+        device tensors are applied on the device with no host synchronisation -- an entry outside ``[0,
+        len(wire_materials))`` there leaves its environment's material as it was."""
+        if self._wmat_rows is None:
+            raise RuntimeError("construct the environment with wire_material=[...] to give environments their own wire material")
+        n, M = self.num_envs, len(self.wire_materials)
+        if torch.is_tensor(index) and index.device.type != "cpu":
+            idx = index.detach().to(device=self.device, dtype=torch.int64).reshape(-1)
+            if idx.numel() == 1:
+                idx = idx.expand(n)
+            if idx.shape != (n,):
+                raise ValueError(f"wire material index must be a scalar or have one entry per environment ({n})")
+            idx = torch.where((idx >= 0) & (idx < M), idx, self._wmat_index[:n])
+        else:
+            a = np.asarray(index.detach().numpy() if torch.is_tensor(index) else index).reshape(-1)
+            if a.size == 1:
+                a = np.broadcast_to(a, (n,))
+            if a.shape != (n,):
+                raise ValueError(f"wire material index must be a scalar or have one entry per environment ({n})")
+            if not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("wire material index must be integers")
+            if a.min() < 0 or a.max() >= M:
+                raise ValueError(f"wire material index out of range [0, {M}) (env.wire_materials: "
+                                 f"{[m.name for m in self.wire_materials]})")
+            idx = torch.from_numpy(a.astype(np.int64)).to(self.device)
+        if mask is not None:
+            m = torch.as_tensor(mask, device=self.device).reshape(-1).to(torch.bool)
+            if m.shape != (n,):
+                raise ValueError(f"mask must have one entry per environment ({n})")
+            idx = torch.where(m, idx, self._wmat_index[:n])
+        cur = self._wmat_index
+        cur[:n].copy_(idx)
+        cur[n:].copy_(cur[n - 1: n].expand(cur.shape[0] - n))  # padding columns repeat the last environment
+        for table, dst in ((self._wmat_geom_table, self._geom_f64), (self._wmat_table, self._wmat_rows)):
+            dst.copy_(torch.gather(table, 0, cur.view(1, 1, -1).expand(1, table.shape[1], -1))[0])
+
+    def get_wire_material_index(self) -> torch.Tensor:
+        """Each environment's current material, an index into ``env.wire_materials`` (int64 [num_envs] device copy)."""
+        if self._wmat_rows is None:
+            raise RuntimeError("construct the environment with wire_material=[...] to give environments their own wire material")
+        return self._wmat_index[: self.num_envs].clone()
+
     # ---- checkpoint / resume (SURVEY.md §5: the reference has none for simulation state) ---------
     def _physics_fingerprint(self) -> str:
         """sha256 over everything that determines the physics of a continuation: the whole
         `wedm_params` block the kernels receive (configuration, module parameters, derived constants,
-        control mode, shard offset) and, with per-environment geometry, the geometry rows."""
+        control mode, shard offset) and, with per-environment geometry, the geometry rows -- with
+        per-environment wire material the fixed per-material row table instead of the current float64
+        rows, which change when an environment switches material (the choice is checkpointed itself)."""
         import ctypes
         import hashlib
 
         h = hashlib.sha256(ctypes.string_at(ctypes.addressof(self.params), ctypes.sizeof(self.params)))
         if self.per_env_geometry:
-            h.update(self._geom_f64.cpu().numpy().tobytes())
+            if self._wmat_rows is not None:
+                h.update(self._wire_material_fingerprint().encode())
+            else:
+                h.update(self._geom_f64.cpu().numpy().tobytes())
             h.update(self._geom_i32.cpu().numpy().tobytes())
+        return h.hexdigest()
+
+    def _wire_material_fingerprint(self) -> str:
+        import hashlib
+
+        h = hashlib.sha256(self._wmat_geom_table.cpu().numpy().tobytes())
+        h.update(self._wmat_table.cpu().numpy().tobytes())
         return h.hexdigest()
 
     def state_dict(self) -> Dict[str, Any]:
@@ -612,7 +715,13 @@ class WireEDMEnv:
         return {"abi_version": _abi.ABI_VERSION, "blocks": self.state.clone_blocks(), "seed": self._seed, "num_envs": self.num_envs,
                 "n_segments": self.n_segments, "env_id_offset": self.env_id_offset, "pulse_stats": self.pulse_stats,
                 "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint(),
-                **self._env_params_state()}
+                **self._env_params_state(), **self._wire_material_state()}
+
+    def _wire_material_state(self) -> Dict[str, Any]:
+        if self._wmat_rows is None:
+            return {"wire_materials": None}
+        return {"wire_materials": [m.name for m in self.wire_materials], "wire_material_table": self._wire_material_fingerprint(),
+                "wire_material_index": self._wmat_index[: self.num_envs].detach().cpu().clone()}
 
     def _env_params_state(self) -> Dict[str, Any]:
         if self._envp_rows is None:
@@ -634,6 +743,13 @@ class WireEDMEnv:
         if (list(theirs) if theirs is not None else None) != mine:
             raise ValueError(f"checkpoint was taken with per-environment physics parameters {theirs}, this environment "
                              f"randomises {mine}")
+        mine_m = [m.name for m in self.wire_materials] if self._wmat_rows is not None else None
+        theirs_m = sd.get("wire_materials")
+        if (list(theirs_m) if theirs_m is not None else None) != mine_m or \
+                (mine_m is not None and sd.get("wire_material_table") != self._wire_material_fingerprint()):
+            raise ValueError(f"checkpoint was taken with per-environment wire materials {theirs_m}, this environment has "
+                             f"{mine_m}" + (" (same names, different constants or geometry)" if theirs_m == mine_m else "")
+                             + ": the material table differs")
         if sd.get("physics") != self._physics_fingerprint():
             raise ValueError("checkpoint was taken with different physics (configuration, module parameters, control "
                              "mode or per-environment geometry): continuing would silently change the trajectory")
@@ -642,10 +758,16 @@ class WireEDMEnv:
                 if tuple(sd[key].shape) != tuple(dst.shape):
                     raise ValueError(f"checkpoint block {key!r} has shape {tuple(sd[key].shape)}, this environment's is "
                                      f"{tuple(dst.shape)}")
+        if mine_m is not None:
+            idx = sd["wire_material_index"]
+            if tuple(idx.shape) != (self.num_envs,):
+                raise ValueError(f"checkpoint block 'wire_material_index' has shape {tuple(idx.shape)}, expected ({self.num_envs},)")
         self.state.load_blocks(sd["blocks"])
         if mine is not None:
             self._envp_src.copy_(sd["env_params_src"])
             self._envp_rows.copy_(sd["env_params_rows"])
+        if mine_m is not None:
+            self.set_wire_material(sd["wire_material_index"].numpy())
         self._seed = int(sd["seed"])
         self.steps_since_reset = int(sd["steps_since_reset"])
 
@@ -736,6 +858,55 @@ class WireEDMEnv:
     def wire_diameter(self) -> float:
         return self.config.wire_diameter
 
+
+
+def _material_table(wire_material, n: int, table=None):
+    """(materials of ``env.wire_materials``, int64 index per environment) of a ``wire_material=`` argument.  ``table``: the
+    materials in a fixed order (``wire_material_table=``; every entry must be one of them); default: the distinct ones, in
+    order of first appearance."""
+    from ..core.material_db import WireMaterial
+
+    if isinstance(wire_material, (str, WireMaterial)):
+        raise ValueError(f"wire_material must be a sequence of num_envs={n} names or WireMaterial objects "
+                         f"(one material for the whole batch: EnvironmentConfig(wire_material=...))")
+    items = list(wire_material)
+    if len(items) != n:
+        raise ValueError(f"wire_material has {len(items)} entries, expected one per environment ({n})")
+    db = get_material_db()
+    fixed = table is not None
+    table = [] if table is None else [db.get_wire_material(str(m)) if isinstance(m, (str, np.str_)) else m for m in table]
+    keys = {}
+    for k, m in enumerate(table):
+        if not isinstance(m, WireMaterial):
+            raise ValueError(f"wire_material_table[{k}] must be a material name or a WireMaterial, got {type(m).__name__}")
+        if any(o.name == m.name for o in table[:k]):
+            raise ValueError(f"wire_material_table names {m.name!r} twice")
+        keys[dataclasses.astuple(m)] = k
+    index = np.empty(n, dtype=np.int64)
+    seen = {}  # id of an item object / a name -> table index (one lookup per distinct item, not per environment)
+    for e, item in enumerate(items):
+        tag = str(item) if isinstance(item, (str, np.str_)) else id(item)
+        k = seen.get(tag)
+        if k is None:
+            if isinstance(item, WireMaterial):
+                mat = item
+            elif isinstance(item, (str, np.str_)):
+                mat = db.get_wire_material(str(item))
+            else:
+                raise ValueError(f"wire_material[{e}] must be a material name or a WireMaterial, got {type(item).__name__}")
+            key = dataclasses.astuple(mat)
+            k = keys.get(key)
+            if k is None:
+                if fixed:
+                    raise ValueError(f"wire_material[{e}] ({mat.name!r}) is not in wire_material_table "
+                                     f"{[m.name for m in table]}")
+                if any(m.name == mat.name for m in table):
+                    raise ValueError(f"wire_material names two different materials {mat.name!r}")
+                k = keys[key] = len(table)
+                table.append(mat)
+            seen[tag] = k
+        index[e] = k
+    return tuple(table), index
 
 
 def _to_numpy(x):

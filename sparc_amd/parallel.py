@@ -17,7 +17,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .envs.wire_edm import DeviceAction, WireEDMEnv
+from .envs.wire_edm import DeviceAction, WireEDMEnv, _material_table
 
 
 def _slice_leaf(x, lo: int, hi: int, total: int):
@@ -39,7 +39,7 @@ class ShardedWireEDMEnv:
     """
 
     def __init__(self, global_num_envs: int, *, process_group: Optional[Any] = None, device: Any = None,
-                 workpiece_height=None, wire_diameter=None, env_params=None, **env_kwargs):
+                 workpiece_height=None, wire_diameter=None, env_params=None, wire_material=None, **env_kwargs):
         if not dist.is_initialized():
             raise RuntimeError("ShardedWireEDMEnv needs torch.distributed.init_process_group first")
         self.group = process_group
@@ -50,12 +50,17 @@ class ShardedWireEDMEnv:
         self.global_num_envs = int(global_num_envs)
         self.num_envs = self.global_num_envs // self.world_size
         self.lo, self.hi = self.rank * self.num_envs, (self.rank + 1) * self.num_envs
+        # one material per GLOBAL environment; every rank gets the whole batch's table (distinct materials in order of first
+        # appearance), so a material index means the same material on every rank
+        mats, mat_index = (None, None) if wire_material is None else _material_table(wire_material, self.global_num_envs)
         self.env = WireEDMEnv(
             num_envs=self.num_envs, device=device, env_id_offset=self.lo,
             workpiece_height=_slice_leaf(workpiece_height, self.lo, self.hi, self.global_num_envs),
             wire_diameter=_slice_leaf(wire_diameter, self.lo, self.hi, self.global_num_envs),
             env_params=None if env_params is None else
             {k: _slice_leaf(v, self.lo, self.hi, self.global_num_envs) for k, v in env_params.items()},
+            wire_material=None if wire_material is None else [mats[k] for k in mat_index[self.lo:self.hi]],
+            wire_material_table=None if wire_material is None else mats,
             **env_kwargs)
         self.device = self.env.device
         self.state = self.env.state
@@ -75,6 +80,12 @@ class ShardedWireEDMEnv:
         """`WireEDMEnv.set_env_params` with values / mask given for the GLOBAL batch (or scalars)."""
         cut = lambda x: _slice_leaf(x, self.lo, self.hi, self.global_num_envs)  # noqa: E731
         self.env.set_env_params({k: cut(v) for k, v in values.items()}, mask=cut(mask))
+
+    def set_wire_material(self, index, mask=None) -> None:
+        """`WireEDMEnv.set_wire_material` with indices / mask given for the GLOBAL batch (or a scalar); the indices refer to
+        the whole batch's table, which every rank's `env.wire_materials` holds in the same order."""
+        cut = lambda x: _slice_leaf(x, self.lo, self.hi, self.global_num_envs)  # noqa: E731
+        self.env.set_wire_material(cut(index), mask=cut(mask))
 
     def make_action(self, servo=0.0, target_voltage=80.0, current_mode=5, ON_time=3.0, OFF_time=80.0) -> DeviceAction:
         cut = lambda x: _slice_leaf(x, self.lo, self.hi, self.global_num_envs)  # noqa: E731

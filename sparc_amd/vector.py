@@ -47,6 +47,17 @@ def uniform_param_sampler(ranges: Dict[str, Tuple[float, float]], generator: Opt
     return sample
 
 
+def uniform_material_sampler(generator: Optional[torch.Generator] = None):
+    """A `material_sampler` for `WireEDMVectorEnv`: every environment draws one of ``env.wire_materials`` uniformly, on the
+    environment's device (``generator`` must live there when given)."""
+
+    def sample(env: WireEDMEnv, reset_mask: torch.Tensor) -> torch.Tensor:
+        return torch.randint(0, len(env.wire_materials), (env.num_envs,), generator=generator, device=env.device,
+                             dtype=torch.int64)
+
+    return sample
+
+
 class WireEDMVectorEnv:
     """Next-step autoreset (Gymnasium's ``AutoresetMode.NEXT_STEP``): the `step()` after the one that
     reported ``terminated`` / ``truncated`` for an environment starts a new episode for it.
@@ -59,7 +70,7 @@ class WireEDMVectorEnv:
     a torch expression."""
 
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
-                 reward=None, param_sampler: Optional[Callable] = None):
+                 reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -69,7 +80,11 @@ class WireEDMVectorEnv:
         every `step()` before the launch (and at `reset()` with every environment marked); the values are applied
         (`WireEDMEnv.set_env_params`) only where ``reset_mask`` is set, so each new episode starts with freshly drawn
         physics.  The environment must have been built with ``env_params`` naming the sampled parameters
-        (see `uniform_param_sampler`)."""
+        (see `uniform_param_sampler`).
+        ``material_sampler``: the same for the wire material -- ``f(env, reset_mask) -> int64[N] device tensor`` of indices
+        into ``env.wire_materials``, applied (`WireEDMEnv.set_wire_material`) where ``reset_mask`` is set, at the same
+        point as ``param_sampler``.  The environment must have been built with ``wire_material=[...]`` (see
+        `uniform_material_sampler`)."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
@@ -90,11 +105,14 @@ class WireEDMVectorEnv:
         self._param_sampler = param_sampler
         if param_sampler is not None and getattr(env, "_envp_rows", None) is None:
             raise ValueError("param_sampler needs an environment built with env_params={...} naming the sampled parameters")
+        self._material_sampler = material_sampler
+        if material_sampler is not None and getattr(env, "_wmat_rows", None) is None:
+            raise ValueError("material_sampler needs an environment built with wire_material=[...] listing the materials")
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
-        if self._param_sampler is not None:
+        if self._param_sampler is not None or self._material_sampler is not None:
             mask = (options or {}).get("mask")
             mask = torch.ones(self.num_envs, dtype=torch.bool, device=self.env.device) if mask is None else \
                 torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
@@ -104,11 +122,14 @@ class WireEDMVectorEnv:
         return obs.clone(), info
 
     def _apply_sampler(self, reset_mask: torch.Tensor) -> None:
-        self.env.set_env_params(self._param_sampler(self.env, reset_mask), mask=reset_mask)
+        if self._param_sampler is not None:
+            self.env.set_env_params(self._param_sampler(self.env, reset_mask), mask=reset_mask)
+        if self._material_sampler is not None:
+            self.env.set_wire_material(self._material_sampler(self.env, reset_mask), mask=reset_mask)
 
     def step(self, action):
         """One control interval for every environment (1000 us by default)."""
-        if self._param_sampler is not None and self.autoreset:
+        if (self._param_sampler is not None or self._material_sampler is not None) and self.autoreset:
             self._apply_sampler(self._need_reset)  # environments about to start a new episode draw their physics
         if self.autoreset:
             if self._in_kernel_reset:
