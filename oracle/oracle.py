@@ -185,6 +185,8 @@ def lib() -> C.CDLL:
     L.wedm_oracle_step_batch.restype = _i
     L.wedm_oracle_step_batch_ex.argtypes = L.wedm_oracle_step_batch.argtypes + [C.c_void_p, C.c_void_p]
     L.wedm_oracle_step_batch_ex.restype = _i
+    L.wedm_oracle_step_batch_wmat.argtypes = L.wedm_oracle_step_batch_ex.argtypes + [C.c_void_p]
+    L.wedm_oracle_step_batch_wmat.restype = _i
     L.wedm_oracle_max_threads.restype = _i
     _lib = L
     return L

@@ -1173,6 +1173,21 @@ static void apply_env_params(const double* rows, int64_t stride, int64_t e, wedm
 #undef EP
 }
 
+/* wedm_bind_wire_material (include/wedm_hip.h, enum wedm_wmat_field): environment e's five rows replace the uniform
+ * constants of the same name, as given.  The material's conductivity and heat capacity arrive through the geometry rows
+ * (WEDM_G_K_COND, WEDM_G_TUF), so these go after apply_geometry.  The kernels copy alpha, tcrit and tbreak into their
+ * `Hot` once per launch (wire_update casts both limits to float32 at every comparison, which is the same value) and read
+ * rho_elec and rho_c where they are used. */
+static void apply_wire_material(const double* rows, int64_t stride, int64_t e, wedm_oracle_consts* c) {
+#define WM(row) rows[(int64_t)(row) * stride + e]
+    c->rho_elec = WM(WEDM_WM_RHO_ELEC);
+    c->alpha_rho = WM(WEDM_WM_ALPHA_RHO);
+    c->rho_c = WM(WEDM_WM_RHO_C);
+    c->critical_temperature = WM(WEDM_WM_CRITICAL_TEMPERATURE);
+    c->breaking_temperature = WM(WEDM_WM_BREAKING_TEMPERATURE);
+#undef WM
+}
+
 /* What the reference driver's summary looks at in one sample (experiments/run_simulation.py:604-627): 0 = no pulse
  * (I <= 0.1 A), 1 = a spark pulse (I > 0.1 A, no short), 2 = a short pulse (I > 0.1 A during a short). */
 static int32_t pulse_kind(const wedm_oracle_env* v) {
@@ -1205,17 +1220,26 @@ static void pulse_tally(const wedm_params* p, const wedm_state_ptrs* s, int32_t*
 int32_t wedm_oracle_step_batch(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
                                const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                int32_t math_mode, int32_t stencil_mode, int32_t n_threads) {
-    return wedm_oracle_step_batch_ex(p, s, g, a, num_envs, n_seg_max, n_substeps, math_mode, stencil_mode, n_threads,
-                                     NULL, NULL);
+    return wedm_oracle_step_batch_wmat(p, s, g, a, num_envs, n_seg_max, n_substeps, math_mode, stencil_mode, n_threads,
+                                       NULL, NULL, NULL);
 }
 
 int32_t wedm_oracle_step_batch_ex(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
                                   const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                   int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
                                   int32_t* pulse) {
+    return wedm_oracle_step_batch_wmat(p, s, g, a, num_envs, n_seg_max, n_substeps, math_mode, stencil_mode, n_threads,
+                                       envp_rows, pulse, NULL);
+}
+
+int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                    const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                    int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                    int32_t* pulse, const double* wmat_rows) {
     if (!p || !s || !a || num_envs <= 0 || n_substeps < 0 || n_seg_max < 1) return WEDM_ERR_BAD_ARG;
     if (n_substeps == 0) return WEDM_OK;
     if (p->per_env_geometry && (!g || !g->f64 || !g->i32)) return WEDM_ERR_BAD_ARG;
+    if (wmat_rows && !p->per_env_geometry) return WEDM_ERR_NOT_BOUND; /* as wedm_bind_wire_material */
     int64_t stride = s->stride;
     int bad = 0;
 #ifdef _OPENMP
@@ -1251,6 +1275,7 @@ int32_t wedm_oracle_step_batch_ex(const wedm_params* p, const wedm_state_ptrs* s
                     for (int q = 0; q < WEDM_PULSE_COUNT; ++q) PULSE(q) = 0;
             }
             if (p->per_env_geometry) apply_geometry(g, stride, e, &v->c);
+            if (wmat_rows) apply_wire_material(wmat_rows, stride, e, &v->c);
             if (envp_rows) apply_env_params(envp_rows, stride, e, &v->c);
             if (v->c.n_seg > WEDM_ORACLE_MAX_SEG || v->c.n_seg < 1) { bad = 1; continue; }
             gather_env(s, e, v);

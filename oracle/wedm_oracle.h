@@ -220,6 +220,16 @@ int32_t wedm_oracle_step_batch_ex(const wedm_params* p, const wedm_state_ptrs* s
                                   const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                   int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
                                   int32_t* pulse);
+/* wedm_oracle_step_batch_ex with the third optional block (HOST pointer or NULL; NULL is exactly
+ * wedm_oracle_step_batch_ex, whose signature stays as it was for its existing callers):
+ *   wmat_rows  float64 [WEDM_WMAT_COUNT][stride], wedm_bind_wire_material: environment e's rows replace rho_elec,
+ *              alpha_rho, rho_c, critical_temperature and breaking_temperature, as given (after the per-environment
+ *              geometry, which carries the material's WEDM_G_K_COND / WEDM_G_TUF, and before envp_rows; the reset reads
+ *              none of them).  Needs wedm_params.per_env_geometry: WEDM_ERR_NOT_BOUND otherwise. */
+int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                    const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                    int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                    int32_t* pulse, const double* wmat_rows);
 int32_t wedm_oracle_max_threads(void);
 int64_t wedm_oracle_sizeof(int32_t which);
 

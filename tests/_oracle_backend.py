@@ -123,22 +123,25 @@ class OracleBackend:
 
 
 class OracleBackendRows(OracleBackend):
-    """`OracleBackend` with the C-ABI's two optional blocks: per-environment physics rows (wedm_bind_env_params) and the
-    per-interval pulse tally (wedm_bind_pulse_stats), stepped by ``wedm_oracle_step_batch_ex``.  The plain class keeps
-    refusing both (the host checks for the bind methods), so what it computes -- and what ``bench.py`` times -- is
-    unchanged."""
+    """`OracleBackend` with the C-ABI's three optional blocks: per-environment physics rows (wedm_bind_env_params), the
+    per-interval pulse tally (wedm_bind_pulse_stats) and per-environment wire material (wedm_bind_wire_material), stepped
+    by ``wedm_oracle_step_batch_wmat``.  The plain class keeps refusing all three (the host checks for the bind methods), so
+    what it computes -- and what ``bench.py`` times -- is unchanged."""
 
     name = "oracle-rows"
 
     def __init__(self, params, num_envs, n_seg_max, device):
         super().__init__(params, num_envs, n_seg_max, device)
-        self._envp, self._pulse = None, None
+        self._envp, self._pulse, self._wmat = None, None, None
 
     def bind_env_params(self, rows_ptr):
         self._envp = rows_ptr
 
     def bind_pulse_stats(self, rows_ptr):
         self._pulse = rows_ptr
+
+    def bind_wire_material(self, rows_ptr):
+        self._wmat = rows_ptr
 
     def reset(self, mask_ptr, seed, reseed, fresh=False):
         super().reset(mask_ptr, seed, reseed, fresh)
@@ -153,10 +156,12 @@ class OracleBackendRows(OracleBackend):
 
     def _run(self, n_substeps, action):
         stencil = max(int(self.stencil_mode), int(self.params.stencil_mode))
-        rc = self._L.wedm_oracle_step_batch_ex(C.byref(self.params), C.byref(self.state), C.byref(self.geom),
-                                               C.byref(action), self.num_envs, self.n_seg_max, n_substeps,
-                                               self.math_mode, stencil, self.n_threads, self._envp, self._pulse)
+        rc = self._L.wedm_oracle_step_batch_wmat(C.byref(self.params), C.byref(self.state), C.byref(self.geom),
+                                                 C.byref(action), self.num_envs, self.n_seg_max, n_substeps,
+                                                 self.math_mode, stencil, self.n_threads, self._envp, self._pulse,
+                                                 self._wmat)
         assert rc == 0, rc
 
     def last_kernel(self):
-        return "oracle" + ("[pulse]" if self._pulse is not None else "") + ("[envp]" if self._envp is not None else "")
+        return "oracle" + ("[pulse]" if self._pulse is not None else "") + ("[envp]" if self._envp is not None else "") + \
+            ("[wmat]" if self._wmat is not None else "")
