@@ -16,7 +16,7 @@
 #ifndef WEDM_FUSED_DENSE
 #define WEDM_FUSED_DENSE false
 #endif
-// the fused kernel's N1 instantiation requests a tile's LDS rows one tile ahead (see PREFETCH there)
+// the fused kernel's F_N1 form requests a tile's LDS rows one tile ahead (see PREFETCH there)
 #ifndef WEDM_FUSED_MIN_BLOCKS
 #define WEDM_FUSED_MIN_BLOCKS 2
 #endif
@@ -70,7 +70,7 @@ struct WalkTable {
     // the tile, which matters only in a microsecond in which some lane of the wave carries current.
     uint32_t kind_ne_mask, kind_nj_mask;
     // kind_n1_mask: full tiles, end cells apart all interior, with exactly ONE flag change (bit 31: at least one of them
-    // changes the ZONE flag, i.e. is a boundary tile in every microsecond): the N1 instantiation of wedm_step_fused runs
+    // changes the ZONE flag, i.e. is a boundary tile in every microsecond): the F_N1 form of wedm_step_fused runs
     // them stage-major with per-cell coefficients, without a boundary tile's predicated stores and maxima
     uint32_t kind_n1_mask;
 };
@@ -127,7 +127,7 @@ __device__ __forceinline__ const double* wedm::kernarg_wmat() {
 // compare per microsecond; the descriptor travels by value in the kernel arguments.  While a
 // trace is due in this launch the kernels keep iterating over terminated environments so that
 // every slot receives a sample (their frozen state).
-// Kernels are instantiated with and without the trace point (template parameter TRACE): the
+// Kernels are instantiated with and without the trace point (form bit F_TRACE, read as TRACE): the
 // inlined sampling code costs the packed kernel 4 more spilled VGPRs (scratch 80 -> 100 B/lane)
 // and the global kernel half its occupancy, so launches without a bound trace run the
 // instantiation that does not contain it.
@@ -233,10 +233,13 @@ __device__ __forceinline__ float stencil_pass(const TA& T, const Geom& g, const 
     return tmax;
 }
 
-// `hot`: k.hot, or (ENVP / MAT) the lane's copy with its environment's rows (envp_apply, wmat_apply)
-template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE, bool ENVP, bool MAT = false>
+// F: the kernel's forms.  `hot`: k.hot, or (F_ENVP / F_MAT) the lane's copy with its environment's rows (envp_apply,
+// wmat_apply)
+template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, const TA& T) {
+    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
+    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     const PulseRef pulse = kernarg_pulse();
     (void)pulse;
     Persist ps;
@@ -253,7 +256,7 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
     for (int it = 0; it < k.n_substeps; ++it) {
         if (!s.done) {
             const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
-            Coef c = scalar_prelude<REPLAY, false, ENVP, MAT>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
+            Coef c = scalar_prelude<F>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
             float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, hot, f64c, s.h_base, s.h_zone);
             scalar_epilogue(hot, s, tmax);
@@ -267,22 +270,23 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
     }
 }
 
-// ENVP: the every-step constants of environment e's rows (wedm_bind_env_params) instead of the uniform ones
-// MAT: those of environment e's wire material (wedm_bind_wire_material), applied after the ENVP rows
-template <bool TRACE, bool F64, bool REPLAY, class TA, bool PULSE = false, bool ENVP = false, bool MAT = false>
+// F: the kernel's forms.  F_ENVP: the every-step constants of environment e's rows (wedm_bind_env_params) instead of the
+// uniform ones.  F_MAT: those of environment e's wire material (wedm_bind_wire_material), applied after the ENVP rows.
+template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
                                              uint32_t gid, Env& s, const TA& T) {
+    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     if (MAT) {
         Hot hv = k.hot;
         if (ENVP) envp_apply(hv, cold->s.stride, e);
         wmat_apply(hv, cold->s.stride, e);
-        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, ENVP, true>(k, hv, cold, g, e, gid, s, T);
+        run_substeps_h<F, TA>(k, hv, cold, g, e, gid, s, T);
     } else if (ENVP) {
         Hot hv = k.hot;
         envp_apply(hv, cold->s.stride, e);
-        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, true>(k, hv, cold, g, e, gid, s, T);
+        run_substeps_h<F, TA>(k, hv, cold, g, e, gid, s, T);
     } else {
-        run_substeps_h<TRACE, F64, REPLAY, TA, PULSE, false>(k, k.hot, cold, g, e, gid, s, T);
+        run_substeps_h<F, TA>(k, k.hot, cold, g, e, gid, s, T);
     }
 }
 

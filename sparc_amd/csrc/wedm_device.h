@@ -23,6 +23,28 @@
 
 namespace wedm {
 
+// ---------------------------------------------------------------- kernel forms
+// A form is a compile-time variant of a step kernel family: every wedm_step_* kernel is a template over a set F of these
+// bits (<int L, uint32_t F>, or <uint32_t F> where the family has no lane count) and static_asserts the bits its family
+// accepts; which (family, lanes, forms) exist is the registry of wedm_kernels.hip.  Code that costs the other launches by
+// its mere presence lives in a form of its own.  (Here rather than in wedm_common.h: scalar_prelude and quiet_prelude_t
+// below take the forms of their caller.)
+enum : uint32_t {
+    F_TRACE = 1u << 0,      // the signal-trace point (wedm_bind_trace)
+    F_F64 = 1u << 1,        // the float64-typed stencil (stencil_mode 1)
+    F_REPLAY = 1u << 2,     // injected variates (wedm_bind_rng_replay)
+    F_PULSE = 1u << 3,      // pulse statistics (wedm_bind_pulse_stats)
+    F_ENVP = 1u << 4,       // per-environment physics rows (wedm_bind_env_params)
+    F_MAT = 1u << 5,        // per-environment wire material (wedm_bind_wire_material)
+    F_FROZEN_OK = 1u << 6,  // tile code that tolerates frozen lanes
+    F_N1 = 1u << 7,         // stage-major code for one-change tiles (fused kernel)
+    F_EXTRA = 1u << 8,      // code for one-change boundary tiles and 1- / 2-cell tails (packed and served kernels)
+    F_CUT = 1u << 9,        // wires whose length is not a multiple of 8 (wide register kernel)
+    F_ONE = 1u << 10,       // one microsecond per launch, no loop (stream kernel)
+    F_CMAX104 = 1u << 11,   // chunks of up to 104 cells in registers, else 64 (stream kernel)
+    F_MINB2 = 1u << 12,     // two blocks per CU, else one (float64 wide register kernel)
+};
+
 // ---------------------------------------------------------------- small helpers
 __device__ __forceinline__ double bits2d(uint64_t u) { return __longlong_as_double((long long)u); }
 __device__ __forceinline__ uint64_t d2bits(double d) { return (uint64_t)__double_as_longlong(d); }
@@ -854,19 +876,21 @@ struct QuietTry {  // what a failed quiet_prelude() hands on: the step's Philox 
     bool have_w;
 };
 
-// REPLAY: the variates come from the caller's table (wedm_bind_rng_replay) instead of Philox — the reference's own
+// F: the calling kernel's forms (the bits below are read, the others ignored).
+// F_REPLAY: the variates come from the caller's table (wedm_bind_rng_replay) instead of Philox — the reference's own
 // draws, so that a native-seed run of the reference can be followed on the device (validation mode, global kernel).
+// F_ENVP: plasma efficiency and base convection come from the environment's rows (wedm_bind_env_params) where they are
+// used; the caller has put the rows of the `Hot` fields into `p` (envp_apply).
+// F_MAT: the electrical resistivity of the Joule factor comes from the environment's wire-material row
+// (wedm_bind_wire_material); the caller has put the material's `Hot` fields into `p` (wmat_apply).
 // SCOLD / lt: the single-microsecond stream kernel's flavour -- cold parameters by scalar loads, crater tables from the
 // lanes' registers (ColdParams, LaneTables): no vector load on the path a fresh spark takes.
-// ENVP: plasma efficiency and base convection come from the environment's rows (wedm_bind_env_params) where they are used;
-// the caller has put the rows of the `Hot` fields into `p` (envp_apply).
-// MAT: the electrical resistivity of the Joule factor comes from the environment's wire-material row
-// (wedm_bind_wire_material); the caller has put the material's `Hot` fields into `p` (wmat_apply).
-template <bool REPLAY = false, bool SCOLD = false, bool ENVP = false, bool MAT = false>
+template <uint32_t F = 0, bool SCOLD = false>
 __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, Persist& ps, bool writer,
                                                const QuietTry& qt = QuietTry{W4{0u, 0u, 0u, 0u}, false},
                                                const LaneTables* lt = nullptr, const LaneTables* lt1 = nullptr) {
+    constexpr bool REPLAY = (F & F_REPLAY) != 0, ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     double rv[WEDM_REPLAY_SLOTS] = {0.0, 0.0, 0.0, 0.0, 0.0};
     // The cold parameter block and the pointer block, fetched ONCE per call (laundered: nothing read through them can
     // be hoisted out of the microsecond loop).  Every rare branch below used to launder its own copy: two dependent
@@ -1139,12 +1163,13 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
 // lane scalar_prelude() computes exactly these assignments.  Only an igniting lane (fresh spark: crater, debris, cache
 // refresh), a short, or a control-step latch still sends the wave through the general path.  Bit-identical; it costs
 // registers, so batches that spark rarely run the instantiation without it.
-// ENVP: the plasma efficiency comes from the environment's row (wedm_bind_env_params), as in scalar_prelude.
-// MAT: the electrical resistivity comes from the environment's wire-material row (wedm_bind_wire_material), as in
-// scalar_prelude.
-template <bool DENSE, bool ENVP = false, bool MAT = false>
+// F: the calling kernel's forms.  F_ENVP: the plasma efficiency comes from the environment's row (wedm_bind_env_params),
+// as in scalar_prelude.  F_MAT: the electrical resistivity comes from the environment's wire-material row
+// (wedm_bind_wire_material), as in scalar_prelude.
+template <bool DENSE, uint32_t F = 0>
 __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold, const Geom& g, int64_t e, uint32_t gid,
                                                 Env& s, QuietTry& qt, Coef& cf) {
+    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     qt.have_w = false;
     if (p.disable_ignition || p.has_random_short) return false;
     const bool live = !s.done;

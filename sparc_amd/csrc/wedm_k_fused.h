@@ -22,16 +22,18 @@ __device__ __forceinline__ float interior_cell(float tm1, float tc, float tp1, f
     return tc + d * tuf;
 }
 
-// FROZEN_OK: see wedm_step_packed.  N1: the instantiation for tile tables with a one-change tile that is a boundary tile in
-// every microsecond (4 096 x 400 over 16 lanes: the end of the workpiece zone falls inside tile 2 of 4): +4.7 % there; the
-// extra code costs tables without such a tile 1-1.5 %, so they run the instantiation without it.
-// F64: wedm_params.stencil_mode 1 -- the stencil as Numba types wire.py:58-123 (float64 expressions rounded at each float32
+// Forms: F_TRACE; F_FROZEN_OK: see wedm_step_packed.  F_N1: the form for tile tables with a one-change tile that is a
+// boundary tile in every microsecond (4 096 x 400 over 16 lanes: the end of the workpiece zone falls inside tile 2 of 4):
+// +4.7 % there; the extra code costs tables without such a tile 1-1.5 %, so they run the form without it.
+// F_F64: wedm_params.stencil_mode 1 -- the stencil as Numba types wire.py:58-123 (float64 expressions rounded at each float32
 // store), on the tile walk: every tile takes the boundary-tile code (per-cell coefficients, interior formula, end cells
-// patched), which is exact for regular tiles too; no stage-major / packed form.  Instantiated with FROZEN_OK only.
-template <int L, bool TRACE, bool FROZEN_OK = false, bool N1 = false, bool F64 = false>
+// patched), which is exact for regular tiles too; no stage-major / packed form.  Only with F_FROZEN_OK, without F_N1.
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_FROZEN_OK | F_N1 | F_F64)) == 0, "forms of wedm_step_fused");
+    constexpr bool TRACE = (F & F_TRACE) != 0, FROZEN_OK = (F & F_FROZEN_OK) != 0, N1 = (F & F_N1) != 0, F64 = (F & F_F64) != 0;
     constexpr bool kFrozenOk = FROZEN_OK;
-    // (the N1 instantiation serves small batches with one wave per SIMD: 4 096 x 400 over 16 lanes)
+    // (the N1 form serves small batches with one wave per SIMD: 4 096 x 400 over 16 lanes)
     constexpr bool PREFETCH = N1 && !F64 && WEDM_PREFETCH_N1;
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;

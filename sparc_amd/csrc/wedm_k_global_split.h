@@ -4,16 +4,19 @@
 // Included by wedm_kernels.hip (one translation unit per WEDM_PART; see the bottom of that file).
 #pragma once
 
-// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats): every launch with the block bound that the
+// Forms: F_TRACE, F_F64, F_REPLAY (injected variates), and
+// F_PULSE: the form that counts pulse statistics (wedm_bind_pulse_stats): every launch with the block bound that the
 // fast kernels' PULSE forms do not take (a trace sample, stencil_mode 1, injected variates, forced kernel 1)
-// ENVP: the instantiation with per-environment physics rows (wedm_bind_env_params): every launch with the rows bound that
+// F_ENVP: the form with per-environment physics rows (wedm_bind_env_params): every launch with the rows bound that
 // kernel 2's ENVP form does not take (a trace sample, stencil_mode 1, injected variates, pulse statistics, single
 // microseconds, forced kernel 1)
-// MAT: the instantiation with per-environment wire material (wedm_bind_wire_material), with or without ENVP: every launch
+// F_MAT: the form with per-environment wire material (wedm_bind_wire_material), with or without F_ENVP: every launch
 // with the rows bound that kernel 2's MAT form does not take (a trace sample, stencil_mode 1, pulse statistics, single
 // microseconds, forced kernel 1); never with injected variates
-template <bool TRACE, bool F64, bool REPLAY, bool PULSE = false, bool ENVP = false, bool MAT = false>
+template <uint32_t F>
 __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_F64 | F_REPLAY | F_PULSE | F_ENVP | F_MAT)) == 0, "forms of wedm_step_global");
+    constexpr bool TRACE = (F & F_TRACE) != 0, PULSE = (F & F_PULSE) != 0;
     const ColdRef cold = kernarg_cold();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= k.num_envs) return;
@@ -35,7 +38,7 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
     load_geom(k.hot, cold, e, g);
-    run_substeps<TRACE, F64, REPLAY, GlobalT, PULSE, ENVP, MAT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
+    run_substeps<F, GlobalT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
     if (WEDM_REWARD_ON(cold)) {
         if (!frozen) write_reward(cold, e, s);
         else cold->s.reward[e] = 0.0f;
@@ -75,8 +78,10 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
 #ifndef WEDM_SPLIT_RB
 #define WEDM_SPLIT_RB 16
 #endif
-template <bool TRACE>
+template <uint32_t F>
 __global__ void __launch_bounds__(256) wedm_step_split(const KArgs k) {
+    static_assert((F & ~F_TRACE) == 0, "forms of wedm_step_split");
+    constexpr bool TRACE = (F & F_TRACE) != 0;
     const ColdRef cold = kernarg_cold();
     __shared__ float sh_f[5][64];    // jf, q, conv_base, conv_zone, adv
     __shared__ int32_t sh_i[4][64];  // joule_on, pidx, adv_on, skip (environment frozen)

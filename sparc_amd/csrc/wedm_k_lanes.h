@@ -7,9 +7,11 @@
 // Any geometry (uniform or one row per environment), L lanes per environment, every cell on the
 // predicated formula with the lane's own n_seg / zone / contact indices.  LDS layout and halo
 // exchange as in the fused kernels; the chunk length is uniform, C = ceil(n_seg_max / L), so an
-// environment with a shorter wire simply leaves the tail of its last chunks unused.
-template <int L, bool TRACE, bool F64>
+// environment with a shorter wire simply leaves the tail of its last chunks unused.  Forms: F_TRACE, F_F64.
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_F64)) == 0, "forms of wedm_step_lanes");
+    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0;
     constexpr bool kFrozenOk = true;  // (predicated cells: a frozen lane costs this kernel nothing extra)
     const ColdRef cold = kernarg_cold();
 #ifndef WEDM_NO_PIN_LANES

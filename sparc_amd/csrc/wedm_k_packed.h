@@ -26,15 +26,18 @@ __device__ __forceinline__ f2 interior2(f2 tm1, f2 tc, f2 tp1, float k, float tu
     return tc + d * tuf;
 }
 
-// FROZEN_OK: the instantiation for handles with in-launch autoreset, i.e. batches in which environments terminate at
+// Forms: F_TRACE, and
+// F_FROZEN_OK: the form for handles with in-launch autoreset, i.e. batches in which environments terminate at
 // different times and wait, frozen, for the next launch.  Without it a wave with a frozen lane walks every cell on the
 // predicated path (~4 x slower: 3.65e9 instead of 1.36e10 env-steps/s on a batch that resets 17 % of its environments per
 // launch); with it such a wave takes a second copy of the tile code in which the frozen lanes do not store.  A separate
-// instantiation, because the mere presence of that copy costs the other waves 2 % (6 % when folded into one copy).
-// EXTRA: the instantiation for tile tables that need them: one-change tiles on the stage-major code (see wedm_step_fused's
-// N1) and a chunk's 1- or 2-cell tail computed with the patched cells (virtual chunks of 25 cells: 400 segments over 8 lanes).
-template <int L, bool TRACE, bool FROZEN_OK = false, bool EXTRA = false>
+// form, because the mere presence of that copy costs the other waves 2 % (6 % when folded into one copy).
+// F_EXTRA: the form for tile tables that need them: one-change tiles on the stage-major code (see wedm_step_fused's
+// F_N1) and a chunk's 1- or 2-cell tail computed with the patched cells (virtual chunks of 25 cells: 400 segments over 8 lanes).
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, WEDM_PACKED_MIN_BLOCKS) wedm_step_packed(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_FROZEN_OK | F_EXTRA)) == 0, "forms of wedm_step_packed");
+    constexpr bool TRACE = (F & F_TRACE) != 0, FROZEN_OK = (F & F_FROZEN_OK) != 0, EXTRA = (F & F_EXTRA) != 0;
     constexpr bool kFrozenOk = FROZEN_OK;
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;

@@ -1,5 +1,5 @@
-// wedm_k_regs.h — the register kernels: wedm_step_regs<CELLS, L> (the headline's kernel: wires of at most 128 segments in the
-// registers of 1 or 2 lanes) and wedm_step_regs_wide<H, L> (4 / 8 / 16 lanes of one DPP row per environment, 32 cells each).
+// wedm_k_regs.h — the register kernels: wedm_step_regs<L> (the headline's kernel: wires of at most 128 segments in the
+// registers of 1 or 2 lanes) and wedm_step_regs_wide<L> (4 / 8 / 16 lanes of one DPP row per environment, 32 cells each).
 //
 // Included by wedm_kernels.hip (one translation unit per WEDM_PART; see the bottom of that file).
 #pragma once
@@ -43,12 +43,15 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 #ifndef WEDM_REGS_PIN2
 #define WEDM_REGS_PIN2 1
 #endif
-// TRACE: the instantiation with the signal-trace point (a launch into which a sample falls: the reference's logger samples
-// after every step, utils/logger.py:110-160); launches without a sample run the instantiation without it.
-// F64: stencil_mode 1 -- the walk in the typing Numba gives wire.py:58-123 (cell_f64 above); everything else is the same kernel.
-// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
-template <int CELLS, int L, bool TRACE = false, bool F64 = false, bool PULSE = false>
+// F_TRACE: the form with the signal-trace point (a launch into which a sample falls: the reference's logger samples
+// after every step, utils/logger.py:110-160); launches without a sample run the form without it.
+// F_F64: stencil_mode 1 -- the walk in the typing Numba gives wire.py:58-123 (cell_f64 above); everything else is the same kernel.
+// F_PULSE: the form that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_F64 | F_PULSE)) == 0, "forms of wedm_step_regs");
+    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
+    constexpr int CELLS = 128;
     // L = 1: one environment per lane (H = 64 pairs, one wave per SIMD at a 512-register budget);
     // L = 2: two lanes per environment, each with half of the wire (H = 32 pairs, two waves per SIMD, the scalar physics
     //        in both lanes as in the LDS kernels; the halves' halos cross by DPP)
@@ -287,15 +290,21 @@ __device__ __forceinline__ float dpp_perm(float x) {
 #ifndef WEDM_WIDE_AUTO_MAX_LANES
 #define WEDM_WIDE_AUTO_MAX_LANES 65536  // one block per CU: 4 096 environments x 16 lanes, 16 384 x 4
 #endif
-// CUT: the instantiation for wires whose end cuts a tile (n_seg not a multiple of 8); the code for that tile costs the
-// regular path 2 - 3 % by its presence (registers), so the other wires run the instantiation without it.
-// TRACE: the instantiation with the signal-trace point (a launch into which a sample falls); built on the CUT form.
-// F64: stencil_mode 1 (the walk in Numba's typing of wire.py:58-123, as in wedm_step_regs)
-// MINB: blocks per CU the register budget admits (2: the float64 typing's instantiation for batches of more than one wave per
-// SIMD -- a lone wave issues a float64 operation every ~7 cycles, two share the pipe; 256 registers, nothing pinned)
-// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
-template <int H, int L, bool CUT, bool TRACE = false, bool F64 = false, int MINB = WEDM_WIDE_MIN_BLOCKS, bool PULSE = false>
-__global__ void __launch_bounds__(256, MINB) wedm_step_regs_wide(const KArgs k) {
+// F_CUT: the form for wires whose end cuts a tile (n_seg not a multiple of 8); the code for that tile costs the
+// regular path 2 - 3 % by its presence (registers), so the other wires run the form without it.
+// F_TRACE: the form with the signal-trace point (a launch into which a sample falls); always with F_CUT.
+// F_F64: stencil_mode 1 (the walk in Numba's typing of wire.py:58-123, as in wedm_step_regs)
+// MINB: blocks per CU the register budget admits: 2 with F_MINB2 (float64 forms only: batches of more than one wave per
+// SIMD -- a lone wave issues a float64 operation every ~7 cycles, two share the pipe; 256 registers, nothing pinned), else
+// 1; the float32 forms WEDM_WIDE_MIN_BLOCKS
+// F_PULSE: the form that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+constexpr int wide_min_blocks(uint32_t F) { return !(F & F_F64) ? WEDM_WIDE_MIN_BLOCKS : (F & F_MINB2) ? 2 : 1; }
+template <int L, uint32_t F>
+__global__ void __launch_bounds__(256, wide_min_blocks(F)) wedm_step_regs_wide(const KArgs k) {
+    static_assert((F & ~(F_CUT | F_TRACE | F_F64 | F_MINB2 | F_PULSE)) == 0 && (!(F & F_MINB2) || (F & F_F64)),
+                  "forms of wedm_step_regs_wide");
+    constexpr bool CUT = (F & F_CUT) != 0, TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
+    constexpr int H = 16, MINB = wide_min_blocks(F);  // H: packed pairs per lane
     static_assert(H % 8 == 0 && H <= 32, "whole tiles");
     static_assert(L == 4 || L == 8 || L == 16, "the lanes of an environment lie in one DPP row");
     constexpr int EPB = 256 / L;

@@ -28,13 +28,18 @@
 // Every wave is its own pipeline, so the loads, arithmetic and stores of different waves overlap by themselves.
 #define WEDM_LDS __attribute__((address_space(3)))
 #define WEDM_GLOBAL __attribute__((address_space(1)))
-// ONE: the instantiation for launches of exactly one microsecond (the host picks it; no loop over further microseconds,
+// Forms: F_TRACE;
+// F_ONE: the form for launches of exactly one microsecond (the host picks it; no loop over further microseconds,
 // and a walk out of registers for the waves that can take it: rest_single below)
-// F64 (with ONE only): stencil_mode 1 -- the register walk in Numba's typing of wire.py:58-123 (cell_f64 / rw_quad of
+// F_CMAX104: a lane holds up to CMAX = 104 wire rows in registers, else 64
+// F_F64 (with F_ONE only): stencil_mode 1 -- the register walk in Numba's typing of wire.py:58-123 (cell_f64 / rw_quad of
 // wedm_common.h); a wave that cannot take the register walk (a frozen environment, a negative plasma heat, a tile with several
 // flag changes) walks every cell of its chunk on the per-cell code in that typing.
-template <int L, bool TRACE, int CMAX, bool ONE = false, bool F64 = false>
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_ONE | F_CMAX104 | F_F64)) == 0, "forms of wedm_step_stream");
+    constexpr bool TRACE = (F & F_TRACE) != 0, ONE = (F & F_ONE) != 0, F64 = (F & F_F64) != 0;
+    constexpr int CMAX = (F & F_CMAX104) ? 104 : 64;
     static_assert(!F64 || (ONE && !TRACE), "the float64 typing exists for the single-microsecond instantiation only");
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
@@ -193,7 +198,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
             const int mm = (s.mode >= 1 && s.mode <= WEDM_MAX_MODE) ? s.mode : 1;
             const LaneTables mine{__shfl(ltab.mean, mm, 64), __shfl(ltab.sd, mm, 64), __shfl(ltab.depth, mm, 64), __shfl(ltab.valid, mm, 64)};
             const LaneTables one{__shfl(ltab.mean, 1, 64), __shfl(ltab.sd, 1, 64), __shfl(ltab.depth, 1, 64), __shfl(ltab.valid, 1, 64)};
-            if (!s.done) cf = scalar_prelude<false, true>(hv, cold, g, e, gid, s, ps, c == 0, qt, &mine, &one);
+            if (!s.done) cf = scalar_prelude<F, true>(hv, cold, g, e, gid, s, ps, c == 0, qt, &mine, &one);
         }
     };
     auto rest = [&](const int it, Coef& cf) {

@@ -1,5 +1,6 @@
-// wedm_kernels.hip — the translation unit(s) of libwedm_hip.so: includes the kernel families, instantiates them (one family per
-// WEDM_PART, compiled in parallel), and holds the host side of the C-ABI of include/wedm_hip.h (launch plan, wedm_create ...).
+// wedm_kernels.hip — the translation unit(s) of libwedm_hip.so: includes the kernel families, lists their instantiations in one
+// registry (compiled in five parts in parallel), and holds the host side of the C-ABI of include/wedm_hip.h (launch plan,
+// wedm_create ...).
 //
 // Device code, by file (DESIGN.md section 4 has the table with what binds each kernel):
 //   wedm_device.h         per-lane physics of one microsecond: Env, prelude (quiet / general), epilogue (monitor + motion),
@@ -14,13 +15,14 @@
 //   wedm_k_packed.h       wedm_step_packed<L>: the same with two virtual chunks per lane in float2 registers
 //   wedm_served.h         wedm_step_served<L>: the packed walk on three waves of a block, the scalar physics of the block's
 //                         environments on the fourth, one microsecond ahead (kernel 9: large batches of long wires)
-//   wedm_k_regs.h         wedm_step_regs<128, L> (the headline: the wire in the registers of two lanes per environment),
-//                         wedm_step_regs_wide<16, L> (4 / 8 / 16 lanes of a DPP row per environment: small batches)
+//   wedm_k_regs.h         wedm_step_regs<L> (the headline: the wire in the registers of two lanes per environment),
+//                         wedm_step_regs_wide<L> (4 / 8 / 16 lanes of a DPP row per environment: small batches)
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
-// Kernels exist in several instantiations (signal trace point, FROZEN_OK for autoreset handles, N1 / EXTRA for tile tables
-// with one-change tiles or short tails): code that costs the other launches 1-2 % by its mere presence lives in its own
-// instantiation, chosen per handle in plan_launch().
+// Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
+// of wedm_device.h: signal trace point, FROZEN_OK for autoreset handles, N1 / EXTRA for tile tables with one-change tiles or
+// short tails, the bound per-environment blocks ...): code that costs the other launches 1-2 % by its mere presence lives in
+// its own form.  The registry below lists the instantiations; plan_launch() computes a launch's form and looks it up there.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-fast-math (see
 // __graft_entry__.build()).  -ffp-contract=off is part of the numerics contract.
@@ -30,6 +32,7 @@
 #include <climits>
 #include <cstddef>
 #include <type_traits>
+#include <utility>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -51,66 +54,170 @@ using namespace wedm;
 #include "wedm_served.h"
 #include "wedm_lanes2.h"
 
-// ------------------------------------------------------------ translation-unit parts (build time only)
-// The kernels exist in about 240 instantiations, which take hipcc minutes in one translation unit.
-// __graft_entry__.build_hip() compiles this file five times in parallel: -DWEDM_PART=1 ... 4 each emit the explicit
-// instantiations of one list below (1: packed, 2: fused, 3: served and packed-LDS, 4: the float64-typed and PULSE register
-// forms), -DWEDM_PART=0 holds the host code, the reset and debug kernels and every instantiation no list names (made where
-// plan_launch() refers to it), with the four lists declared `extern template`; the five objects link into the one shared
-// library.  Without -DWEDM_PART the file is one self-contained translation unit (the diagnostic builds of tools/ use it
-// that way).
-#define WEDM_BOOLS3(X, K, L) X(K<L, false, false, false>) X(K<L, false, false, true>) X(K<L, false, true, false>) \
-                             X(K<L, false, true, true>) X(K<L, true, false, false>) X(K<L, true, false, true>)   \
-                             X(K<L, true, true, false>) X(K<L, true, true, true>)
-#define WEDM_L4(G, X) G(X, 1) G(X, 2) G(X, 4) G(X, 8)
-#define WEDM_L5(G, X) WEDM_L4(G, X) G(X, 16)
-// part 1: wedm_step_packed<L, TRACE, FROZEN_OK, EXTRA>
-#define WEDM_P1(X, L) WEDM_BOOLS3(X, wedm_step_packed, L)
-// part 2: wedm_step_fused<L, TRACE, FROZEN_OK, N1>, and stencil_mode 1 on the tile walk: <L, TRACE, FROZEN_OK = true, N1 = false, F64 = true>
-#define WEDM_P2(X, L) WEDM_BOOLS3(X, wedm_step_fused, L) \
-                      X(wedm_step_fused<L, false, true, false, true>) X(wedm_step_fused<L, true, true, false, true>)
-// part 3: wedm_step_lanes_pk<L, TRACE>, its PULSE, ENVP and MAT forms (float32 stencil, no trace sample); the served kernels
-// (wedm_served.h) <L, EXTRA>, wedm_step_lanes_served<L>, wedm_step_regs_served
-#define WEDM_P3(X, L) X(wedm_step_lanes_pk<L, false>) X(wedm_step_lanes_pk<L, true>) \
-                      X(wedm_step_lanes_pk<L, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true>) \
-                      X(wedm_step_lanes_pk<L, false, false, false, false, true>) X(wedm_step_lanes_pk<L, false, false, false, true, true>)
-// part 4: stencil_mode 1 on kernel 2 <L, TRACE, F64 = true> and on the stream kernel's single-microsecond instantiation
-// <L, false, 64, ONE = true, F64 = true>; the register kernel <128, L, TRACE, F64 = true> and its PULSE form; the wide
-// register kernel <16, L, CUT, TRACE, F64 = true, MINB> (a traced launch runs the CUT form, as in float32; MINB = 1 for a
-// batch of one wave per SIMD, 2 beyond) and its PULSE forms
-#define WEDM_P4(X, L) X(wedm_step_lanes_pk<L, false, true>) X(wedm_step_lanes_pk<L, true, true>) \
-                      X(wedm_step_stream<L, false, 64, true, true>)
-#define WEDM_P4_REGS(X, L) X(wedm_step_regs<128, L, false, true>) X(wedm_step_regs<128, L, true, true>) \
-                           X(wedm_step_regs<128, L, false, false, true>)
-#define WEDM_P4_WIDE_F64(X, L, mb) X(wedm_step_regs_wide<16, L, false, false, true, mb>) \
-                                   X(wedm_step_regs_wide<16, L, true, false, true, mb>) X(wedm_step_regs_wide<16, L, true, true, true, mb>)
-#define WEDM_P4_WIDE(X, L) WEDM_P4_WIDE_F64(X, L, 1) WEDM_P4_WIDE_F64(X, L, 2)                                \
-                           X(wedm_step_regs_wide<16, L, false, false, false, WEDM_WIDE_MIN_BLOCKS, true>) \
-                           X(wedm_step_regs_wide<16, L, true, false, false, WEDM_WIDE_MIN_BLOCKS, true>)
-#define WEDM_PART1_LIST(X) WEDM_L4(WEDM_P1, X)
-#define WEDM_PART2_LIST(X) WEDM_L5(WEDM_P2, X)
-#define WEDM_PART3_LIST(X) WEDM_L5(WEDM_P3, X) X(wedm_step_served<4, false>) X(wedm_step_served<4, true>)     \
-                           X(wedm_step_served<8, false>) X(wedm_step_served<8, true>) X(wedm_step_lanes_served<4>) \
-                           X(wedm_step_lanes_served<8>) X(wedm_step_lanes_served<16>) X(wedm_step_regs_served<128>)
-#define WEDM_PART4_LIST(X) WEDM_L5(WEDM_P4, X) WEDM_P4_REGS(X, 1) WEDM_P4_REGS(X, 2) \
-                           WEDM_P4_WIDE(X, 4) WEDM_P4_WIDE(X, 8) WEDM_P4_WIDE(X, 16)
-#define WEDM_INST(...) template __global__ void __VA_ARGS__(const KArgs);
-#define WEDM_EXT(...) extern template __global__ void __VA_ARGS__(const KArgs);
-#if defined(WEDM_PART) && WEDM_PART == 1
-WEDM_PART1_LIST(WEDM_INST)
-#elif defined(WEDM_PART) && WEDM_PART == 2
-WEDM_PART2_LIST(WEDM_INST)
-#elif defined(WEDM_PART) && WEDM_PART == 3
-WEDM_PART3_LIST(WEDM_INST)
-#elif defined(WEDM_PART) && WEDM_PART == 4
-WEDM_PART4_LIST(WEDM_INST)
-#else
-#if defined(WEDM_PART)
-WEDM_PART1_LIST(WEDM_EXT)
-WEDM_PART2_LIST(WEDM_EXT)
-WEDM_PART3_LIST(WEDM_EXT)
-WEDM_PART4_LIST(WEDM_EXT)
+// ------------------------------------------------------------ the registry of instantiations
+// Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are about 260,
+// which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file five times in
+// parallel: -DWEDM_PART=N defines registry_partN(), which instantiates what it lists (1: the packed kernel, 2: the fused
+// kernel, 3: the served kernels and kernel 2's float32 forms, 4: the float64-typed forms of kernels 2, 6, 7 and 8 and the
+// PULSE forms of 7 and 8, 0: the rest); -DWEDM_PART=0 also holds the host code and the reset and debug kernels, and
+// registry() there joins the five slices.  The five objects link into the one shared library.  Without -DWEDM_PART the file
+// is one self-contained translation unit (the diagnostic builds of tools/ use it that way).
+
+// kernel numbers of wedm_set_kernel (include/wedm_hip.h; the ABI carries them as int32_t)
+enum Kernel : int32_t {
+    K_AUTO = 0, K_GLOBAL = 1, K_LANES_PK = 2, K_FUSED = 3, K_PACKED = 4, K_SPLIT = 5, K_STREAM = 6, K_REGS = 7, K_WIDE = 8,
+    K_SERVED = 9, K_LANES = 10, K_LANES_SERVED = 11, K_REGS_SERVED = 12
+};
+
+struct KernelForm {
+    Kernel kernel;
+    int lanes;       // lanes per environment (0: a family without that choice)
+    uint32_t forms;  // F_* bits
+    const void* fn;
+};
+typedef std::vector<KernelForm> Slice;
+
+// kernel K's instantiation for (L, F)
+template <Kernel K, int L, uint32_t F> static const void* instantiation() {
+    if constexpr (K == K_GLOBAL) return (const void*)wedm_step_global<F>;
+    else if constexpr (K == K_LANES_PK) return (const void*)wedm_step_lanes_pk<L, F>;
+    else if constexpr (K == K_FUSED) return (const void*)wedm_step_fused<L, F>;
+    else if constexpr (K == K_PACKED) return (const void*)wedm_step_packed<L, F>;
+    else if constexpr (K == K_SPLIT) return (const void*)wedm_step_split<F>;
+    else if constexpr (K == K_STREAM) return (const void*)wedm_step_stream<L, F>;
+    else if constexpr (K == K_REGS) return (const void*)wedm_step_regs<L, F>;
+    else if constexpr (K == K_WIDE) return (const void*)wedm_step_regs_wide<L, F>;
+    else if constexpr (K == K_SERVED) return (const void*)wedm_step_served<L, F>;
+    else if constexpr (K == K_LANES) return (const void*)wedm_step_lanes<L, F>;
+    else if constexpr (K == K_LANES_SERVED) return (const void*)wedm_step_lanes_served<L, F>;
+    else {
+        static_assert(K == K_REGS_SERVED, "a kernel family");
+        return (const void*)wedm_step_regs_served<F>;
+    }
+}
+
+template <int... Ls> using Lanes = std::integer_sequence<int, Ls...>;
+template <uint32_t... Fs> using Forms = std::integer_sequence<uint32_t, Fs...>;
+using L5 = Lanes<1, 2, 4, 8, 16>;
+using NoLanes = Lanes<0>;
+// subset i of the bits of `set` (bit b of i selects the b-th lowest bit of `set`)
+constexpr uint32_t subset(uint32_t set, uint32_t i) {
+    uint32_t r = 0;
+    for (; set; set &= set - 1, i >>= 1)
+        if (i & 1u) r |= set & (0u - set);
+    return r;
+}
+template <uint32_t SET, uint32_t WITH, uint32_t... I>
+Forms<(WITH | subset(SET, I))...> subsets(std::integer_sequence<uint32_t, I...>);
+// every subset of the bits of SET, each with the bits of WITH
+template <uint32_t SET, uint32_t WITH = 0>
+using Every = decltype(subsets<SET, WITH>(std::make_integer_sequence<uint32_t, 1u << __builtin_popcount(SET)>{}));
+
+// appends kernel K's instantiations for every L of Ls and every F of Fs
+template <Kernel K, int... Ls, uint32_t... Fs>
+static void add(Slice& s, Lanes<Ls...>, Forms<Fs...>) {
+    const auto with_lanes = [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        (s.push_back({K, L, Fs, instantiation<K, L, Fs>()}), ...);
+    };
+    (with_lanes(std::integral_constant<int, Ls>{}), ...);
+}
+
+Slice registry_part0();
+Slice registry_part1();
+Slice registry_part2();
+Slice registry_part3();
+Slice registry_part4();
+
+#if !defined(WEDM_PART) || WEDM_PART == 1
+Slice registry_part1() {
+    Slice s;
+    add<K_PACKED>(s, Lanes<1, 2, 4, 8>{}, Every<F_TRACE | F_FROZEN_OK | F_EXTRA>{});
+    return s;
+}
 #endif
+
+#if !defined(WEDM_PART) || WEDM_PART == 2
+Slice registry_part2() {
+    Slice s;
+    add<K_FUSED>(s, L5{}, Every<F_TRACE | F_FROZEN_OK | F_N1>{});
+    add<K_FUSED>(s, L5{}, Every<F_TRACE, F_FROZEN_OK | F_F64>{});  // stencil_mode 1 on the tile walk
+    return s;
+}
+#endif
+
+#if !defined(WEDM_PART) || WEDM_PART == 3
+Slice registry_part3() {
+    Slice s;
+    add<K_LANES_PK>(s, L5{}, Forms<0, F_TRACE, F_PULSE, F_ENVP, F_MAT, F_ENVP | F_MAT>{});
+    add<K_SERVED>(s, Lanes<4, 8>{}, Every<F_EXTRA>{});
+    add<K_LANES_SERVED>(s, Lanes<4, 8, 16>{}, Forms<0>{});
+    add<K_REGS_SERVED>(s, NoLanes{}, Forms<0>{});
+    return s;
+}
+#endif
+
+#if !defined(WEDM_PART) || WEDM_PART == 4
+Slice registry_part4() {
+    Slice s;
+    add<K_LANES_PK>(s, L5{}, Every<F_TRACE, F_F64>{});
+    add<K_STREAM>(s, L5{}, Forms<F_ONE | F_F64>{});
+    add<K_REGS>(s, Lanes<1, 2>{}, Forms<F_F64, F_TRACE | F_F64, F_PULSE>{});
+    // the float64 wide forms at one or two blocks per CU; a traced launch runs the CUT form
+    add<K_WIDE>(s, Lanes<4, 8, 16>{}, Every<F_CUT | F_MINB2, F_F64>{});
+    add<K_WIDE>(s, Lanes<4, 8, 16>{}, Every<F_MINB2, F_CUT | F_TRACE | F_F64>{});
+    add<K_WIDE>(s, Lanes<4, 8, 16>{}, Every<F_CUT, F_PULSE>{});
+    return s;
+}
+#endif
+
+#if !defined(WEDM_PART) || WEDM_PART == 0
+Slice registry_part0() {
+    Slice s;
+    add<K_GLOBAL>(s, NoLanes{}, Every<F_TRACE | F_F64 | F_PULSE | F_ENVP | F_MAT>{});
+    add<K_GLOBAL>(s, NoLanes{}, Every<F_TRACE | F_PULSE | F_ENVP, F_REPLAY>{});  // injected variates: float32, no MAT
+    add<K_LANES>(s, L5{}, Every<F_TRACE | F_F64>{});
+    add<K_STREAM>(s, L5{}, Every<F_TRACE | F_CMAX104>{});
+    add<K_STREAM>(s, L5{}, Forms<F_ONE>{});
+    add<K_SPLIT>(s, NoLanes{}, Every<F_TRACE>{});
+    add<K_REGS>(s, Lanes<1, 2>{}, Every<F_TRACE>{});
+    add<K_WIDE>(s, Lanes<4, 8, 16>{}, Forms<0, F_CUT, F_CUT | F_TRACE>{});
+    return s;
+}
+
+// every instantiation: the slices of the five parts
+static const Slice& registry() {
+    static const Slice all = [] {
+        Slice a;
+        for (Slice (*part)() : {registry_part0, registry_part1, registry_part2, registry_part3, registry_part4}) {
+            const Slice s = part();
+            a.insert(a.end(), s.begin(), s.end());
+        }
+        return a;
+    }();
+    return all;
+}
+// kernel k's instantiation for L lanes per environment and the forms F; nullptr if there is none
+static const void* find_instantiation(Kernel k, int L, uint32_t F) {
+    for (const KernelForm& f : registry())
+        if (f.kernel == k && f.lanes == L && f.forms == F) return f.fn;
+    return nullptr;
+}
+// kernel k (as wedm_set_kernel numbers it) has a form with the bit `form`; kernel 0, the automatic choice, has every form
+static bool has_form(int32_t k, uint32_t form) {
+    if (k == K_AUTO) return true;
+    for (const KernelForm& f : registry())
+        if (f.kernel == k && (f.forms & form)) return true;
+    return false;
+}
+static std::string form_names(uint32_t F) {
+    static const char* const names[] = {"TRACE", "F64", "REPLAY", "PULSE", "ENVP", "MAT", "FROZEN_OK",
+                                        "N1", "EXTRA", "CUT", "ONE", "CMAX104", "MINB2"};
+    std::string s;
+    for (int b = 0; b < (int)(sizeof(names) / sizeof(names[0])); ++b)
+        if ((F >> b) & 1u) s += (s.empty() ? "F_" : " | F_") + std::string(names[b]);
+    return s.empty() ? "none" : s;
+}
 
 __global__ void __launch_bounds__(256)
 wedm_reset_kernel(const wedm_params p, const wedm_state_ptrs s, int32_t num_envs, int32_t n_seg_max,
@@ -223,12 +330,6 @@ struct LaunchPlan {
     size_t lds = 0;
     const WalkTable* walk = nullptr;
     char name[160] = {0};
-};
-
-// kernel numbers of wedm_set_kernel (include/wedm_hip.h; the ABI carries them as int32_t)
-enum Kernel : int32_t {
-    K_AUTO = 0, K_GLOBAL = 1, K_LANES_PK = 2, K_FUSED = 3, K_PACKED = 4, K_SPLIT = 5, K_STREAM = 6, K_REGS = 7, K_WIDE = 8,
-    K_SERVED = 9, K_LANES = 10, K_LANES_SERVED = 11, K_REGS_SERVED = 12
 };
 
 // What the planner knows of a walk table (wedm_create builds them; wedm_ctx::walk_dev holds the tables, same index).
@@ -511,19 +612,6 @@ static int served_lanes(const wedm_ctx* c) {
     return ok ? L : 0;
 }
 
-// forms of a family beyond the float32 stencil: the kernels with a float64-typed (stencil_mode 1), a pulse-counting
-// (wedm_bind_pulse_stats), a per-environment-rows (wedm_bind_env_params) and a per-environment-material
-// (wedm_bind_wire_material) instantiation
-static constexpr uint32_t kernels(std::initializer_list<Kernel> ks) {
-    uint32_t m = 0;
-    for (const Kernel k : ks) m |= 1u << k;
-    return m;
-}
-static constexpr uint32_t F64_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_FUSED, K_STREAM, K_REGS, K_WIDE, K_LANES});
-static constexpr uint32_t PULSE_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK, K_REGS, K_WIDE});
-static constexpr uint32_t ENVP_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK});
-static constexpr uint32_t MAT_FORMS = kernels({K_AUTO, K_GLOBAL, K_LANES_PK});
-
 struct Choice {
     Kernel kernel = K_AUTO;
     int lanes = 0;  // lanes per environment (0: the family has no such choice)
@@ -595,7 +683,7 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     // and no injected variates
     if (mat && replay)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) and a per-environment wire material (wedm_bind_wire_material) cannot be combined");
-    if (mat && !((MAT_FORMS >> forced) & 1u))
+    if (mat && !has_form(forced, F_MAT))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with a per-environment wire material bound (wedm_bind_wire_material) only kernels 0 (auto), 1 and 2 run");
     if (replay) {
         if (forced != K_AUTO && forced != K_GLOBAL)
@@ -603,18 +691,18 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
         if (f64) return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates and stencil_mode 1 cannot be combined");
         forced = K_GLOBAL;
     }
-    if (envp && !((ENVP_FORMS >> forced) & 1u))
+    if (envp && !has_form(forced, F_ENVP))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound (wedm_bind_env_params) only kernels 0 (auto), 1 and 2 run");
     // Numba's typing of the stencil: the register kernels (uniform geometry; at most 128 / 512 segments), the fused tile walk
     // (uniform geometry), the predicated LDS kernel (any geometry), or in place in global memory; no packed LDS form, no served
     // form, no stream / split kernel
-    if (f64 && !((F64_FORMS >> forced) & 1u))
+    if (f64 && !has_form(forced, F_F64))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: stencil_mode 1 (float64 stencil expressions) runs on kernels 1, 2 (10), 3, 6 (single microseconds without a trace sample), 7 and 8 only");
     if (f64 && forced == K_STREAM && !stream_f64_ok)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: under stencil_mode 1 the stream kernel runs launches of one microsecond without a trace sample, chunks of at most 64 cells");
     if (forced == K_WIDE && !wl)
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: wide register kernel needs uniform geometry, 9 to 512 segments and lanes 0, 4, 8 or 16 with 32 cells per lane covering the wire");
-    if (pulse && !((PULSE_FORMS >> forced) & 1u))
+    if (pulse && !has_form(forced, F_PULSE))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
 
     int32_t v = forced;
@@ -704,130 +792,91 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     return WEDM_OK;
 }
 
-// f(std::bool_constant<b>...) for the runtime flags: instantiates every combination of them, so pass only flags whose every
-// combination exists
-template <class F> static const void* with_flags(F f) { return f(); }
-template <class F, class... B> static const void* with_flags(F f, bool b, B... rest) {
-    if (b) return with_flags([&](auto... t) { return f(std::true_type{}, t...); }, rest...);
-    return with_flags([&](auto... t) { return f(std::false_type{}, t...); }, rest...);
-}
-// f(std::integral_constant<int, L>, flags...) for the runtime L among `Ls`: only the lane counts the family is instantiated for
-template <int... Ls, class F, class... B> static const void* by_lanes(int L, F f, B... flags) {
-    const void* fn = nullptr;
-    ((L == Ls ? (void)(fn = with_flags([&](auto... t) { return f(std::integral_constant<int, Ls>{}, t...); }, flags...)) : (void)0), ...);
-    return fn;
-}
-
 static const char* const kernel_names[] = {"", "wedm_step_global", "wedm_step_lanes_pk", "wedm_step_fused", "wedm_step_packed",
                                            "wedm_step_split", "wedm_step_stream", "wedm_step_regs", "wedm_step_regs_wide",
                                            "wedm_step_served", "wedm_step_lanes", "wedm_step_lanes_served", "wedm_step_regs_served"};
 
 // What wedm_step launches for (single microsecond?, trace point?) under the handle's current settings: decided once
 // and cached (the decision walks a cost model over five lane counts; on the one-launch-per-microsecond path that and
-// a hipFuncSetAttribute per call were a measurable part of the host time per launch).  The choice, then one branch per
-// family from its flags to the instantiation, grid, block, LDS image and walk table.
+// a hipFuncSetAttribute per call were a measurable part of the host time per launch).  The choice, then per family the
+// form of the launch, its grid, block, LDS image and walk table; the instantiation is the registry's entry for the form.
 static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, LaunchPlan& out) {
     Choice ch;
     if (int32_t rc = choose_kernel(ctx, single, tr, ch)) return rc;
     const int L = ch.lanes, n = ctx->num_envs;
     const bool f64 = ctx->p.stencil_mode != 0, replay = ctx->replay != nullptr, pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
     const bool mat = ctx->wmat != nullptr;  // (never with injected variates, never with pulse statistics on kernel 2: choose_kernel)
+    // the form: the launch's trace point and the handle's bindings (kernel 1 has a form for each such set; the PULSE, ENVP
+    // and MAT forms of the other families carry neither TRACE nor F64), then each family's own bits below
+    uint32_t F = (tr ? F_TRACE : 0u) | (f64 ? F_F64 : 0u) | (replay ? F_REPLAY : 0u) | (pulse ? F_PULSE : 0u) |
+                 (envp ? F_ENVP : 0u) | (mat ? F_MAT : 0u);
+    if (ch.kernel != K_GLOBAL && (F & (F_PULSE | F_ENVP | F_MAT))) F &= ~(F_TRACE | F_F64);
     const WalkInfo* w = nullptr;  // the walk table the launch reads
-    bool fz = false;              // the FROZEN_OK instantiation (named in the kernel string)
-    const void* fn = nullptr;
+    bool fz = false;              // the FROZEN_OK form (named in the kernel string)
     int grid = blocks(n, 256 / std::max(L, 1)), block = 256;
     size_t fl = 0;
     switch (ch.kernel) {
-        case K_GLOBAL:  // injected variates / stencil_mode 1 / the float32 stencil, each with PULSE and ENVP forms; MAT forms
-            fn = replay ? with_flags([](auto t, auto p, auto e) { return (const void*)wedm_step_global<t, false, true, p, e>; }, tr, pulse, envp)
-               : mat    ? with_flags([](auto t, auto d, auto p, auto e) { return (const void*)wedm_step_global<t, d, false, p, e, true>; }, tr, f64, pulse, envp)
-                        : with_flags([](auto t, auto d, auto p, auto e) { return (const void*)wedm_step_global<t, d, false, p, e>; }, tr, f64, pulse, envp);
-            break;
-        case K_LANES_PK:
-            fl = lanes_pk_lds(ctx, L);
-            fn = mat   ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto e) { return (const void*)wedm_step_lanes_pk<l, false, false, false, e, true>; }, envp)
-               : pulse ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, true>; })
-               : envp  ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_pk<l, false, false, false, true>; })
-                       : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_lanes_pk<l, t, d>; }, tr, f64);
-            break;
-        case K_LANES:
-            fl = lanes_lds(ctx, L);
-            fn = by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_lanes<l, t, d>; }, tr, f64);
-            break;
+        case K_LANES_PK: fl = lanes_pk_lds(ctx, L); break;
+        case K_LANES: fl = lanes_lds(ctx, L); break;
         case K_FUSED:
             // handles with in-launch autoreset expect terminations, and so do handles whose kernels have reported a frozen
-            // environment (wedm_ctx::frozen_seen): the instantiation that tolerates frozen lanes; N1: the table has a
-            // one-change tile that is a boundary tile in every microsecond
+            // environment (wedm_ctx::frozen_seen): the form that tolerates frozen lanes; N1: the table has a one-change
+            // tile that is a boundary tile in every microsecond.  (stencil_mode 1: FROZEN_OK always, no N1)
             w = walk_of(ctx, W_LDS, L);
             fl = fused_lds(ctx, L);
             fz = frozen_ok;
-            fn = f64 ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t) { return (const void*)wedm_step_fused<l, t, true, false, true>; }, tr)
-                     : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto z, auto n1) { return (const void*)wedm_step_fused<l, t, z, n1>; },
-                                                tr, frozen_ok, w->n1z);
+            F |= f64 ? F_FROZEN_OK : (frozen_ok ? F_FROZEN_OK : 0u) | (w->n1z ? F_N1 : 0u);
             break;
         case K_PACKED:
             w = walk_of(ctx, W_LDS, 2 * L);
             fl = packed_lds(ctx, L);
             fz = frozen_ok;
-            fn = by_lanes<1, 2, 4, 8>(L, [](auto l, auto t, auto z, auto x) { return (const void*)wedm_step_packed<l, t, z, x>; },
-                                      tr, frozen_ok, walk_extra(w));
+            F |= (frozen_ok ? F_FROZEN_OK : 0u) | (walk_extra(w) ? F_EXTRA : 0u);
             break;
         case K_SERVED:  // three walker waves + the scalar wave
             w = walk_of(ctx, W_LDS, 2 * L);
             fl = served_lds(ctx, L);
             grid = blocks(n, 192 / L);
-            fn = by_lanes<4, 8>(L, [](auto l, auto x) { return (const void*)wedm_step_served<l, x>; }, walk_extra(w));
+            F |= walk_extra(w) ? F_EXTRA : 0u;
             break;
         case K_LANES_SERVED:
             fl = lanes_served_lds(ctx, L);
             grid = blocks(n, 192 / L);
-            fn = by_lanes<4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_lanes_served<l>; });
             break;
         case K_STREAM: {
-            // launches of one microsecond without a trace sample, chunks of at most 64 cells: the instantiation without the
-            // loop (stencil_mode 1: the only one); else the rows a lane holds in registers: 64 (128 segments over 2 lanes, 400
+            // launches of one microsecond without a trace sample, chunks of at most 64 cells: the form without the loop
+            // (stencil_mode 1: the only one); else the rows a lane holds in registers: 64 (128 segments over 2 lanes, 400
             // over 8) or 104 (400 over 4)
             w = walk_of(ctx, W_STREAM, L);
             fl = stream_lds(ctx, L);
             const bool one = WEDM_STREAM_REGWALK && single && !tr && w->C <= 64;
-            fn = (one || f64) ? by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto d) { return (const void*)wedm_step_stream<l, false, 64, true, d>; }, f64)
-                              : by_lanes<1, 2, 4, 8, 16>(L, [](auto l, auto t, auto c64) { return (const void*)wedm_step_stream<l, t, c64 ? 64 : 104>; },
-                                                         tr, w->C <= 64);
+            F = (one || f64) ? F_ONE | (F & F_F64) : F | (w->C > 64 ? F_CMAX104 : 0u);
             break;
         }
-        case K_SPLIT:
-            grid = blocks(n, 64);
-            fn = with_flags([](auto t) { return (const void*)wedm_step_split<t>; }, tr);
-            break;
+        case K_SPLIT: grid = blocks(n, 64); break;
         case K_REGS:  // the table of two chunks of 64 cells (one lane) / four of 32 (two lanes)
             w = &ctx->walk[L == 1 ? W_REGS2 : W_REGS4];
-            fn = pulse ? by_lanes<1, 2>(L, [](auto l) { return (const void*)wedm_step_regs<128, l, false, false, true>; })
-                       : by_lanes<1, 2>(L, [](auto l, auto t, auto d) { return (const void*)wedm_step_regs<128, l, t, d>; }, tr, f64);
             break;
-        case K_WIDE: {
+        case K_WIDE:
             // CUT: wires whose length is not a multiple of 8, and every traced launch.  (stencil_mode 1: a batch of more than
-            // one wave per SIMD runs the two-blocks-per-CU instantiation -- 32 768 x 400: 1.93e9 against 1.52e9; 4 096 x 400:
+            // one wave per SIMD runs the two-blocks-per-CU form -- 32 768 x 400: 1.93e9 against 1.52e9; 4 096 x 400:
             // 1.33e9 against 1.45e9)
-            const bool cut = (ctx->p.n_seg & 7) != 0, two = (int64_t)n * L > (int64_t)WEDM_WIDE_AUTO_MAX_LANES;
-            if (f64)
-                fn = tr ? by_lanes<4, 8, 16>(L, [](auto l, auto m) { return (const void*)wedm_step_regs_wide<16, l, true, true, true, m ? 2 : 1>; }, two)
-                        : by_lanes<4, 8, 16>(L, [](auto l, auto c, auto m) { return (const void*)wedm_step_regs_wide<16, l, c, false, true, m ? 2 : 1>; },
-                                             cut, two);
-            else
-                fn = tr ? by_lanes<4, 8, 16>(L, [](auto l) { return (const void*)wedm_step_regs_wide<16, l, true, true>; })
-                        : by_lanes<4, 8, 16>(L, [](auto l, auto c, auto p) {
-                              return (const void*)wedm_step_regs_wide<16, l, c, false, false, WEDM_WIDE_MIN_BLOCKS, p>; }, cut, pulse);
+            if ((ctx->p.n_seg & 7) != 0 || tr) F |= F_CUT;
+            if (f64 && (int64_t)n * L > (int64_t)WEDM_WIDE_AUTO_MAX_LANES) F |= F_MINB2;
             break;
-        }
         case K_REGS_SERVED:  // two walker waves + the scalar wave; the table of four chunks of 32 cells
             w = &ctx->walk[W_REGS4];
             fl = sizeof(ServedBox<64>);
             grid = blocks(n, 64);
             block = 192;
-            fn = (const void*)wedm_step_regs_served<128>;
             break;
+        case K_GLOBAL:
         case K_AUTO: break;
     }
+    const void* fn = find_instantiation(ch.kernel, L, F);
+    if (!fn)  // (an internal error: choose_kernel leaves no launch without its form)
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, std::string("wedm_step: internal error: no instantiation of ") + kernel_names[ch.kernel] +
+                                                   " for " + std::to_string(L) + " lanes and the forms " + form_names(F));
     if (fl) {
         // The attribute belongs to the kernel FUNCTION, not to this handle or plan: two live handles with different wire
         // lengths can resolve to the same instantiation, and a later plan with a smaller image must not lower the limit

@@ -11,7 +11,7 @@
 // environment's last cell, a plasma cell) are computed by the predicated formula from OLD values before the walk and written
 // after it, exactly as wedm_step_lanes does.  Cells past an environment's wire keep their value (the write-back copies all
 // n_seg_max rows).  A wave with a negative plasma heat walks cell by cell on the predicated formula (same results).
-// F64 (round 4): the same walk with every interior cell in Numba's typing of wire.py:58-123 (cell_f64 of wedm_common.h: 18 float64
+// F_F64 (round 4): the same walk with every interior cell in Numba's typing of wire.py:58-123 (cell_f64 of wedm_common.h: 18 float64
 // operations per cell, the two cells of a pair one after the other) -- stencil_mode 1 on per-environment geometry.
 #pragma once
 
@@ -179,14 +179,18 @@ __device__ __forceinline__ float lanes_pk_step(float* col, const LanesPkGeom& q,
     return tmax;
 }
 
-// PULSE: the instantiation that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
-// ENVP: the instantiation with per-environment physics rows (wedm_bind_env_params; float32 stencil, no trace sample): each
+// Forms: F_TRACE, F_F64, and
+// F_PULSE: the form that counts pulse statistics (wedm_bind_pulse_stats; float32 stencil, no trace sample).
+// F_ENVP: the form with per-environment physics rows (wedm_bind_env_params; float32 stencil, no trace sample): each
 // lane's `hv` takes its environment's rows once per launch, the pinned constants become per-lane VGPR values.
-// MAT: the instantiation with per-environment wire material (wedm_bind_wire_material; float32 stencil, no trace sample, no
-// pulse statistics), with or without ENVP: `hv` takes the material's alpha / tcrit / tbreak after the ENVP rows, rho_c and
-// rho_elec are read from the rows where they are used.
-template <int L, bool TRACE, bool F64 = false, bool PULSE = false, bool ENVP = false, bool MAT = false>
+// F_MAT: the form with per-environment wire material (wedm_bind_wire_material; float32 stencil, no trace sample, no
+// pulse statistics), with or without F_ENVP: `hv` takes the material's alpha / tcrit / tbreak after the ENVP rows, rho_c
+// and rho_elec are read from the rows where they are used.
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
+    static_assert((F & ~(F_TRACE | F_F64 | F_PULSE | F_ENVP | F_MAT)) == 0, "forms of wedm_step_lanes_pk");
+    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
+    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
     if (ENVP || MAT) {
@@ -262,8 +266,8 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE, ENVP, MAT>(hv, cold, g, e, gid, s, qt, cf);
-        if (!was_quiet && !s.done) cf = scalar_prelude<false, false, ENVP, MAT>(hv, cold, g, e, gid, s, ps, c == 0, qt);
+        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE, F>(hv, cold, g, e, gid, s, qt, cf);
+        if (!was_quiet && !s.done) cf = scalar_prelude<F>(hv, cold, g, e, gid, s, ps, c == 0, qt);
         freeze_wire(s);
         const bool keep = !s.done;
 
@@ -299,8 +303,9 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
 // on the scalar wave, one microsecond ahead of the walkers where it can prove that the step does not break the wire
 // (wedm_served.h: mailbox, protocol, proof).  Three blocks per CU at 168 registers.  No trace point, freeze-on-termination
 // only (other launches run wedm_step_lanes_pk).
-template <int L>
+template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_lanes_served(const KArgs k) {
+    static_assert(F == 0, "wedm_step_lanes_served has one form");
     constexpr int NT = 192, EPB = NT / L;
     static_assert(EPB <= 64, "one lane of the scalar wave per environment of the block");
     typedef ServedBox<EPB> Box;

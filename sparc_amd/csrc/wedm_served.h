@@ -340,11 +340,14 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
 
 // ============================================ served packed kernel: L lanes / env, 2 cells / op, scalar physics on a wave of its own
 // Walk, LDS image and tile table are wedm_step_packed's (two virtual chunks per lane in float2 registers; the table built for
-// 2 L chunks; one-change tiles and 1- / 2-cell tails with EXTRA).  A wave with a frozen (terminated) environment keeps the
-// tile code, its lanes do not store (wedm_step_packed's FROZEN_OK, always on here).
+// 2 L chunks; one-change tiles and 1- / 2-cell tails with F_EXTRA).  A wave with a frozen (terminated) environment keeps
+// the tile code, its lanes do not store (wedm_step_packed's F_FROZEN_OK, always on here).
 // Not here (the launch plan keeps such launches on wedm_step_packed): a trace sample inside the launch, keep_stepping_terminated.
-template <int L, bool EXTRA, int WW = 3>
-__global__ void __launch_bounds__((WW + 1) * 64, WEDM_SERVED_WAVES_PER_EU) wedm_step_served(const KArgs k) {
+template <int L, uint32_t F>
+__global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_served(const KArgs k) {
+    static_assert((F & ~F_EXTRA) == 0, "forms of wedm_step_served");
+    constexpr bool EXTRA = (F & F_EXTRA) != 0;
+    constexpr int WW = 3;         // walker waves; with the scalar wave, blocks of (WW + 1) * 64 = 256 threads
     constexpr int NT = WW * 64;   // walker threads = columns of the LDS image
     constexpr int EPB = NT / L;   // environments per block
     static_assert(EPB <= 64 && WW <= 4, "one lane of the scalar wave per environment of the block");
@@ -716,16 +719,17 @@ __global__ void __launch_bounds__((WW + 1) * 64, WEDM_SERVED_WAVES_PER_EU) wedm_
 }
 
 // ============================================ served register kernel: the wire in the walkers' registers, no LDS image
-// wedm_step_regs<128, 2>'s walk (wedm_regs_walk.inc) on TWO walker waves of a block -- two lanes per environment, 32 packed
+// wedm_step_regs<2>'s walk (wedm_regs_walk.inc) on TWO walker waves of a block -- two lanes per environment, 32 packed
 // pairs each --, the scalar physics of the block's 64 environments on a third wave, all 64 of its lanes busy.  Blocks of three
 // waves, four to a CU at 168 registers: 256 environments per CU, 65 536 in ONE round.  LDS holds the mailbox only.
-// By name only (kernel 12), measured at 65 536 x 128 (round 4): fused launches 1.666e10 env-steps/s against wedm_step_regs<128, 2>'s
+// By name only (kernel 12), measured at 65 536 x 128 (round 4): fused launches 1.666e10 env-steps/s against wedm_step_regs<2>'s
 // 1.674e10 -- a sixth fewer instructions, given back by spills: the walk with 64 wire registers per lane wants 239 registers
 // and spills 53 at the 168 that three waves per SIMD leave, the scalar wave 113 -- and launches of ONE microsecond 41.7 us
 // against wedm_step_stream's 20.4 us (every state row loaded and stored, scratch traffic cold at every launch).
-template <int CELLS>
+template <uint32_t F>
 __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_served(const KArgs k) {
-    constexpr int L = 2, H = CELLS / (2 * L), EPB = 64, NT = 128;
+    static_assert(F == 0, "wedm_step_regs_served has one form");
+    constexpr int CELLS = 128, L = 2, H = CELLS / (2 * L), EPB = 64, NT = 128;
     static_assert(H % 8 == 0 && H / 8 <= 16, "whole tiles");
     constexpr int SW = WEDM_REGS_SW2;
     typedef ServedBox<EPB> Box;
