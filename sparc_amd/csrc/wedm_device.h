@@ -1147,6 +1147,71 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
     return cf;
 }
 
+// ------------------------------------------------- scalar work split over the two lanes of one environment
+// Where two neighbouring lanes (2 i, 2 i + 1) hold the SAME environment (wedm_step_regs<2>), code that runs one
+// instruction sequence on two independent operand sets need not run both sets in both lanes: the even lane ("A") takes
+// one set, the odd lane ("B") the other, and they hand each other the result through the quad permute [1,0,3,2] of
+// swap_with_neighbour.  Every operation is the same integer / IEEE operation on the same operands; only the lane that
+// executes it changes, so the results are bit for bit what both lanes would have computed.
+// The exchanges must run with a lane's partner active.  The two lanes of an environment hold identical scalar state
+// and therefore take the same branches, so a lane's partner is active whenever the lane is; the callers below also keep
+// the exchanges in wave-uniform control flow.  Used only by the two-lane register kernel.
+__device__ __forceinline__ bool pair_lane_b() { return (threadIdx.x & 1u) != 0u; }
+// the even lane's value in both lanes / the odd lane's value in both lanes: quad permutes [0,0,2,2] and [1,1,3,3]
+// (a quad permute reads no lane outside the quad, so the result needs no `old` value: mov_dpp leaves it undefined and
+// saves the move that update_dpp(0, ..) spends on it)
+__device__ __forceinline__ uint32_t pair_from_a(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int32_t)x, 0xA0, 0xF, 0xF, true); }
+__device__ __forceinline__ uint32_t pair_from_b(uint32_t x) { return (uint32_t)__builtin_amdgcn_mov_dpp((int32_t)x, 0xF5, 0xF, 0xF, true); }
+__device__ __forceinline__ double pair_from_a(double x) {
+    const uint64_t u = d2bits(x);
+    return bits2d(((uint64_t)pair_from_a((uint32_t)(u >> 32)) << 32) | pair_from_a((uint32_t)u));
+}
+__device__ __forceinline__ double pair_from_b(double x) {
+    const uint64_t u = d2bits(x);
+    return bits2d(((uint64_t)pair_from_b((uint32_t)(u >> 32)) << 32) | pair_from_b((uint32_t)u));
+}
+
+// Philox4x32-10 of philox4(), one multiplication chain per lane.  A round of philox4 is
+//     p0 = M0 c0, p1 = M1 c2;  c0' = hi(p1) ^ c1 ^ k0, c1' = lo(p1), c2' = hi(p0) ^ c3 ^ k1, c3' = lo(p0):
+// lane A holds (X, lo) = (c0, c3), multiplies by M0 and owns key k0; lane B holds (c2, c1), multiplies by M1 and owns k1.
+// Both run   m = mul X;  t = hi(m) ^ lo;  lo = lo(m);  X = partner(t) ^ k;  k += weyl
+// -- one 64-bit multiply and two xors (the partner's t as the DPP operand of the second) instead of two and four.
+// After the tenth round A holds (c0, c3) and B holds (c2, c1).
+// WEDM_PAIR_KEYS_HOISTED 0: one running key per lane, opaque per call, advanced by an add per round; 1: the compiler is
+// free to keep the ten round keys of a launch in registers (what it does for philox4 in a microsecond loop).
+#ifndef WEDM_PAIR_KEYS_HOISTED
+#define WEDM_PAIR_KEYS_HOISTED 0
+#endif
+#ifndef WEDM_PAIR_DIV
+#define WEDM_PAIR_DIV 1
+#endif
+struct PhiloxHalf { uint32_t X, lo; };
+__device__ __forceinline__ PhiloxHalf philox4_pair(bool lane_b, uint32_t key0, uint32_t key1, uint32_t time, uint32_t episode,
+                                                   uint32_t gid, uint32_t stream) {
+#if !WEDM_PAIR_KEYS_HOISTED
+    // (the lane's choice among launch constants -- key, episode, environment -- made opaque per call: hoisted out of a
+    // microsecond loop the selected values are registers the loop does not have, and come back as scratch loads)
+    uint32_t odd = lane_b ? 1u : 0u;
+    asm volatile("" : "+v"(odd));
+    lane_b = odd != 0u;
+#endif
+    const uint32_t mul = lane_b ? 0xCD9E8D57u : 0xD2511F53u, weyl = lane_b ? 0xBB67AE85u : 0x9E3779B9u;
+    uint32_t X = lane_b ? gid : time, lo = lane_b ? episode : stream, k = lane_b ? key1 : key0;
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t m = (uint64_t)mul * X;
+        const uint32_t t = (uint32_t)(m >> 32) ^ lo;
+        lo = (uint32_t)m;
+        X = (uint32_t)swap_with_neighbour((int32_t)t) ^ k;
+        k += weyl;
+    }
+    return PhiloxHalf{X, lo};
+}
+// the four words of philox4() in both lanes (off the hot line: the general prelude's rolls)
+__device__ __forceinline__ W4 philox4_pair_words(PhiloxHalf h) {
+    return W4{pair_from_a(h.X), pair_from_b(h.lo), pair_from_b(h.X), pair_from_a(h.lo)};
+}
+
 // ------------------------------------------------- quiet-step fast path (wave-uniform)
 // In an ordinary microsecond nothing discrete happens to an environment: no short timer runs,
 // the generator idles or rests, the action is not latched, the gap is far from a hard short, the
@@ -1166,7 +1231,12 @@ __device__ __forceinline__ Coef scalar_prelude(const Hot& p, const ColdRef cold,
 // F: the calling kernel's forms.  F_ENVP: the plasma efficiency comes from the environment's row (wedm_bind_env_params),
 // as in scalar_prelude.  F_MAT: the electrical resistivity comes from the environment's wire-material row
 // (wedm_bind_wire_material), as in scalar_prelude.
-template <bool DENSE, uint32_t F = 0>
+// PAIR: the caller's lanes 2 i and 2 i + 1 hold the same environment (wedm_step_regs<2>).  The step's Philox words are
+// then computed half in each lane (philox4_pair), and the line's two float64 quotients -- debris / cavity and
+// ln 2 / (a d0^2 + b d0 + c), independent of each other -- by ONE division sequence: the even lane divides the first
+// pair of operands, the odd lane the second, and each takes the other's quotient by DPP.  For that the ignition
+// denominator is formed before the first ballot (it has no side effect; when no lane idles its quotient is unused).
+template <bool DENSE, uint32_t F = 0, bool PAIR = false>
 __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold, const Geom& g, int64_t e, uint32_t gid,
                                                 Env& s, QuietTry& qt, Coef& cf) {
     constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
@@ -1184,7 +1254,15 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
     // dielectric (dielectric.py:87-139): this step's density and the cache test
     const double cavity = g.cavity_coeff * (d0 * 0.001);
     double rho = 0.0;
-    if (cavity > 0) {
+    double lam_pair = 0.0;
+    if (PAIR && WEDM_PAIR_DIV) {
+        const bool lane_b = pair_lane_b();
+        const double den = p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c;
+        const double quot = (lane_b ? p.ln2 : s.debris) / (lane_b ? den : cavity);
+        const double qq = pair_from_a(quot);
+        lam_pair = pair_from_b(quot);
+        if (cavity > 0) rho = qq < 1.0 ? qq : 1.0;
+    } else if (cavity > 0) {
         const double qq = s.debris / cavity;
         rho = qq < 1.0 ? qq : 1.0;
     }
@@ -1193,16 +1271,31 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
     if (!__all(q || !live)) return false;
     // ignition roll of the idle lanes (ignition.py:321-327)
     bool ign = false;
+    PhiloxHalf wh{0u, 0u};
     if (__any(idle && live)) {
-        const double lam = p.ln2 / (p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c);
-        const W4 w = philox4(s.key0, s.key1, (uint32_t)s.time, (uint32_t)s.episode, gid, 0u);
-        ign = idle && live && (u32_to_unit(w.z) < lam);
+        if (PAIR) {
+            wh = philox4_pair(pair_lane_b(), s.key0, s.key1, (uint32_t)s.time, (uint32_t)s.episode, gid, 0u);
+            if (!WEDM_PAIR_DIV) lam_pair = p.ln2 / (p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c);
+            ign = idle && live && (u32_to_unit(pair_from_b(wh.X)) < lam_pair);   // w.z is the odd lane's X
+        } else {
+            const double lam = p.ln2 / (p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c);
+            const W4 w = philox4(s.key0, s.key1, (uint32_t)s.time, (uint32_t)s.episode, gid, 0u);
+            ign = idle && live && (u32_to_unit(w.z) < lam);
 #ifndef WEDM_NO_PHILOX_REUSE
-        qt.w = w;          // every lane of the wave computed its words: the general path need not repeat them
+            qt.w = w;      // every lane of the wave computed its words: the general path need not repeat them
+#endif
+        }
+#ifndef WEDM_NO_PHILOX_REUSE
         qt.have_w = true;
 #endif
     }
-    if (__any(ign)) return false;
+    if (__any(ign)) {
+#ifndef WEDM_NO_PHILOX_REUSE
+        // (the general path wants all four words: exchanged here, off the quiet line, still with every lane active)
+        if (PAIR) qt.w = philox4_pair_words(wh);
+#endif
+        return false;
+    }
     bool burning = false;
     if (live) {
         const double Vt = s.tvolt != 0.0 ? s.tvolt : p.default_target_voltage;

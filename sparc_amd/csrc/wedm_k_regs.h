@@ -43,6 +43,9 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 #ifndef WEDM_REGS_PIN2
 #define WEDM_REGS_PIN2 1
 #endif
+#ifndef WEDM_REGS_PAIR_SPLIT
+#define WEDM_REGS_PAIR_SPLIT 1  // two lanes: Philox and the quiet line's two divisions half in each lane (quiet_prelude_t<.., PAIR>)
+#endif
 // F_TRACE: the form with the signal-trace point (a launch into which a sample falls: the reference's logger samples
 // after every step, utils/logger.py:110-160); launches without a sample run the form without it.
 // F_F64: stencil_mode 1 -- the walk in the typing Numba gives wire.py:58-123 (cell_f64 above); everything else is the same kernel.
@@ -166,7 +169,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_REGS_DENSE>(hv, cold, g, e, gid, s, qt, cf);
+        const bool was_quiet = quiet_prelude_t<WEDM_REGS_DENSE, 0u, L == 2 && WEDM_REGS_PAIR_SPLIT>(hv, cold, g, e, gid, s, qt, cf);
         if (!was_quiet) {
             if (!s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, writer, qt);
             build_conv();
