@@ -122,6 +122,8 @@ __device__ __forceinline__ const double* wedm::kernarg_wmat() {
     return *p;
 }
 
+#include "wedm_lifecycle.h"
+
 // ------------------------------------------------------------ signal trace
 // The sample schedule is host-made and identical for every wave: `it == trace_next` is a scalar
 // compare per microsecond; the descriptor travels by value in the kernel arguments.  While a
@@ -239,17 +241,10 @@ template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, const ColdRef cold, const Geom& g, int64_t e,
                                                uint32_t gid, Env& s, const TA& T) {
     constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
-    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
-    const PulseRef pulse = kernarg_pulse();
-    (void)pulse;
+    constexpr bool MAT = (F & F_MAT) != 0;
     Persist ps;
     init_persist<false, MAT>(hot, cold, e, s, ps);
-    StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) {
-        const wedm_params* pp = cold->p;
-        f64c = StencilF64{pp->temp_ref, MAT ? WEDM_WMAT_ROW(kernarg_wmat(), WEDM_WM_ALPHA_RHO, cold->s.stride) : pp->alpha_rho,
-                          ENVP ? WEDM_ENVP_ROW(kernarg_envp(), WEDM_EP_DIELECTRIC_TEMPERATURE, cold->s.stride) : pp->dielectric_temperature};
-    }
+    const StencilF64 f64c = stencil_f64_consts<F>(cold, e);
     const bool tracing = WEDM_TRACING(k);
     int trace_next = k.trace_next, trace_slot = k.trace_slot;
     (void)trace_next; (void)trace_slot;
@@ -259,9 +254,7 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
             Coef c = scalar_prelude<F>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
             float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, hot, f64c, s.h_base, s.h_zone);
-            scalar_epilogue(hot, s, tmax);
-            pulse_tally<PULSE>(pulse, cold, e, s, pk, true);
-            if (s.ctrl) control_step_outputs(cold, e, s, true);
+            env_step_done<F>(hot, cold, e, s, tmax, pk, true);
         } else if (!tracing) {
             break;
         }
@@ -275,19 +268,7 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
 template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
                                              uint32_t gid, Env& s, const TA& T) {
-    constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
-    if (MAT) {
-        Hot hv = k.hot;
-        if (ENVP) envp_apply(hv, cold->s.stride, e);
-        wmat_apply(hv, cold->s.stride, e);
-        run_substeps_h<F, TA>(k, hv, cold, g, e, gid, s, T);
-    } else if (ENVP) {
-        Hot hv = k.hot;
-        envp_apply(hv, cold->s.stride, e);
-        run_substeps_h<F, TA>(k, hv, cold, g, e, gid, s, T);
-    } else {
-        run_substeps_h<F, TA>(k, k.hot, cold, g, e, gid, s, T);
-    }
+    run_substeps_h<F, TA>(k, launch_hot<F>(k, cold, e, true), cold, g, e, gid, s, T);
 }
 
 // np.max over finite temperatures; maps to v_max_f32 / v_max3_f32

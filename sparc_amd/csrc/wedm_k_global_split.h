@@ -39,12 +39,7 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     Geom g;
     load_geom(k.hot, cold, e, g);
     run_substeps<F, GlobalT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
-    if (WEDM_REWARD_ON(cold)) {
-        if (!frozen) write_reward(cold, e, s);
-        else cold->s.reward[e] = 0.0f;
-    }
-    store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
+    env_close(k, cold, e, s, frozen, true);
 }
 
 // phase stamps of the split kernel (diagnostic build -DWEDM_STAMPS only): raw s_memtime at
@@ -112,15 +107,8 @@ __global__ void __launch_bounds__(256) wedm_step_split(const KArgs k) {
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     bool frozen0 = true;
     if (c == 0) {
-        if (live) load_env(cold, e, s);
-        else s.done = WEDM_DEAD_LANE;
-        if (reinit) reinit_env(cold, e, s, true);
-        unfreeze_wire(k.hot, s);  // keep_stepping_terminated: nothing is frozen
-        frozen0 = s.done;
-        if (!s.done) {
-            s.ipk = peak_current(cold, s.mode, e);
-            init_persist(k.hot, cold, e, s, ps);
-        }
+        env_open<F>(cold, e, live, true, s);  // (the same `reinit`)
+        frozen0 = env_start<F>(k.hot, cold, e, s, ps);
     }
     int trace_next = k.trace_next, trace_slot = k.trace_slot;
     (void)trace_next; (void)trace_slot;
@@ -207,8 +195,7 @@ __global__ void __launch_bounds__(256) wedm_step_split(const KArgs k) {
             float m = sh_max[0][el];
 #pragma unroll
             for (int q = 1; q < WEDM_QL; ++q) m = fmax_gt(m, sh_max[q][el]);
-            scalar_epilogue(k.hot, s, m);
-            if (s.ctrl) control_step_outputs(cold, e, s, true);
+            env_step_done<F>(k.hot, cold, e, s, m, 0, true);
         }
         if (TRACE && it == trace_next) {  // wave-uniform schedule; T rows of the step just finished
             const wedm_trace_desc& tr = k.trace;
@@ -227,14 +214,7 @@ __global__ void __launch_bounds__(256) wedm_step_split(const KArgs k) {
         if (it + 1 < k.n_substeps) __syncthreads();  // the next step's halo reads follow this step's stores
     }
     WEDM_SPLIT_STAMP(5);
-    if (c == 0 && live) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    env_close(k, cold, e, s, frozen0, c == 0 && live);
     WEDM_SPLIT_STAMP(6);
     WEDM_SPLIT_STAMP_OUT();
 }

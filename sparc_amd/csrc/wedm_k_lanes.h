@@ -58,8 +58,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
     const int cbase = c * C;
     const int n = g.n_seg;  // this lane's environment
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
-    StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) { const wedm_params* pp = cold->p; f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature}; }
+    const StencilF64 f64c = stencil_f64_consts<F>(cold, e);
     if (c == 0) col[0] = spool;
 
     const bool tracing = WEDM_TRACING(k);
@@ -170,24 +169,13 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
         }
 #pragma unroll
         for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
-        unfreeze_wire(hv, s);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
-        }
+        env_end_us<F>(hv, cold, e, s, tmax, 0, c == 0);
         WEDM_TRACE_POINT(k, it, e, s, c == 0,
                          for (int j = 0; j < C && cbase + j < n; ++j) tT[(int64_t)(cbase + j) * tcnt] = col[j * 256]);
     }
 
     __syncthreads();
     copy_wire<L, false>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
-    if (live && c == 0) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    env_close(k, cold, e, s, frozen0, live && c == 0);
 }
 

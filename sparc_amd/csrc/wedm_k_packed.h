@@ -415,12 +415,8 @@ __global__ void __launch_bounds__(256, WEDM_PACKED_MIN_BLOCKS) wedm_step_packed(
         }
 #pragma unroll
         for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
-        unfreeze_wire(hv, s);
         WEDM_STAMP(st3);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
-        }
+        env_end_us<F>(hv, cold, e, s, tmax, 0, c == 0);
         WEDM_TRACE_POINT(k, it, e, s, c == 0,
                          for (int r = 0; r < Cv; ++r) {
                              if (baseA + r < n) tT[(int64_t)(baseA + r) * tcnt] = col[(2 * r) * 256];
@@ -433,14 +429,7 @@ __global__ void __launch_bounds__(256, WEDM_PACKED_MIN_BLOCKS) wedm_step_packed(
 
     __syncthreads();
     copy_wire<L, false>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
-    if (live && c == 0) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    env_close(k, cold, e, s, frozen0, live && c == 0);
 }
 
 

@@ -386,11 +386,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
         }
 #pragma unroll
         for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
-        unfreeze_wire(hv, s);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
-        }
+        env_end_us<F>(hv, cold, e, s, tmax, 0, c == 0);
         WEDM_TRACE_POINT(k, it, e, s, c == 0,
                          for (int j = 0; j < C && cbase + j < n; ++j) tT[(int64_t)(cbase + j) * tcnt] = col[j * 256]);
     };
@@ -537,8 +533,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
 #pragma unroll
         for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
         unfreeze_wire(hv, s);
-        scalar_epilogue(hv, s, tmax);
-        if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
+        env_step_done<F>(hv, cold, e, s, tmax, 0, c == 0);  // (the register walk runs only where no lane is done)
     };
     const bool idle = __all(s.done) && !tracing;  // nothing to advance and nothing to sample
     {

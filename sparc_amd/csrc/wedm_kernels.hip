@@ -6,6 +6,8 @@
 //   wedm_device.h         per-lane physics of one microsecond: Env, prelude (quiet / general), epilogue (monitor + motion),
 //                         Philox, the portable exp / log / cube, stencil_cell
 //   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors / copy_wire, tile_staged / quad_staged
+//   wedm_lifecycle.h      an environment's launch lifecycle as helpers: launch_hot, env_open / env_start, env_end_us /
+//                         env_step_done, env_close, stencil_f64_consts (the file's head says which family calls which)
 //   wedm_k_global_split.h wedm_step_global (in place in global memory; stencil_mode 1, injected variates, very long wires),
 //                         wedm_step_split (single microseconds where the stream kernel does not fit)
 //   wedm_k_stream.h       wedm_step_stream<L>: single microseconds (the reference's step() cadence), uniform geometry

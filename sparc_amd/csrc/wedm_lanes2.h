@@ -192,13 +192,8 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
     constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     const ColdRef cold = kernarg_cold();
-    Hot hv = k.hot;
-    if (ENVP || MAT) {
-        const int64_t ee = (int64_t)blockIdx.x * (256 / L) + threadIdx.x / L;
-        const int64_t er = ee < k.num_envs ? ee : 0;  // (a lane past the batch reads environment 0's rows)
-        if (ENVP) envp_apply(hv, cold->s.stride, er);
-        if (MAT) wmat_apply(hv, cold->s.stride, er);
-    }
+    const int64_t e_hot = (int64_t)blockIdx.x * (256 / L) + threadIdx.x / L;
+    Hot hv = launch_hot<F>(k, cold, e_hot, e_hot < k.num_envs);
     pin_mechanics_in_vgprs(hv);
     pin_quiet_in_vgprs(hv);
     extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -221,8 +216,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     Geom g;
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     load_geom(k.hot, cold, live ? e : 0, g);
-    StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) { const wedm_params* pp = cold->p; f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature}; }
+    const StencilF64 f64c = stencil_f64_consts<F>(cold, e);
     if (live) load_env(cold, e, s);
     else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
     float* col = lds + tid;
@@ -273,12 +267,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
 
         float tmax = lanes_pk_step<L, 256, F64>(col, pkg, keep, g, cf, ps, spool, tref, alpha, tdiel, f64c, s.h_base, s.h_zone);
         tmax = max_over_env_lanes<L>(tmax);
-        unfreeze_wire(hv, s);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, c == 0);
-            if (s.ctrl) control_step_outputs(cold, e, s, c == 0);
-        }
+        env_end_us<F>(hv, cold, e, s, tmax, pk, c == 0);
         WEDM_TRACE_POINT(k, it, e, s, c == 0,
                          for (int r = 0; r < Cv; ++r) {
                              if (baseA + r < n) tT[(int64_t)(baseA + r) * tcnt] = col[(2 * r) * 256];
@@ -288,14 +277,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
 
     __syncthreads();
     copy_wire<L, false>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
-    if (live && c == 0) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    env_close(k, cold, e, s, frozen0, live && c == 0);
 }
 
 // ============================================ served form: the scalar physics of the block's environments on a fourth wave

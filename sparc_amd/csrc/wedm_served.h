@@ -307,8 +307,7 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
             { WEDM_SV_WAIT_BEGIN(); sv_wait_lanes(&box->tm_seq[(sl < EPB ? sl * LPE : 0) >> 6], (uint32_t)it + 1u); WEDM_SV_WAIT_END(); }
             const float tm = sl < EPB ? box->tmax[slot][sl] : spool;
             if (!s.done) {
-                scalar_epilogue(hv, s, tm);
-                if (s.ctrl) control_step_outputs(cold, e, s, true);
+                env_step_done<0>(hv, cold, e, s, tm, 0, true);
                 M = tm;
             }
             have_m = true;
@@ -328,14 +327,7 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
     sv_stamps_out(svs, stamp_row);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();  // (B) the walkers' last step is in LDS
-    if (live) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    env_close(k, cold, e, s, frozen0, live);
 }
 
 // ============================================ served packed kernel: L lanes / env, 2 cells / op, scalar physics on a wave of its own
