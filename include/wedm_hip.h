@@ -34,6 +34,18 @@
  * reset (spool temperature), never read into a result, never rewritten by a step.
  * (ABI v3 had T[seg][env]: one dword per lane and instruction, which is what bound
  * the one-launch-per-microsecond kernels: DESIGN.md section 4.2.)
+ *
+ * What a launch writes (tests/test_memory_contract.py holds every kernel to it).  Every block is [rows][stride]; only
+ * the first num_envs columns of a row are the library's, the columns [num_envs, stride) are the caller's padding, and
+ * what lies before a block's first row and behind its last one is somebody else's memory.
+ *   1. wedm_step and wedm_reset write only: columns [0, num_envs) of the rows of the bound state blocks (f64, i32, i8,
+ *      T, obs, stats, reward, crater_log); the same columns of the pulse block, where bound; in a bound trace ring, the
+ *      slots and the environment window its descriptor names.
+ *   2. Columns [num_envs, stride) of every one of those rows are never written, and no launch writes a byte before a
+ *      block's first row or after its last row, the action leaves, the reset mask, the geometry, env-param and
+ *      wire-material rows, the replay table, or the device copy of the params.
+ *   3. 2 holds at every stride >= num_envs that wedm_bind_state accepts, not only at multiples of 64, and the results in
+ *      the owned columns are the same at every such stride.
  */
 #ifndef WEDM_HIP_H
 #define WEDM_HIP_H
@@ -337,7 +349,7 @@ typedef struct wedm_state_ptrs {
     int8_t* i8;         /* [WEDM_I8_COUNT ][stride] */
     float* T;           /* [WEDM_T_QUADS(n_seg_max)][stride][4], see WEDM_T_INDEX */
     float* obs;         /* [obs_dim][stride] or NULL */
-    int64_t stride;     /* >= num_envs, multiple of 64 recommended */
+    int64_t stride;     /* >= num_envs, multiple of 64 recommended (any other is served too: "What a launch writes") */
     double* stats;      /* [WEDM_STAT_COUNT][stride] or NULL (statistics not kept) */
     float* reward;      /* [stride] or NULL; written when wedm_params.reward_mode != 0 */
     /* `MaterialRemovalModule.crater_volumes_um3` (material.py:133): every sampled crater volume [um^3] of an
