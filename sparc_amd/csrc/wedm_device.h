@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "../../include/wedm_hip.h"
+#include "wedm_env_rows.h"
 
 namespace wedm {
 
@@ -418,35 +419,26 @@ __device__ __forceinline__ double peak_current(const ColdRef cold, int32_t mode,
     return (mode >= 1 && mode <= WEDM_MAX_MODE) ? cold->tb.mode_current[mode] : opaque(cold->p)->default_current;
 }
 
+// ---- the register state and its rows: load_env ... env_i8_row expand the lists of wedm_env_rows.h, one statement per line and
+// in the lists' order.  WEDM_LOAD_ROWS / WEDM_ZERO_ROWS / WEDM_STORE_ROWS(set): the lines with a tag in the set, all three blocks.
+#define WEDM_STATE_BLOCKS(CONST)                                       \
+    const ColdPtr c = cold.get(); const int64_t stride = c->s.stride; \
+    const struct { CONST double* f64; CONST int32_t* i32; CONST int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
+#define WEDM_LD_F(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) v.m = (decltype(v.m))*WEDM_ROW(s.f64, row);
+#define WEDM_LD_I(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) v.m = (decltype(v.m))*WEDM_ROW(s.i32, row);
+#define WEDM_LD_B(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) v.m = (decltype(v.m))*WEDM_ROW(s.i8, row);
+#define WEDM_LOAD_ROWS(set) WEDM_ENV_F64(WEDM_LD_F, set) WEDM_ENV_I32(WEDM_LD_I, set) WEDM_ENV_I8(WEDM_LD_B, WEDM_LD_B, set)
+#define WEDM_ZERO(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) v.m = 0;
+#define WEDM_ZERO_ROWS(set) WEDM_ENV_F64(WEDM_ZERO, set) WEDM_ENV_I32(WEDM_ZERO, set) WEDM_ENV_I8(WEDM_ZERO, WEDM_ZERO, set)
+#define WEDM_ST_F(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) *WEDM_ROW(s.f64, row) = (double)v.m;
+#define WEDM_ST_I(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) *WEDM_ROW(s.i32, row) = (int32_t)v.m;
+#define WEDM_ST_B(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) *WEDM_ROW(s.i8, row) = (int8_t)v.m;
+#define WEDM_ST_DONE(set, m, row, stage, role, owner) if constexpr (WEDM_HAS(set, stage, role, owner)) *WEDM_ROW(s.i8, row) = (int8_t)done_row(cold, v);
+#define WEDM_STORE_ROWS(set) WEDM_ENV_F64(WEDM_ST_F, set) WEDM_ENV_I32(WEDM_ST_I, set) WEDM_ENV_I8(WEDM_ST_B, WEDM_ST_DONE, set)
+
 __device__ __forceinline__ void load_env(const ColdRef cold, int64_t e, Env& v) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { const double* f64; const int32_t* i32; const int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-    v.wp = *WEDM_ROW(s.f64, WEDM_F_WORKPIECE_POS); v.x = *WEDM_ROW(s.f64, WEDM_F_WIRE_POS);
-    v.v = *WEDM_ROW(s.f64, WEDM_F_WIRE_VEL); v.prev_a = *WEDM_ROW(s.f64, WEDM_F_PREV_ACCEL);
-    v.debris = *WEDM_ROW(s.f64, WEDM_F_DEBRIS_VOLUME); v.rho = *WEDM_ROW(s.f64, WEDM_F_DEBRIS_DENSITY);
-    v.flow = *WEDM_ROW(s.f64, WEDM_F_FLOW); v.last_gap = *WEDM_ROW(s.f64, WEDM_F_LAST_GAP);
-    v.last_rho = *WEDM_ROW(s.f64, WEDM_F_LAST_DENSITY); v.wire_last_flow = *WEDM_ROW(s.f64, WEDM_F_WIRE_LAST_FLOW);
-    v.V = *WEDM_ROW(s.f64, WEDM_F_VOLTAGE); v.I = *WEDM_ROW(s.f64, WEDM_F_CURRENT);
-    v.y = *WEDM_ROW(s.f64, WEDM_F_SPARK_Y); v.last_crater = *WEDM_ROW(s.f64, WEDM_F_LAST_CRATER);
-    v.cavity = *WEDM_ROW(s.f64, WEDM_F_CAVITY); v.tdelta = *WEDM_ROW(s.f64, WEDM_F_TARGET_DELTA);
-    v.tvolt = *WEDM_ROW(s.f64, WEDM_F_TARGET_VOLTAGE); v.on = *WEDM_ROW(s.f64, WEDM_F_ON_TIME);
-    v.off = *WEDM_ROW(s.f64, WEDM_F_OFF_TIME); v.tpos = *WEDM_ROW(s.f64, WEDM_F_TARGET_POS);
-    v.unwind = *WEDM_ROW(s.f64, WEDM_F_UNWIND_VEL); v.vacc = *WEDM_ROW(s.f64, WEDM_F_VOLT_ACC);
-    v.h_base = (float)*WEDM_ROW(s.f64, WEDM_F_H_BASE); v.h_zone = (float)*WEDM_ROW(s.f64, WEDM_F_H_ZONE);
-    v.tmax = (float)*WEDM_ROW(s.f64, WEDM_F_TMAX);
-    v.time = *WEDM_ROW(s.i32, WEDM_I_TIME); v.tss = *WEDM_ROW(s.i32, WEDM_I_SINCE_SERVO);
-    v.tsov = *WEDM_ROW(s.i32, WEDM_I_SINCE_OPEN_V); v.tsi = *WEDM_ROW(s.i32, WEDM_I_SINCE_IGNITION);
-    v.tse = *WEDM_ROW(s.i32, WEDM_I_SINCE_SPARK_END); v.dur = *WEDM_ROW(s.i32, WEDM_I_SPARK_DUR);
-    v.rnd_rem = *WEDM_ROW(s.i32, WEDM_I_RANDOM_SHORT_REM); v.deb_rem = *WEDM_ROW(s.i32, WEDM_I_DEBRIS_SHORT_REM);
-    v.tcrit = *WEDM_ROW(s.i32, WEDM_I_TIME_CRITICAL); v.mode = *WEDM_ROW(s.i32, WEDM_I_CURRENT_MODE);
-    v.episode = *WEDM_ROW(s.i32, WEDM_I_EPISODE);
-    v.key0 = (uint32_t)*WEDM_ROW(s.i32, WEDM_I_KEY_LO); v.key1 = (uint32_t)*WEDM_ROW(s.i32, WEDM_I_KEY_HI);
-    v.sparks = *WEDM_ROW(s.i32, WEDM_I_SPARK_COUNT);
-    v.state = *WEDM_ROW(s.i8, WEDM_B_SPARK_STATE); v.is_short = *WEDM_ROW(s.i8, WEDM_B_IS_SHORT);
-    v.broken = *WEDM_ROW(s.i8, WEDM_B_WIRE_BROKEN); v.reached = *WEDM_ROW(s.i8, WEDM_B_TARGET_REACHED);
-    v.done = *WEDM_ROW(s.i8, WEDM_B_DONE); v.ctrl = *WEDM_ROW(s.i8, WEDM_B_CTRL_STEP);
-    v.err = *WEDM_ROW(s.i8, WEDM_B_ERROR);
+    WEDM_STATE_BLOCKS(const)
+    WEDM_LOAD_ROWS(ROW_ALL)
     v.ipk = 0.0;
 }
 
@@ -473,77 +465,31 @@ __device__ __forceinline__ int32_t done_row(const ColdRef cold, const Env& v) {
 }
 
 __device__ __forceinline__ void store_env(const ColdRef cold, int64_t e, const Env& v) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { double* f64; int32_t* i32; int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-    *WEDM_ROW(s.f64, WEDM_F_WORKPIECE_POS) = v.wp; *WEDM_ROW(s.f64, WEDM_F_WIRE_POS) = v.x;
-    *WEDM_ROW(s.f64, WEDM_F_WIRE_VEL) = v.v; *WEDM_ROW(s.f64, WEDM_F_PREV_ACCEL) = v.prev_a;
-    *WEDM_ROW(s.f64, WEDM_F_DEBRIS_VOLUME) = v.debris; *WEDM_ROW(s.f64, WEDM_F_DEBRIS_DENSITY) = v.rho;
-    *WEDM_ROW(s.f64, WEDM_F_FLOW) = v.flow; *WEDM_ROW(s.f64, WEDM_F_LAST_GAP) = v.last_gap;
-    *WEDM_ROW(s.f64, WEDM_F_LAST_DENSITY) = v.last_rho; *WEDM_ROW(s.f64, WEDM_F_WIRE_LAST_FLOW) = v.wire_last_flow;
-    *WEDM_ROW(s.f64, WEDM_F_VOLTAGE) = v.V; *WEDM_ROW(s.f64, WEDM_F_CURRENT) = v.I;
-    *WEDM_ROW(s.f64, WEDM_F_SPARK_Y) = v.y; *WEDM_ROW(s.f64, WEDM_F_LAST_CRATER) = v.last_crater;
-    *WEDM_ROW(s.f64, WEDM_F_CAVITY) = v.cavity; *WEDM_ROW(s.f64, WEDM_F_TARGET_DELTA) = v.tdelta;
-    *WEDM_ROW(s.f64, WEDM_F_TARGET_VOLTAGE) = v.tvolt; *WEDM_ROW(s.f64, WEDM_F_ON_TIME) = v.on;
-    *WEDM_ROW(s.f64, WEDM_F_OFF_TIME) = v.off; *WEDM_ROW(s.f64, WEDM_F_VOLT_ACC) = v.vacc;
-    *WEDM_ROW(s.f64, WEDM_F_H_BASE) = (double)v.h_base; *WEDM_ROW(s.f64, WEDM_F_H_ZONE) = (double)v.h_zone;
-    *WEDM_ROW(s.f64, WEDM_F_TMAX) = (double)v.tmax;
-    *WEDM_ROW(s.i32, WEDM_I_TIME) = v.time; *WEDM_ROW(s.i32, WEDM_I_SINCE_SERVO) = v.tss;
-    *WEDM_ROW(s.i32, WEDM_I_SINCE_OPEN_V) = v.tsov; *WEDM_ROW(s.i32, WEDM_I_SINCE_IGNITION) = v.tsi;
-    *WEDM_ROW(s.i32, WEDM_I_SINCE_SPARK_END) = v.tse; *WEDM_ROW(s.i32, WEDM_I_SPARK_DUR) = v.dur;
-    *WEDM_ROW(s.i32, WEDM_I_RANDOM_SHORT_REM) = v.rnd_rem; *WEDM_ROW(s.i32, WEDM_I_DEBRIS_SHORT_REM) = v.deb_rem;
-    *WEDM_ROW(s.i32, WEDM_I_TIME_CRITICAL) = v.tcrit; *WEDM_ROW(s.i32, WEDM_I_CURRENT_MODE) = v.mode;
-    *WEDM_ROW(s.i32, WEDM_I_SPARK_COUNT) = v.sparks;
-    *WEDM_ROW(s.i8, WEDM_B_SPARK_STATE) = (int8_t)v.state; *WEDM_ROW(s.i8, WEDM_B_IS_SHORT) = (int8_t)v.is_short;
-    *WEDM_ROW(s.i8, WEDM_B_WIRE_BROKEN) = (int8_t)v.broken; *WEDM_ROW(s.i8, WEDM_B_TARGET_REACHED) = (int8_t)v.reached;
-    *WEDM_ROW(s.i8, WEDM_B_DONE) = (int8_t)done_row(cold, v); *WEDM_ROW(s.i8, WEDM_B_CTRL_STEP) = (int8_t)v.ctrl;
-    *WEDM_ROW(s.i8, WEDM_B_ERROR) = (int8_t)v.err;
+    WEDM_STATE_BLOCKS()
+    WEDM_STORE_ROWS(ROW_STORED)
 }
 
 // ---- single-microsecond launches (wedm_step_split2): the state crosses HBM once per microsecond, so
 // only the rows a microsecond READS are loaded and only the rows it can have CHANGED are stored.
-// Write-only rows (assigned by every step before any use): last_crater, cavity, tmax, the control-step
-// flag; with the ignition module enabled also current and is_short_circuit.
+// Which rows every step assigns before any use (write-only), always or by a launch-level switch: the `role` column of wedm_env_rows.h.
 // h64: when given, the two convection coefficients are handed back as loaded (float64) and v.h_base / v.h_zone are left for
 // the caller to convert LATER: the conversion is the first use of loaded data, and placed here it made the compiler wait
 // for the state rows (a whole memory round trip) before the single-microsecond kernel could request its wire rows.
 __device__ __forceinline__ void load_env_inputs(const ColdRef cold, int64_t e, Env& v, bool ignition_on, double* h64 = nullptr,
                                                 bool keep_stepping = false) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { const double* f64; const int32_t* i32; const int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-    v.wp = *WEDM_ROW(s.f64, WEDM_F_WORKPIECE_POS); v.x = *WEDM_ROW(s.f64, WEDM_F_WIRE_POS);
-    v.v = *WEDM_ROW(s.f64, WEDM_F_WIRE_VEL); v.prev_a = *WEDM_ROW(s.f64, WEDM_F_PREV_ACCEL);
-    v.debris = *WEDM_ROW(s.f64, WEDM_F_DEBRIS_VOLUME); v.rho = *WEDM_ROW(s.f64, WEDM_F_DEBRIS_DENSITY);
-    v.flow = *WEDM_ROW(s.f64, WEDM_F_FLOW); v.last_gap = *WEDM_ROW(s.f64, WEDM_F_LAST_GAP);
-    v.last_rho = *WEDM_ROW(s.f64, WEDM_F_LAST_DENSITY); v.wire_last_flow = *WEDM_ROW(s.f64, WEDM_F_WIRE_LAST_FLOW);
-    v.V = *WEDM_ROW(s.f64, WEDM_F_VOLTAGE); v.y = *WEDM_ROW(s.f64, WEDM_F_SPARK_Y);
-    v.tdelta = *WEDM_ROW(s.f64, WEDM_F_TARGET_DELTA); v.tvolt = *WEDM_ROW(s.f64, WEDM_F_TARGET_VOLTAGE);
-    v.on = *WEDM_ROW(s.f64, WEDM_F_ON_TIME); v.off = *WEDM_ROW(s.f64, WEDM_F_OFF_TIME);
-    v.tpos = *WEDM_ROW(s.f64, WEDM_F_TARGET_POS); v.unwind = *WEDM_ROW(s.f64, WEDM_F_UNWIND_VEL);
-    v.vacc = *WEDM_ROW(s.f64, WEDM_F_VOLT_ACC);
+    WEDM_STATE_BLOCKS(const)
+    WEDM_ENV_F64_DOUBLES(WEDM_LD_F, ROW_IN) WEDM_ENV_F64_SUMS(WEDM_LD_F, ROW_IN)
+    static_assert((0u WEDM_ENV_F64_FLOATS(WEDM_ROW_BIT, ROW_IN)) == ((1u << WEDM_F_H_BASE) | (1u << WEDM_F_H_ZONE)),
+                  "load_env_inputs() loads the unconditional inputs among the float members by hand (the h64 hand-back)");
     if (h64) { h64[0] = *WEDM_ROW(s.f64, WEDM_F_H_BASE); h64[1] = *WEDM_ROW(s.f64, WEDM_F_H_ZONE); v.h_base = 0.0f; v.h_zone = 0.0f; }
     else { v.h_base = (float)*WEDM_ROW(s.f64, WEDM_F_H_BASE); v.h_zone = (float)*WEDM_ROW(s.f64, WEDM_F_H_ZONE); }
-    v.time = *WEDM_ROW(s.i32, WEDM_I_TIME); v.tss = *WEDM_ROW(s.i32, WEDM_I_SINCE_SERVO);
-    v.tsov = *WEDM_ROW(s.i32, WEDM_I_SINCE_OPEN_V); v.tsi = *WEDM_ROW(s.i32, WEDM_I_SINCE_IGNITION);
-    v.tse = *WEDM_ROW(s.i32, WEDM_I_SINCE_SPARK_END); v.dur = *WEDM_ROW(s.i32, WEDM_I_SPARK_DUR);
-    v.rnd_rem = *WEDM_ROW(s.i32, WEDM_I_RANDOM_SHORT_REM); v.deb_rem = *WEDM_ROW(s.i32, WEDM_I_DEBRIS_SHORT_REM);
-    v.tcrit = *WEDM_ROW(s.i32, WEDM_I_TIME_CRITICAL); v.mode = *WEDM_ROW(s.i32, WEDM_I_CURRENT_MODE);
-    v.episode = *WEDM_ROW(s.i32, WEDM_I_EPISODE);
-    v.key0 = (uint32_t)*WEDM_ROW(s.i32, WEDM_I_KEY_LO); v.key1 = (uint32_t)*WEDM_ROW(s.i32, WEDM_I_KEY_HI);
-    v.sparks = *WEDM_ROW(s.i32, WEDM_I_SPARK_COUNT);
-    v.state = *WEDM_ROW(s.i8, WEDM_B_SPARK_STATE);
-    v.broken = *WEDM_ROW(s.i8, WEDM_B_WIRE_BROKEN); v.reached = *WEDM_ROW(s.i8, WEDM_B_TARGET_REACHED);
-    v.done = *WEDM_ROW(s.i8, WEDM_B_DONE); v.err = *WEDM_ROW(s.i8, WEDM_B_ERROR);
-    v.I = 0.0; v.is_short = 0;
-    if (!ignition_on) {  // the caller forces the spark (single_spark_animation.py): both are inputs then
-        v.I = *WEDM_ROW(s.f64, WEDM_F_CURRENT);
-        v.is_short = *WEDM_ROW(s.i8, WEDM_B_IS_SHORT);
-    }
-    v.last_crater = 0.0; v.cavity = 0.0; v.tmax = 0.0f; v.ctrl = 0;
-    // keep_stepping_terminated: a broken wire's temperature monitor stands still (wire.py:260-261), so the maximum is an
-    // input for such a lane (wave-uniform switch; the default mode never loads the row)
-    if (keep_stepping) v.tmax = (float)*WEDM_ROW(s.f64, WEDM_F_TMAX);
+    WEDM_ENV_I32(WEDM_LD_I, ROW_IN) WEDM_ENV_I8(WEDM_LD_B, WEDM_LD_B, ROW_IN)
+    // every other member is assigned by the step before any use and starts from zero: current and the short flag ...
+    WEDM_ZERO_ROWS(ROW_IN_FORCED)
+    if (!ignition_on) { WEDM_LOAD_ROWS(ROW_IN_FORCED) }  // ... unless the caller forces the spark (single_spark_animation.py)
+    WEDM_ZERO_ROWS(ROW_OUT | ROW_IN_KEEPSTEP)
+    // keep_stepping_terminated: a broken wire's temperature monitor stands still (wire.py:260-261), so the maximum is an input
+    if (keep_stepping) { WEDM_LOAD_ROWS(ROW_IN_KEEPSTEP) }  // (wave-uniform switch; the default mode never loads the row)
     v.ipk = 0.0;
 }
 
@@ -558,7 +504,6 @@ __device__ __forceinline__ double swap_with_neighbour(double x) {
     const uint32_t lo = (uint32_t)swap_with_neighbour((int32_t)(uint32_t)u), hi = (uint32_t)swap_with_neighbour((int32_t)(uint32_t)(u >> 32));
     return bits2d(((uint64_t)hi << 32) | lo);
 }
-struct PairRaw { double f[11]; int32_t i[7]; int32_t b[3]; double cur; int32_t shrt; };  // a lane's own row of every pair, as loaded
 
 #define WEDM_PAIR_F64(X) X(0, WEDM_F_WORKPIECE_POS, WEDM_F_WIRE_POS) X(1, WEDM_F_WIRE_VEL, WEDM_F_PREV_ACCEL) \
     X(2, WEDM_F_DEBRIS_VOLUME, WEDM_F_DEBRIS_DENSITY) X(3, WEDM_F_FLOW, WEDM_F_LAST_GAP) X(4, WEDM_F_LAST_DENSITY, WEDM_F_WIRE_LAST_FLOW) \
@@ -568,21 +513,25 @@ struct PairRaw { double f[11]; int32_t i[7]; int32_t b[3]; double cur; int32_t s
     X(2, WEDM_I_SINCE_SPARK_END, WEDM_I_SPARK_DUR) X(3, WEDM_I_RANDOM_SHORT_REM, WEDM_I_DEBRIS_SHORT_REM) \
     X(4, WEDM_I_TIME_CRITICAL, WEDM_I_CURRENT_MODE) X(5, WEDM_I_EPISODE, WEDM_I_KEY_LO) X(6, WEDM_I_KEY_HI, WEDM_I_SPARK_COUNT)
 #define WEDM_PAIR_I8(X) X(0, WEDM_B_SPARK_STATE, WEDM_B_WIRE_BROKEN) X(1, WEDM_B_TARGET_REACHED, WEDM_B_DONE) X(2, WEDM_B_ERROR, WEDM_B_ERROR)
+// (every pair is one load instruction, so the pairs are chosen by hand; what they must cover follows from the `role` column:
+// the inputs, and TMAX, which fills the odd slot and is an input under keep_stepping.  ERROR pairs with itself.)
+#define WEDM_PAIR_ONE(k, A, B) +1
+#define WEDM_PAIR_BITS(k, A, B) | (1u << (A)) | (1u << (B))
+constexpr int PAIRS_F64 = 0 WEDM_PAIR_F64(WEDM_PAIR_ONE), PAIRS_I32 = 0 WEDM_PAIR_I32(WEDM_PAIR_ONE), PAIRS_I8 = 0 WEDM_PAIR_I8(WEDM_PAIR_ONE);
+static_assert((0u WEDM_PAIR_F64(WEDM_PAIR_BITS)) == WEDM_F64_ROWS(ROW_IN | ROW_IN_KEEPSTEP) && (0u WEDM_PAIR_I32(WEDM_PAIR_BITS)) == WEDM_I32_ROWS(ROW_IN | ROW_IN_KEEPSTEP) &&
+              (0u WEDM_PAIR_I8(WEDM_PAIR_BITS)) == WEDM_I8_ROWS(ROW_IN | ROW_IN_KEEPSTEP) && WEDM_F64_ROWS(ROW_IN_FORCED) == 1u << WEDM_F_CURRENT &&
+              WEDM_I32_ROWS(ROW_IN_FORCED) == 0 && WEDM_I8_ROWS(ROW_IN_FORCED) == 1u << WEDM_B_IS_SHORT,
+              "the paired loader must load exactly the rows load_env_inputs() loads: the pairs (WEDM_PAIR_*) the roles IN and IN_KEEPSTEP of "
+              "wedm_env_rows.h, PairRaw::cur and PairRaw::shrt the role IN_FORCED");
+struct PairRaw { double f[PAIRS_F64]; int32_t i[PAIRS_I32]; int32_t b[PAIRS_I8]; double cur; int32_t shrt; };  // a lane's own row of every pair, as loaded
 
 // requests: 21 loads (+ 2 when the caller forces the spark) instead of 40
+#define WEDM_PAIR_LD_F(k, A, B) r.f[k] = s.f64[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
+#define WEDM_PAIR_LD_I(k, A, B) r.i[k] = s.i32[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
+#define WEDM_PAIR_LD_B(k, A, B) r.b[k] = s.i8[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
 __device__ __forceinline__ void load_env_inputs_paired_issue(const ColdRef cold, int64_t e, bool odd, bool ignition_on, PairRaw& r) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { const double* f64; const int32_t* i32; const int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-#define WEDM_LD(k, A, B) r.f[k] = s.f64[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
-    WEDM_PAIR_F64(WEDM_LD)
-#undef WEDM_LD
-#define WEDM_LD(k, A, B) r.i[k] = s.i32[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
-    WEDM_PAIR_I32(WEDM_LD)
-#undef WEDM_LD
-#define WEDM_LD(k, A, B) r.b[k] = s.i8[(int64_t)(odd ? (int)(B) : (int)(A)) * stride + e];
-    WEDM_PAIR_I8(WEDM_LD)
-#undef WEDM_LD
+    WEDM_STATE_BLOCKS(const)
+    WEDM_PAIR_F64(WEDM_PAIR_LD_F) WEDM_PAIR_I32(WEDM_PAIR_LD_I) WEDM_PAIR_I8(WEDM_PAIR_LD_B)
     r.cur = 0.0; r.shrt = 0;
     if (!ignition_on) {  // the caller forces the spark (single_spark_animation.py): current and the short flag are inputs then
         r.cur = *WEDM_ROW(s.f64, WEDM_F_CURRENT);
@@ -593,24 +542,24 @@ __device__ __forceinline__ void load_env_inputs_paired_issue(const ColdRef cold,
 // the wait for those loads, where the caller wants it (see env_loaded_here)
 __device__ __forceinline__ void pair_raw_loaded_here(PairRaw& r) {
 #pragma unroll
-    for (int k = 0; k < 11; ++k) asm volatile("" : "+v"(r.f[k]));
+    for (int k = 0; k < PAIRS_F64; ++k) asm volatile("" : "+v"(r.f[k]));
 #pragma unroll
-    for (int k = 0; k < 7; ++k) asm volatile("" : "+v"(r.i[k]));
+    for (int k = 0; k < PAIRS_I32; ++k) asm volatile("" : "+v"(r.i[k]));
 #pragma unroll
-    for (int k = 0; k < 3; ++k) asm volatile("" : "+v"(r.b[k]));
+    for (int k = 0; k < PAIRS_I8; ++k) asm volatile("" : "+v"(r.b[k]));
     asm volatile("" : "+v"(r.cur), "+v"(r.shrt));
 }
 
 // the swap: every lane ends up with both rows of every pair (what load_env_inputs would have loaded)
 __device__ __forceinline__ void load_env_inputs_paired_finish(const PairRaw& r, bool odd, Env& v, bool keep_stepping, double* h64) {
-    double fa[11], fb[11];
-    int32_t ia[7], ib[7], ba[3], bb[3];
+    double fa[PAIRS_F64], fb[PAIRS_F64];
+    int32_t ia[PAIRS_I32], ib[PAIRS_I32], ba[PAIRS_I8], bb[PAIRS_I8];
 #pragma unroll
-    for (int k = 0; k < 11; ++k) { const double o = swap_with_neighbour(r.f[k]); fa[k] = odd ? o : r.f[k]; fb[k] = odd ? r.f[k] : o; }
+    for (int k = 0; k < PAIRS_F64; ++k) { const double o = swap_with_neighbour(r.f[k]); fa[k] = odd ? o : r.f[k]; fb[k] = odd ? r.f[k] : o; }
 #pragma unroll
-    for (int k = 0; k < 7; ++k) { const int32_t o = swap_with_neighbour(r.i[k]); ia[k] = odd ? o : r.i[k]; ib[k] = odd ? r.i[k] : o; }
+    for (int k = 0; k < PAIRS_I32; ++k) { const int32_t o = swap_with_neighbour(r.i[k]); ia[k] = odd ? o : r.i[k]; ib[k] = odd ? r.i[k] : o; }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) { const int32_t o = swap_with_neighbour(r.b[k]); ba[k] = odd ? o : r.b[k]; bb[k] = odd ? r.b[k] : o; }
+    for (int k = 0; k < PAIRS_I8; ++k) { const int32_t o = swap_with_neighbour(r.b[k]); ba[k] = odd ? o : r.b[k]; bb[k] = odd ? r.b[k] : o; }
     v.wp = fa[0]; v.x = fb[0]; v.v = fa[1]; v.prev_a = fb[1]; v.debris = fa[2]; v.rho = fb[2]; v.flow = fa[3]; v.last_gap = fb[3];
     v.last_rho = fa[4]; v.wire_last_flow = fb[4]; v.V = fa[5]; v.y = fb[5]; v.tdelta = fa[6]; v.tvolt = fb[6]; v.on = fa[7]; v.off = fb[7];
     v.tpos = fa[8]; v.unwind = fb[8]; v.vacc = fa[9];
@@ -629,47 +578,25 @@ __device__ __forceinline__ void load_env_inputs_paired_finish(const PairRaw& r, 
 // second group (workpiece position, dielectric / convection caches, latched action, short timers,
 // spark count, error flag): those rows are left alone.
 __device__ __forceinline__ void store_env_after_prelude(const ColdRef cold, int64_t e, const Env& v, bool quiet_only) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { double* f64; int32_t* i32; int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-    *WEDM_ROW(s.f64, WEDM_F_DEBRIS_VOLUME) = v.debris; *WEDM_ROW(s.f64, WEDM_F_DEBRIS_DENSITY) = v.rho;
-    *WEDM_ROW(s.f64, WEDM_F_VOLTAGE) = v.V; *WEDM_ROW(s.f64, WEDM_F_CURRENT) = v.I;
-    *WEDM_ROW(s.f64, WEDM_F_SPARK_Y) = v.y; *WEDM_ROW(s.f64, WEDM_F_LAST_CRATER) = v.last_crater;
-    *WEDM_ROW(s.f64, WEDM_F_CAVITY) = v.cavity;
-    *WEDM_ROW(s.i32, WEDM_I_SPARK_DUR) = v.dur;
-    *WEDM_ROW(s.i8, WEDM_B_SPARK_STATE) = (int8_t)v.state; *WEDM_ROW(s.i8, WEDM_B_IS_SHORT) = (int8_t)v.is_short;
-    *WEDM_ROW(s.i8, WEDM_B_CTRL_STEP) = (int8_t)v.ctrl;
+    WEDM_STATE_BLOCKS()
+    WEDM_STORE_ROWS(ROW_PRE_QUIET)
     if (quiet_only) return;
-    *WEDM_ROW(s.f64, WEDM_F_WORKPIECE_POS) = v.wp;
-    *WEDM_ROW(s.f64, WEDM_F_FLOW) = v.flow; *WEDM_ROW(s.f64, WEDM_F_LAST_GAP) = v.last_gap;
-    *WEDM_ROW(s.f64, WEDM_F_LAST_DENSITY) = v.last_rho; *WEDM_ROW(s.f64, WEDM_F_WIRE_LAST_FLOW) = v.wire_last_flow;
-    *WEDM_ROW(s.f64, WEDM_F_TARGET_DELTA) = v.tdelta; *WEDM_ROW(s.f64, WEDM_F_TARGET_VOLTAGE) = v.tvolt;
-    *WEDM_ROW(s.f64, WEDM_F_ON_TIME) = v.on; *WEDM_ROW(s.f64, WEDM_F_OFF_TIME) = v.off;
-    *WEDM_ROW(s.f64, WEDM_F_H_BASE) = (double)v.h_base; *WEDM_ROW(s.f64, WEDM_F_H_ZONE) = (double)v.h_zone;
-    *WEDM_ROW(s.i32, WEDM_I_RANDOM_SHORT_REM) = v.rnd_rem; *WEDM_ROW(s.i32, WEDM_I_DEBRIS_SHORT_REM) = v.deb_rem;
-    *WEDM_ROW(s.i32, WEDM_I_CURRENT_MODE) = v.mode; *WEDM_ROW(s.i32, WEDM_I_SPARK_COUNT) = v.sparks;
-    *WEDM_ROW(s.i8, WEDM_B_ERROR) = (int8_t)v.err;
+    WEDM_STORE_ROWS(ROW_PRE_GENERAL)
 }
 
 // Rows the scalar epilogue assigns (mechanics, clocks, temperature monitor, termination, voltage sum).
 __device__ __forceinline__ void store_env_after_epilogue(const ColdRef cold, int64_t e, const Env& v) {
-    const ColdPtr c = cold.get();
-    const int64_t stride = c->s.stride;
-    const struct { double* f64; int32_t* i32; int8_t* i8; } s{c->s.f64, c->s.i32, c->s.i8};
-    *WEDM_ROW(s.f64, WEDM_F_WIRE_POS) = v.x; *WEDM_ROW(s.f64, WEDM_F_WIRE_VEL) = v.v;
-    *WEDM_ROW(s.f64, WEDM_F_PREV_ACCEL) = v.prev_a; *WEDM_ROW(s.f64, WEDM_F_TMAX) = (double)v.tmax;
-    *WEDM_ROW(s.f64, WEDM_F_VOLT_ACC) = v.vacc;
-    *WEDM_ROW(s.i32, WEDM_I_TIME) = v.time; *WEDM_ROW(s.i32, WEDM_I_SINCE_SERVO) = v.tss;
-    *WEDM_ROW(s.i32, WEDM_I_SINCE_OPEN_V) = v.tsov; *WEDM_ROW(s.i32, WEDM_I_SINCE_IGNITION) = v.tsi;
-    *WEDM_ROW(s.i32, WEDM_I_SINCE_SPARK_END) = v.tse; *WEDM_ROW(s.i32, WEDM_I_TIME_CRITICAL) = v.tcrit;
-    *WEDM_ROW(s.i8, WEDM_B_WIRE_BROKEN) = (int8_t)v.broken; *WEDM_ROW(s.i8, WEDM_B_TARGET_REACHED) = (int8_t)v.reached;
-    *WEDM_ROW(s.i8, WEDM_B_DONE) = (int8_t)done_row(cold, v);
+    WEDM_STATE_BLOCKS()
+    // (block by block as everywhere, but the monitor before the running sums: the order these stores have always had)
+    WEDM_ENV_F64_DOUBLES(WEDM_ST_F, ROW_EPILOGUE) WEDM_ENV_F64_FLOATS(WEDM_ST_F, ROW_EPILOGUE) WEDM_ENV_F64_SUMS(WEDM_ST_F, ROW_EPILOGUE)
+    WEDM_ENV_I32(WEDM_ST_I, ROW_EPILOGUE) WEDM_ENV_I8(WEDM_ST_B, WEDM_ST_DONE, ROW_EPILOGUE)
 }
 
 // Make the compiler treat every loaded state register as USED here: it inserts the wait for the state
 // loads at this point (and afterwards knows that none of them is pending).  Needed where vector-memory
 // operations the compiler cannot count follow (the LDS-DMA loop of wedm_step_stream): a later first use of a
 // state register would otherwise be a conservative `s_waitcnt vmcnt(0)` behind them.
+// (Every member by hand, not from the lists: where one statement ends and the next begins decides which loads each wait covers.)
 __device__ __forceinline__ void env_loaded_here(Env& v) {
     asm volatile("" : "+v"(v.wp), "+v"(v.x), "+v"(v.v), "+v"(v.prev_a), "+v"(v.debris), "+v"(v.rho), "+v"(v.flow),
                       "+v"(v.last_gap), "+v"(v.last_rho), "+v"(v.wire_last_flow), "+v"(v.V), "+v"(v.I), "+v"(v.y),
@@ -683,69 +610,13 @@ __device__ __forceinline__ void env_loaded_here(Env& v) {
 }
 
 // ----------------------------------------------------------------- signal trace
-// Row r of each state block as the registers hold it (the value store_env would write).
-__device__ __forceinline__ double env_f64_row(const Env& v, int row) {
-    switch (row) {
-        case WEDM_F_WORKPIECE_POS: return v.wp;
-        case WEDM_F_WIRE_POS: return v.x;
-        case WEDM_F_WIRE_VEL: return v.v;
-        case WEDM_F_PREV_ACCEL: return v.prev_a;
-        case WEDM_F_DEBRIS_VOLUME: return v.debris;
-        case WEDM_F_DEBRIS_DENSITY: return v.rho;
-        case WEDM_F_FLOW: return v.flow;
-        case WEDM_F_LAST_GAP: return v.last_gap;
-        case WEDM_F_LAST_DENSITY: return v.last_rho;
-        case WEDM_F_WIRE_LAST_FLOW: return v.wire_last_flow;
-        case WEDM_F_VOLTAGE: return v.V;
-        case WEDM_F_CURRENT: return v.I;
-        case WEDM_F_SPARK_Y: return v.y;
-        case WEDM_F_LAST_CRATER: return v.last_crater;
-        case WEDM_F_CAVITY: return v.cavity;
-        case WEDM_F_TARGET_DELTA: return v.tdelta;
-        case WEDM_F_TARGET_VOLTAGE: return v.tvolt;
-        case WEDM_F_ON_TIME: return v.on;
-        case WEDM_F_OFF_TIME: return v.off;
-        case WEDM_F_TARGET_POS: return v.tpos;
-        case WEDM_F_UNWIND_VEL: return v.unwind;
-        case WEDM_F_H_BASE: return (double)v.h_base;
-        case WEDM_F_H_ZONE: return (double)v.h_zone;
-        case WEDM_F_TMAX: return (double)v.tmax;
-        case WEDM_F_VOLT_ACC: return v.vacc;
-    }
-    return 0.0;
-}
-__device__ __forceinline__ int32_t env_i32_row(const Env& v, int row) {
-    switch (row) {
-        case WEDM_I_TIME: return v.time;
-        case WEDM_I_SINCE_SERVO: return v.tss;
-        case WEDM_I_SINCE_OPEN_V: return v.tsov;
-        case WEDM_I_SINCE_IGNITION: return v.tsi;
-        case WEDM_I_SINCE_SPARK_END: return v.tse;
-        case WEDM_I_SPARK_DUR: return v.dur;
-        case WEDM_I_RANDOM_SHORT_REM: return v.rnd_rem;
-        case WEDM_I_DEBRIS_SHORT_REM: return v.deb_rem;
-        case WEDM_I_TIME_CRITICAL: return v.tcrit;
-        case WEDM_I_CURRENT_MODE: return v.mode;
-        case WEDM_I_EPISODE: return v.episode;
-        case WEDM_I_KEY_LO: return (int32_t)v.key0;
-        case WEDM_I_KEY_HI: return (int32_t)v.key1;
-        case WEDM_I_SPARK_COUNT: return v.sparks;
-    }
-    return 0;
-}
+// Row r of each state block as the registers hold it (the value store_env would write; 0 for a row no register holds).
 // (`keep_stepping`: wedm_params.keep_stepping_terminated -- row DONE is then `terminated` of the step, see done_row())
-__device__ __forceinline__ int32_t env_i8_row(const Env& v, int row, bool keep_stepping) {
-    switch (row) {
-        case WEDM_B_SPARK_STATE: return v.state;
-        case WEDM_B_IS_SHORT: return v.is_short;
-        case WEDM_B_WIRE_BROKEN: return v.broken;
-        case WEDM_B_TARGET_REACHED: return v.reached;
-        case WEDM_B_DONE: return keep_stepping ? (v.broken | v.reached) : v.done;
-        case WEDM_B_CTRL_STEP: return v.ctrl;
-        case WEDM_B_ERROR: return v.err;
-    }
-    return 0;
-}
+#define WEDM_CASE(a, m, row, stage, role, owner) case row: return v.m;
+#define WEDM_CASE_DONE(a, m, row, stage, role, owner) case row: return keep_stepping ? (v.broken | v.reached) : v.done;
+__device__ __forceinline__ double env_f64_row(const Env& v, int row) { switch (row) { WEDM_ENV_F64(WEDM_CASE, ~) } return 0.0; }
+__device__ __forceinline__ int32_t env_i32_row(const Env& v, int row) { switch (row) { WEDM_ENV_I32(WEDM_CASE, ~) } return 0; }
+__device__ __forceinline__ int32_t env_i8_row(const Env& v, int row, bool keep_stepping) { switch (row) { WEDM_ENV_I8(WEDM_CASE, WEDM_CASE_DONE, ~) } return 0; }
 
 // Column of environment e in the trace buffers, or -1 when it is not traced.
 __device__ __forceinline__ int64_t trace_column(const wedm_trace_desc& tr, int64_t e) {
@@ -1631,7 +1502,7 @@ __device__ __forceinline__ void reinit_env(const ColdRef cold, int64_t e, Env& s
     s.mode = (keep_modules && c->s.i8[(int64_t)WEDM_B_MODE_CACHED * c->s.stride + e]) ? -1 : 0;
     s.episode = episode; s.key0 = k0; s.key1 = k1;
     s.state = 0; s.is_short = 0; s.broken = 0; s.reached = 0; s.done = 0; s.ctrl = 0; s.err = 0;
-    if (!keep_modules) {
+    if (!keep_modules) {  // the members whose line in wedm_env_rows.h says MODULE (wedm_reset_kernel takes its masks from that column)
         s.prev_a = 0.0; s.debris = 0.0; s.flow = 0.0; s.last_gap = -1.0; s.last_rho = -1.0; s.wire_last_flow = 0.0;
         s.h_base = 0.0f; s.h_zone = 0.0f; s.rnd_rem = 0; s.deb_rem = 0; s.sparks = 0;
     }

@@ -5,6 +5,8 @@
 // Device code, by file (DESIGN.md section 4 has the table with what binds each kernel):
 //   wedm_device.h         per-lane physics of one microsecond: Env, prelude (quiet / general), epilogue (monitor + motion),
 //                         Philox, the portable exp / log / cube, stencil_cell
+//   wedm_env_rows.h       which Env member holds which state row, when it is final, whether a step reads it and whether a
+//                         reference-semantics reset keeps it: the lists load_env / store_env / the trace are expanded from
 //   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors / copy_wire, tile_staged / quad_staged
 //   wedm_lifecycle.h      an environment's launch lifecycle as helpers: launch_hot, env_open / env_start, env_end_us /
 //                         env_step_done, env_close, stencil_f64_consts (the file's head says which family calls which)
@@ -235,11 +237,10 @@ wedm_reset_kernel(const wedm_params p, const wedm_state_ptrs s, int32_t num_envs
     // (dielectric.py:69-80), the convection cache and coefficients (wire.py:205,224), the short timers and the current
     // cache (ignition.py:75-81), the crater list and its statistics (material.py:133).
     const bool keep_modules = p.reset_semantics != 0 && !(reseed & WEDM_RESET_FRESH);
-    constexpr uint32_t module_f64 = (1u << WEDM_F_PREV_ACCEL) | (1u << WEDM_F_DEBRIS_VOLUME) | (1u << WEDM_F_FLOW) |
-                                    (1u << WEDM_F_LAST_GAP) | (1u << WEDM_F_LAST_DENSITY) | (1u << WEDM_F_WIRE_LAST_FLOW) |
-                                    (1u << WEDM_F_H_BASE) | (1u << WEDM_F_H_ZONE);
-    constexpr uint32_t module_i32 = (1u << WEDM_I_RANDOM_SHORT_REM) | (1u << WEDM_I_DEBRIS_SHORT_REM) | (1u << WEDM_I_SPARK_COUNT);
-    constexpr uint32_t module_i8 = 1u << WEDM_B_MODE_CACHED;
+    // (which rows those are: the `owner` column of wedm_env_rows.h)
+    constexpr uint32_t module_f64 = WEDM_F64_ROWS(ROW_MODULE) WEDM_UNHELD_F64(WEDM_UNHELD_MODULE_BIT),
+                       module_i32 = WEDM_I32_ROWS(ROW_MODULE) WEDM_UNHELD_I32(WEDM_UNHELD_MODULE_BIT),
+                       module_i8 = WEDM_I8_ROWS(ROW_MODULE) WEDM_UNHELD_I8(WEDM_UNHELD_MODULE_BIT);
     for (int f = 0; f < WEDM_F64_COUNT; ++f)
         if (!(keep_modules && ((module_f64 >> f) & 1u))) *WEDM_ROW(s.f64, f) = 0.0;
     for (int f = 0; f < WEDM_I32_COUNT; ++f)
@@ -1076,10 +1077,13 @@ int32_t wedm_bind_trace(wedm_ctx* ctx, const wedm_trace_desc* desc) {
                    i8_all = (1u << WEDM_I8_COUNT) - 1u;
     if ((desc->f64_mask & ~f64_all) || (desc->i32_mask & ~i32_all) || (desc->i8_mask & ~i8_all))
         return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_bind_trace: mask names a row that does not exist");
-    if (desc->i32_mask & (1u << WEDM_I_TIME_HI))
-        return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_bind_trace: TIME_HI is maintained at the end of a launch only (read it from the state block)");
-    if (desc->f64_mask & (1u << WEDM_F_VOLT_SUM))
-        return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_bind_trace: VOLT_SUM is published at control steps only (read it from the state block)");
+    // a sample is taken from the registers: the rows that no register holds (wedm_env_rows.h) cannot be traced.  MODE_CACHED has
+    // always been accepted all the same (its samples are 0: DESIGN.md section 3, open points); that stays until it is decided.
+#define WEDM_REFUSE(row, owner, why) if (mask & (1u << row)) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_bind_trace: " why " (read it from the state block)");
+    { const uint32_t mask = desc->i32_mask; WEDM_UNHELD_I32(WEDM_REFUSE) }
+    { const uint32_t mask = desc->f64_mask; WEDM_UNHELD_F64(WEDM_REFUSE) }
+    { const uint32_t mask = desc->i8_mask & ~(1u << WEDM_B_MODE_CACHED); WEDM_UNHELD_I8(WEDM_REFUSE) }
+#undef WEDM_REFUSE
     if ((desc->f64_mask != 0) != (desc->f64 != nullptr) || (desc->i32_mask != 0) != (desc->i32 != nullptr) ||
         (desc->i8_mask != 0) != (desc->i8 != nullptr))
         return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_bind_trace: a buffer must be given exactly for the non-empty masks");

@@ -384,3 +384,74 @@ def test_default_reset_and_freeze_differ_from_the_reference_where_documented(gol
     env.step_many(env.make_action(a[0], a[1], int(a[4]), a[2], a[3]), fz.n_steps)
     first = int(np.argmax(fz.int_row("terminated") != 0))
     assert int(env.state.time[1]) == first + 1 and bool(env.state.done[1])      # frozen at the terminating step
+
+
+# ------------------------------------------------------------------ every register-held row through the trace
+# The state rows that no register of the kernels holds (sparc_amd/csrc/wedm_env_rows.h, WEDM_UNHELD_*): a trace sample is
+# taken from the registers, so these cannot be compared through it.
+ROWS_NOT_IN_REGISTERS = ("voltage_sum_at_control_step", "time_high32", "ignition_mode_cached")
+EVERY_ROW_LAUNCHES = (1, 7, 650)    # 658 us -> 219 samples through a 64-slot ring
+EVERY_ROW_TERMINATING_ENV = 5
+
+
+def every_row_signals():
+    from sparc_amd.core.state import _FIELDS
+
+    assert all(name in _FIELDS for name in ROWS_NOT_IN_REGISTERS)    # the exclusion list names rows that exist
+    return [name for name in _FIELDS if name not in ROWS_NOT_IN_REGISTERS]
+
+
+def every_row_run(device, backend, freeze, kernel=None):
+    """8 environments (a partly filled wave) of 128 segments, one of them reaching its target, every traceable row of the
+    registers bound; returns the trace and the kernel names of the three launches."""
+    from sparc_amd import WireModuleParameters
+
+    kw = dict(backend=backend) if backend is not None else {}
+    env = WireEDMEnv(num_envs=8, device=device, wire_params=WireModuleParameters(segment_len=0.625),
+                     freeze_terminated=freeze, **kw)
+    if kernel is not None:
+        env.set_kernel(*kernel)
+    env.reset(seed=321)
+    env.state.workpiece_position = 25.0
+    env.state.wire_position = 10.0
+    env.state.target_position = 5000.0
+    env.state.target_position[EVERY_ROW_TERMINATING_ENV] = 25.0005
+    trace = env.bind_trace(every_row_signals(), every=3, capacity=64)
+    act, names = env.make_action(0.1, 80.0, 5, 3.0, 80.0), []
+    for k in EVERY_ROW_LAUNCHES:
+        env.step_many(act, k)
+        names.append(env._backend.last_kernel())
+    return trace, names
+
+
+_every_row_oracle = {}
+
+
+def every_row_oracle(freeze):
+    """The oracle's ring, computed once per `freeze_terminated` and shared by the kernels compared with it."""
+    if freeze not in _every_row_oracle:
+        trace, _ = every_row_run("cpu", OracleBackend, freeze)
+        got = trace.read()
+        assert got["done"].any() and got["is_target_distance_reached"].any()     # rows DONE and TARGET_REACHED are not all zero
+        assert not got["done"][:, [e for e in range(8) if e != EVERY_ROW_TERMINATING_ENV]].any()
+        assert int((got["spark_state"] == 1).sum()) > 0
+        _every_row_oracle[freeze] = trace
+    return _every_row_oracle[freeze]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("variant,lanes,freeze,family", [
+    (1, 0, True, "wedm_step_global"), (6, 0, True, "wedm_step_stream"), (7, 0, True, "wedm_step_regs<"),
+    (7, 1, True, "wedm_step_regs<"), (8, 0, True, "wedm_step_regs_wide"),
+    (1, 0, False, "wedm_step_global"),      # row DONE as `terminated` of the step: done_row()'s other branch
+])
+def test_every_register_held_row_traces_like_the_oracle(variant, lanes, freeze, family):
+    """Every row a kernel holds in registers, sampled by the trace point inside launches of 1, 7 and 650 us, equals the
+    oracle's sample of the memory row: every slot of every block of a ring that wraps, NaN-aware."""
+    from tests.test_gpu_parity import assert_rings_equal
+
+    want = every_row_oracle(freeze)
+    trace, names = every_row_run("cuda:0", None, freeze, kernel=(variant, lanes))
+    assert all(family in name for name in names), names
+    assert trace.count == want.count == sum(EVERY_ROW_LAUNCHES) // 3
+    assert_rings_equal(trace, want)
