@@ -17,6 +17,8 @@
 //   wedm_lanes2.h         wedm_step_lanes_pk<L>: any geometry, packed float32 walk (kernel 2: BASELINE config 5), and its served form
 //   wedm_k_fused.h        wedm_step_fused<L>: uniform geometry, wire chunks in LDS, wave-uniform tile table
 //   wedm_k_packed.h       wedm_step_packed<L>: the same with two virtual chunks per lane in float2 registers
+//   wedm_packed_walk.inc  the packed LDS walk itself (per-lane tile flags; one microsecond: halos, tiles, patches), included as
+//                         text by wedm_step_packed and by the walkers of wedm_step_served
 //   wedm_served.h         wedm_step_served<L>: the packed walk on three waves of a block, the scalar physics of the block's
 //                         environments on the fourth, one microsecond ahead (kernel 9: large batches of long wires)
 //   wedm_k_regs.h         wedm_step_regs<L> (the headline: the wire in the registers of two lanes per environment),

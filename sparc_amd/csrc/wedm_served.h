@@ -1,6 +1,8 @@
 // wedm_served.h — "served" kernels: the float64 scalar physics of a block's environments on a wave of its own.
 //
 // Included by wedm_kernels.hip (it uses that file's KArgs, WalkTable, copy_wire, tile8_staged, interior_cell ...).
+// The walkers of wedm_step_served run the text of wedm_packed_walk.inc (wedm_step_packed's walk, column stride 192, the frozen
+// flag from the mailbox) with this kernel's own tiles and tails; those of wedm_step_regs_served the text of wedm_regs_walk.inc.
 //
 // Why.  In every kernel with L >= 4 lanes per environment the scalar physics of a microsecond (wire_edm.py:116-157 without
 // the stencil: ~340 wave-level instructions, most of them float64) is executed by every lane of the environment -- once per
@@ -335,6 +337,35 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
 // 2 L chunks; one-change tiles and 1- / 2-cell tails with F_EXTRA).  A wave with a frozen (terminated) environment keeps
 // the tile code, its lanes do not store (wedm_step_packed's F_FROZEN_OK, always on here).
 // Not here (the launch plan keeps such launches on wedm_step_packed): a trace sample inside the launch, keep_stepping_terminated.
+// This kernel's pieces of the walk, expanded by wedm_packed_walk.inc where it uses them (its head says what each has to do).
+// Tail cells: ONE packed pair per tail position -- both virtual chunks together, the Joule term only where some lane of the
+// wave carries current, exactly as the tiles do it -- instead of two scalar cells with the Joule term always.
+#define WEDM_PACKED_WALK_TAILS_FROM_OLD()                                                                                      \
+    f2 ttp[2] = {f2{0.0f, 0.0f}, f2{0.0f, 0.0f}}; /* [q] = (chunk A, chunk B) */                                               \
+    if (use_tail) {                                                                                                            \
+        const float jfl = (cf.joule_on && !done) ? cf.jf : 0.0f;                                                               \
+        const bool joule_tail = __any(jfl != 0.0f);                                                                            \
+        _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                                                        \
+            if (q < tail) {                                                                                                    \
+                const int r = Cv - tail + q;                                                                                   \
+                const uint32_t ba = tail_bits >> (4 * (2 * q)), bb = tail_bits >> (4 * (2 * q + 1));                           \
+                const f2 tm = {col[(2 * (r - 1)) * CS], col[(2 * (r - 1) + 1) * CS]};                                          \
+                const f2 tcc = {col[(2 * r) * CS], col[(2 * r + 1) * CS]};                                                     \
+                const f2 tp = {col[(2 * (r + 1)) * CS], col[(2 * (r + 1) + 1) * CS]};                                          \
+                const f2 conv = {(ba & 1u) ? ps.conv_zone : ps.conv_base, (bb & 1u) ? ps.conv_zone : ps.conv_base};            \
+                const f2 jfe = {(ba & 2u) ? jfl : 0.0f, (bb & 2u) ? jfl : 0.0f};                                               \
+                ttp[q] = joule_tail ? interior2<true>(tm, tcc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref)          \
+                                    : interior2<false>(tm, tcc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);        \
+            }                                                                                                                  \
+        }                                                                                                                      \
+    }
+#define WEDM_PACKED_WALK_TAIL_NEW(q, v) ((v) ? ttp[q].y : ttp[q].x)
+#define WEDM_PACKED_WALK_DONE done
+#define WEDM_PACKED_WALK_REGULAR_TILE(JOULE)                                 \
+    _Pragma("unroll") for (int o = 0; o < 8; o += WEDM_SERVED_STAGE_W)       \
+        tile_staged<f2, JOULE, false, WEDM_SERVED_STAGE_W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref)
+#define WEDM_PACKED_WALK_ONECHANGE_TILE() percell_tile(joule_wave, old, tn, split, conv_lo, conv_hi, jfe_lo, jfe_hi)
+
 template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_served(const KArgs k) {
     static_assert((F & ~F_EXTRA) == 0, "forms of wedm_step_served");
@@ -391,45 +422,11 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
 
     const int baseA = 2 * c * Cv, baseB = baseA + Cv;  // first wire cell of each virtual chunk
     const int n_tiles = wt->n_tiles;
-    // per-lane tile flags for both virtual chunks, gathered once (see wedm_step_fused)
-    uint32_t zlA = 0u, zlB = 0u, jlA = 0u, jlB = 0u, zhA = 0u, zhB = 0u, jhA = 0u, jhB = 0u, kind_n = 0u, kind_s = 0u;
-    uint32_t split_pack[3] = {0u, 0u, 0u};
-    for (int t = 0; t < n_tiles; ++t) {
-        const uint32_t lo = wt->zj[8 * t], hi = wt->zj[8 * t + 7], kd = wt->kind[t];
-        split_pack[t >> 3] |= (wt->split[t] & 15u) << ((t & 7) * 4);
-        zlA |= ((lo >> (2 * c)) & 1u) << t;      zlB |= ((lo >> (2 * c + 1)) & 1u) << t;
-        jlA |= ((lo >> (16 + 2 * c)) & 1u) << t; jlB |= ((lo >> (17 + 2 * c)) & 1u) << t;
-        zhA |= ((hi >> (2 * c)) & 1u) << t;      zhB |= ((hi >> (2 * c + 1)) & 1u) << t;
-        jhA |= ((hi >> (16 + 2 * c)) & 1u) << t; jhB |= ((hi >> (17 + 2 * c)) & 1u) << t;
-        kind_n |= (kd == TILE_N ? 1u : 0u) << t;
-        kind_s |= (kd == TILE_S ? 1u : 0u) << t;
-    }
-    kind_n = __builtin_amdgcn_readfirstlane(kind_n);
-    kind_s = __builtin_amdgcn_readfirstlane(kind_s);
-    const uint32_t kind_ne = __builtin_amdgcn_readfirstlane(wt->kind_ne_mask), kind_nj = __builtin_amdgcn_readfirstlane(wt->kind_nj_mask);
-    const uint32_t kind_n1 = EXTRA ? (__builtin_amdgcn_readfirstlane(wt->kind_n1_mask) & 0x7fffffffu) : 0u;
-#pragma unroll
-    for (int q = 0; q < 3; ++q) split_pack[q] = __builtin_amdgcn_readfirstlane(split_pack[q]);
-    if (c == 0) col[0] = spool;  // wire cell 0 (row 0 of lane 0's chunk A) is held at the spool temperature
-
-    // which of this lane's virtual chunks holds wire cell i (0: none, 1: A, 2: B)
-    auto owner = [&](int i) -> int {
-        if (i >= baseA && i < baseA + Cv) return 1;
-        if (i >= baseB && i < baseB + Cv) return 2;
-        return 0;
-    };
-    const int own_last = (n >= 2) ? owner(n - 1) : 0;
-    const int t_last = (n - 1 - baseB) >> 3;
-    const int tail = (EXTRA && Cv > 8 && (Cv & 7) >= 1 && (Cv & 7) <= 2) ? (Cv & 7) : 0;
-    uint32_t tail_bits = 0u;
-    for (int q = 0; q < tail; ++q) {
-        const uint32_t zj = wt->zj[Cv - tail + q], iv = wt->iv[Cv - tail + q];
-#pragma unroll
-        for (int v = 0; v < 2; ++v) {
-            const int vc = 2 * c + v;
-            tail_bits |= (((zj >> vc) & 1u) | (((zj >> (16 + vc)) & 1u) << 1) | (((iv >> vc) & 1u) << 2) | (((iv >> (16 + vc)) & 1u) << 3)) << (4 * (2 * q + v));
-        }
-    }
+    constexpr int CS = NT;             // column stride of the LDS image: one column per walker thread
+    constexpr bool FROZEN_OK = true;   // (wedm_step_packed's F_FROZEN_OK, always on here)
+#define WEDM_PACKED_WALK_SETUP
+#include "wedm_packed_walk.inc"
+#undef WEDM_PACKED_WALK_SETUP
 
     WEDM_SV_LOOP_START();
     for (int it = 0; it < k.n_substeps; ++it) {
@@ -444,259 +441,31 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
         ps.adv_on = (fl & SV_ADV) ? 1 : 0;
         const bool done = !live || (fl & SV_DONE);
 
-        // ---- halos (OLD values, read before any store of this step)
-        const float halo_l = (c > 0) ? col[(R - 1) * NT - 1] : spool;  // left neighbour lane's B[Cv-1]
-        const float halo_r = (c < L - 1) ? col[1] : 0.0f;               // right neighbour lane's A[0]
-        const float a_last = col[(R - 2) * NT];                        // own A[Cv-1]: left halo of B
-        const float b_first = col[NT];                                  // own B[0]: right halo of A
-        col[R * NT] = b_first;
-        col[(R + 1) * NT] = halo_r;
-
-        const bool frozen_wave = __any(done);
-        const bool all_slow = __any(cf.q < 0.0f);  // a negative plasma heat: every cell on the predicated path (same results)
-        const uint32_t slow_now = all_slow ? 0xffffffffu : kind_s;
-        // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows
-        const uint32_t n_now = (kind_n | kind_ne | (__any(cf.joule_on && !done && cf.jf != 0.0f) ? 0u : kind_nj)) & ~(all_slow ? 0xffffffffu : 0u);
-
-        // full predicated formula for one owned cell, from OLD values (patched cells)
-        auto patch_value = [&](int i, int own) -> float {
-            const int v = own - 1, r = i - (v ? baseB : baseA), row = 2 * r + v;
-            const float left = col[(r > 0 ? row - 2 : row) * NT];
-            float tm = r > 0 ? left : (v ? a_last : halo_l);
-            if (i == 1) tm = spool;
-            const float tp = col[(row + 2) * NT];
-            return stencil_cell(i, n, tm, col[row * NT], tp, g, cf, ps, tref, alpha, tdiel);
-        };
-        const int own_pl = (!done && cf.pidx >= 1) ? owner(cf.pidx) : 0;
-        float tpl = 0.0f, tlast = 0.0f;
-        if (__any(own_pl != 0)) {
-            if (own_pl) tpl = patch_value(cf.pidx, own_pl);
-        }
-        if (own_last && !done) tlast = patch_value(n - 1, own_last);
-
-        // ---- tail cells: new values from OLD ones, now (not on the predicated path, whose last tile covers them)
-        const bool use_tail = EXTRA && tail != 0 && !all_slow;
-        // (as ONE packed pair per tail position -- both virtual chunks together, the Joule term only where some lane of the
-        // wave carries current, exactly as the tiles do it -- instead of two scalar cells with the Joule term always)
-        f2 ttp[2] = {f2{0.0f, 0.0f}, f2{0.0f, 0.0f}};  // [q] = (chunk A, chunk B)
-        if (use_tail) {
-            const float jfl = (cf.joule_on && !done) ? cf.jf : 0.0f;
-            const bool joule_tail = __any(jfl != 0.0f);
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                if (q < tail) {
-                    const int r = Cv - tail + q;
-                    const uint32_t ba = tail_bits >> (4 * (2 * q)), bb = tail_bits >> (4 * (2 * q + 1));
-                    const f2 tm = {col[(2 * (r - 1)) * NT], col[(2 * (r - 1) + 1) * NT]};
-                    const f2 tcc = {col[(2 * r) * NT], col[(2 * r + 1) * NT]};
-                    const f2 tp = {col[(2 * (r + 1)) * NT], col[(2 * (r + 1) + 1) * NT]};
-                    const f2 conv = {(ba & 1u) ? ps.conv_zone : ps.conv_base, (bb & 1u) ? ps.conv_zone : ps.conv_base};
-                    const f2 jfe = {(ba & 2u) ? jfl : 0.0f, (bb & 2u) ? jfl : 0.0f};
-                    ttp[q] = joule_tail ? interior2<true>(tm, tcc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref)
-                                        : interior2<false>(tm, tcc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                }
-            }
-        }
-        const int n_walk = use_tail ? n_tiles - 1 : n_tiles;
-
         float tmax = spool;
-        f2 tm1 = {halo_l, a_last};
-        f2 tc = {col[0], col[NT]};
-        WEDM_SV_PHASE(pa);  // mailbox, halos, patched cells and tails from old values
-        {
-            const float jf_lane = (cf.joule_on && !done) ? cf.jf : 0.0f;
-            const bool joule_wave = __any(jf_lane != 0.0f);
-            const float cz = ps.conv_zone, cb = ps.conv_base;
-
-            auto load8 = [&](auto clamp, f2 (&dst)[8], int r0) {
+        // a tile with one coefficient change at `split`: the pairs' coefficients are selected group by group, right before
+        // the stage-major group that uses them (all eight up front are 32 registers the walker does not have)
+        auto percell_tile = [&](bool joule_wave, const f2 (&old)[10], f2 (&tn)[8], int split, f2 conv_lo, f2 conv_hi, f2 jfe_lo, f2 jfe_hi) {
+            constexpr int W = WEDM_SERVED_STAGE_W;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    int p = r0 + 1 + u;
-                    if (decltype(clamp)::value) p = p < Cv ? p : Cv;  // pair Cv is the halo pair; later pairs are never used
-                    dst[u].x = col[(2 * p) * NT];
-                    dst[u].y = col[(2 * p + 1) * NT];
+            for (int o = 0; o < 8; o += W) {
+                f2 cv[8], jv[8];  // (only entries o .. o + W - 1 are set and read)
+#pragma unroll
+                for (int u = 0; u < W; ++u) {
+                    cv[o + u] = (o + u) < split ? conv_lo : conv_hi;
+                    jv[o + u] = (o + u) < split ? jfe_lo : jfe_hi;
                 }
-            };
-            auto store2 = [&](int r, f2 v) {
-                col[(2 * r) * NT] = v.x;
-                col[(2 * r + 1) * NT] = v.y;
-            };
-            // a tile with one coefficient change at `split`: the pairs' coefficients are selected group by group, right before
-            // the stage-major group that uses them (all eight up front are 32 registers the walker does not have)
-            auto percell_tile = [&](const f2 (&old)[10], f2 (&tn)[8], int split, f2 conv_lo, f2 conv_hi, f2 jfe_lo, f2 jfe_hi) {
-                constexpr int W = WEDM_SERVED_STAGE_W;
-#pragma unroll
-                for (int o = 0; o < 8; o += W) {
-                    f2 cv[8], jv[8];  // (only entries o .. o + W - 1 are set and read)
-#pragma unroll
-                    for (int u = 0; u < W; ++u) {
-                        cv[o + u] = (o + u) < split ? conv_lo : conv_hi;
-                        jv[o + u] = (o + u) < split ? jfe_lo : jfe_hi;
-                    }
-                    if (joule_wave) tile_staged<f2, true, true, W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    else tile_staged<f2, false, true, W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                }
-            };
-            auto tile = [&](auto frozen, int t, f2 (&cur)[8]) {
-                constexpr bool FROZEN = decltype(frozen)::value;  // the copy for a wave with frozen lanes: they do not store
-                const int r0 = 8 * t;
-                if (r0 + 8 <= Cv) load8(std::false_type{}, cur, r0);
-                else load8(std::true_type{}, cur, r0);
-                const f2 conv_lo = {((zlA >> t) & 1u) ? cz : cb, ((zlB >> t) & 1u) ? cz : cb};
-                const f2 jfe_lo = {((jlA >> t) & 1u) ? jf_lane : 0.0f, ((jlB >> t) & 1u) ? jf_lane : 0.0f};
-                if ((n_now >> t) & 1u) {
-                    f2 old[10], tn[8], cv[8], jv[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) old[u + 2] = cur[u];
-                    cv[0] = conv_lo; jv[0] = jfe_lo;
-                    if (joule_wave && __any(jfe_lo.x != 0.0f || jfe_lo.y != 0.0f)) {
-#pragma unroll
-                        for (int o = 0; o < 8; o += WEDM_SERVED_STAGE_W)
-                            tile_staged<f2, true, false, WEDM_SERVED_STAGE_W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    } else {
-#pragma unroll
-                        for (int o = 0; o < 8; o += WEDM_SERVED_STAGE_W)
-                            tile_staged<f2, false, false, WEDM_SERVED_STAGE_W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    }
-                    tn[0].x = (c == 0 && t == 0) ? spool : tn[0].x;
-                    const float last_y = (own_last == 2 && t == t_last) ? spool : tn[7].y;
-                    float m0 = fmax_gt(tn[0].x, tn[0].y), m1 = fmax_gt(tn[1].x, tn[1].y);
-                    if (!FROZEN || !done) {
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) store2(r0 + u, tn[u]);
-                    }
-#pragma unroll
-                    for (int u = 2; u < 6; u += 2) {
-                        m0 = fmax_gt(m0, fmax_gt(tn[u].x, tn[u].y));
-                        m1 = fmax_gt(m1, fmax_gt(tn[u + 1].x, tn[u + 1].y));
-                    }
-                    m0 = fmax_gt(m0, fmax_gt(tn[6].x, tn[6].y));
-                    m1 = fmax_gt(m1, fmax_gt(tn[7].x, last_y));
-                    tmax = fmax_gt(tmax, fmax_gt(m0, m1));
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else if (EXTRA && (((kind_n1 & ~slow_now) >> t) & 1u)) {
-                    const int split = (int)((split_pack[t >> 3] >> ((t & 7) * 4)) & 15u);
-                    const f2 conv_hi = {((zhA >> t) & 1u) ? cz : cb, ((zhB >> t) & 1u) ? cz : cb};
-                    const f2 jfe_hi = {((jhA >> t) & 1u) ? jf_lane : 0.0f, ((jhB >> t) & 1u) ? jf_lane : 0.0f};
-                    f2 old[10], tn[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) old[u + 2] = cur[u];
-                    percell_tile(old, tn, split, conv_lo, conv_hi, jfe_lo, jfe_hi);
-                    tn[0].x = (c == 0 && t == 0) ? spool : tn[0].x;
-                    const float last_y = (own_last == 2 && t == t_last) ? spool : tn[7].y;
-                    if (!FROZEN || !done) {
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) store2(r0 + u, tn[u]);
-                    }
-                    float m0 = fmax_gt(tn[0].x, tn[0].y), m1 = fmax_gt(tn[1].x, tn[1].y);
-#pragma unroll
-                    for (int u = 2; u < 6; u += 2) {
-                        m0 = fmax_gt(m0, fmax_gt(tn[u].x, tn[u].y));
-                        m1 = fmax_gt(m1, fmax_gt(tn[u + 1].x, tn[u + 1].y));
-                    }
-                    m0 = fmax_gt(m0, fmax_gt(tn[6].x, tn[6].y));
-                    m1 = fmax_gt(m1, fmax_gt(tn[7].x, last_y));
-                    tmax = fmax_gt(tmax, fmax_gt(m0, m1));
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else if (!((slow_now >> t) & 1u)) {
-                    // TILE_B: interior formula everywhere, one flag change at `split`; boundary and
-                    // out-of-wire cells stay out of the max (patched afterwards / never read)
-                    const int split = (int)((split_pack[t >> 3] >> ((t & 7) * 4)) & 15u);
-                    const int cnt = (Cv - r0) < 8 ? (Cv - r0) : 8;
-                    const f2 conv_hi = {((zhA >> t) & 1u) ? cz : cb, ((zhB >> t) & 1u) ? cz : cb};
-                    const f2 jfe_hi = {((jhA >> t) & 1u) ? jf_lane : 0.0f, ((jhB >> t) & 1u) ? jf_lane : 0.0f};
-                    const uint32_t imA = (uint32_t)(baseA + r0 - 1), imB = (uint32_t)(baseB + r0 - 1);
-                    const uint32_t span = (uint32_t)(n - 3);
-                    f2 old[10], tn[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) old[u + 2] = cur[u];
-                    percell_tile(old, tn, split, conv_lo, conv_hi, jfe_lo, jfe_hi);
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (u < cnt) {
-                            if (!FROZEN || !done) store2(r0 + u, tn[u]);
-                            const bool inA = (n >= 3) && (imA + (uint32_t)u <= span);
-                            const bool inB = (n >= 3) && (imB + (uint32_t)u <= span);
-                            tmax = inA ? fmax_gt(tmax, tn[u].x) : tmax;
-                            tmax = inB ? fmax_gt(tmax, tn[u].y) : tmax;
-                        }
-                    }
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else {
-                    // TILE_S: per-cell predicated fallback for both components (rare)
-#pragma unroll 1
-                    for (int u = 0; u < 8; ++u) {
-                        const int r = r0 + u;
-                        const uint32_t zj = wt->zj[r], iv = wt->iv[r];
-                        const f2 tp1 = cur[0];
-#pragma unroll
-                        for (int v = 0; v < 2; ++v) {
-                            const int vcid = 2 * c + v;
-                            const bool zbit = (zj >> vcid) & 1u, jbit = (zj >> (16 + vcid)) & 1u;
-                            const bool inter = ((iv >> vcid) & 1u) && !all_slow;
-                            const bool valid = ((iv >> (16 + vcid)) & 1u) && !done;
-                            const float conv = zbit ? cz : cb, jfe = jbit ? jf_lane : 0.0f;
-                            const float m = v ? tm1.y : tm1.x, cc = v ? tc.y : tc.x, pp = v ? tp1.y : tp1.x;
-                            float x = interior_cell<true>(m, cc, pp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                            if (!inter && valid) {
-                                const int i = (v ? baseB : baseA) + r;
-                                x = (i >= 1) ? stencil_cell(i, n, (i == 1) ? spool : m, cc, pp, g, cf, ps, tref, alpha, tdiel) : spool;
-                            }
-                            if (valid) {
-                                col[(2 * r + v) * NT] = x;
-                                tmax = fmax_gt(tmax, x);
-                            }
-                        }
-                        tm1 = tc;
-                        tc = tp1;
-                        f2 first = cur[0];
-#pragma unroll
-                        for (int q = 0; q < 7; ++q) cur[q] = cur[q + 1];
-                        cur[7] = first;
-                    }
-                }
-            };
-            f2 bufA[8];
-            if (!frozen_wave) {
-                for (int t = 0; t < n_walk; ++t) tile(std::false_type{}, t, bufA);
-            } else {
-                for (int t = 0; t < n_walk; ++t) tile(std::true_type{}, t, bufA);
+                if (joule_wave) tile_staged<f2, true, true, W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
+                else tile_staged<f2, false, true, W>(old, tn, o, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
             }
-        }
-        WEDM_SV_PHASE(pb);  // the tiles
-        // ---- patches (after every store of the walk): tail cells, then boundary condition, last cell, plasma cell
-        if (use_tail && !done) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                if (q < tail) {
-#pragma unroll
-                    for (int v = 0; v < 2; ++v) {
-                        if ((tail_bits >> (4 * (2 * q + v))) & 4u) {  // interior: exists, counts, and is not the wire's last cell
-                            const float x = v ? ttp[q].y : ttp[q].x;
-                            col[(2 * (Cv - tail + q) + v) * NT] = x;
-                            tmax = fmax_gt(tmax, x);
-                        }
-                    }
-                }
-            }
-        }
-        if (c == 0 && !done) col[0] = spool;
-        if (own_last && !done) {
-            const int v = own_last - 1;
-            col[(2 * (n - 1 - (v ? baseB : baseA)) + v) * NT] = tlast;
-            tmax = fmax_gt(tmax, tlast);
-        }
-        if (own_pl) {
-            const int v = own_pl - 1;
-            col[(2 * (cf.pidx - (v ? baseB : baseA)) + v) * NT] = tpl;
-            tmax = fmax_gt(tmax, tpl);
-        }
+        };
+        constexpr bool kWalkTiles = true;
+#define WEDM_PACKED_WALK_MARK_TILES WEDM_SV_PHASE(pa)    // mailbox, halos, patched cells and tails from old values
+#define WEDM_PACKED_WALK_MARK_PATCHES WEDM_SV_PHASE(pb)  // the tiles
+#define WEDM_PACKED_WALK_US
+#include "wedm_packed_walk.inc"
+#undef WEDM_PACKED_WALK_US
+#undef WEDM_PACKED_WALK_MARK_TILES
+#undef WEDM_PACKED_WALK_MARK_PATCHES
         tmax = max_over_env_lanes<L>(tmax);
         if (c == 0) box->tmax[slot][el] = tmax;
         asm volatile("" ::: "memory");
@@ -709,6 +478,11 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
     __syncthreads();  // (B)
     copy_wire_nt<L, NT, false>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
 }
+#undef WEDM_PACKED_WALK_TAILS_FROM_OLD
+#undef WEDM_PACKED_WALK_TAIL_NEW
+#undef WEDM_PACKED_WALK_DONE
+#undef WEDM_PACKED_WALK_REGULAR_TILE
+#undef WEDM_PACKED_WALK_ONECHANGE_TILE
 
 // ============================================ served register kernel: the wire in the walkers' registers, no LDS image
 // wedm_step_regs<2>'s walk (wedm_regs_walk.inc) on TWO walker waves of a block -- two lanes per environment, 32 packed
