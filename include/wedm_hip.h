@@ -39,7 +39,7 @@
  * the first num_envs columns of a row are the library's, the columns [num_envs, stride) are the caller's padding, and
  * what lies before a block's first row and behind its last one is somebody else's memory.
  *   1. wedm_step and wedm_reset write only: columns [0, num_envs) of the rows of the bound state blocks (f64, i32, i8,
- *      T, obs, stats, reward, crater_log); the same columns of the pulse block, where bound; in a bound trace ring, the
+ *      T, obs, stats, reward, crater_log); the same columns of the pulse and signal-statistics blocks, where bound; in a bound trace ring, the
  *      slots and the environment window its descriptor names.
  *   2. Columns [num_envs, stride) of every one of those rows are never written, and no launch writes a byte before a
  *      block's first row or after its last row, the action leaves, the reset mask, the geometry, env-param and
@@ -185,6 +185,38 @@ enum wedm_pulse_field {
     WEDM_P_SHORT_LAST,         /* short pulses of the last completed interval       */
     WEDM_P_SHORT_STEPS_LAST,   /* short-circuit samples of the last completed interval */
     WEDM_PULSE_COUNT
+};
+
+/* ------------------------------------------------ signal statistics (optional)
+ * What a controller works from over one control interval besides the voltage sum (WEDM_F_VOLT_SUM) and the pulse counts:
+ * the current and the energy that went into the gap, how close the wire came to the workpiece and how hot it got at its
+ * worst.  A SAMPLE is what it is for the pulse block: the state after one physics step an environment ran (a frozen
+ * environment has none; with keep_stepping_terminated every step it keeps running is one).  With V = state.voltage,
+ * I = state.current, gap = workpiece_position - wire_position (the float64 expression observation column 0 rounds) and
+ * tmax = row WEDM_F_TMAX after the step, the *_ACC rows are updated sample by sample, in step order, in float64:
+ * SAMPLES += 1, CURRENT += I, ENERGY += V * I (the product rounded to float64, then the addition: never fused), GAP += gap,
+ * GAP_MIN = min(GAP_MIN, gap), TMAX_PEAK = max(TMAX_PEAK, (double)tmax).  At every control step (this step's sample
+ * included) the kernels publish the six accumulators into the *_LAST rows and restart them from their identities
+ * 0, 0, 0, 0, +inf, -inf: a publication has SAMPLES >= 1 and never holds an infinity.  A reset (wedm_reset, the in-launch
+ * autoreset, either reset_semantics) sets the *_ACC rows to their identities and the *_LAST rows to 0.  The accumulators
+ * survive launches: single microseconds and one fused launch give the same rows.
+ * Observation: a control step also writes five float32 columns, (float) of CURRENT_LAST, ENERGY_LAST, GAP_LAST,
+ * GAP_MIN_LAST, TMAX_PEAK_LAST (raw sums, not means), at columns base .. base + 4, where base = 11 while a pulse block is
+ * bound (wedm_bind_pulse_stats) and 8 otherwise; only where wedm_params.obs_dim >= base + 5.                          */
+enum wedm_sig_field {
+    WEDM_SG_SAMPLES_ACC = 0,   /* samples since the last control step                          */
+    WEDM_SG_CURRENT_ACC,       /* sum of state.current over them                     [A]       */
+    WEDM_SG_ENERGY_ACC,        /* sum of state.voltage * state.current               [V A]     */
+    WEDM_SG_GAP_ACC,           /* sum of workpiece_position - wire_position          [um]      */
+    WEDM_SG_GAP_MIN_ACC,       /* smallest such gap (+inf while there is no sample)  [um]      */
+    WEDM_SG_TMAX_PEAK_ACC,     /* largest WEDM_F_TMAX (-inf while there is no sample)          */
+    WEDM_SG_SAMPLES_LAST,      /* the same six of the last completed interval                  */
+    WEDM_SG_CURRENT_LAST,
+    WEDM_SG_ENERGY_LAST,
+    WEDM_SG_GAP_LAST,
+    WEDM_SG_GAP_MIN_LAST,
+    WEDM_SG_TMAX_PEAK_LAST,
+    WEDM_SIG_COUNT
 };
 
 /* ------------------------------------ per-environment physics parameters (optional)
@@ -480,6 +512,15 @@ int32_t wedm_bind_env_params(wedm_ctx* ctx, const double* rows);
  * and injected variates (wedm_bind_rng_replay), make wedm_step return WEDM_ERR_UNSUPPORTED.  wedm_reset reads none of
  * the rows.                                                                                                            */
 int32_t wedm_bind_wire_material(wedm_ctx* ctx, const double* rows);
+
+/* binds (rows != NULL) or removes (rows == NULL) the caller-owned signal-statistics block
+ * float64 [WEDM_SIG_COUNT][stride] described at wedm_sig_field (same stride as the state blocks; WEDM_ERR_NOT_BOUND before
+ * wedm_bind_state).  While it is bound, wedm_step runs the kernels' SIG instantiations: kernel 2's packed form for a fused
+ * launch of the float32 stencil without a trace sample and without pulse statistics (with or without per-environment
+ * physics parameters and wire material), kernel 1 for every other launch; wedm_set_kernel values other than 0, 1 and 2,
+ * and injected variates (wedm_bind_rng_replay), make wedm_step return WEDM_ERR_UNSUPPORTED.  The control steps also write
+ * the five observation columns described at wedm_sig_field.  Binding does not clear the block: wedm_reset does.        */
+int32_t wedm_bind_signal_stats(wedm_ctx* ctx, double* rows);
 
 /* binds (desc != NULL) or removes (desc == NULL) the signal trace; resets the sample counter.
  * Terminated environments keep being sampled (their frozen state).                        */

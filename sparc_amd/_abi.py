@@ -139,6 +139,29 @@ PULSE_COUNT = 6
 PULSE_OBS_NAMES = ("spark_pulses", "short_pulses", "short_steps")
 
 
+class SIG(enum.IntEnum):
+    """Rows of the optional signal-statistics block (``enum wedm_sig_field``, float64)."""
+
+    SAMPLES_ACC = 0
+    CURRENT_ACC = 1
+    ENERGY_ACC = 2
+    GAP_ACC = 3
+    GAP_MIN_ACC = 4
+    TMAX_PEAK_ACC = 5
+    SAMPLES_LAST = 6
+    CURRENT_LAST = 7
+    ENERGY_LAST = 8
+    GAP_LAST = 9
+    GAP_MIN_LAST = 10
+    TMAX_PEAK_LAST = 11
+
+
+SIG_COUNT = 12
+# obs columns of an environment built with signal_stats=True: five published rows as float32 (raw sums over the interval,
+# not means), at columns 8-12, or 11-15 behind the pulse columns
+SIGNAL_OBS_NAMES = ("current_sum", "energy_sum", "gap_sum", "gap_min", "tmax_peak")
+
+
 class ENVP(enum.IntEnum):
     """Rows of the optional per-environment physics block (``enum wedm_envp_field``, float64)."""
 

@@ -62,6 +62,8 @@ def load() -> C.CDLL:
     L.wedm_bind_rng_replay.restype = C.c_int32
     L.wedm_bind_pulse_stats.argtypes = [ctx, C.c_void_p]
     L.wedm_bind_pulse_stats.restype = C.c_int32
+    L.wedm_bind_signal_stats.argtypes = [ctx, C.c_void_p]
+    L.wedm_bind_signal_stats.restype = C.c_int32
     L.wedm_bind_env_params.argtypes = [ctx, C.c_void_p]
     L.wedm_bind_env_params.restype = C.c_int32
     L.wedm_bind_wire_material.argtypes = [ctx, C.c_void_p]
@@ -90,7 +92,7 @@ def load() -> C.CDLL:
 
 EXPORTS = (
     "wedm_abi_version", "wedm_create", "wedm_destroy", "wedm_bind_state", "wedm_bind_geometry",
-    "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
+    "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
 )
 
@@ -182,6 +184,10 @@ class HipBackend:
     def bind_pulse_stats(self, rows_ptr) -> None:
         """`rows_ptr`: device address of an int32 [PULSE_COUNT][stride] block, or None (unbind)."""
         self._check(self._L.wedm_bind_pulse_stats(self._ctx, rows_ptr))
+
+    def bind_signal_stats(self, rows_ptr) -> None:
+        """`rows_ptr`: device address of a float64 [SIG_COUNT][stride] block, or None (unbind).  After `bind_state`."""
+        self._check(self._L.wedm_bind_signal_stats(self._ctx, rows_ptr))
 
     def bind_env_params(self, rows_ptr) -> None:
         """`rows_ptr`: device address of a float64 [ENVP_COUNT][stride] block, or None (unbind)."""

@@ -196,7 +196,7 @@ _WIDE = {"time": "time_low32", "time_since_open_voltage": "time_since_open_volta
 
 class BatchedEDMState:
     def __init__(self, num_envs: int, n_seg_max: int, obs_dim: int, device, crater_log_capacity: int = 0,
-                 pulse_stats: bool = False):
+                 pulse_stats: bool = False, signal_stats: bool = False):
         stride = (num_envs + 63) // 64 * 64
         object.__setattr__(self, "num_envs", num_envs)
         object.__setattr__(self, "n_seg_max", n_seg_max)
@@ -219,6 +219,9 @@ class BatchedEDMState:
         # per-interval pulse statistics (include/wedm_hip.h, enum wedm_pulse_field), optional
         object.__setattr__(self, "pulse", torch.zeros((_abi.PULSE_COUNT, stride), dtype=torch.int32, **kw)
                            if pulse_stats else None)
+        # per-interval signal statistics (include/wedm_hip.h, enum wedm_sig_field), optional
+        object.__setattr__(self, "signal", torch.zeros((_abi.SIG_COUNT, stride), dtype=torch.float64, **kw)
+                           if signal_stats else None)
         # read-only attributes computed on access (registered by the environment):
         # dielectric_flow_rate (dielectric.py:160-162), wire_average_temperature (wire.py:339-347)
         object.__setattr__(self, "derived", {})
@@ -311,10 +314,12 @@ class BatchedEDMState:
             out["crater_log"] = self.crater_log.detach().cpu().clone()
         if self.pulse is not None:  # the interval's running counts: part of the state
             out["pulse"] = self.pulse.detach().cpu().clone()
+        if self.signal is not None:  # the interval's running sums and extrema: part of the state
+            out["signal"] = self.signal.detach().cpu().clone()
         return out
 
     def load_blocks(self, blocks) -> None:
-        for k in ("f64", "i32", "i8", "T", "obs", "stats", "reward", "crater_log", "pulse"):
+        for k in ("f64", "i32", "i8", "T", "obs", "stats", "reward", "crater_log", "pulse", "signal"):
             if k in blocks and getattr(self, k) is not None:
                 if tuple(blocks[k].shape) != tuple(getattr(self, k).shape):
                     raise ValueError(f"state block {k!r} has shape {tuple(blocks[k].shape)}, this environment's is "

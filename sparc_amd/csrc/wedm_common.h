@@ -94,6 +94,7 @@ struct KArgs {
     int32_t* pulse;          // wedm_bind_pulse_stats block or NULL (read by the PULSE instantiations only, via kernarg_pulse)
     const double* envp;      // wedm_bind_env_params rows or NULL (read by the ENVP instantiations only, via kernarg_envp)
     const double* wmat;      // wedm_bind_wire_material rows or NULL (read by the MAT instantiations only, via kernarg_wmat)
+    double* sig;             // wedm_bind_signal_stats block or NULL (read by the SIG instantiations only, via kernarg_sig)
 };
 
 // The by-value `cold` member as the kernels read it: through the kernarg segment (wedm_device.h).
@@ -120,6 +121,11 @@ __device__ __forceinline__ const double* wedm::kernarg_wmat() {
     WmatSlot p = (WmatSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, wmat));
     asm volatile("" : "+s"(p));
     return *p;
+}
+
+// The signal-statistics block's pointer as the SIG instantiations read it: through the kernarg segment (wedm_device.h, SigRef)
+__device__ __forceinline__ SigRef kernarg_sig() {
+    return SigRef{(SigSlot)((const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(KArgs, sig))};
 }
 
 #include "wedm_lifecycle.h"
@@ -237,9 +243,10 @@ __device__ __forceinline__ float stencil_pass(const TA& T, const Geom& g, const 
 
 // F: the kernel's forms.  `hot`: k.hot, or (F_ENVP / F_MAT) the lane's copy with its environment's rows (envp_apply,
 // wmat_apply)
+// `sg`: the environment's signal-statistics accumulators (F_SIG forms; the caller loads and stores them)
 template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, const ColdRef cold, const Geom& g, int64_t e,
-                                               uint32_t gid, Env& s, const TA& T) {
+                                               uint32_t gid, Env& s, const TA& T, Sig& sg) {
     constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
     constexpr bool MAT = (F & F_MAT) != 0;
     Persist ps;
@@ -254,7 +261,7 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
             Coef c = scalar_prelude<F>(hot, cold, g, e, gid, s, ps, true);  // single steps: the quiet test does not pay
             // (keep_stepping_terminated: the wire module returns at once on a broken wire, wire.py:260-261)
             float tmax = s.broken ? s.tmax : stencil_pass<F64>(T, g, c, ps, hot, f64c, s.h_base, s.h_zone);
-            env_step_done<F>(hot, cold, e, s, tmax, pk, true);
+            env_step_done<F>(hot, cold, e, s, tmax, pk, true, sg);
         } else if (!tracing) {
             break;
         }
@@ -267,8 +274,8 @@ __device__ __forceinline__ void run_substeps_h(const KArgs& k, const Hot& hot, c
 // uniform ones.  F_MAT: those of environment e's wire material (wedm_bind_wire_material), applied after the ENVP rows.
 template <uint32_t F, class TA>
 __device__ __forceinline__ void run_substeps(const KArgs& k, const ColdRef cold, const Geom& g, int64_t e,
-                                             uint32_t gid, Env& s, const TA& T) {
-    run_substeps_h<F, TA>(k, launch_hot<F>(k, cold, e, true), cold, g, e, gid, s, T);
+                                             uint32_t gid, Env& s, const TA& T, Sig& sg) {
+    run_substeps_h<F, TA>(k, launch_hot<F>(k, cold, e, true), cold, g, e, gid, s, T, sg);
 }
 
 // np.max over finite temperatures; maps to v_max_f32 / v_max3_f32

@@ -44,6 +44,7 @@ enum : uint32_t {
     F_ONE = 1u << 10,       // one microsecond per launch, no loop (stream kernel)
     F_CMAX104 = 1u << 11,   // chunks of up to 104 cells in registers, else 64 (stream kernel)
     F_MINB2 = 1u << 12,     // two blocks per CU, else one (float64 wide register kernel)
+    F_SIG = 1u << 13,       // signal statistics (wedm_bind_signal_stats)
 };
 
 // ---------------------------------------------------------------- small helpers
@@ -1477,6 +1478,107 @@ __device__ __forceinline__ void pulse_reinit(const PulseRef pulse, const ColdRef
     const int64_t stride = cold->s.stride;
 #pragma unroll
     for (int q = 0; q < WEDM_PULSE_COUNT; ++q) __hip_atomic_store(WEDM_ROW(rows, q), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ------------------------------------------------- signal statistics (wedm_bind_signal_stats, enum wedm_sig_field)
+// The block's pointer travels at the END of the kernel arguments, after the wire-material pointer, and is read through the
+// kernel-argument segment at the point of use (kernarg_sig, wedm_common.h), like the pulse block's.
+typedef double* const WEDM_AS4* SigSlot;
+struct SigRef {
+    SigSlot slot;
+    __device__ __forceinline__ double* get() const {
+        SigSlot p = slot;
+        asm volatile("" : "+s"(p));
+        return *p;
+    }
+};
+
+// The six accumulators of one environment (rows WEDM_SG_*_ACC).  Unlike a pulse edge, every sample updates every one of
+// them, so they do not live in memory during a launch: the SIG instantiations load them when they open the environment
+// (sig_load), carry them in registers through the microsecond loop and store them when the launch closes (sig_store).
+// Every lane of an environment carries a replica; only the writer lane touches memory.  Without F_SIG the struct is never
+// read or written and costs nothing.
+struct Sig { double n, cur, en, gap, gmin, tpk; };
+
+__device__ __forceinline__ void sig_identities(Sig& g) {
+    g.n = 0.0; g.cur = 0.0; g.en = 0.0; g.gap = 0.0; g.gmin = __builtin_inf(); g.tpk = -__builtin_inf();
+}
+
+// the accumulator rows of environment e (`live`: not a lane past the batch, whose replica is never stored)
+template <bool SIG>
+__device__ __forceinline__ void sig_load(const SigRef sig, const ColdRef cold, int64_t e, bool live, Sig& g) {
+    if (!SIG) return;
+    sig_identities(g);
+    if (!live) return;
+    const double* const rows = sig.get();
+    const int64_t stride = cold->s.stride;
+    g.n = *WEDM_ROW(rows, WEDM_SG_SAMPLES_ACC); g.cur = *WEDM_ROW(rows, WEDM_SG_CURRENT_ACC);
+    g.en = *WEDM_ROW(rows, WEDM_SG_ENERGY_ACC); g.gap = *WEDM_ROW(rows, WEDM_SG_GAP_ACC);
+    g.gmin = *WEDM_ROW(rows, WEDM_SG_GAP_MIN_ACC); g.tpk = *WEDM_ROW(rows, WEDM_SG_TMAX_PEAK_ACC);
+}
+
+// the launch's close: the accumulators back into their rows, in the lane for which `store` holds
+template <bool SIG>
+__device__ __forceinline__ void sig_store(const SigRef sig, const ColdRef cold, int64_t e, bool store, const Sig& g) {
+    if (!SIG || !store) return;
+    double* const rows = sig.get();
+    const int64_t stride = cold->s.stride;
+    *WEDM_ROW(rows, WEDM_SG_SAMPLES_ACC) = g.n; *WEDM_ROW(rows, WEDM_SG_CURRENT_ACC) = g.cur;
+    *WEDM_ROW(rows, WEDM_SG_ENERGY_ACC) = g.en; *WEDM_ROW(rows, WEDM_SG_GAP_ACC) = g.gap;
+    *WEDM_ROW(rows, WEDM_SG_GAP_MIN_ACC) = g.gmin; *WEDM_ROW(rows, WEDM_SG_TMAX_PEAK_ACC) = g.tpk;
+}
+
+// The tally of one sample, called where pulse_tally is: right before control_step_outputs() for a step the environment ran.
+// The energy term is the product V * I rounded to float64 and then added: the build's -ffp-contract=off (part of the
+// numerics contract) keeps the compiler from fusing the two into one fma, which would round once.  At a control step the
+// writer lane publishes the accumulators (this sample included) into the *_LAST rows and, as float32, into the observation
+// columns base .. base + 4 (base 11 in a PULSE form, whose block owns columns 8-10, else 8) where obs_dim holds them; every
+// lane restarts its replica from the identities.  Plain vector stores: nothing else writes these rows during a launch.
+template <bool SIG, bool PULSE>
+__device__ __forceinline__ void sig_tally(const SigRef sig, const ColdRef cold, int64_t e, const Env& s, bool writer, Sig& g) {
+    if (!SIG) return;
+    const double gap = s.wp - s.x, tm = (double)s.tmax;
+    const double vi = s.V * s.I;
+    g.n += 1.0;
+    g.cur += s.I;
+    g.en += vi;
+    g.gap += gap;
+    g.gmin = gap < g.gmin ? gap : g.gmin;
+    g.tpk = tm > g.tpk ? tm : g.tpk;
+    if (s.ctrl) {
+        if (writer) {
+            double* const rows = sig.get();
+            const ColdPtr c = cold.get();
+            const int64_t stride = c->s.stride;
+            *WEDM_ROW(rows, WEDM_SG_SAMPLES_LAST) = g.n; *WEDM_ROW(rows, WEDM_SG_CURRENT_LAST) = g.cur;
+            *WEDM_ROW(rows, WEDM_SG_ENERGY_LAST) = g.en; *WEDM_ROW(rows, WEDM_SG_GAP_LAST) = g.gap;
+            *WEDM_ROW(rows, WEDM_SG_GAP_MIN_LAST) = g.gmin; *WEDM_ROW(rows, WEDM_SG_TMAX_PEAK_LAST) = g.tpk;
+            constexpr int base = PULSE ? 11 : 8;
+            float* const obs = c->s.obs;
+            if (obs && opaque(c->p)->obs_dim >= base + 5) {
+                float* const o = obs + e;
+                o[(int64_t)(base + 0) * stride] = (float)g.cur;
+                o[(int64_t)(base + 1) * stride] = (float)g.en;
+                o[(int64_t)(base + 2) * stride] = (float)g.gap;
+                o[(int64_t)(base + 3) * stride] = (float)g.gmin;
+                o[(int64_t)(base + 4) * stride] = (float)g.tpk;
+            }
+        }
+        sig_identities(g);
+    }
+}
+
+// reinit_env()'s part for the signal block (the in-launch autoreset): the replica to the identities (the close stores it
+// into the *_ACC rows), the *_LAST rows to zero by the writer lane
+template <bool SIG>
+__device__ __forceinline__ void sig_reinit(const SigRef sig, const ColdRef cold, int64_t e, bool writer, Sig& g) {
+    if (!SIG) return;
+    sig_identities(g);
+    if (!writer) return;
+    double* const rows = sig.get();
+    const int64_t stride = cold->s.stride;
+#pragma unroll
+    for (int q = WEDM_SG_SAMPLES_LAST; q < WEDM_SIG_COUNT; ++q) *WEDM_ROW(rows, q) = 0.0;
 }
 
 // wedm_params.autoreset: what wedm_reset_kernel(mask = DONE, reseed = 0) writes for one environment,

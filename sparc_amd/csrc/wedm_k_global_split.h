@@ -13,10 +13,14 @@
 // F_MAT: the form with per-environment wire material (wedm_bind_wire_material), with or without F_ENVP: every launch
 // with the rows bound that kernel 2's MAT form does not take (a trace sample, stencil_mode 1, pulse statistics, single
 // microseconds, forced kernel 1); never with injected variates
+// F_SIG: the form with signal statistics (wedm_bind_signal_stats), with every subset of the above but F_REPLAY: every
+// launch with the block bound that kernel 2's SIG forms do not take (a trace sample, stencil_mode 1, pulse statistics,
+// single microseconds, forced kernel 1).  The accumulators are in the lane's registers from the opening to the close.
 template <uint32_t F>
 __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
-    static_assert((F & ~(F_TRACE | F_F64 | F_REPLAY | F_PULSE | F_ENVP | F_MAT)) == 0, "forms of wedm_step_global");
-    constexpr bool TRACE = (F & F_TRACE) != 0, PULSE = (F & F_PULSE) != 0;
+    static_assert((F & ~(F_TRACE | F_F64 | F_REPLAY | F_PULSE | F_ENVP | F_MAT | F_SIG)) == 0 && !((F & F_SIG) && (F & F_REPLAY)),
+                  "forms of wedm_step_global");
+    constexpr bool TRACE = (F & F_TRACE) != 0, PULSE = (F & F_PULSE) != 0, SIG = (F & F_SIG) != 0;
     const ColdRef cold = kernarg_cold();
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= k.num_envs) return;
@@ -29,17 +33,21 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
         return;
     }
     const GlobalT T = global_wire(cold->s.T, cold->s.stride, e);
+    Sig sg;
+    sig_load<SIG>(kernarg_sig(), cold, e, true, sg);
     if (reinit) {  // next-step autoreset: wedm_reset for this environment, inside the launch
         reinit_env(cold, e, s, true);
         pulse_reinit<PULSE>(kernarg_pulse(), cold, e, true);
+        sig_reinit<SIG>(kernarg_sig(), cold, e, true, sg);
         for (int q = 0; q < WEDM_T_QUADS(k.n_seg_max); ++q) T.stq(q, f4v{k.hot.spool, k.hot.spool, k.hot.spool, k.hot.spool});
     }
     unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
     load_geom(k.hot, cold, e, g);
-    run_substeps<F, GlobalT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T);
+    run_substeps<F, GlobalT>(k, cold, g, e, k.hot.env_id_offset + (uint32_t)e, s, T, sg);
     env_close(k, cold, e, s, frozen, true);
+    sig_store<SIG>(kernarg_sig(), cold, e, true, sg);
 }
 
 // phase stamps of the split kernel (diagnostic build -DWEDM_STAMPS only): raw s_memtime at

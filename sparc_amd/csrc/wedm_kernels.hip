@@ -1,5 +1,5 @@
 // wedm_kernels.hip — the translation unit(s) of libwedm_hip.so: includes the kernel families, lists their instantiations in one
-// registry (compiled in five parts in parallel), and holds the host side of the C-ABI of include/wedm_hip.h (launch plan,
+// registry (compiled in six parts in parallel), and holds the host side of the C-ABI of include/wedm_hip.h (launch plan,
 // wedm_create ...).
 //
 // Device code, by file (DESIGN.md section 4 has the table with what binds each kernel):
@@ -62,11 +62,11 @@ using namespace wedm;
 
 // ------------------------------------------------------------ the registry of instantiations
 // Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are about 260,
-// which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file five times in
+// which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file six times in
 // parallel: -DWEDM_PART=N defines registry_partN(), which instantiates what it lists (1: the packed kernel, 2: the fused
 // kernel, 3: the served kernels and kernel 2's float32 forms, 4: the float64-typed forms of kernels 2, 6, 7 and 8 and the
-// PULSE forms of 7 and 8, 0: the rest); -DWEDM_PART=0 also holds the host code and the reset and debug kernels, and
-// registry() there joins the five slices.  The five objects link into the one shared library.  Without -DWEDM_PART the file
+// PULSE forms of 7 and 8, 5: the SIG forms of kernels 1 and 2, 0: the rest); -DWEDM_PART=0 also holds the host code and the
+// reset and debug kernels, and registry() there joins the six slices.  The six objects link into the one shared library.  Without -DWEDM_PART the file
 // is one self-contained translation unit (the diagnostic builds of tools/ use it that way).
 
 // kernel numbers of wedm_set_kernel (include/wedm_hip.h; the ABI carries them as int32_t)
@@ -134,6 +134,7 @@ Slice registry_part1();
 Slice registry_part2();
 Slice registry_part3();
 Slice registry_part4();
+Slice registry_part5();
 
 #if !defined(WEDM_PART) || WEDM_PART == 1
 Slice registry_part1() {
@@ -177,6 +178,17 @@ Slice registry_part4() {
 }
 #endif
 
+#if !defined(WEDM_PART) || WEDM_PART == 5
+// signal statistics (wedm_bind_signal_stats): kernel 1 with every other binding but injected variates, kernel 2's packed
+// form with or without the per-environment rows
+Slice registry_part5() {
+    Slice s;
+    add<K_GLOBAL>(s, NoLanes{}, Every<F_TRACE | F_F64 | F_PULSE | F_ENVP | F_MAT, F_SIG>{});
+    add<K_LANES_PK>(s, L5{}, Every<F_ENVP | F_MAT, F_SIG>{});
+    return s;
+}
+#endif
+
 #if !defined(WEDM_PART) || WEDM_PART == 0
 Slice registry_part0() {
     Slice s;
@@ -191,11 +203,11 @@ Slice registry_part0() {
     return s;
 }
 
-// every instantiation: the slices of the five parts
+// every instantiation: the slices of the six parts
 static const Slice& registry() {
     static const Slice all = [] {
         Slice a;
-        for (Slice (*part)() : {registry_part0, registry_part1, registry_part2, registry_part3, registry_part4}) {
+        for (Slice (*part)() : {registry_part0, registry_part1, registry_part2, registry_part3, registry_part4, registry_part5}) {
             const Slice s = part();
             a.insert(a.end(), s.begin(), s.end());
         }
@@ -218,7 +230,7 @@ static bool has_form(int32_t k, uint32_t form) {
 }
 static std::string form_names(uint32_t F) {
     static const char* const names[] = {"TRACE", "F64", "REPLAY", "PULSE", "ENVP", "MAT", "FROZEN_OK",
-                                        "N1", "EXTRA", "CUT", "ONE", "CMAX104", "MINB2"};
+                                        "N1", "EXTRA", "CUT", "ONE", "CMAX104", "MINB2", "SIG"};
     std::string s;
     for (int b = 0; b < (int)(sizeof(names) / sizeof(names[0])); ++b)
         if ((F >> b) & 1u) s += (s.empty() ? "F_" : " | F_") + std::string(names[b]);
@@ -290,6 +302,18 @@ wedm_reset_pulse_kernel(int32_t* rows, int64_t stride, int32_t num_envs, const u
     if (e >= num_envs) return;
     if (mask && !mask[e]) return;
     for (int q = 0; q < WEDM_PULSE_COUNT; ++q) *WEDM_ROW(rows, q) = 0;
+}
+
+// wedm_reset's part for the signal-statistics block (wedm_bind_signal_stats), in its own launch for the same reason: the
+// accumulators to their identities, the published rows to zero
+__global__ void __launch_bounds__(256)
+wedm_reset_signal_kernel(double* rows, int64_t stride, int32_t num_envs, const uint8_t* mask) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= num_envs) return;
+    if (mask && !mask[e]) return;
+    for (int q = 0; q < WEDM_SIG_COUNT; ++q) *WEDM_ROW(rows, q) = 0.0;
+    *WEDM_ROW(rows, WEDM_SG_GAP_MIN_ACC) = __builtin_inf();
+    *WEDM_ROW(rows, WEDM_SG_TMAX_PEAK_ACC) = -__builtin_inf();
 }
 
 // Probe of the device math the physics relies on (test hook; see wedm_debug_math).
@@ -373,6 +397,7 @@ struct wedm_ctx {
     int32_t* pulse = nullptr;          // wedm_bind_pulse_stats: [WEDM_PULSE_COUNT][stride] or NULL
     const double* envp = nullptr;      // wedm_bind_env_params: [WEDM_ENVP_COUNT][stride] or NULL
     const double* wmat = nullptr;      // wedm_bind_wire_material: [WEDM_WMAT_COUNT][stride] or NULL
+    double* sig = nullptr;             // wedm_bind_signal_stats: [WEDM_SIG_COUNT][stride] or NULL
     std::string err;
     std::string last_kernel;
     LaunchPlan plans[2][2][2];         // [single microsecond][trace point][frozen-lane tile code]: cached launch decisions
@@ -628,6 +653,7 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     const wedm_params& P = ctx->p;
     const bool uniform = uniform_geometry(ctx), f64 = P.stencil_mode != 0, replay = ctx->replay != nullptr;
     const bool pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr, mat = ctx->wmat != nullptr;
+    const bool sig = ctx->sig != nullptr;
     // kernel 3 (one chunk per lane) and kernel 4 (two packed chunks per lane, table of 2L chunks).
     // Auto-selection by a small cost model fitted to measurements:
     //   cycles per step ~ rounds * (4500 + tiles_per_lane * 8 * cell_cost),  tiles_per_lane: see eff_tiles,
@@ -690,6 +716,11 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) and a per-environment wire material (wedm_bind_wire_material) cannot be combined");
     if (mat && !has_form(forced, F_MAT))
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with a per-environment wire material bound (wedm_bind_wire_material) only kernels 0 (auto), 1 and 2 run");
+    // signal statistics: kernels 1 and 2 only, and no injected variates
+    if (sig && replay)
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) and signal statistics (wedm_bind_signal_stats) cannot be combined");
+    if (sig && !has_form(forced, F_SIG))
+        return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with signal statistics bound (wedm_bind_signal_stats) only kernels 0 (auto), 1 and 2 run");
     if (replay) {
         if (forced != K_AUTO && forced != K_GLOBAL)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: injected variates (wedm_bind_rng_replay) run on kernel 1 only");
@@ -711,22 +742,26 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
         return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound (wedm_bind_pulse_stats) only kernels 0 (auto), 1, 2, 7 and 8 run");
 
     int32_t v = forced;
-    if (pulse || envp || mat) {
+    if (pulse || envp || mat || sig) {
         // bound rows: the float32 stencil without a trace sample or injected variates runs the caller's kernel, and a fused
         // launch under auto what the automatic choice takes among the forms there are (pulse: 8 or 7, else kernel 2's packed
-        // form; envp, mat: kernel 2's packed form); every other launch runs kernel 1, and so does every launch with pulse
-        // statistics and rows bound (kernel 2's ENVP and MAT forms count no pulses)
+        // form; envp, mat, sig: kernel 2's packed form); every other launch runs kernel 1, and so does every launch with pulse
+        // statistics and rows or signal statistics bound (kernel 2's ENVP, MAT and SIG forms count no pulses; kernels 7 and 8
+        // have no SIG form)
         const bool fast = !tr && !f64 && !replay;
         v = fast ? forced : K_GLOBAL;
-        if (v == K_AUTO && !single) v = pulse && wide_auto ? K_WIDE : pulse && regs_auto ? K_REGS : use_pk ? K_LANES_PK : K_GLOBAL;
+        if (v == K_AUTO && !single)
+            v = pulse && sig ? K_GLOBAL : pulse && wide_auto ? K_WIDE : pulse && regs_auto ? K_REGS : use_pk ? K_LANES_PK : K_GLOBAL;
         if (v == K_AUTO) v = K_GLOBAL;
         if (v == K_LANES_PK && !use_pk && pulse)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with pulse statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
         if (v == K_LANES_PK && !use_pk && envp)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with per-environment physics parameters bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
-        if (v == K_LANES_PK && !use_pk)
+        if (v == K_LANES_PK && !use_pk && mat)
             return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with a per-environment wire material bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
-        if ((envp || mat) && pulse) v = K_GLOBAL;
+        if (v == K_LANES_PK && !use_pk)
+            return fail(ctx, WEDM_ERR_UNSUPPORTED, "wedm_step: with signal statistics bound kernel 2 runs its packed form only, and no lane count puts its chunks in LDS");
+        if ((envp || mat || sig) && pulse) v = K_GLOBAL;
     } else if (v == K_AUTO) {
         // (stencil_mode 1, single microseconds: the stream kernel where the float32 launch takes it too and every tile of
         // the table has register-walk code)
@@ -811,11 +846,12 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     const int L = ch.lanes, n = ctx->num_envs;
     const bool f64 = ctx->p.stencil_mode != 0, replay = ctx->replay != nullptr, pulse = ctx->pulse != nullptr, envp = ctx->envp != nullptr;
     const bool mat = ctx->wmat != nullptr;  // (never with injected variates, never with pulse statistics on kernel 2: choose_kernel)
+    const bool sig = ctx->sig != nullptr;   // (the same)
     // the form: the launch's trace point and the handle's bindings (kernel 1 has a form for each such set; the PULSE, ENVP
     // and MAT forms of the other families carry neither TRACE nor F64), then each family's own bits below
     uint32_t F = (tr ? F_TRACE : 0u) | (f64 ? F_F64 : 0u) | (replay ? F_REPLAY : 0u) | (pulse ? F_PULSE : 0u) |
-                 (envp ? F_ENVP : 0u) | (mat ? F_MAT : 0u);
-    if (ch.kernel != K_GLOBAL && (F & (F_PULSE | F_ENVP | F_MAT))) F &= ~(F_TRACE | F_F64);
+                 (envp ? F_ENVP : 0u) | (mat ? F_MAT : 0u) | (sig ? F_SIG : 0u);
+    if (ch.kernel != K_GLOBAL && (F & (F_PULSE | F_ENVP | F_MAT | F_SIG))) F &= ~(F_TRACE | F_F64);
     const WalkInfo* w = nullptr;  // the walk table the launch reads
     bool fz = false;              // the FROZEN_OK form (named in the kernel string)
     int grid = blocks(n, 256 / std::max(L, 1)), block = 256;
@@ -892,9 +928,9 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
     char lanes_s[16] = "", lds_s[32] = "";
     if (L) std::snprintf(lanes_s, sizeof(lanes_s), "<%d>", L);
     if (fl) std::snprintf(lds_s, sizeof(lds_s), ",%zuB", fl);
-    std::snprintf(out.name, sizeof(out.name), "%s%s%s%s%s%s<<<%d,%d%s>>>", kernel_names[ch.kernel], lanes_s,
+    std::snprintf(out.name, sizeof(out.name), "%s%s%s%s%s%s%s<<<%d,%d%s>>>", kernel_names[ch.kernel], lanes_s,
                   replay ? "[injected variates]" : f64 ? "[f64 stencil]" : fz ? "[frozen lanes ok]" : "", pulse ? "[pulse]" : "",
-                  envp ? "[envp]" : "", mat ? "[wmat]" : "", grid, block, lds_s);
+                  envp ? "[envp]" : "", mat ? "[wmat]" : "", sig ? "[sig]" : "", grid, block, lds_s);
     out.fn = fn;
     out.grid = grid;
     out.block = block;
@@ -1135,6 +1171,15 @@ int32_t wedm_bind_wire_material(wedm_ctx* ctx, const double* rows) {
     return WEDM_OK;
 }
 
+int32_t wedm_bind_signal_stats(wedm_ctx* ctx, double* rows) {
+    if (!ctx) return WEDM_ERR_BAD_ARG;
+    if (rows && !ctx->bound)  // the block's stride is the state blocks'
+        return fail(ctx, WEDM_ERR_NOT_BOUND, "wedm_bind_signal_stats: call wedm_bind_state first");
+    ctx->sig = rows;
+    ctx->invalidate_plans();
+    return WEDM_OK;
+}
+
 int32_t wedm_set_kernel(wedm_ctx* ctx, int32_t variant) {
     if (!ctx) return WEDM_ERR_BAD_ARG;
     if (variant < 0 || variant > 12) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_set_kernel: variant must be 0..12");
@@ -1177,6 +1222,12 @@ int32_t wedm_reset(wedm_ctx* ctx, const uint8_t* mask, uint64_t seed, int32_t re
                            ctx->num_envs, mask);
         e = hipGetLastError();
         if (e != hipSuccess) return hip_fail(ctx, e, "wedm_reset launch (pulse statistics)");
+    }
+    if (ctx->sig) {  // nor is the signal-statistics block: re-initialised by every reset, either semantics
+        hipLaunchKernelGGL(wedm_reset_signal_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, ctx->sig, ctx->s.stride,
+                           ctx->num_envs, mask);
+        e = hipGetLastError();
+        if (e != hipSuccess) return hip_fail(ctx, e, "wedm_reset launch (signal statistics)");
     }
     if (!mask && ctx->frozen_seen) *(volatile int32_t*)ctx->frozen_seen = 0;  // every environment reset: none is frozen
     return WEDM_OK;
@@ -1233,6 +1284,7 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
     k.pulse = ctx->pulse;
     k.envp = ctx->envp;
     k.wmat = ctx->wmat;
+    k.sig = ctx->sig;
     k.trace = ctx->trace;
     k.trace_next = INT32_MAX;
     k.trace_slot = 0;

@@ -186,10 +186,14 @@ __device__ __forceinline__ float lanes_pk_step(float* col, const LanesPkGeom& q,
 // F_MAT: the form with per-environment wire material (wedm_bind_wire_material; float32 stencil, no trace sample, no
 // pulse statistics), with or without F_ENVP: `hv` takes the material's alpha / tcrit / tbreak after the ENVP rows, rho_c
 // and rho_elec are read from the rows where they are used.
+// F_SIG: the form with signal statistics (wedm_bind_signal_stats; float32 stencil, no trace sample, no pulse statistics),
+// with or without F_ENVP and F_MAT: every lane of an environment carries the six accumulators in registers from the opening
+// to the close (12 VGPRs; the ENVP | MAT form is at the 256-register budget with or without them: DESIGN.md 4.10 has the
+// resource rows and why this beats a read-modify-write of the rows per sample).
 template <int L, uint32_t F>
 __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
-    static_assert((F & ~(F_TRACE | F_F64 | F_PULSE | F_ENVP | F_MAT)) == 0, "forms of wedm_step_lanes_pk");
-    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0;
+    static_assert((F & ~(F_TRACE | F_F64 | F_PULSE | F_ENVP | F_MAT | F_SIG)) == 0, "forms of wedm_step_lanes_pk");
+    constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0, PULSE = (F & F_PULSE) != 0, SIG = (F & F_SIG) != 0;
     constexpr bool ENVP = (F & F_ENVP) != 0, MAT = (F & F_MAT) != 0;
     const ColdRef cold = kernarg_cold();
     const int64_t e_hot = (int64_t)blockIdx.x * (256 / L) + threadIdx.x / L;
@@ -221,9 +225,12 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
     float* col = lds + tid;
     const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all L lanes of the environment agree)
+    Sig sg;
+    sig_load<SIG>(kernarg_sig(), cold, e, live, sg);
     if (reinit) {
         reinit_env(cold, e, s, c == 0);
         pulse_reinit<PULSE>(kernarg_pulse(), cold, e, c == 0);
+        sig_reinit<SIG>(kernarg_sig(), cold, e, c == 0, sg);
         for (int row = 0; row < R; ++row) col[row * 256] = k.hot.spool;
     }
     unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
@@ -267,7 +274,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
 
         float tmax = lanes_pk_step<L, 256, F64>(col, pkg, keep, g, cf, ps, spool, tref, alpha, tdiel, f64c, s.h_base, s.h_zone);
         tmax = max_over_env_lanes<L>(tmax);
-        env_end_us<F>(hv, cold, e, s, tmax, pk, c == 0);
+        env_end_us<F>(hv, cold, e, s, tmax, pk, c == 0, sg);
         WEDM_TRACE_POINT(k, it, e, s, c == 0,
                          for (int r = 0; r < Cv; ++r) {
                              if (baseA + r < n) tT[(int64_t)(baseA + r) * tcnt] = col[(2 * r) * 256];
@@ -278,6 +285,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     __syncthreads();
     copy_wire<L, false>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
     env_close(k, cold, e, s, frozen0, live && c == 0);
+    sig_store<SIG>(kernarg_sig(), cold, e, live && c == 0, sg);
 }
 
 // ============================================ served form: the scalar physics of the block's environments on a fourth wave

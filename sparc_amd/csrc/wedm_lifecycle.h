@@ -64,25 +64,43 @@ __device__ __forceinline__ bool env_start(const Hot& hot, const ColdRef cold, in
 }
 
 // What follows the walk of a microsecond the environment ran: the epilogue on the step's maximum temperature, the pulse
-// tally against `prev_pulse` (pulse_kind() before the step's prelude; F_PULSE forms) and, at a control step, the outputs.
+// tally against `prev_pulse` (pulse_kind() before the step's prelude; F_PULSE forms), the signal-statistics tally into the
+// lane's accumulators `sg` (F_SIG forms) and, at a control step, the outputs.
+template <uint32_t F>
+__device__ __forceinline__ void env_step_done(const Hot& hv, const ColdRef cold, int64_t e, Env& s, float tmax, int32_t prev_pulse,
+                                              bool writer, Sig& sg) {
+    scalar_epilogue(hv, s, tmax);
+    pulse_tally<(F & F_PULSE) != 0>(kernarg_pulse(), cold, e, s, prev_pulse, writer);
+    sig_tally<(F & F_SIG) != 0, (F & F_PULSE) != 0>(kernarg_sig(), cold, e, s, writer, sg);
+    if (s.ctrl) control_step_outputs(cold, e, s, writer);
+}
+// (the families without F_SIG forms: no accumulators)
 template <uint32_t F>
 __device__ __forceinline__ void env_step_done(const Hot& hv, const ColdRef cold, int64_t e, Env& s, float tmax, int32_t prev_pulse,
                                               bool writer) {
-    scalar_epilogue(hv, s, tmax);
-    pulse_tally<(F & F_PULSE) != 0>(kernarg_pulse(), cold, e, s, prev_pulse, writer);
-    if (s.ctrl) control_step_outputs(cold, e, s, writer);
+    static_assert(!(F & F_SIG), "an F_SIG form hands in its accumulators");
+    Sig none;
+    env_step_done<F>(hv, cold, e, s, tmax, prev_pulse, writer, none);
 }
 
 // The end of a microsecond in a kernel that froze broken wires around its walk (freeze_wire)
 template <uint32_t F>
 __device__ __forceinline__ void env_end_us(const Hot& hv, const ColdRef cold, int64_t e, Env& s, float tmax, int32_t prev_pulse,
-                                           bool writer) {
+                                           bool writer, Sig& sg) {
     unfreeze_wire(hv, s);
-    if (!s.done) env_step_done<F>(hv, cold, e, s, tmax, prev_pulse, writer);
+    if (!s.done) env_step_done<F>(hv, cold, e, s, tmax, prev_pulse, writer, sg);
+}
+template <uint32_t F>
+__device__ __forceinline__ void env_end_us(const Hot& hv, const ColdRef cold, int64_t e, Env& s, float tmax, int32_t prev_pulse,
+                                           bool writer) {
+    static_assert(!(F & F_SIG), "an F_SIG form hands in its accumulators");
+    Sig none;
+    env_end_us<F>(hv, cold, e, s, tmax, prev_pulse, writer, none);
 }
 
 // Closes the launch, in the lane for which `store` holds (the environment's writer, not past the batch): the reward -- a
-// frozen environment earns nothing, not the previous launch's reward --, the clock's high word and the state rows.
+// frozen environment earns nothing, not the previous launch's reward --, the clock's high word and the state rows.  An
+// F_SIG form stores its accumulators next to it (sig_store, wedm_device.h), under the same `store`.
 __device__ __forceinline__ void env_close(const KArgs& k, const ColdRef cold, int64_t e, const Env& s, bool frozen0, bool store) {
     if (!store) return;
     if (WEDM_REWARD_ON(cold)) {

@@ -153,6 +153,7 @@ class WireEDMEnv:
         reset_semantics: str = "full",
         freeze_terminated: bool = True,
         pulse_stats: bool = False,
+        signal_stats: bool = False,
         env_params: Optional[Dict[str, Any]] = None,
         wire_material=None,
         wire_material_table=None,
@@ -185,6 +186,13 @@ class WireEDMEnv:
         (experiments/run_simulation.py:597-636) and the short-circuit steps of every control interval; the observation
         gains three columns (``spark_pulses``, ``short_pulses``, ``short_steps`` of the last completed interval: ``obs_dim``
         11) and `get_pulse_statistics` returns them.  Needs a backend with ``bind_pulse_stats`` (the HIP library).
+        ``signal_stats``: sum, inside the kernels, what went into the gap over every control interval and keep its extrema:
+        the current, the energy ``voltage * current`` and the gap ``workpiece_position - wire_position`` summed over the
+        interval's physics steps, the smallest gap and the highest ``wire_max_temperature`` (include/wedm_hip.h, enum
+        wedm_sig_field).  The observation gains the five columns `SIGNAL_OBS_NAMES` (raw float32 sums of the last completed
+        interval, behind the pulse columns when both are on: ``obs_dim`` 13 or 16) and `get_signal_statistics` returns the
+        float64 values and the interval's means.  Combines with every other keyword.  Needs a backend with
+        ``bind_signal_stats`` (the HIP library).
         ``env_params``: domain randomisation -- a dict from physics-parameter names (the dataclass field names listed in
         `sparc_amd.core.env_params`: ignition thresholds, flushing efficiency, dielectric temperature, plasma heat share,
         convection, servo dynamics) to a scalar or one value per environment (sequence, NumPy array or tensor).  Names
@@ -248,8 +256,13 @@ class WireEDMEnv:
         if backend is not None and self.pulse_stats and not hasattr(backend, "bind_pulse_stats"):
             raise ValueError(f"pulse_stats=True needs a backend that counts pulses inside its step (bind_pulse_stats); "
                              f"{getattr(backend, '__name__', backend)!r} has none")
-        self.obs_dim = _abi.OBS_DIM + (len(_abi.PULSE_OBS_NAMES) if self.pulse_stats else 0)
-        self.obs_names = _abi.OBS_NAMES + (_abi.PULSE_OBS_NAMES if self.pulse_stats else ())
+        self.signal_stats = bool(signal_stats)
+        if backend is not None and self.signal_stats and not hasattr(backend, "bind_signal_stats"):
+            raise ValueError(f"signal_stats=True needs a backend that tallies the interval's signals inside its step "
+                             f"(bind_signal_stats); {getattr(backend, '__name__', backend)!r} has none")
+        self.obs_names = _abi.OBS_NAMES + (_abi.PULSE_OBS_NAMES if self.pulse_stats else ()) + \
+            (_abi.SIGNAL_OBS_NAMES if self.signal_stats else ())
+        self.obs_dim = len(self.obs_names)
         if env_params is not None:
             if backend is not None and not hasattr(backend, "bind_env_params"):
                 raise ValueError(f"env_params needs a backend that reads per-environment physics rows (bind_env_params); "
@@ -297,7 +310,8 @@ class WireEDMEnv:
 
         # ---- state (caller-owned memory) + backend
         self.state = BatchedEDMState(self.num_envs, self.n_segments, self.obs_dim, self.device,
-                                     crater_log_capacity=int(crater_log_capacity), pulse_stats=self.pulse_stats)
+                                     crater_log_capacity=int(crater_log_capacity), pulse_stats=self.pulse_stats,
+                                     signal_stats=self.signal_stats)
         from ..utils.logger import dielectric_flow_rate
 
         base_flow = float(self.dielectric_params.base_flow_rate)
@@ -314,6 +328,8 @@ class WireEDMEnv:
             self._backend.bind_geometry(_abi.GeomPtrs(self._geom_f64.data_ptr(), self._geom_i32.data_ptr()))
         if self.pulse_stats:
             self._backend.bind_pulse_stats(self.state.pulse.data_ptr())
+        if self.signal_stats:
+            self._backend.bind_signal_stats(self.state.signal.data_ptr())
         # ---- per-environment physics parameters (include/wedm_hip.h, enum wedm_envp_field), optional
         self.env_param_names: Tuple[str, ...] = ()
         self._envp_src = self._envp_rows = None  # float64 [len(envp.NAMES), stride] user-facing / [ENVP_COUNT, stride] device
@@ -714,6 +730,7 @@ class WireEDMEnv:
         ``weights_only=True``)."""
         return {"abi_version": _abi.ABI_VERSION, "blocks": self.state.clone_blocks(), "seed": self._seed, "num_envs": self.num_envs,
                 "n_segments": self.n_segments, "env_id_offset": self.env_id_offset, "pulse_stats": self.pulse_stats,
+                "signal_stats": self.signal_stats,
                 "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint(),
                 **self._env_params_state(), **self._wire_material_state()}
 
@@ -738,6 +755,9 @@ class WireEDMEnv:
         if bool(sd.get("pulse_stats", False)) != self.pulse_stats:
             raise ValueError(f"checkpoint was taken with pulse_stats={bool(sd.get('pulse_stats', False))}, this environment has "
                              f"pulse_stats={self.pulse_stats}: the observation and the interval counts differ")
+        if bool(sd.get("signal_stats", False)) != self.signal_stats:
+            raise ValueError(f"checkpoint was taken with signal_stats={bool(sd.get('signal_stats', False))}, this environment "
+                             f"has signal_stats={self.signal_stats}: the observation and the interval sums differ")
         mine = list(self.env_param_names) if self._envp_rows is not None else None
         theirs = sd.get("env_param_names")
         if (list(theirs) if theirs is not None else None) != mine:
@@ -832,6 +852,27 @@ class WireEDMEnv:
         n = self.num_envs
         return {"spark_pulses": rows[P.SPARK_LAST, :n], "short_pulses": rows[P.SHORT_LAST, :n],
                 "short_steps": rows[P.SHORT_STEPS_LAST, :n]}
+
+    def get_signal_statistics(self) -> Dict[str, torch.Tensor]:
+        """What went into the gap over the last completed control interval, per environment, as the kernels published it at
+        its control step (float64; zeros until the first control step after a reset): ``samples`` = physics steps the
+        environment ran in the interval, ``current_sum`` [A], ``energy_sum`` [V A] and ``gap_sum`` [um] over them,
+        ``gap_min`` [um] and ``tmax_peak`` their extrema; ``mean_current``, ``mean_power`` and ``mean_gap`` = the sums
+        divided by ``samples`` (0 where there were none).  Needs ``signal_stats=True``."""
+        rows = self.state.signal
+        if rows is None:
+            raise RuntimeError("construct the environment with signal_stats=True to keep the interval's signal statistics")
+        S = _abi.SIG
+        n = self.num_envs
+        samples = rows[S.SAMPLES_LAST, :n]
+        out = {"samples": samples, "current_sum": rows[S.CURRENT_LAST, :n], "energy_sum": rows[S.ENERGY_LAST, :n],
+               "gap_sum": rows[S.GAP_LAST, :n], "gap_min": rows[S.GAP_MIN_LAST, :n], "tmax_peak": rows[S.TMAX_PEAK_LAST, :n]}
+        none = samples == 0
+        denom = torch.where(none, torch.ones_like(samples), samples)
+        zero = torch.zeros_like(samples)
+        for mean, total in (("mean_current", "current_sum"), ("mean_power", "energy_sum"), ("mean_gap", "gap_sum")):
+            out[mean] = torch.where(none, zero, out[total] / denom)
+        return out
 
     def get_crater_volumes(self, env_index: int) -> torch.Tensor:
         """`MaterialRemovalModule.crater_volumes_um3` (material.py:133) of one environment since its reset, oldest

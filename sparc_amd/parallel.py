@@ -65,7 +65,7 @@ class ShardedWireEDMEnv:
         self.device = self.env.device
         self.state = self.env.state
         # outputs are the rank-major concatenation of the inputs (the layout every backend accepts)
-        self.obs_dim = self.env.obs_dim  # (11 with pulse_stats=True)
+        self.obs_dim = self.env.obs_dim  # (11 with pulse_stats=True, five more with signal_stats=True: both go through env_kwargs)
         self._obs_all = torch.empty((self.world_size * self.obs_dim, self.num_envs), dtype=torch.float32,
                                     device=self.device)
         self._done_all = torch.empty((self.world_size * self.num_envs,), dtype=torch.uint8, device=self.device)

@@ -1,12 +1,12 @@
 #!/usr/bin/env python
 """Per-kernel register / scratch / LDS usage of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage), compiled as
-the build compiles it: the five WEDM_PART translation units, in parallel.
+the build compiles it: the six WEDM_PART translation units, in parallel.
 
     python tools/kernel_resources.py [--tsv] [--out DIR] [extra hipcc flags...]
 
 --tsv      one line per instantiation, tab-separated and sorted by name: the mangled name, the demangled name and the eight
            columns.  Nothing is truncated, so two builds compare with a plain `diff`.
---out DIR  keep the objects there, in DIR/part0 ... part4 (with -save-temps=obj among the extra flags: the gfx950 assembly too)
+--out DIR  keep the objects there, in DIR/part0 ... part5 (with -save-temps=obj among the extra flags: the gfx950 assembly too)
 """
 import re
 import shutil
@@ -42,7 +42,7 @@ def compile_part(part):
     return subprocess.Popen(cmd, cwd=str(g.HIP_SRC.parent), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
 
 
-procs = [compile_part(part) for part in (1, 2, 0, 3, 4)]
+procs = [compile_part(part) for part in (1, 2, 0, 3, 4, 5)]
 rows, cur, failed = [], None, None
 for p in procs:
     err = p.communicate()[1]
