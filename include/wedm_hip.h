@@ -595,6 +595,22 @@ int32_t wedm_debug_math(int32_t kind, const double* a, const double* b, double* 
  * tests poison the LDS (1e30) before every test.                                                                  */
 int32_t wedm_debug_poison_lds(float value, void* stream);
 
+/* TEST HOOKS: which instantiation of a step kernel a launch ran.  The library compiles every step kernel in many
+ * instantiations -- (kernel number of wedm_set_kernel, lanes per environment, a set of form bits) -- and wedm_step picks one
+ * per launch from the handle's settings, the table geometry and the batch size.  wedm_last_kernel()'s string names the
+ * family and the bindings only; these three name the instantiation itself, so that a test can hold every one of them to
+ * the oracle.  Host code only: none of them launches anything.
+ *
+ * wedm_debug_registry: entry `index` (0-based) of the list of compiled instantiations -> *kernel (1..12), *lanes (0 for a
+ *   family without a lane count), *forms (the form bits).  index == -1: the number of entries -> *kernel (lanes and forms
+ *   may be NULL).  Any other index outside the list, or a NULL output: WEDM_ERR_BAD_ARG.  Needs no context and no device.
+ * wedm_debug_last_form: the entry the last wedm_step of `ctx` launched.  WEDM_ERR_BAD_ARG before the first launch.
+ * wedm_debug_form_name: the name of form bit `bit` (0 = "TRACE", 1 = "F64", ...) as the library's messages spell it;
+ *   "" for a bit number past the last form (or below 0).  A static string.                                            */
+int32_t wedm_debug_registry(int32_t index, int32_t* kernel, int32_t* lanes, uint32_t* forms);
+int32_t wedm_debug_last_form(wedm_ctx* ctx, int32_t* kernel, int32_t* lanes, uint32_t* forms);
+const char* wedm_debug_form_name(int32_t bit);
+
 #ifdef __cplusplus
 }
 #endif

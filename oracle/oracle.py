@@ -19,7 +19,7 @@ LIB_PATH = HERE / "libwedm_oracle.so"
 
 MATH_LIBM, MATH_PORTABLE = 0, 1
 STENCIL_F32, STENCIL_F64 = 0, 1
-RNG_PHILOX, RNG_REPLAY = 0, 1
+RNG_PHILOX, RNG_REPLAY, RNG_SLOTS = 0, 1, 2
 MAX_SEG = 4096
 
 _d, _i = C.c_double, C.c_int32
@@ -187,6 +187,8 @@ def lib() -> C.CDLL:
     L.wedm_oracle_step_batch_ex.restype = _i
     L.wedm_oracle_step_batch_wmat.argtypes = L.wedm_oracle_step_batch_ex.argtypes + [C.c_void_p]
     L.wedm_oracle_step_batch_wmat.restype = _i
+    L.wedm_oracle_step_batch_replay.argtypes = L.wedm_oracle_step_batch_wmat.argtypes + [C.c_void_p, C.c_int64]
+    L.wedm_oracle_step_batch_replay.restype = _i
     L.wedm_oracle_max_threads.restype = _i
     _lib = L
     return L

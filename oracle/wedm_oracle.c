@@ -222,10 +222,17 @@ static double rng_replay_next(wedm_oracle_env* env) {
     return r->replay[r->replay_pos++];
 }
 
+/* wedm_bind_rng_replay as the kernels read it: this step's variates by slot (enum wedm_replay_slot), whichever were drawn */
+static double rng_slot(wedm_oracle_env* env, int slot) {
+    env->rng.draws_this_step++;
+    return env->rng.replay[slot];
+}
+
 /* env.np_random.random(): slot 0 debris roll (ignition.py:233), 1 random-short roll
  * (ignition.py:239), 2 ignition roll (ignition.py:327) */
 static double rng_random(wedm_oracle_env* env, int slot) {
     if (env->rng.mode == WEDM_ORACLE_RNG_REPLAY) return rng_replay_next(env);
+    if (env->rng.mode == WEDM_ORACLE_RNG_SLOTS) return rng_slot(env, slot);
     env->rng.draws_this_step++;
     double u[4];
     wedm_oracle_step_uniforms(env->rng.seed, env->rng.env_id, env->rng.episode, (uint32_t)env->time, u);
@@ -235,6 +242,7 @@ static double rng_random(wedm_oracle_env* env, int slot) {
  * NumPy: low + (high - low) * next_double. */
 static double rng_uniform_y(wedm_oracle_env* env) {
     if (env->rng.mode == WEDM_ORACLE_RNG_REPLAY) return rng_replay_next(env);
+    if (env->rng.mode == WEDM_ORACLE_RNG_SLOTS) return rng_slot(env, WEDM_RS_SPARK_Y);
     env->rng.draws_this_step++;
     double u[4];
     wedm_oracle_step_uniforms(env->rng.seed, env->rng.env_id, env->rng.episode, (uint32_t)env->time, u);
@@ -243,6 +251,7 @@ static double rng_uniform_y(wedm_oracle_env* env) {
 /* env.np_random.normal(mean, std), material.py:127.  NumPy: loc + scale * z. */
 static double rng_normal(wedm_oracle_env* env, double mean, double std) {
     if (env->rng.mode == WEDM_ORACLE_RNG_REPLAY) return rng_replay_next(env);
+    if (env->rng.mode == WEDM_ORACLE_RNG_SLOTS) return rng_slot(env, WEDM_RS_CRATER_UM3);
     env->rng.draws_this_step++;
     double z = wedm_oracle_std_normal(env->rng.seed, env->rng.env_id, env->rng.episode,
                                       (uint32_t)env->time, NULL);
@@ -1236,6 +1245,15 @@ int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs*
                                     const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                     int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
                                     int32_t* pulse, const double* wmat_rows) {
+    return wedm_oracle_step_batch_replay(p, s, g, a, num_envs, n_seg_max, n_substeps, math_mode, stencil_mode, n_threads,
+                                         envp_rows, pulse, wmat_rows, NULL, 0);
+}
+
+int32_t wedm_oracle_step_batch_replay(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                      const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                      int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                      int32_t* pulse, const double* wmat_rows, const double* replay, int64_t replay_steps) {
+    if (replay && replay_steps < 1) return WEDM_ERR_BAD_ARG;
     if (!p || !s || !a || num_envs <= 0 || n_substeps < 0 || n_seg_max < 1) return WEDM_ERR_BAD_ARG;
     if (n_substeps == 0) return WEDM_OK;
     if (p->per_env_geometry && (!g || !g->f64 || !g->i32)) return WEDM_ERR_BAD_ARG;
@@ -1252,7 +1270,9 @@ int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs*
         consts_from_params(p, &v->c);
         v->math_mode = math_mode;
         v->stencil_mode = stencil_mode;
-        v->rng.mode = WEDM_ORACLE_RNG_PHILOX;
+        double slots[WEDM_REPLAY_SLOTS] = {0.0, 0.0, 0.0, 0.0, 0.0}; /* wedm_bind_rng_replay: the step's variates, by slot */
+        v->rng.mode = replay ? WEDM_ORACLE_RNG_SLOTS : WEDM_ORACLE_RNG_PHILOX;
+        v->rng.replay = replay ? slots : NULL;
         v->disable_ignition = p->disable_ignition;
 #ifdef _OPENMP
 #pragma omp for schedule(static)
@@ -1292,6 +1312,11 @@ int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs*
              * reference's step() would be (wire_edm.py:116-157 has no guard), DONE = `terminated` of the last step */
             for (int k = 0; k < n_substeps && (!done || p->keep_stepping_terminated); ++k) {
                 const int32_t prev = pulse ? pulse_kind(v) : 0; /* the previous sample: the state before the step */
+                if (replay) { /* wedm_bind_rng_replay: row `time / dt_us` of the table, the last one (and the error flag) past it */
+                    int64_t step = (int64_t)v->time / p->dt_us;
+                    if (step >= replay_steps) { v->error |= 1; step = replay_steps - 1; }
+                    for (int q = 0; q < WEDM_REPLAY_SLOTS; ++q) slots[q] = replay[(step * WEDM_REPLAY_SLOTS + q) * stride + e];
+                }
                 done = wedm_oracle_step(v, &act);
                 if (pulse) pulse_tally(p, s, pulse, e, v, prev);
                 if (v->last_ctrl_step) write_obs(p, s, e, v);

@@ -44,7 +44,8 @@ enum { WEDM_ORACLE_MATH_LIBM = 0, WEDM_ORACLE_MATH_PORTABLE = 1 };
  *        wire.py:58-123 (without fastmath re-association).  Reported, not pinned. */
 enum { WEDM_ORACLE_STENCIL_F32 = 0, WEDM_ORACLE_STENCIL_F64 = 1 };
 
-enum { WEDM_ORACLE_RNG_PHILOX = 0, WEDM_ORACLE_RNG_REPLAY = 1 };
+enum { WEDM_ORACLE_RNG_PHILOX = 0, WEDM_ORACLE_RNG_REPLAY = 1,
+       WEDM_ORACLE_RNG_SLOTS = 2 /* `replay` holds this step's WEDM_REPLAY_SLOTS variates, read by slot (wedm_bind_rng_replay) */ };
 
 /* Raw (un-derived) configuration: EnvironmentConfig + the five *ModuleParameters
  * + the brass row of data/wire_materials.json.                                  */
@@ -230,6 +231,14 @@ int32_t wedm_oracle_step_batch_wmat(const wedm_params* p, const wedm_state_ptrs*
                                     const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
                                     int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
                                     int32_t* pulse, const double* wmat_rows);
+/* wedm_oracle_step_batch_wmat with injected variates (HOST pointer or NULL; NULL is exactly wedm_oracle_step_batch_wmat):
+ *   replay     float64 [replay_steps][WEDM_REPLAY_SLOTS][stride], wedm_bind_rng_replay: at physics step time / dt_us
+ *              since the reset environment e reads its five variates by slot (enum wedm_replay_slot) instead of drawing
+ *              them from Philox; a step past the table reads the last row and sets WEDM_B_ERROR, as the kernel does. */
+int32_t wedm_oracle_step_batch_replay(const wedm_params* p, const wedm_state_ptrs* s, const wedm_geom_ptrs* g,
+                                      const wedm_action_ptrs* a, int32_t num_envs, int32_t n_seg_max, int32_t n_substeps,
+                                      int32_t math_mode, int32_t stencil_mode, int32_t n_threads, const double* envp_rows,
+                                      int32_t* pulse, const double* wmat_rows, const double* replay, int64_t replay_steps);
 int32_t wedm_oracle_max_threads(void);
 int64_t wedm_oracle_sizeof(int32_t which);
 

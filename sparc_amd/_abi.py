@@ -230,6 +230,43 @@ GEOM_I32_COUNT = 6
 
 REPLAY_SLOTS = 5  # enum wedm_replay_slot: debris roll, random-short roll, ignition roll, spark y [mm], crater volume [um^3]
 
+
+class KERNEL(enum.IntEnum):
+    """The kernel numbers of wedm_set_kernel (`enum Kernel` of sparc_amd/csrc/wedm_kernels.hip)."""
+    AUTO = 0
+    GLOBAL = 1
+    LANES_PK = 2
+    FUSED = 3
+    PACKED = 4
+    SPLIT = 5
+    STREAM = 6
+    REGS = 7
+    WIDE = 8
+    SERVED = 9
+    LANES = 10
+    LANES_SERVED = 11
+    REGS_SERVED = 12
+
+
+class FORM(enum.IntFlag):
+    """The form bits of a step kernel's instantiation (the `F_*` enum of sparc_amd/csrc/wedm_device.h), as
+    wedm_debug_registry and wedm_debug_last_form report them."""
+    TRACE = 1 << 0
+    F64 = 1 << 1
+    REPLAY = 1 << 2
+    PULSE = 1 << 3
+    ENVP = 1 << 4
+    MAT = 1 << 5
+    FROZEN_OK = 1 << 6
+    N1 = 1 << 7
+    EXTRA = 1 << 8
+    CUT = 1 << 9
+    ONE = 1 << 10
+    CMAX104 = 1 << 11
+    MINB2 = 1 << 12
+    SIG = 1 << 13
+
+
 OBS_DIM = 8
 OBS_NAMES = ("gap", "wire_velocity", "voltage", "current", "spark_state", "debris_density", "flow_rate", "tmax")
 

@@ -84,6 +84,12 @@ def load() -> C.CDLL:
     L.wedm_debug_math.restype = C.c_int32
     L.wedm_debug_poison_lds.argtypes = [C.c_float, C.c_void_p]
     L.wedm_debug_poison_lds.restype = C.c_int32
+    L.wedm_debug_registry.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    L.wedm_debug_registry.restype = C.c_int32
+    L.wedm_debug_last_form.argtypes = [ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
+    L.wedm_debug_last_form.restype = C.c_int32
+    L.wedm_debug_form_name.argtypes = [C.c_int32]
+    L.wedm_debug_form_name.restype = C.c_char_p
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -94,7 +100,25 @@ EXPORTS = (
     "wedm_abi_version", "wedm_create", "wedm_destroy", "wedm_bind_state", "wedm_bind_geometry",
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
+    "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name",
 )
+
+
+def registry() -> list:
+    """Every compiled instantiation of a step kernel as (kernel, lanes, forms), in the library's order
+    (`wedm_debug_registry`); needs no device."""
+    L = load()
+    k, lanes, forms = C.c_int32(), C.c_int32(), C.c_uint32()
+    rc = L.wedm_debug_registry(-1, C.byref(k), None, None)
+    if rc != _abi.OK:
+        raise WedmError(rc, "wedm_debug_registry(-1)")
+    out = []
+    for i in range(k.value):
+        rc = L.wedm_debug_registry(i, C.byref(k), C.byref(lanes), C.byref(forms))
+        if rc != _abi.OK:
+            raise WedmError(rc, f"wedm_debug_registry({i})")
+        out.append((k.value, lanes.value, forms.value))
+    return out
 
 
 def build_id() -> str:
@@ -209,6 +233,13 @@ class HipBackend:
 
     def last_kernel(self) -> str:
         return (self._L.wedm_last_kernel(self._ctx) or b"").decode()
+
+    def last_form(self) -> tuple:
+        """(kernel, lanes, forms) of the instantiation the last launch ran (`_abi.KERNEL`, lanes per environment,
+        `_abi.FORM` bits): `wedm_debug_last_form`."""
+        k, lanes, forms = C.c_int32(), C.c_int32(), C.c_uint32()
+        self._check(self._L.wedm_debug_last_form(self._ctx, C.byref(k), C.byref(lanes), C.byref(forms)))
+        return k.value, lanes.value, forms.value
 
     def last_occupancy(self) -> int:
         """Blocks per CU the occupancy API admits for the last launch's kernel, block size and LDS (diagnostic)."""

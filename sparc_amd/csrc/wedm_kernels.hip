@@ -61,8 +61,8 @@ using namespace wedm;
 #include "wedm_lanes2.h"
 
 // ------------------------------------------------------------ the registry of instantiations
-// Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are about 260,
-// which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file six times in
+// Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are 317
+// (wedm_debug_registry counts them), which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file six times in
 // parallel: -DWEDM_PART=N defines registry_partN(), which instantiates what it lists (1: the packed kernel, 2: the fused
 // kernel, 3: the served kernels and kernel 2's float32 forms, 4: the float64-typed forms of kernels 2, 6, 7 and 8 and the
 // PULSE forms of 7 and 8, 5: the SIG forms of kernels 1 and 2, 0: the rest); -DWEDM_PART=0 also holds the host code and the
@@ -228,12 +228,13 @@ static bool has_form(int32_t k, uint32_t form) {
         if (f.kernel == k && (f.forms & form)) return true;
     return false;
 }
+// the F_* bits' names, by bit number (wedm_debug_form_name hands them out: tests/test_registry_host.py ties them to the enum)
+static const char* const form_bit_names[] = {"TRACE", "F64", "REPLAY", "PULSE", "ENVP", "MAT", "FROZEN_OK",
+                                             "N1", "EXTRA", "CUT", "ONE", "CMAX104", "MINB2", "SIG"};
 static std::string form_names(uint32_t F) {
-    static const char* const names[] = {"TRACE", "F64", "REPLAY", "PULSE", "ENVP", "MAT", "FROZEN_OK",
-                                        "N1", "EXTRA", "CUT", "ONE", "CMAX104", "MINB2", "SIG"};
     std::string s;
-    for (int b = 0; b < (int)(sizeof(names) / sizeof(names[0])); ++b)
-        if ((F >> b) & 1u) s += (s.empty() ? "F_" : " | F_") + std::string(names[b]);
+    for (int b = 0; b < (int)(sizeof(form_bit_names) / sizeof(form_bit_names[0])); ++b)
+        if ((F >> b) & 1u) s += (s.empty() ? "F_" : " | F_") + std::string(form_bit_names[b]);
     return s.empty() ? "none" : s;
 }
 
@@ -359,6 +360,9 @@ struct LaunchPlan {
     size_t lds = 0;
     const WalkTable* walk = nullptr;
     char name[160] = {0};
+    // the registry entry `fn` is (wedm_debug_last_form)
+    int32_t kernel = 0, lanes = 0;
+    uint32_t forms = 0;
 };
 
 // What the planner knows of a walk table (wedm_create builds them; wedm_ctx::walk_dev holds the tables, same index).
@@ -932,6 +936,9 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
                   replay ? "[injected variates]" : f64 ? "[f64 stencil]" : fz ? "[frozen lanes ok]" : "", pulse ? "[pulse]" : "",
                   envp ? "[envp]" : "", mat ? "[wmat]" : "", sig ? "[sig]" : "", grid, block, lds_s);
     out.fn = fn;
+    out.kernel = ch.kernel;
+    out.lanes = L;
+    out.forms = F;
     out.grid = grid;
     out.block = block;
     out.lds = fl;
@@ -1321,6 +1328,33 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
         ctx->trace_us += n_substeps;
     }
     return WEDM_OK;
+}
+
+int32_t wedm_debug_registry(int32_t index, int32_t* kernel, int32_t* lanes, uint32_t* forms) {
+    const Slice& r = registry();
+    if (index == -1) {
+        if (!kernel) return WEDM_ERR_BAD_ARG;
+        *kernel = (int32_t)r.size();
+        return WEDM_OK;
+    }
+    if (index < 0 || index >= (int32_t)r.size() || !kernel || !lanes || !forms) return WEDM_ERR_BAD_ARG;
+    *kernel = r[index].kernel;
+    *lanes = r[index].lanes;
+    *forms = r[index].forms;
+    return WEDM_OK;
+}
+
+int32_t wedm_debug_last_form(wedm_ctx* ctx, int32_t* kernel, int32_t* lanes, uint32_t* forms) {
+    if (!ctx || !kernel || !lanes || !forms) return WEDM_ERR_BAD_ARG;
+    if (!ctx->last_plan) return fail(ctx, WEDM_ERR_BAD_ARG, "wedm_debug_last_form: no launch yet");
+    *kernel = ctx->last_plan->kernel;
+    *lanes = ctx->last_plan->lanes;
+    *forms = ctx->last_plan->forms;
+    return WEDM_OK;
+}
+
+const char* wedm_debug_form_name(int32_t bit) {
+    return bit >= 0 && bit < (int32_t)(sizeof(form_bit_names) / sizeof(form_bit_names[0])) ? form_bit_names[bit] : "";
 }
 
 int32_t wedm_debug_math(int32_t kind, const double* a, const double* b, double* out, int32_t n, void* stream) {

@@ -107,7 +107,7 @@ class OracleBackend:
         self._trace, self._trace_us, self._trace_count = desc, 0, 0
 
     def bind_rng_replay(self, table_ptr, n_steps):
-        raise NotImplementedError("the CPU seam replays recorded draws per environment through oracle.Env.rng (RNG_REPLAY)")
+        raise NotImplementedError("injected variates: OracleBackendRows (the plain seam draws from Philox only)")
 
     def trace_samples(self):
         return self._trace_count
@@ -124,8 +124,9 @@ class OracleBackend:
 
 class OracleBackendRows(OracleBackend):
     """`OracleBackend` with the C-ABI's three optional blocks: per-environment physics rows (wedm_bind_env_params), the
-    per-interval pulse tally (wedm_bind_pulse_stats) and per-environment wire material (wedm_bind_wire_material), stepped
-    by ``wedm_oracle_step_batch_wmat``.  The plain class keeps refusing all three (the host checks for the bind methods), so
+    per-interval pulse tally (wedm_bind_pulse_stats) and per-environment wire material (wedm_bind_wire_material), and with
+    injected variates (wedm_bind_rng_replay: the table read by step and slot, as the kernels read it), stepped by
+    ``wedm_oracle_step_batch_replay``.  The plain class keeps refusing all three (the host checks for the bind methods), so
     what it computes -- and what ``bench.py`` times -- is unchanged."""
 
     name = "oracle-rows"
@@ -133,6 +134,7 @@ class OracleBackendRows(OracleBackend):
     def __init__(self, params, num_envs, n_seg_max, device):
         super().__init__(params, num_envs, n_seg_max, device)
         self._envp, self._pulse, self._wmat = None, None, None
+        self._replay, self._replay_steps = None, 0
 
     def bind_env_params(self, rows_ptr):
         self._envp = rows_ptr
@@ -142,6 +144,9 @@ class OracleBackendRows(OracleBackend):
 
     def bind_wire_material(self, rows_ptr):
         self._wmat = rows_ptr
+
+    def bind_rng_replay(self, table_ptr, n_steps):
+        self._replay, self._replay_steps = table_ptr, (int(n_steps) if table_ptr else 0)
 
     def reset(self, mask_ptr, seed, reseed, fresh=False):
         super().reset(mask_ptr, seed, reseed, fresh)
@@ -156,12 +161,12 @@ class OracleBackendRows(OracleBackend):
 
     def _run(self, n_substeps, action):
         stencil = max(int(self.stencil_mode), int(self.params.stencil_mode))
-        rc = self._L.wedm_oracle_step_batch_wmat(C.byref(self.params), C.byref(self.state), C.byref(self.geom),
-                                                 C.byref(action), self.num_envs, self.n_seg_max, n_substeps,
-                                                 self.math_mode, stencil, self.n_threads, self._envp, self._pulse,
-                                                 self._wmat)
+        rc = self._L.wedm_oracle_step_batch_replay(C.byref(self.params), C.byref(self.state), C.byref(self.geom),
+                                                   C.byref(action), self.num_envs, self.n_seg_max, n_substeps,
+                                                   self.math_mode, stencil, self.n_threads, self._envp, self._pulse,
+                                                   self._wmat, self._replay, self._replay_steps)
         assert rc == 0, rc
 
     def last_kernel(self):
         return "oracle" + ("[pulse]" if self._pulse is not None else "") + ("[envp]" if self._envp is not None else "") + \
-            ("[wmat]" if self._wmat is not None else "")
+            ("[wmat]" if self._wmat is not None else "") + ("[injected variates]" if self._replay is not None else "")

@@ -283,3 +283,36 @@ def test_pulse_rows_are_cleared_by_a_reset_and_survive_a_plain_backend_refusal()
     for kw in (dict(pulse_stats=True), dict(env_params={"zeta": 0.5})):
         with pytest.raises(ValueError, match="backend"):
             WireEDMEnv(num_envs=4, device="cpu", backend=OracleBackend, **kw)
+
+
+def test_batch_seam_with_injected_variates_follows_the_reference_recording(golden_dir):
+    """The oracle side of wedm_bind_rng_replay (`wedm_oracle_step_batch_replay`: the table read by step and slot, as the
+    kernels read it) against the reference's own run: with the recorded NumPy PCG64 draws of fixture F1 as the table, every
+    environment of a batch equals the recording, ints at every checked step and floats wherever the fixture holds them, bit
+    for bit in the libm math mode.  This makes the oracle the checker of kernel 1's REPLAY forms
+    (tests/test_registry_coverage.py)."""
+    from oracle import oracle as orc
+    from tests._fixture_env import check_step, env_from_fixture
+    from tests._golden import Fixture, replay_table
+
+    class LibmRows(OracleBackendRows):
+        math_mode = orc.MATH_LIBM
+        n_threads = 1
+
+    fx = Fixture(golden_dir / "f1_config1_native.npz")
+    env = env_from_fixture(fx, 3, device="cpu", backend=LibmRows)
+    env.bind_rng_replay(replay_table(fx))
+    servo, tv, on, off, mode = fx.actions[0]
+    act = env.make_action(servo, tv, int(mode), on, off)
+    assert len(fx.actions) == 1 and int(fx.int_row("spark_state").max()) > 0
+    step = -1
+    for us in [1] + [7] * ((fx.n_steps - 1) // 7) + [(fx.n_steps - 1) % 7]:   # (the fixture holds the floats of steps 0, 7, 14, ...)
+        if us:
+            env.step_many(act, us)
+            step += us
+            for e in range(3):
+                check_step(env, fx, e, step, exact_floats=True)
+    assert step == fx.n_steps - 1 and env._backend.last_kernel() == "oracle[injected variates]"
+    assert not bool(env.state.error.any())
+    T = env.state.wire_temperature.numpy()[:, : fx.T_snaps.shape[1]]
+    assert all(np.array_equal(T[e], fx.T_snaps[-1]) for e in range(3))
