@@ -1,6 +1,10 @@
 // wedm_k_fused.h — wedm_step_fused<L>: uniform geometry, L lanes per environment, wire chunks in LDS, wave-uniform tile table.
 //
 // Included by wedm_kernels.hip (one translation unit per WEDM_PART; see the bottom of that file).
+// The walk itself -- per microsecond the halos, the patched cells, the tiles, the patches, the reduction over the environment's
+// lanes and the trace point -- is the text of wedm_fused_walk.inc, shared with wedm_step_stream; here are the kernel's frame
+// (staging, lifecycle, the lane's tile flags gathered from the walk table) and its own pieces of the walk: the stencil's two
+// typings, the tail cells, the one-change tiles' test and the instrumentation.
 #pragma once
 
 // ===================================================== fused kernel, L lanes / env
@@ -22,6 +26,65 @@ __device__ __forceinline__ float interior_cell(float tm1, float tc, float tp1, f
     return tc + d * tuf;
 }
 
+// This kernel's pieces of the walk, expanded by wedm_fused_walk.inc where it uses them (its head says what each has to do).
+#define WEDM_FUSED_WALK_CELLWISE all_slow
+// one cell by the full predicated formula / one interior cell, in the stencil's typing: the kernel's lambdas cell_full / cell_interior
+#define WEDM_FUSED_WALK_FULL_CELL(i, tm, tc, tp) cell_full(i, tm, tc, tp, cf, ps)
+#define WEDM_FUSED_WALK_INTERIOR_CELL(tp, zone, contacts, conv, jfe)      \
+    (F64 ? cell_interior(tm1, tc, tp, zone, contacts, cf, ps, jf_lane) \
+         : interior_cell<true>(tm1, tc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref))
+// Tail cells (see `tail` in the kernel): new values from OLD ones, before the walk; not on the predicated path, whose last
+// tile covers them.  Written behind the walk; bits per tail cell: valid (the cell exists) and interior (it counts for the
+// maximum and is not the wire's last cell, which the patch after it writes).
+#define WEDM_FUSED_WALK_TAILS_FROM_OLD()                                                                                          \
+    const bool use_tail = tail != 0 && !all_slow;                                                                                 \
+    float tt0 = 0.0f, tt1 = 0.0f;                                                                                                 \
+    if (use_tail) {                                                                                                               \
+        const float jfl = (cf.joule_on && !s.done) ? cf.jf : 0.0f;                                                                \
+        const int j0 = C - tail;                                                                                                  \
+        const float a0 = col[(j0 - 1) * 256], b0 = col[j0 * 256], c0 = col[(j0 + 1) * 256]; /* row C holds the right halo */      \
+        tt0 = interior_cell<true>(a0, b0, c0, g.k, g.tuf, (tail_bits & 1u) ? ps.conv_zone : ps.conv_base, tdiel, ps.adv,          \
+                                  (tail_bits & 2u) ? jfl : 0.0f, alpha, tref);                                                    \
+        if (tail == 2) {                                                                                                          \
+            const float c1 = col[(j0 + 2) * 256];                                                                                 \
+            tt1 = interior_cell<true>(b0, c0, c1, g.k, g.tuf, (tail_bits & 16u) ? ps.conv_zone : ps.conv_base, tdiel, ps.adv,     \
+                                      (tail_bits & 32u) ? jfl : 0.0f, alpha, tref);                                               \
+        }                                                                                                                         \
+    }                                                                                                                             \
+    const int n_walk = use_tail ? n_tiles - 1 : n_tiles
+#define WEDM_FUSED_WALK_BEFORE_PATCHES()                                                                    \
+    WEDM_STAMP(st2);                                                                                        \
+    if (use_tail && !s.done) {                                                                              \
+        if (tail_bits & 4u) { col[(C - tail) * 256] = tt0; tmax = fmax_gt(tmax, tt0); }                     \
+        if (tail == 2 && (tail_bits & 64u)) { col[(C - 1) * 256] = tt1; tmax = fmax_gt(tmax, tt1); }        \
+    }
+#define WEDM_FUSED_WALK_IS_ONECHANGE(t) (N1 && (((kind_n1 & ~slow_now) >> (t)) & 1u))
+#define WEDM_FUSED_WALK_TILE_B_OK true
+// (nothing leaves the LDS column during the walk: copy_wire writes the block back after the last microsecond)
+#define WEDM_FUSED_WALK_OUT_REGULAR() do { } while (0)
+#define WEDM_FUSED_WALK_OUT_B_DECL do { } while (0)
+#define WEDM_FUSED_WALK_OUT_B_CELL(u, v) do { } while (0)
+#define WEDM_FUSED_WALK_OUT_B() do { } while (0)
+#ifdef WEDM_ABL_NO_STENCIL
+#define WEDM_FUSED_WALK_MARK_TILES asm volatile("" ::"v"(cf.jf), "v"(cf.q), "v"(cf.pidx), "v"(ps.conv_base), "v"(ps.conv_zone), "v"(tpl), "v"(tlast))
+#else
+#define WEDM_FUSED_WALK_MARK_TILES do { } while (0)
+#endif
+#ifdef WEDM_STAMPS_TILES
+// (diagnostic buckets: regular tiles, boundary tiles, and -- in the third -- one-change tiles of the N1 instantiation together
+// with the predicated fallback)
+#define WEDM_FUSED_WALK_TILE_BEGIN \
+    WEDM_STAMP(tk0);               \
+    const int tkind = ((n_now >> t) & 1u) ? 0 : (WEDM_FUSED_WALK_IS_ONECHANGE(t) ? 2 : (!((slow_now >> t) & 1u) ? 1 : 2))
+#define WEDM_FUSED_WALK_TILE_END \
+    WEDM_STAMP(tk1);             \
+    if (tkind == 0) { accN += tk1 - tk0; ++cntN; } else if (tkind == 1) { accB += tk1 - tk0; ++cntB; } else { accS += tk1 - tk0; ++cntS; }
+#else
+#define WEDM_FUSED_WALK_TILE_BEGIN do { } while (0)
+#define WEDM_FUSED_WALK_TILE_END do { } while (0)
+#endif
+#define WEDM_FUSED_WALK_MARK_REDUCED WEDM_STAMP(st3)
+
 // Forms: F_TRACE; F_FROZEN_OK: see wedm_step_packed.  F_N1: the form for tile tables with a one-change tile that is a
 // boundary tile in every microsecond (4 096 x 400 over 16 lanes: the end of the workpiece zone falls inside tile 2 of 4):
 // +4.7 % there; the extra code costs tables without such a tile 1-1.5 %, so they run the form without it.
@@ -35,6 +98,11 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
     constexpr bool kFrozenOk = FROZEN_OK;
     // (the N1 form serves small batches with one wave per SIMD: 4 096 x 400 over 16 lanes)
     constexpr bool PREFETCH = N1 && !F64 && WEDM_PREFETCH_N1;
+#ifdef WEDM_ABL_NO_STENCIL
+    constexpr bool kWalkTiles = false;
+#else
+    constexpr bool kWalkTiles = true;
+#endif
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
     pin_hot_in_vgprs(hv);  // 178 -> 225 VGPRs, SGPR spill traffic in the loop 111 -> 37 instructions: +8 %
@@ -147,253 +215,7 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
         WEDM_STAMP(st1);
         freeze_wire(s);
 
-        // ---- halos: OLD neighbour values, read before any lane of this wave stores.  The right
-        // halo goes into the chunk's extra LDS row C, so cell C-1 is walked like any other.
-        const float halo_l = (c > 0) ? col[(C - 1) * 256 - 1] : spool;
-        const float halo_r = (c < L - 1) ? col[1] : 0.0f;
-        col[C * 256] = halo_r;
-
-        // a wave with a negative plasma heat (or, without FROZEN_OK, with a frozen environment) walks every cell on the
-        // predicated path; results are identical, only slower
-        const bool frozen_wave = FROZEN_OK && __any(s.done);
-        const bool all_slow = __any(cf.q < 0.0f) || (!FROZEN_OK && __any(s.done));
-        const uint32_t slow_now = all_slow ? 0xffffffffu : kind_s;
-        // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows
-        const uint32_t n_now = (kind_n | kind_ne | (__any(cf.joule_on && !s.done && cf.jf != 0.0f) ? 0u : kind_nj)) & ~(all_slow ? 0xffffffffu : 0u);
-
-        // ---- patched cells: the plasma cell and the wire's last cell are computed with the
-        // full predicated formula from OLD values now and written after the walk
-        const bool owns_pl = !s.done && cf.pidx >= 1 && cf.pidx >= cbase && cf.pidx < cbase + C;
-        float tpl = 0.0f, tlast = 0.0f;
-        if (__any(owns_pl)) {
-            if (owns_pl) {
-                const int jp = cf.pidx - cbase;
-                float tm = jp > 0 ? col[(jp - 1) * 256] : halo_l;
-                if (cf.pidx == 1) tm = spool;
-                const float tcc = col[jp * 256];
-                const float tp = jp < C - 1 ? col[(jp + 1) * 256] : halo_r;
-                tpl = cell_full(cf.pidx, tm, tcc, tp, cf, ps);
-            }
-        }
-        if (owns_last && !s.done) {
-            const int jl = n - 1 - cbase;
-            float tm = jl > 0 ? col[(jl - 1) * 256] : halo_l;
-            if (n - 1 == 1) tm = spool;
-            tlast = cell_full(n - 1, tm, col[jl * 256], 0.0f, cf, ps);
-        }
-
-        // ---- tail cells (see `tail`): new values from OLD ones, now; not on the predicated path, whose last tile covers them
-        const bool use_tail = tail != 0 && !all_slow;
-        float tt0 = 0.0f, tt1 = 0.0f;
-        if (use_tail) {
-            const float jfl = (cf.joule_on && !s.done) ? cf.jf : 0.0f;
-            const int j0 = C - tail;
-            const float a0 = col[(j0 - 1) * 256], b0 = col[j0 * 256], c0 = col[(j0 + 1) * 256];  // row C holds the right halo
-            tt0 = interior_cell<true>(a0, b0, c0, g.k, g.tuf, (tail_bits & 1u) ? ps.conv_zone : ps.conv_base, tdiel, ps.adv,
-                                      (tail_bits & 2u) ? jfl : 0.0f, alpha, tref);
-            if (tail == 2) {
-                const float c1 = col[(j0 + 2) * 256];
-                tt1 = interior_cell<true>(b0, c0, c1, g.k, g.tuf, (tail_bits & 16u) ? ps.conv_zone : ps.conv_base, tdiel, ps.adv,
-                                          (tail_bits & 32u) ? jfl : 0.0f, alpha, tref);
-            }
-        }
-        const int n_walk = use_tail ? n_tiles - 1 : n_tiles;
-
-        float tmax = spool;
-        float tm1 = halo_l;
-        float tc = col[0];
-#ifdef WEDM_ABL_NO_STENCIL
-        asm volatile("" ::"v"(cf.jf), "v"(cf.q), "v"(cf.pidx), "v"(ps.conv_base), "v"(ps.conv_zone), "v"(tpl), "v"(tlast));
-        if (false) {
-#else
-        {
-#endif
-            const float jf_lane = (cf.joule_on && !s.done) ? cf.jf : 0.0f;
-            const bool joule_wave = __any(jf_lane != 0.0f);
-
-            // tile t covers cells j = 8t..8t+7; cur[u] = OLD T[j+1+u]; `nxt` is loaded one tile ahead
-            // CLAMP = false: all eight rows exist (j + 8 <= C), one base address + immediate offsets
-            auto load8 = [&](auto clamp, float (&dst)[8], int j) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    int row = j + 1 + u;
-                    if (decltype(clamp)::value) row = row < C ? row : C;  // rows past the chunk are never used; row C is the halo
-                    dst[u] = col[row * 256];
-                }
-            };
-            auto tile = [&](auto frozen, int t, float (&cur)[8], float (&nxt)[8]) {
-                constexpr bool FROZEN = decltype(frozen)::value;  // the copy for a wave with frozen lanes: they do not store
-                const int j = 8 * t;
-                // PREFETCH (a lone wave per SIMD: nothing else hides the LDS round trip): the NEXT tile's eight rows are
-                // requested before this tile is computed -- rows this tile does not store (it stores j .. j + 7, they are
-                // j + 9 .. j + 16), so they are still the old values the explicit scheme needs
-                if (PREFETCH) { if (t + 1 < n_walk) load8(std::true_type{}, nxt, j + 8); }
-                else load8(std::true_type{}, cur, j);  // (an unclamped variant for full tiles pays in the packed kernel only)
-                const float conv_lo = ((zone_lo >> t) & 1u) ? ps.conv_zone : ps.conv_base;
-                const float jfe_lo = ((joule_lo >> t) & 1u) ? jf_lane : 0.0f;
-#ifdef WEDM_STAMPS_TILES
-                WEDM_STAMP(tk0);
-                // (diagnostic buckets: regular tiles, boundary tiles, and -- in the third -- one-change tiles of the N1
-                // instantiation together with the predicated fallback)
-                const int tkind = ((n_now >> t) & 1u) ? 0 : ((N1 && (((kind_n1 & ~slow_now) >> t) & 1u)) ? 2 : (!((slow_now >> t) & 1u) ? 1 : 2));
-#endif
-                if ((n_now >> t) & 1u) {
-                    float old[10], tn[8], cv[8], jv[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) old[u + 2] = cur[u];
-                    cv[0] = conv_lo; jv[0] = jfe_lo;
-                    if (joule_wave && __any(jfe_lo != 0.0f))
-                        tile8_staged<float, true, false>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    else
-                        tile8_staged<float, false, false>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    // the wire's end cells, where a regular tile holds one (kind_ne / kind_nj): cell 0 stays at the spool
-                    // temperature; the last cell is kept out of the maximum here and patched after the walk
-                    tn[0] = (c == 0 && t == 0) ? spool : tn[0];
-                    const float last_v = (owns_last && t == t_last) ? spool : tn[7];
-                    if (!FROZEN || !s.done) {
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) col[(j + u) * 256] = tn[u];
-                    }
-                    float m0 = fmax_gt(tn[0], tn[1]), m1 = fmax_gt(tn[2], tn[3]);
-                    m0 = fmax_gt(m0, fmax_gt(tn[4], tn[5]));
-                    m1 = fmax_gt(m1, fmax_gt(tn[6], last_v));
-                    tmax = fmax_gt(tmax, fmax_gt(m0, m1));
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else if (N1 && (((kind_n1 & ~slow_now) >> t) & 1u)) {
-                    // one flag change at `split`, nothing else irregular (end cells apart): stage-major with per-cell
-                    // coefficients, stores and maximum as in a regular tile
-                    const int split = (int)((split_pack[t >> 3] >> ((t & 7) * 4)) & 15u);
-                    const float conv_hi = ((zone_hi >> t) & 1u) ? ps.conv_zone : ps.conv_base;
-                    const float jfe_hi = ((joule_hi >> t) & 1u) ? jf_lane : 0.0f;
-                    float old[10], tn[8], cv[8], jv[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        old[u + 2] = cur[u];
-                        cv[u] = u < split ? conv_lo : conv_hi;
-                        jv[u] = u < split ? jfe_lo : jfe_hi;
-                    }
-                    if (joule_wave) tile8_staged<float, true, true>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    else tile8_staged<float, false, true>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    tn[0] = (c == 0 && t == 0) ? spool : tn[0];
-                    const float last_v = (owns_last && t == t_last) ? spool : tn[7];
-                    if (!FROZEN || !s.done) {
-#pragma unroll
-                        for (int u = 0; u < 8; ++u) col[(j + u) * 256] = tn[u];
-                    }
-                    float m0 = fmax_gt(tn[0], tn[1]), m1 = fmax_gt(tn[2], tn[3]);
-                    m0 = fmax_gt(m0, fmax_gt(tn[4], tn[5]));
-                    m1 = fmax_gt(m1, fmax_gt(tn[6], last_v));
-                    tmax = fmax_gt(tmax, fmax_gt(m0, m1));
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else if (!((slow_now >> t) & 1u)) {
-                    // TILE_B: interior formula everywhere, one flag change at `split`, boundary and
-                    // out-of-wire cells excluded from the max (they are patched / never read)
-                    const int split = (int)((split_pack[t >> 3] >> ((t & 7) * 4)) & 15u);
-                    const int cnt = (C - j) < 8 ? (C - j) : 8;
-                    const float conv_hi = ((zone_hi >> t) & 1u) ? ps.conv_zone : ps.conv_base;
-                    const float jfe_hi = ((joule_hi >> t) & 1u) ? jf_lane : 0.0f;
-                    const uint32_t im1 = (uint32_t)(cbase + j - 1);  // (i - 1) of the tile's first cell
-                    const uint32_t span = (uint32_t)(n - 3);         // interior <=> (i - 1) <= n - 3 (unsigned)
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (u < cnt) {
-                            const float conv = u < split ? conv_lo : conv_hi;
-                            const float jfe = u < split ? jfe_lo : jfe_hi;
-                            float tn;
-                            if (F64) tn = cell_interior(tm1, tc, cur[u], ((u < split ? zone_lo : zone_hi) >> t) & 1u,
-                                                        ((u < split ? joule_lo : joule_hi) >> t) & 1u, cf, ps, jf_lane);
-                            else tn = interior_cell<true>(tm1, tc, cur[u], g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                            if (!FROZEN || !s.done) col[(j + u) * 256] = tn;
-                            const bool inter = (n >= 3) && (im1 + (uint32_t)u <= span);
-                            tmax = inter ? fmax_gt(tmax, tn) : tmax;
-                            tm1 = tc;
-                            tc = cur[u];
-                        }
-                    }
-                } else {
-#pragma unroll 1
-                    for (int u = 0; u < 8; ++u) {
-                        const int jj = j + u;
-                        const uint32_t zj = wt->zj[jj], iv = wt->iv[jj];
-                        const bool zbit = (zj >> c) & 1u, jbit = (zj >> (16 + c)) & 1u;
-                        const bool inter = ((iv >> c) & 1u) && !all_slow;
-                        const bool valid = ((iv >> (16 + c)) & 1u) && !s.done;
-                        const float conv = zbit ? ps.conv_zone : ps.conv_base;
-                        const float jfe = jbit ? jf_lane : 0.0f;
-                        const float tp1 = cur[0];
-                        float tn = F64 ? cell_interior(tm1, tc, tp1, zbit, jbit, cf, ps, jf_lane)
-                                       : interior_cell<true>(tm1, tc, tp1, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                        if (!inter && valid) {  // boundary cells and irregular waves: predicated formula
-                            const int i = cbase + jj;
-                            tn = (i >= 1) ? cell_full(i, (i == 1) ? spool : tm1, tc, tp1, cf, ps) : spool;
-                        }
-                        if (valid) {
-                            col[jj * 256] = tn;
-                            tmax = fmax_gt(tmax, tn);
-                        }
-                        tm1 = tc;
-                        tc = tp1;
-                        // rotate the prefetch window (this fallback is rare; keep its code small)
-                        float* w = const_cast<float*>(&cur[0]);
-                        float first = w[0];
-#pragma unroll
-                        for (int q = 0; q < 7; ++q) w[q] = w[q + 1];
-                        w[7] = first;
-                    }
-                }
-#ifdef WEDM_STAMPS_TILES
-                WEDM_STAMP(tk1);
-                if (tkind == 0) { accN += tk1 - tk0; ++cntN; } else if (tkind == 1) { accB += tk1 - tk0; ++cntB; } else { accS += tk1 - tk0; ++cntS; }
-#endif
-            };
-            float bufA[8];
-            if (PREFETCH) {
-                float bufB[8];
-                load8(std::true_type{}, bufA, 0);
-                if (!FROZEN_OK || !frozen_wave) {
-                    for (int t = 0; t < n_walk; t += 2) {
-                        tile(std::false_type{}, t, bufA, bufB);
-                        if (t + 1 < n_walk) tile(std::false_type{}, t + 1, bufB, bufA);
-                    }
-                } else {
-                    for (int t = 0; t < n_walk; t += 2) {
-                        tile(std::true_type{}, t, bufA, bufB);
-                        if (t + 1 < n_walk) tile(std::true_type{}, t + 1, bufB, bufA);
-                    }
-                }
-            } else if (!FROZEN_OK || !frozen_wave) {
-                for (int t = 0; t < n_walk; ++t) tile(std::false_type{}, t, bufA, bufA);
-            } else {
-                for (int t = 0; t < n_walk; ++t) tile(std::true_type{}, t, bufA, bufA);
-            }
-        }
-        WEDM_STAMP(st2);
-        // ---- patches (after every store of the walk): tail cells, then boundary condition, last cell, plasma cell
-        if (use_tail && !s.done) {
-            // (valid: the cell exists; interior: it counts for the maximum and is not the wire's last cell, which the
-            // patch below writes)
-            if (tail_bits & 4u) { col[(C - tail) * 256] = tt0; tmax = fmax_gt(tmax, tt0); }
-            if (tail == 2 && (tail_bits & 64u)) { col[(C - 1) * 256] = tt1; tmax = fmax_gt(tmax, tt1); }
-        }
-        if (c == 0 && !s.done) col[0] = spool;
-        if (owns_last && !s.done) {
-            col[(n - 1 - cbase) * 256] = tlast;
-            tmax = fmax_gt(tmax, tlast);
-        }
-        if (owns_pl) {
-            col[(cf.pidx - cbase) * 256] = tpl;
-            tmax = fmax_gt(tmax, tpl);
-        }
-#pragma unroll
-        for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
-        WEDM_STAMP(st3);
-        env_end_us<F>(hv, cold, e, s, tmax, 0, c == 0);
-        WEDM_TRACE_POINT(k, it, e, s, c == 0,
-                         for (int j = 0; j < C && cbase + j < n; ++j) tT[(int64_t)(cbase + j) * tcnt] = col[j * 256]);
+#include "wedm_fused_walk.inc"
         WEDM_STAMP(st4);
         WEDM_STAMP_ACC();
     }
@@ -403,5 +225,18 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
     copy_wire<L, false>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
     env_close(k, cold, e, s, frozen0, live && c == 0);
 }
-
-
+#undef WEDM_FUSED_WALK_CELLWISE
+#undef WEDM_FUSED_WALK_FULL_CELL
+#undef WEDM_FUSED_WALK_INTERIOR_CELL
+#undef WEDM_FUSED_WALK_TAILS_FROM_OLD
+#undef WEDM_FUSED_WALK_BEFORE_PATCHES
+#undef WEDM_FUSED_WALK_IS_ONECHANGE
+#undef WEDM_FUSED_WALK_TILE_B_OK
+#undef WEDM_FUSED_WALK_OUT_REGULAR
+#undef WEDM_FUSED_WALK_OUT_B_DECL
+#undef WEDM_FUSED_WALK_OUT_B_CELL
+#undef WEDM_FUSED_WALK_OUT_B
+#undef WEDM_FUSED_WALK_MARK_TILES
+#undef WEDM_FUSED_WALK_TILE_BEGIN
+#undef WEDM_FUSED_WALK_TILE_END
+#undef WEDM_FUSED_WALK_MARK_REDUCED

@@ -1,6 +1,9 @@
 // wedm_k_stream.h — wedm_step_stream<L>: single microseconds (the reference's step() cadence), uniform geometry.
 //
 // Included by wedm_kernels.hip (one translation unit per WEDM_PART; see the bottom of that file).
+// The LDS walk of a microsecond (`rest`) is the text of wedm_fused_walk.inc, shared with wedm_step_fused; here are the kernel's
+// frame (the loads up front, the prelude, the register walk `rest_single`, the write-back and the split close) and its own
+// pieces of the walk: the tiles of a launch's last microsecond stored straight to global memory, and the float64 typing.
 #pragma once
 
 // ===================================================== stream kernel (1 us / launch, uniform geometry)
@@ -28,6 +31,54 @@
 // Every wave is its own pipeline, so the loads, arithmetic and stores of different waves overlap by themselves.
 #define WEDM_LDS __attribute__((address_space(3)))
 #define WEDM_GLOBAL __attribute__((address_space(1)))
+// This kernel's pieces of the walk, expanded by wedm_fused_walk.inc where it uses them (its head says what each has to do).
+// No frozen-lane copy of the tile code, no one-change tiles, no second buffer, no tail cells: a frozen lane makes the wave
+// all_slow, and in the float64 typing every tile is walked cell by cell (this path is the rare one there).
+#define WEDM_FUSED_WALK_CELLWISE (all_slow || F64)
+#define WEDM_FUSED_WALK_FULL_CELL(i, tm, tc, tp) rw_cell<F64>(i, n, tm, tc, tp, g, cf, ps, tref, alpha, tdiel, f64c, s.h_base, s.h_zone)
+#define WEDM_FUSED_WALK_INTERIOR_CELL(tp, zone, contacts, conv, jfe)                                                              \
+    (F64 ? cell_f64<true>(tm1, tc, tp, g.k64, g.tuf64, (double)((zone) ? s.h_zone : s.h_base) * g.a64, f64c.tdiel, ps.adv64,     \
+                          ((contacts) && jf_lane != 0.0f) ? cf.jf64 : 0.0, f64c.alpha, f64c.tref)                                 \
+         : interior_cell<true>(tm1, tc, tp, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref))
+#define WEDM_FUSED_WALK_TAILS_FROM_OLD() const int n_walk = n_tiles
+#define WEDM_FUSED_WALK_IS_ONECHANGE(t) false
+#define WEDM_FUSED_WALK_TILE_B_OK !F64
+// The launch's last microsecond: a regular tile also goes straight to global memory, two words; of a boundary tile every
+// cell that exists, except wire cell 0 (spool temperature, never rewritten) -- the cells patched after the walk are stored
+// again behind these (same lane, same address: in order).
+#define WEDM_FUSED_WALK_OUT_REGULAR()                                      \
+    if (last) {                                                            \
+        char* const Tw = (char*)cold->s.T;                                 \
+        const uint32_t off = offc + (uint32_t)(j >> 2) * rowb;             \
+        *(f4v*)(Tw + off) = f4v{tn[0], tn[1], tn[2], tn[3]};               \
+        *(f4v*)(Tw + off + rowb) = f4v{tn[4], tn[5], tn[6], tn[7]};        \
+        stored |= 1u << t;                                                 \
+    }
+#define WEDM_FUSED_WALK_OUT_B_DECL float tnv[8]
+#define WEDM_FUSED_WALK_OUT_B_CELL(u, v) tnv[u] = v
+#define WEDM_FUSED_WALK_OUT_B()                                                                                                   \
+    if (last) {                                                                                                                   \
+        char* const Tw = (char*)cold->s.T;                                                                                        \
+        const uint32_t offt = offc + (uint32_t)(j >> 2) * rowb;                                                                   \
+        if (no_ragged && cnt == 8) { /* every cell of every lane exists: two unconditional 16-byte stores */                      \
+            tnv[0] = (im1 == 0xffffffffu) ? spool : tnv[0]; /* wire cell 0 */                                                     \
+            *(f4v*)(Tw + offt) = f4v{tnv[0], tnv[1], tnv[2], tnv[3]};                                                             \
+            *(f4v*)(Tw + offt + rowb) = f4v{tnv[4], tnv[5], tnv[6], tnv[7]};                                                      \
+        } else {                                                                                                                  \
+            _Pragma("unroll") for (int u = 0; u < 8; ++u)                                                                         \
+                if (u < cnt && im1 + (uint32_t)u < (uint32_t)(n - 1)) *(float*)(Tw + offt + cell_off(u)) = tnv[u];                \
+        }                                                                                                                         \
+        stored |= 1u << t;                                                                                                        \
+    }
+// (the cells patched behind the walk, chunk-local, for the write-back after the launch's last microsecond)
+#define WEDM_FUSED_WALK_BEFORE_PATCHES()                     \
+    WEDM_S2_STAMP(3); /* walk done */                        \
+    patch0 = (owns_last && !s.done) ? n - 1 - cbase : -1;    \
+    patch1 = owns_pl ? cf.pidx - cbase : -1
+#define WEDM_FUSED_WALK_MARK_TILES do { } while (0)
+#define WEDM_FUSED_WALK_TILE_BEGIN do { } while (0)
+#define WEDM_FUSED_WALK_TILE_END do { } while (0)
+#define WEDM_FUSED_WALK_MARK_REDUCED do { } while (0)
 // Forms: F_TRACE;
 // F_ONE: the form for launches of exactly one microsecond (the host picks it; no loop over further microseconds,
 // and a walk out of registers for the waves that can take it: rest_single below)
@@ -40,6 +91,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     static_assert((F & ~(F_TRACE | F_ONE | F_CMAX104 | F_F64)) == 0, "forms of wedm_step_stream");
     constexpr bool TRACE = (F & F_TRACE) != 0, ONE = (F & F_ONE) != 0, F64 = (F & F_F64) != 0;
     constexpr int CMAX = (F & F_CMAX104) ? 104 : 64;
+    constexpr bool FROZEN_OK = false, PREFETCH = false, kWalkTiles = true;  // (what wedm_fused_walk.inc asks of its includer)
     static_assert(!F64 || (ONE && !TRACE), "the float64 typing exists for the single-microsecond instantiation only");
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
@@ -204,191 +256,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     auto rest = [&](const int it, Coef& cf) {
         const bool last = ONE || it + 1 == k.n_substeps;
         freeze_wire(s);
-        // ---- halos: OLD neighbour values, read before any lane of this wave stores.  The right
-        // halo goes into the chunk's extra LDS row C, so cell C-1 is walked like any other.
-        const float halo_l = (c > 0) ? col[(C - 1) * 256 - 1] : spool;
-        const float halo_r = (c < L - 1) ? col[1] : 0.0f;
-        col[C * 256] = halo_r;
-
-        // a wave with a frozen environment (or a negative plasma heat) walks every cell on the
-        // predicated path; results are identical, only slower
-        const bool all_slow = __any(cf.q < 0.0f) || __any(s.done);
-        const uint32_t slow_now = (all_slow || F64) ? 0xffffffffu : kind_s;  // (F64: this path is the rare one, every tile cell by cell)
-        // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows
-        const uint32_t n_now = (kind_n | kind_ne | (__any(cf.joule_on && !s.done && cf.jf != 0.0f) ? 0u : kind_nj)) & ~((all_slow || F64) ? 0xffffffffu : 0u);
-
-        // ---- patched cells: the plasma cell and the wire's last cell are computed with the
-        // full predicated formula from OLD values now and written after the walk
-        const bool owns_pl = !s.done && cf.pidx >= 1 && cf.pidx >= cbase && cf.pidx < cbase + C;
-        float tpl = 0.0f, tlast = 0.0f;
-        if (__any(owns_pl)) {
-            if (owns_pl) {
-                const int jp = cf.pidx - cbase;
-                float tm = jp > 0 ? col[(jp - 1) * 256] : halo_l;
-                if (cf.pidx == 1) tm = spool;
-                const float tcc = col[jp * 256];
-                const float tp = jp < C - 1 ? col[(jp + 1) * 256] : halo_r;
-                tpl = rw_cell<F64>(cf.pidx, n, tm, tcc, tp, g, cf, ps, tref, alpha, tdiel, f64c, s.h_base, s.h_zone);
-            }
-        }
-        if (owns_last && !s.done) {
-            const int jl = n - 1 - cbase;
-            float tm = jl > 0 ? col[(jl - 1) * 256] : halo_l;
-            if (n - 1 == 1) tm = spool;
-            tlast = rw_cell<F64>(n - 1, n, tm, col[jl * 256], 0.0f, g, cf, ps, tref, alpha, tdiel, f64c, s.h_base, s.h_zone);
-        }
-
-        float tmax = spool;
-        float tm1 = halo_l;
-        float tc = col[0];
-        {
-            const float jf_lane = (cf.joule_on && !s.done) ? cf.jf : 0.0f;
-            const bool joule_wave = __any(jf_lane != 0.0f);
-
-            // tile t covers cells j = 8t..8t+7; cur[u] = OLD T[j+1+u]; `nxt` is loaded one tile ahead
-            // CLAMP = false: all eight rows exist (j + 8 <= C), one base address + immediate offsets
-            auto load8 = [&](auto clamp, float (&dst)[8], int j) {
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    int row = j + 1 + u;
-                    if (decltype(clamp)::value) row = row < C ? row : C;  // rows past the chunk are never used; row C is the halo
-                    dst[u] = col[row * 256];
-                }
-            };
-            auto tile = [&](int t, float (&cur)[8], float (&nxt)[8]) {
-                const int j = 8 * t;
-                (void)nxt;
-                load8(std::true_type{}, cur, j);  // (an unclamped variant for full tiles pays in the packed kernel only)
-                const float conv_lo = ((zone_lo >> t) & 1u) ? ps.conv_zone : ps.conv_base;
-                const float jfe_lo = ((joule_lo >> t) & 1u) ? jf_lane : 0.0f;
-                if ((n_now >> t) & 1u) {
-                    float old[10], tn[8], cv[8], jv[8];
-                    old[0] = tm1; old[1] = tc;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) old[u + 2] = cur[u];
-                    cv[0] = conv_lo; jv[0] = jfe_lo;
-                    if (joule_wave && __any(jfe_lo != 0.0f))
-                        tile8_staged<float, true, false>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    else
-                        tile8_staged<float, false, false>(old, tn, g.k, g.tuf, cv, tdiel, ps.adv, jv, alpha, tref);
-                    // the wire's end cells, where a regular tile holds one (kind_ne / kind_nj): cell 0 stays at the spool
-                    // temperature; the last cell is kept out of the maximum here and patched after the walk
-                    tn[0] = (c == 0 && t == 0) ? spool : tn[0];
-                    const float last_v = (owns_last && t == t_last) ? spool : tn[7];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) col[(j + u) * 256] = tn[u];
-                    if (last) {  // the launch's last microsecond: the tile also goes straight to global memory, two words
-                        char* const Tw = (char*)cold->s.T;
-                        const uint32_t off = offc + (uint32_t)(j >> 2) * rowb;
-                        *(f4v*)(Tw + off) = f4v{tn[0], tn[1], tn[2], tn[3]};
-                        *(f4v*)(Tw + off + rowb) = f4v{tn[4], tn[5], tn[6], tn[7]};
-                        stored |= 1u << t;
-                    }
-                    float m0 = fmax_gt(tn[0], tn[1]), m1 = fmax_gt(tn[2], tn[3]);
-                    m0 = fmax_gt(m0, fmax_gt(tn[4], tn[5]));
-                    m1 = fmax_gt(m1, fmax_gt(tn[6], last_v));
-                    tmax = fmax_gt(tmax, fmax_gt(m0, m1));
-                    tm1 = cur[6];
-                    tc = cur[7];
-                } else if (!F64 && !((slow_now >> t) & 1u)) {
-                    // TILE_B: interior formula everywhere, one flag change at `split`, boundary and
-                    // out-of-wire cells excluded from the max (they are patched / never read)
-                    const int split = (int)((split_pack[t >> 3] >> ((t & 7) * 4)) & 15u);
-                    const int cnt = (C - j) < 8 ? (C - j) : 8;
-                    const float conv_hi = ((zone_hi >> t) & 1u) ? ps.conv_zone : ps.conv_base;
-                    const float jfe_hi = ((joule_hi >> t) & 1u) ? jf_lane : 0.0f;
-                    const uint32_t im1 = (uint32_t)(cbase + j - 1);  // (i - 1) of the tile's first cell
-                    const uint32_t span = (uint32_t)(n - 3);         // interior <=> (i - 1) <= n - 3 (unsigned)
-                    float tnv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (u < cnt) {
-                            const float conv = u < split ? conv_lo : conv_hi;
-                            const float jfe = u < split ? jfe_lo : jfe_hi;
-                            float tn = interior_cell<true>(tm1, tc, cur[u], g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                            col[(j + u) * 256] = tn;
-                            tnv[u] = tn;
-                            const bool inter = (n >= 3) && (im1 + (uint32_t)u <= span);
-                            tmax = inter ? fmax_gt(tmax, tn) : tmax;
-                            tm1 = tc;
-                            tc = cur[u];
-                        }
-                    }
-                    if (last) {
-                        // the launch's last microsecond: every cell of the tile that exists, except wire cell 0
-                        // (spool temperature, never rewritten), goes straight to global memory; the cells patched
-                        // after the walk are stored again behind these (same lane, same address: in order)
-                        char* const Tw = (char*)cold->s.T;
-                        const uint32_t offt = offc + (uint32_t)(j >> 2) * rowb;
-                        if (no_ragged && cnt == 8) {  // every cell of every lane exists: two unconditional 16-byte stores
-                            tnv[0] = (im1 == 0xffffffffu) ? spool : tnv[0];  // wire cell 0
-                            *(f4v*)(Tw + offt) = f4v{tnv[0], tnv[1], tnv[2], tnv[3]};
-                            *(f4v*)(Tw + offt + rowb) = f4v{tnv[4], tnv[5], tnv[6], tnv[7]};
-                        } else {
-#pragma unroll
-                            for (int u = 0; u < 8; ++u)
-                                if (u < cnt && im1 + (uint32_t)u < (uint32_t)(n - 1)) *(float*)(Tw + offt + cell_off(u)) = tnv[u];
-                        }
-                        stored |= 1u << t;
-                    }
-                } else {
-#pragma unroll 1
-                    for (int u = 0; u < 8; ++u) {
-                        const int jj = j + u;
-                        const uint32_t zj = wt->zj[jj], iv = wt->iv[jj];
-                        const bool zbit = (zj >> c) & 1u, jbit = (zj >> (16 + c)) & 1u;
-                        const bool inter = ((iv >> c) & 1u) && !all_slow;
-                        const bool valid = ((iv >> (16 + c)) & 1u) && !s.done;
-                        const float conv = zbit ? ps.conv_zone : ps.conv_base;
-                        const float jfe = jbit ? jf_lane : 0.0f;
-                        const float tp1 = cur[0];
-                        float tn;
-                        if (F64)
-                            tn = cell_f64<true>(tm1, tc, tp1, g.k64, g.tuf64, (double)(zbit ? s.h_zone : s.h_base) * g.a64, f64c.tdiel, ps.adv64,
-                                                (jbit && jf_lane != 0.0f) ? cf.jf64 : 0.0, f64c.alpha, f64c.tref);
-                        else
-                            tn = interior_cell<true>(tm1, tc, tp1, g.k, g.tuf, conv, tdiel, ps.adv, jfe, alpha, tref);
-                        if (!inter && valid) {  // boundary cells and irregular waves: predicated formula
-                            const int i = cbase + jj;
-                            tn = (i >= 1) ? rw_cell<F64>(i, n, (i == 1) ? spool : tm1, tc, tp1, g, cf, ps, tref, alpha, tdiel, f64c, s.h_base, s.h_zone)
-                                          : spool;
-                        }
-                        if (valid) {
-                            col[jj * 256] = tn;
-                            tmax = fmax_gt(tmax, tn);
-                        }
-                        tm1 = tc;
-                        tc = tp1;
-                        // rotate the prefetch window (this fallback is rare; keep its code small)
-                        float* w = const_cast<float*>(&cur[0]);
-                        float first = w[0];
-#pragma unroll
-                        for (int q = 0; q < 7; ++q) w[q] = w[q + 1];
-                        w[7] = first;
-                    }
-                }
-            };
-            float bufA[8];
-            for (int t = 0; t < n_tiles; ++t) tile(t, bufA, bufA);
-        }
-        WEDM_S2_STAMP(3);  // walk done
-        // ---- patches (after every store of the walk): boundary condition, last cell, plasma cell
-        patch0 = (owns_last && !s.done) ? n - 1 - cbase : -1;
-        patch1 = owns_pl ? cf.pidx - cbase : -1;
-        if (c == 0 && !s.done) col[0] = spool;
-        if (owns_last && !s.done) {
-            col[(n - 1 - cbase) * 256] = tlast;
-            tmax = fmax_gt(tmax, tlast);
-        }
-        if (owns_pl) {
-            col[(cf.pidx - cbase) * 256] = tpl;
-            tmax = fmax_gt(tmax, tpl);
-        }
-#pragma unroll
-        for (int m = 1; m < L; m <<= 1) tmax = fmax_gt(tmax, __shfl_xor(tmax, m));
-        env_end_us<F>(hv, cold, e, s, tmax, 0, c == 0);
-        WEDM_TRACE_POINT(k, it, e, s, c == 0,
-                         for (int j = 0; j < C && cbase + j < n; ++j) tT[(int64_t)(cbase + j) * tcnt] = col[j * 256]);
+#include "wedm_fused_walk.inc"
     };
     // A launch of ONE microsecond (the reference's cadence) whose wave has nothing frozen and no tile on the predicated
     // path never reads a NEW temperature again, so the walk runs out of the registers the wire was loaded into: no LDS
@@ -616,5 +484,18 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     WEDM_S2_STAMP_VM(6);  // stores landed
     WEDM_S2_STAMP_OUT();
 }
-
-
+#undef WEDM_FUSED_WALK_CELLWISE
+#undef WEDM_FUSED_WALK_FULL_CELL
+#undef WEDM_FUSED_WALK_INTERIOR_CELL
+#undef WEDM_FUSED_WALK_TAILS_FROM_OLD
+#undef WEDM_FUSED_WALK_IS_ONECHANGE
+#undef WEDM_FUSED_WALK_TILE_B_OK
+#undef WEDM_FUSED_WALK_OUT_REGULAR
+#undef WEDM_FUSED_WALK_OUT_B_DECL
+#undef WEDM_FUSED_WALK_OUT_B_CELL
+#undef WEDM_FUSED_WALK_OUT_B
+#undef WEDM_FUSED_WALK_BEFORE_PATCHES
+#undef WEDM_FUSED_WALK_MARK_TILES
+#undef WEDM_FUSED_WALK_TILE_BEGIN
+#undef WEDM_FUSED_WALK_TILE_END
+#undef WEDM_FUSED_WALK_MARK_REDUCED

@@ -16,6 +16,8 @@
 //   wedm_k_lanes.h        wedm_step_lanes<L>: any geometry, cell by cell (kernel 10; stencil_mode 1)
 //   wedm_lanes2.h         wedm_step_lanes_pk<L>: any geometry, packed float32 walk (kernel 2: BASELINE config 5), and its served form
 //   wedm_k_fused.h        wedm_step_fused<L>: uniform geometry, wire chunks in LDS, wave-uniform tile table
+//   wedm_fused_walk.inc   the one-chunk LDS walk itself (one microsecond: halos, patched cells, tiles, patches, reduction, trace
+//                         point), included as text by wedm_step_fused and by the LDS walk of wedm_step_stream
 //   wedm_k_packed.h       wedm_step_packed<L>: the same with two virtual chunks per lane in float2 registers
 //   wedm_packed_walk.inc  the packed LDS walk itself (per-lane tile flags; one microsecond: halos, tiles, patches), included as
 //                         text by wedm_step_packed and by the walkers of wedm_step_served
