@@ -561,6 +561,13 @@ __device__ __forceinline__ float rw_cell(int i, int n_seg, float tm1, float tc, 
     } while (0)
 #define WEDM_STAMP_DECL unsigned long long st0 = 0, st1 = 0, st2 = 0, st3 = 0, st4 = 0, acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0, tk0 = 0, tk1 = 0, accN = 0, accB = 0, accS = 0, cntN = 0, cntB = 0, cntS = 0
 #define WEDM_STAMP_ACC() do { acc0 += st1 - st0; acc1 += st2 - st1; acc2 += st3 - st2; acc3 += st4 - st3; } while (0)
+// the register kernel: the four phases of the microseconds the quiet prelude handled, and in the second block's slots those of
+// the general path's (prelude, walk, reduction + epilogue; their number; the number of quiet ones) -- tools/stamps_regs.py
+#define WEDM_STAMP_ACC_SPLIT(quiet)                                                             \
+    do {                                                                                        \
+        if (quiet) { WEDM_STAMP_ACC(); ++cntS; }                                                \
+        else { accN += st1 - st0; accB += st2 - st1; accS += st4 - st2; ++cntN; }               \
+    } while (0)
 #define WEDM_STAMP_OUT()                                                                         \
     do {                                                                                         \
         if (k.dbg && (threadIdx.x & 63) == 0) {                                                  \
@@ -574,6 +581,7 @@ __device__ __forceinline__ float rw_cell(int i, int n_seg, float tm1, float tc, 
 #define WEDM_STAMP(var) do { } while (0)
 #define WEDM_STAMP_DECL do { } while (0)
 #define WEDM_STAMP_ACC() do { } while (0)
+#define WEDM_STAMP_ACC_SPLIT(quiet) do { } while (0)
 #define WEDM_STAMP_OUT() do { } while (0)
 #endif
 

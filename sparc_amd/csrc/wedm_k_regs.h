@@ -76,7 +76,18 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     }
     const int tid = threadIdx.x;
     const int c = tid % L;  // this lane's part of the wire
-    const int64_t e = (int64_t)blockIdx.x * EPB + tid / L;
+    int64_t e = (int64_t)blockIdx.x * EPB + tid / L;
+    // The same index from the wave's first environment (a scalar) and the lane's number in the wave: formed anew in every
+    // microsecond and after the loop, three instructions each time, instead of the index, the Philox word made of it and
+    // the wire's address held in registers through the launch -- five registers the two-lane form does not have (it kept
+    // the Philox word and the episode in scratch, and reloaded both at the head of every microsecond).
+    const uint32_t wave_env0 = __builtin_amdgcn_readfirstlane((uint32_t)e);
+    auto env_index = [&]() -> int64_t {
+        uint32_t all = ~0u;
+        asm volatile("" : "+s"(all));  // (opaque: or the lane's number is computed once and kept)
+        const uint32_t lane = __builtin_amdgcn_mbcnt_hi(all, __builtin_amdgcn_mbcnt_lo(all, 0u));
+        return (int64_t)(wave_env0 + lane / L);
+    };
     const bool live = e < k.num_envs;
     const bool writer = c == 0;
     const WalkTable* __restrict__ wt = k.walk;  // 2 L chunks of H cells
@@ -98,7 +109,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
     // the wire: word q = cells 4 q .. 4 q + 3 of this environment, 16 bytes per lane
     const int nq = (n + 3) >> 2;
-    float* const Te = cold->s.T + (live ? e : 0) * 4;
+    float* Te = cold->s.T + (live ? e : 0) * 4;
     const int q0 = base / 4;  // this lane's first word
     f2 P[H];
 #pragma unroll
@@ -125,22 +136,20 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
         s.ipk = peak_current(cold, s.mode, e);
         init_persist(k.hot, cold, e, s, ps);
     }
-    const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
 
     // tile flags of this lane's two chunks (bit t: the tile's first cell lies in the workpiece zone / between the contacts);
-    // wave-uniform with one lane per environment
+    // wave-uniform with one lane per environment.  The four masks share one register, a byte each (zone A, zone B, Joule A,
+    // Joule B): only the general prelude's build_conv and a busy walk read them.
+    static_assert(H / 8 <= 8, "tile flags: a byte per mask");
     const int n_tiles = wt->n_tiles;
-    uint32_t zoneA = 0u, zoneB = 0u, jouleA = 0u, jouleB = 0u, joule_any = 0u;
+    uint32_t tile_flags = 0u, joule_any = 0u;
     for (int t = 0; t < n_tiles; ++t) {
         const uint32_t lo = wt->zj[8 * t];
-        zoneA |= ((lo >> (2 * c)) & 1u) << t;       zoneB |= ((lo >> (2 * c + 1)) & 1u) << t;
-        jouleA |= ((lo >> (16 + 2 * c)) & 1u) << t; jouleB |= ((lo >> (17 + 2 * c)) & 1u) << t;
+        tile_flags |= (((lo >> (2 * c)) & 1u) << t) | (((lo >> (2 * c + 1)) & 1u) << (8 + t));
+        tile_flags |= (((lo >> (16 + 2 * c)) & 1u) << (16 + t)) | (((lo >> (17 + 2 * c)) & 1u) << (24 + t));
         joule_any |= ((lo >> 16) != 0u ? 1u : 0u) << t;
     }
-    if (L == 1) {
-        zoneA = __builtin_amdgcn_readfirstlane(zoneA); zoneB = __builtin_amdgcn_readfirstlane(zoneB);
-        jouleA = __builtin_amdgcn_readfirstlane(jouleA); jouleB = __builtin_amdgcn_readfirstlane(jouleB);
-    }
+    if (L == 1) tile_flags = __builtin_amdgcn_readfirstlane(tile_flags);
     joule_any = __builtin_amdgcn_readfirstlane(joule_any);
     const uint32_t kind_n = __builtin_amdgcn_readfirstlane(wt->kind_n_mask);
     const uint32_t kind_ne = __builtin_amdgcn_readfirstlane(wt->kind_ne_mask), kind_nj = __builtin_amdgcn_readfirstlane(wt->kind_nj_mask);
@@ -154,18 +163,23 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     // the lane's coefficients (the quiet one never does).  F64: the float32 h_eff entries themselves (quad_f64 forms (double)h * A)
     f2 convp[H / 8];
     auto build_conv = [&]() {
+        const uint32_t zoneA = tile_flags & 0xFFu, zoneB = (tile_flags >> 8) & 0xFFu;
         const float cz = F64 ? s.h_zone : ps.conv_zone, cb = F64 ? s.h_base : ps.conv_base;
 #pragma unroll
         for (int t = 0; t < H / 8; ++t)
             convp[t] = f2{((zoneA >> t) & 1u) ? cz : cb, ((zoneB >> t) & 1u) ? cz : cb};
     };
     build_conv();
+    WEDM_STAMP_DECL;
     const bool tracing = WEDM_TRACING(k);
     int trace_next = k.trace_next, trace_slot = k.trace_slot;
     (void)trace_next; (void)trace_slot;
 
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
+        WEDM_STAMP(st0);
+        e = env_index();
+        const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
@@ -175,13 +189,15 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
             build_conv();
         }
         freeze_wire(s);
+        WEDM_STAMP(st1);
         const bool act = !s.done;
         float tmax = spool;
         // (what the rare code of a tile derives from these -- a lane mask per uniform predicate, one per tile or per cell
         // -- would otherwise be computed once before the loop and kept: a thousand scalar registers spilled into vector
         // lanes and read back on the hot path too.  Opaque per microsecond, the predicates are scalar compares where used.)
-        if (L == 1) asm volatile("" : "+s"(zoneA), "+s"(zoneB), "+s"(jouleA), "+s"(jouleB));
-        else asm volatile("" : "+v"(zoneA), "+v"(zoneB), "+v"(jouleA), "+v"(jouleB));
+        if (L == 1) asm volatile("" : "+s"(tile_flags));
+        else asm volatile("" : "+v"(tile_flags));
+        const uint32_t jouleA = (tile_flags >> 16) & 0xFFu, jouleB = tile_flags >> 24;
         Geom gw = g;  // (uniform geometry: the same in every lane)
         gw.n_seg = __builtin_amdgcn_readfirstlane(g.n_seg); gw.az_start = __builtin_amdgcn_readfirstlane(g.az_start);
         gw.az_end = __builtin_amdgcn_readfirstlane(g.az_end); gw.cb = __builtin_amdgcn_readfirstlane(g.cb);
@@ -203,13 +219,17 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
         }
         const float rw_h_base = s.h_base, rw_h_zone = s.h_zone;  // (the predicated float64-typed cell reads the entries themselves)
 #include "wedm_regs_walk.inc"
+        WEDM_STAMP(st2);
         if (L == 2) tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
         unfreeze_wire(hv, s);
+        WEDM_STAMP(st3);
         if (!s.done) {
             scalar_epilogue(hv, s, tmax);
             pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, writer);
             if (s.ctrl) control_step_outputs(cold, e, s, writer);
         }
+        WEDM_STAMP(st4);
+        WEDM_STAMP_ACC_SPLIT(was_quiet);
         WEDM_TRACE_POINT(k, it, e, s, writer,
                          // (unrolled: a register file has no dynamic index; two running pointers made opaque after every pair,
                          // or the 2 H addresses are all computed up front and kept: 244 spilled registers in the two-lane form)
@@ -223,7 +243,10 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
                              asm volatile("" : "+v"(pa), "+v"(pb));
                          });
     }
+    WEDM_STAMP_OUT();
 
+    e = env_index();
+    Te = cold->s.T + (live ? e : 0) * 4;
     if (live) {
 #pragma unroll
         for (int q = 0; q < 2 * H / 4; ++q) {

@@ -7,22 +7,38 @@
 // is live) and the running maximum `tmax`; kF64 (the stencil's typing: rw_quad / rw_cell of wedm_common.h), f64c and
 // rw_h_base / rw_h_zone (read by the float64 typing only).
         if (act) {  // (the lanes of terminated environments sit the walk out: their registers stay)
-            // a wave with a negative plasma heat walks every cell on the predicated formula (identical results, slower)
-            const bool all_slow = __any(cf.q < 0.0f);
-            // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows
-            const float jf_lane = cf.joule_on ? (kF64 ? 1.0f : cf.jf) : 0.0f;  // (float64 typing: a flag, the factor is cf.jf64)
-            const bool joule_wave = __any(jf_lane != 0.0f);
-            const uint32_t n_now = all_slow ? 0u : (kind_n | kind_ne | (joule_wave ? 0u : kind_nj));
-            // the tiles that hold some lane's plasma cell (a lane's own cells only)
-            const int pcell = (cf.pidx >= 1 && cf.pidx >= base && cf.pidx < base + 2 * H) ? cf.pidx - base : -1;  // lane-local
+            // PLAIN: no lane of the wave carries current or a plasma heat in this microsecond (the ordinary one; cf is null in
+            // every lane): no Joule term, no plasma cell, and which tiles need more than the regular code is a constant of
+            // the launch -- formed once, as a scalar, and opaque per microsecond (or it is hoisted as per-tile predicates and
+            // kept).  Only a busy wave derives the masks from cf.  One tile text serves both: a second copy of the walk for
+            // PLAIN waves sends the allocator from 100 to 370 bytes of scratch per lane in wedm_step_regs<2>.
+            uint32_t n_now = __builtin_amdgcn_readfirstlane(kind_n | kind_ne | kind_nj);
+            uint32_t general = __builtin_amdgcn_readfirstlane(~(kind_n | kind_ne | kind_nj) | last_tile);
+            asm volatile("" : "+s"(n_now), "+s"(general));
+            bool all_slow = false, joule_wave = false;
+            float jf_lane = 0.0f;
+            int pcell = -1;
             uint32_t ptiles = 0u;
-            if (__any(pcell >= 0)) {
-                const int pt = pcell >= 0 ? ((pcell & (H - 1)) >> 3) : -1;
+#ifndef WEDM_REGS_WALK_NO_PLAIN  // (A/B: every microsecond on the busy entry, the walk as it was before the PLAIN one)
+            if (__any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f))
+#endif
+            {
+                // a wave with a negative plasma heat walks every cell on the predicated formula (identical results, slower)
+                all_slow = __any(cf.q < 0.0f);
+                // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows
+                jf_lane = cf.joule_on ? (kF64 ? 1.0f : cf.jf) : 0.0f;  // (float64 typing: a flag, the factor is cf.jf64)
+                joule_wave = __any(jf_lane != 0.0f);
+                n_now = all_slow ? 0u : (kind_n | kind_ne | (joule_wave ? 0u : kind_nj));
+                // the tiles that hold some lane's plasma cell (a lane's own cells only)
+                pcell = (cf.pidx >= 1 && cf.pidx >= base && cf.pidx < base + 2 * H) ? cf.pidx - base : -1;  // lane-local
+                if (__any(pcell >= 0)) {
+                    const int pt = pcell >= 0 ? ((pcell & (H - 1)) >> 3) : -1;
 #pragma unroll
-                for (int t = 0; t < H / 8; ++t) ptiles |= __any(pt == t) ? (1u << t) : 0u;
+                    for (int t = 0; t < H / 8; ++t) ptiles |= __any(pt == t) ? (1u << t) : 0u;
+                }
+                // tiles that need more than the regular code without a Joule term
+                general = ~n_now | (joule_wave ? joule_any : 0u) | ptiles | last_tile;
             }
-            // tiles that need more than the regular code without a Joule term
-            const uint32_t general = ~n_now | (joule_wave ? joule_any : 0u) | ptiles | last_tile;
             f2 leftp = f2{halo_l, a_last};  // OLD pair before the tile
 #pragma unroll
             for (int t = 0; t < H / 8; ++t) {

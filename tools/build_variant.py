@@ -3,7 +3,7 @@
 
     python tools/build_variant.py W8 -DWEDM_STAGE_W=8      ->  build/ablate/libwedm_W8.so
 
-Same three-translation-unit parallel build as __graft_entry__.build_hip(); load it with WEDM_HIP_LIB=<path>
+Same six-translation-unit parallel build as __graft_entry__.build_hip(); load it with WEDM_HIP_LIB=<path>
 (tools/ab_*.sh alternate between the in-tree library and such variants on one box)."""
 import subprocess
 import sys
@@ -27,7 +27,7 @@ obj_dir.mkdir(parents=True, exist_ok=True)
 out.parent.mkdir(parents=True, exist_ok=True)
 flags = [f for f in g.HIPCC_FLAGS if f != "-shared"] + ["-w", f'-DWEDM_BUILD_ID="{g.kernel_build_id()}+{tag}"'] + extra
 procs, objs = [], []
-for part in (1, 2, 0, 3, 4):
+for part in (1, 2, 0, 3, 4, 5):
     if only is not None and part != only:
         objs.append(ROOT / "build" / "obj" / f"wedm_kernels.part{part}.o")
         continue
