@@ -128,21 +128,11 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
     Geom g;
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     load_geom(k.hot, cold, live ? e : 0, g);
-    if (live) load_env(cold, e, s);
-    else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
+    WEDM_ENV_LOAD()
     float* col = lds + tid;
-    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all L lanes of the environment agree)
-    if (reinit) {
-        reinit_env(cold, e, s, c == 0);
-        for (int j = 0; j < C; ++j) col[j * 256] = k.hot.spool;
-    }
-    unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
-    const bool frozen0 = s.done;
-    WEDM_REPORT_FROZEN(frozen0 && live);
-    if (!s.done) {
-        s.ipk = peak_current(cold, s.mode, e);
-        init_persist(k.hot, cold, e, s, ps);
-    }
+    Sig none;  // (no F_SIG forms: nothing reads it)
+    WEDM_ENV_RESET(c == 0, none, for (int j = 0; j < C; ++j) col[j * 256] = k.hot.spool)
+    WEDM_ENV_START(const bool frozen0, WEDM_REPORT_FROZEN(frozen0 && live))
     const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
 
     const int cbase = c * C;

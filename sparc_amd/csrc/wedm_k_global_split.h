@@ -35,12 +35,9 @@ __global__ void __launch_bounds__(256) wedm_step_global(const KArgs k) {
     const GlobalT T = global_wire(cold->s.T, cold->s.stride, e);
     Sig sg;
     sig_load<SIG>(kernarg_sig(), cold, e, true, sg);
-    if (reinit) {  // next-step autoreset: wedm_reset for this environment, inside the launch
-        reinit_env(cold, e, s, true);
-        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, true);
-        sig_reinit<SIG>(kernarg_sig(), cold, e, true, sg);
-        for (int q = 0; q < WEDM_T_QUADS(k.n_seg_max); ++q) T.stq(q, f4v{k.hot.spool, k.hot.spool, k.hot.spool, k.hot.spool});
-    }
+    // next-step autoreset: wedm_reset for this environment, inside the launch
+    WEDM_ENV_RESET_UNDER(reinit, true, sg,
+                         for (int q = 0; q < WEDM_T_QUADS(k.n_seg_max); ++q) T.stq(q, f4v{k.hot.spool, k.hot.spool, k.hot.spool, k.hot.spool}))
     unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
     s.ipk = s.done ? 0.0 : peak_current(cold, s.mode, e);
     Geom g;
@@ -116,7 +113,7 @@ __global__ void __launch_bounds__(256) wedm_step_split(const KArgs k) {
     bool frozen0 = true;
     if (c == 0) {
         env_open<F>(cold, e, live, true, s);  // (the same `reinit`)
-        frozen0 = env_start<F>(k.hot, cold, e, s, ps);
+        frozen0 = env_start<F>(k, cold, e, s, ps);
     }
     int trace_next = k.trace_next, trace_slot = k.trace_slot;
     (void)trace_next; (void)trace_slot;

@@ -34,6 +34,53 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 }
 
 
+// ---- what the two register kernels do with their wire around the loop, written once as text that both expand (functions
+// moved their allocation: wedm_lifecycle.h).  The text names the kernel's H, F64, k, cold, e, live, c, n, base, stride, g.
+// The float64 constants of the typing straight from the parameter block (uniform geometry: wave-uniform)
+#define WEDM_REGS_F64_CONSTS()                                                                                \
+    StencilF64 f64c{0.0, 0.0, 0.0};                                                                           \
+    if (F64) {                                                                                                \
+        const wedm_params* pp = cold->p;                                                                      \
+        f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature};                           \
+        g.k64 = pp->k_cond; g.tuf64 = pp->tuf; g.a64 = pp->a_surf;                                            \
+    }
+// The wire into P[]: word q = cells 4 q .. 4 q + 3 of this environment, 16 bytes per lane (q0: this lane's first word);
+// words past the wire's end: zeros (padding)
+#define WEDM_REGS_LOAD_WIRE()                                                                                 \
+    const int nq = (n + 3) >> 2;                                                                              \
+    float* Te = cold->s.T + (live ? e : 0) * 4;                                                               \
+    const int q0 = base / 4;                                                                                  \
+    f2 P[H];                                                                                                  \
+    _Pragma("unroll") for (int q = 0; q < H / 4; ++q) {                                                       \
+        const f4v a = (q0 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f}; \
+        const f4v b = (q0 + H / 4 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + H / 4 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f}; \
+        _Pragma("unroll") for (int u = 0; u < 4; ++u) P[4 * q + u] = f2{a[u], b[u]};                          \
+    }
+// The autoreset's wipe (after WEDM_ENV_RESET: the lanes of a reset environment take the spool temperature), and wire cell 0,
+// which is held at the spool temperature (wire.py:83)
+#define WEDM_REGS_WIPE_WIRE()                                                                                 \
+    if (__any(reinit)) {                                                                                      \
+        _Pragma("unroll") for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];                \
+    }                                                                                                         \
+    if (c == 0) P[0].x = spool;
+// P[] back into the wire's words at Te; the wire's last, partial word cell by cell: the cells past the end are padding and
+// keep their value
+#define WEDM_REGS_STORE_WIRE()                                                                                \
+    if (live) {                                                                                               \
+        _Pragma("unroll") for (int q = 0; q < 2 * H / 4; ++q) {                                               \
+            const int m = (q % (H / 4)) * 4;                                                                  \
+            const bool hi = q >= H / 4;                                                                       \
+            const f4v w = hi ? f4v{P[m].y, P[m + 1].y, P[m + 2].y, P[m + 3].y} : f4v{P[m].x, P[m + 1].x, P[m + 2].x, P[m + 3].x}; \
+            const int cell = base + 4 * q;                                                                    \
+            if (cell + 3 < n) {                                                                               \
+                *(f4v*)(Te + (int64_t)(q0 + q) * stride * 4) = w;                                             \
+            } else {                                                                                          \
+                _Pragma("unroll") for (int u = 0; u < 4; ++u)                                                 \
+                    if (cell + u < n) Te[(int64_t)(q0 + q) * stride * 4 + u] = w[u];                          \
+            }                                                                                                 \
+        }                                                                                                     \
+    }
+
 #ifndef WEDM_REGS_DENSE
 #define WEDM_REGS_DENSE WEDM_PACKED_DENSE  // the quiet line also carries sparks that keep burning or end (see WEDM_PACKED_DENSE)
 #endif
@@ -99,43 +146,14 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     Geom g;
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     load_geom(k.hot, cold, live ? e : 0, g);
-    StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) {  // (uniform geometry: the float64 constants of the typing straight from the parameter block, wave-uniform)
-        const wedm_params* pp = cold->p;
-        f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature};
-        g.k64 = pp->k_cond; g.tuf64 = pp->tuf; g.a64 = pp->a_surf;
-    }
-    if (live) load_env(cold, e, s);
-    else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
-    // the wire: word q = cells 4 q .. 4 q + 3 of this environment, 16 bytes per lane
-    const int nq = (n + 3) >> 2;
-    float* Te = cold->s.T + (live ? e : 0) * 4;
-    const int q0 = base / 4;  // this lane's first word
-    f2 P[H];
-#pragma unroll
-    for (int q = 0; q < H / 4; ++q) {
-        const f4v a = (q0 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-        const f4v b = (q0 + H / 4 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + H / 4 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) P[4 * q + u] = f2{a[u], b[u]};
-    }
+    WEDM_REGS_F64_CONSTS()
+    WEDM_ENV_LOAD()
+    WEDM_REGS_LOAD_WIRE()
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
-    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all lanes of the environment agree)
-    if (reinit) {
-        reinit_env(cold, e, s, writer);
-        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, writer);
-    }
-    if (__any(reinit)) {
-#pragma unroll
-        for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];
-    }
-    if (c == 0) P[0].x = spool;  // wire cell 0 is held at the spool temperature (wire.py:83)
-    unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
-    const bool frozen0 = s.done;
-    if (!s.done) {
-        s.ipk = peak_current(cold, s.mode, e);
-        init_persist(k.hot, cold, e, s, ps);
-    }
+    Sig none;  // (no F_SIG forms: nothing reads it)
+    WEDM_ENV_RESET(writer, none, )
+    WEDM_REGS_WIPE_WIRE()
+    WEDM_ENV_START(const bool frozen0, )
 
     // tile flags of this lane's two chunks (bit t: the tile's first cell lies in the workpiece zone / between the contacts);
     // wave-uniform with one lane per environment.  The four masks share one register, a byte each (zone A, zone B, Joule A,
@@ -221,13 +239,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
 #include "wedm_regs_walk.inc"
         WEDM_STAMP(st2);
         if (L == 2) tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
-        unfreeze_wire(hv, s);
-        WEDM_STAMP(st3);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, writer);
-            if (s.ctrl) control_step_outputs(cold, e, s, writer);
-        }
+        WEDM_ENV_END_US(hv, tmax, pk, writer, none, WEDM_STAMP(st3))
         WEDM_STAMP(st4);
         WEDM_STAMP_ACC_SPLIT(was_quiet);
         WEDM_TRACE_POINT(k, it, e, s, writer,
@@ -246,31 +258,9 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     WEDM_STAMP_OUT();
 
     e = env_index();
-    Te = cold->s.T + (live ? e : 0) * 4;
-    if (live) {
-#pragma unroll
-        for (int q = 0; q < 2 * H / 4; ++q) {
-            const int m = (q % (H / 4)) * 4;
-            const bool hi = q >= H / 4;
-            const f4v w = hi ? f4v{P[m].y, P[m + 1].y, P[m + 2].y, P[m + 3].y} : f4v{P[m].x, P[m + 1].x, P[m + 2].x, P[m + 3].x};
-            const int cell = base + 4 * q;
-            if (cell + 3 < n) {
-                *(f4v*)(Te + (int64_t)(q0 + q) * stride * 4) = w;
-            } else {  // the wire's last, partial word: the cells past the end are padding and keep their value
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (cell + u < n) Te[(int64_t)(q0 + q) * stride * 4 + u] = w[u];
-            }
-        }
-    }
-    if (live && writer) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    Te = cold->s.T + (live ? e : 0) * 4;  // (formed again from the index, like the index: not held through the loop)
+    WEDM_REGS_STORE_WIRE()
+    if (live && writer) { WEDM_ENV_CLOSE(frozen0) }
 }
 
 
@@ -353,43 +343,14 @@ __global__ void __launch_bounds__(256, wide_min_blocks(F)) wedm_step_regs_wide(c
     Geom g;
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     load_geom(k.hot, cold, live ? e : 0, g);
-    StencilF64 f64c{0.0, 0.0, 0.0};
-    if (F64) {  // (uniform geometry: the float64 constants of the typing straight from the parameter block)
-        const wedm_params* pp = cold->p;
-        f64c = StencilF64{pp->temp_ref, pp->alpha_rho, pp->dielectric_temperature};
-        g.k64 = pp->k_cond; g.tuf64 = pp->tuf; g.a64 = pp->a_surf;
-    }
-    if (live) load_env(cold, e, s);
-    else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
-    // the wire: word q = cells 4 q .. 4 q + 3 of this environment, 16 bytes per lane; words past the end: zeros (padding)
-    const int nq = (n + 3) >> 2;
-    float* const Te = cold->s.T + (live ? e : 0) * 4;
-    const int q0 = base / 4;  // this lane's first word
-    f2 P[H];
-#pragma unroll
-    for (int q = 0; q < H / 4; ++q) {
-        const f4v a = (q0 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-        const f4v b = (q0 + H / 4 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + H / 4 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) P[4 * q + u] = f2{a[u], b[u]};
-    }
+    WEDM_REGS_F64_CONSTS()
+    WEDM_ENV_LOAD()
+    WEDM_REGS_LOAD_WIRE()
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
-    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all lanes of the environment agree)
-    if (reinit) {
-        reinit_env(cold, e, s, writer);
-        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, writer);
-    }
-    if (__any(reinit)) {
-#pragma unroll
-        for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];
-    }
-    if (c == 0) P[0].x = spool;  // wire cell 0 is held at the spool temperature (wire.py:83)
-    unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
-    const bool frozen0 = s.done;
-    if (!s.done) {
-        s.ipk = peak_current(cold, s.mode, e);
-        init_persist(k.hot, cold, e, s, ps);
-    }
+    Sig none;  // (no F_SIG forms: nothing reads it)
+    WEDM_ENV_RESET(writer, none, )
+    WEDM_REGS_WIPE_WIRE()
+    WEDM_ENV_START(const bool frozen0, )
     const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
 
     // cells of this lane's two chunks that exist (0 .. H each), per-cell flags as bit masks (bit m: cell m of the chunk)
@@ -597,13 +558,7 @@ __global__ void __launch_bounds__(256, wide_min_blocks(F)) wedm_step_regs_wide(c
         tmax = fmax_gt(tmax, dpp_perm<0x4E>(tmax));   // quad_perm [2,3,0,1]
         if (L >= 8) tmax = fmax_gt(tmax, dpp_perm<0x141>(tmax));  // row_half_mirror
         if (L >= 16) tmax = fmax_gt(tmax, dpp_perm<0x140>(tmax)); // row_mirror
-        unfreeze_wire(hv, s);
-        WEDM_STAMP(st3);
-        if (!s.done) {
-            scalar_epilogue(hv, s, tmax);
-            pulse_tally<PULSE>(kernarg_pulse(), cold, e, s, pk, writer);
-            if (s.ctrl) control_step_outputs(cold, e, s, writer);
-        }
+        WEDM_ENV_END_US(hv, tmax, pk, writer, none, WEDM_STAMP(st3))
         WEDM_STAMP(st4);
         WEDM_STAMP_ACC();
         WEDM_TRACE_POINT(k, it, e, s, writer,
@@ -614,30 +569,8 @@ __global__ void __launch_bounds__(256, wide_min_blocks(F)) wedm_step_regs_wide(c
     }
     WEDM_STAMP_OUT();
 
-    if (live) {
-#pragma unroll
-        for (int q = 0; q < 2 * H / 4; ++q) {
-            const int m = (q % (H / 4)) * 4;
-            const bool hi = q >= H / 4;
-            const f4v w = hi ? f4v{P[m].y, P[m + 1].y, P[m + 2].y, P[m + 3].y} : f4v{P[m].x, P[m + 1].x, P[m + 2].x, P[m + 3].x};
-            const int cell = base + 4 * q;
-            if (cell + 3 < n) {
-                *(f4v*)(Te + (int64_t)(q0 + q) * stride * 4) = w;
-            } else {  // the wire's last, partial word: the cells past the end are padding and keep their value
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (cell + u < n) Te[(int64_t)(q0 + q) * stride * 4 + u] = w[u];
-            }
-        }
-    }
-    if (live && writer) {
-        if (WEDM_REWARD_ON(cold)) {
-            if (!frozen0) write_reward(cold, e, s);
-            else cold->s.reward[e] = 0.0f;  // a frozen environment earns nothing (not the previous launch's reward)
-        }
-        store_time_hi(cold, e, s, (uint32_t)k.n_substeps * (uint32_t)k.hot.dt_us);
-        store_env(cold, e, s);
-    }
+    WEDM_REGS_STORE_WIRE()
+    if (live && writer) { WEDM_ENV_CLOSE(frozen0) }
 }
 
 

@@ -8,8 +8,10 @@
 //   wedm_env_rows.h       which Env member holds which state row, when it is final, whether a step reads it and whether a
 //                         reference-semantics reset keeps it: the lists load_env / store_env / the trace are expanded from
 //   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors / copy_wire, tile_staged / quad_staged
-//   wedm_lifecycle.h      an environment's launch lifecycle as helpers: launch_hot, env_open / env_start, env_end_us /
-//                         env_step_done, env_close, stencil_f64_consts (the file's head says which family calls which)
+//   wedm_lifecycle.h      an environment's launch lifecycle, each part written once as text the kernels expand (WEDM_ENV_LOAD /
+//                         _RESET / _START, _END_US / _STEP_DONE, _CLOSE) and the helpers that wrap it (env_open / env_start,
+//                         env_end_us / env_step_done, env_close); launch_hot, stencil_f64_consts (the file's head says who
+//                         expands what)
 //   wedm_k_global_split.h wedm_step_global (in place in global memory; stencil_mode 1, injected variates, very long wires),
 //                         wedm_step_split (single microseconds where the stream kernel does not fit)
 //   wedm_k_stream.h       wedm_step_stream<L>: single microseconds (the reference's step() cadence), uniform geometry
@@ -25,6 +27,7 @@
 //                         environments on the fourth, one microsecond ahead (kernel 9: large batches of long wires)
 //   wedm_k_regs.h         wedm_step_regs<L> (the headline: the wire in the registers of two lanes per environment),
 //                         wedm_step_regs_wide<L> (4 / 8 / 16 lanes of a DPP row per environment: small batches)
+//                         and, as text (WEDM_REGS_*), what both and wedm_step_regs_served do with the wire around the loop
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*

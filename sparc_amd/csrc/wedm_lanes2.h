@@ -221,24 +221,13 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     Persist ps{0.0f, 0.0f, 0.0f, 0};
     load_geom(k.hot, cold, live ? e : 0, g);
     const StencilF64 f64c = stencil_f64_consts<F>(cold, e);
-    if (live) load_env(cold, e, s);
-    else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; }
+    WEDM_ENV_LOAD()
     float* col = lds + tid;
-    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset (all L lanes of the environment agree)
+    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // (before the accumulators' load: after it, the SIG forms' code moves)
     Sig sg;
     sig_load<SIG>(kernarg_sig(), cold, e, live, sg);
-    if (reinit) {
-        reinit_env(cold, e, s, c == 0);
-        pulse_reinit<PULSE>(kernarg_pulse(), cold, e, c == 0);
-        sig_reinit<SIG>(kernarg_sig(), cold, e, c == 0, sg);
-        for (int row = 0; row < R; ++row) col[row * 256] = k.hot.spool;
-    }
-    unfreeze_wire(k.hot, s);  // keep_stepping_terminated: the DONE row is `terminated` of the last step and freezes nothing
-    const bool frozen0 = s.done;
-    if (!s.done) {
-        s.ipk = peak_current(cold, s.mode, e);
-        init_persist<false, MAT>(k.hot, cold, e, s, ps);
-    }
+    WEDM_ENV_RESET_UNDER(reinit, c == 0, sg, for (int row = 0; row < R; ++row) col[row * 256] = k.hot.spool)
+    WEDM_ENV_START(const bool frozen0, )
     const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
     const int baseA = 2 * c * Cv, baseB = baseA + Cv;  // first wire cell of each virtual chunk
     const int n = g.n_seg;                              // this lane's environment

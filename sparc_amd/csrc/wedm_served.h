@@ -201,8 +201,9 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
     load_geom(k.hot, cold, live ? e : 0, g);
     if (live) load_env(cold, e, s);
     else { s.done = WEDM_DEAD_LANE; s.unwind = 0.0; s.h_base = 0.0f; s.h_zone = 0.0f; s.broken = 0; s.ctrl = 0; s.tmax = spool; s.tcrit = 0; }
-    const bool reinit = live && s.done && WEDM_AUTORESET(cold);  // next-step autoreset
-    if (reinit) reinit_env(cold, e, s, true);
+    constexpr uint32_t F = 0;  // (the served kernels have no bound-block forms)
+    Sig none;                  // (nothing reads it)
+    WEDM_ENV_RESET(true, none, )
     const bool frozen0 = s.done;
     if (!s.done) {
         s.ipk = peak_current(cold, s.mode, e);
@@ -522,27 +523,12 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
     const int64_t stride = cold->s.stride;
     const int base = c * 2 * H;  // this lane's first cell
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
-    // the wire first: word q = cells 4 q .. 4 q + 3 of this environment, 16 bytes per lane
-    const int nq = (n + 3) >> 2;
-    float* const Te = cold->s.T + (live ? e : 0) * 4;
-    const int q0 = base / 4;  // this lane's first word
-    f2 P[H];
-#pragma unroll
-    for (int q = 0; q < H / 4; ++q) {
-        const f4v a = (q0 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-        const f4v b = (q0 + H / 4 + q < nq) ? *(const f4v*)(Te + (int64_t)(q0 + H / 4 + q) * stride * 4) : f4v{0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int u = 0; u < 4; ++u) P[4 * q + u] = f2{a[u], b[u]};
-    }
+    WEDM_REGS_LOAD_WIRE()  // (the wire first)
     Geom g;
     load_geom(k.hot, cold, 0, g);  // uniform geometry
     // next-step autoreset: the environment's wire starts at the spool temperature (the scalar wave re-initialises the state)
     const bool reinit = live && WEDM_AUTORESET(cold) && cold->s.i8[(int64_t)WEDM_B_DONE * stride + e] != 0;
-    if (__any(reinit)) {
-#pragma unroll
-        for (int m = 0; m < H; ++m) P[m] = reinit ? f2{spool, spool} : P[m];
-    }
-    if (c == 0) P[0].x = spool;  // wire cell 0 is held at the spool temperature (wire.py:83)
+    WEDM_REGS_WIPE_WIRE()
     // tile flags of this lane's two chunks (bit t: the tile's first cell lies in the workpiece zone / between the contacts)
     const int n_tiles = wt->n_tiles;
     uint32_t zoneA = 0u, zoneB = 0u, jouleA = 0u, jouleB = 0u, joule_any = 0u;
@@ -608,21 +594,6 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
     WEDM_SV_LOOP_END();
     sv_stamps_out(svs, stamp_row);
 
-    if (live) {
-#pragma unroll
-        for (int q = 0; q < 2 * H / 4; ++q) {
-            const int m = (q % (H / 4)) * 4;
-            const bool hi = q >= H / 4;
-            const f4v w = hi ? f4v{P[m].y, P[m + 1].y, P[m + 2].y, P[m + 3].y} : f4v{P[m].x, P[m + 1].x, P[m + 2].x, P[m + 3].x};
-            const int cell = base + 4 * q;
-            if (cell + 3 < n) {
-                *(f4v*)(Te + (int64_t)(q0 + q) * stride * 4) = w;
-            } else {  // the wire's last, partial word: the cells past the end are padding and keep their value
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (cell + u < n) Te[(int64_t)(q0 + q) * stride * 4 + u] = w[u];
-            }
-        }
-    }
+    WEDM_REGS_STORE_WIRE()
     __syncthreads();  // (B)
 }
