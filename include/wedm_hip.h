@@ -580,6 +580,49 @@ int64_t wedm_sizeof_params(void);
  * record it next to a kernel's name; nothing in the library depends on it.                                          */
 int32_t wedm_last_occupancy(wedm_ctx* ctx);
 
+/* ---------------------------------------------------- copying environments (snapshot, restore, fork)
+ * Every block of this ABI is [rows][stride] with the environment as the column, so moving the state of environment a into
+ * environment b -- or into a snapshot's block, or back -- is one operation on every block: column a of every row to
+ * column b.  A PLANE names one block on both sides of the copy.  The blocks map to planes like this:
+ *   T [WEDM_T_QUADS(n_seg_max)][stride][4]                              rows = WEDM_T_QUADS(n_seg_max), elem_bytes 16
+ *   f64, stats, crater_log, the signal block, env-param and wire-material rows   elem_bytes 8
+ *   i32, obs, reward, the pulse block                                   elem_bytes 4
+ *   i8                                                                  elem_bytes 1
+ * Strides are in elements of elem_bytes.  src_cols / dst_cols are the columns that may be named on either side (num_envs
+ * of an environment's block, not its stride: the padding columns are not environments).
+ * Not state, and so no plane of any caller in this repository: a bound trace ring, the replay table, the geometry rows
+ * (height and diameter belong to the slot, not to what is being simulated in it).                                   */
+#define WEDM_COPY_MAX_PLANES 16
+typedef struct wedm_copy_plane {
+    const void* src;     /* first row of the source block                                   */
+    void* dst;           /* first row of the destination block (may be the same memory)     */
+    int32_t rows;        /* rows of both blocks, >= 0                                       */
+    int32_t elem_bytes;  /* 1, 4, 8 or 16; both base pointers are aligned to it             */
+    int64_t src_stride;  /* elements from one row to the next, >= src_cols                  */
+    int64_t dst_stride;  /* elements from one row to the next, >= dst_cols                  */
+    int32_t src_cols;    /* valid source columns:      src_idx must lie in [0, src_cols)    */
+    int32_t dst_cols;    /* valid destination columns: dst_idx must lie in [0, dst_cols)    */
+} wedm_copy_plane;
+
+/* For every i in [0, count) and every plane: column src_idx[i] of each of the plane's rows is copied to column dst_idx[i],
+ * bit for bit (raw integer words: a NaN keeps its payload), in one launch on `stream` (more than 65 535 * 8 rows in all:
+ * several).  Stateless: no wedm_ctx, the device is the current one, every byte is the caller's -- planes may lie in one
+ * set of blocks (fork) or in two (snapshot, restore).  `planes` is HOST memory, read before the call returns; src_idx,
+ * dst_idx and status are device pointers.
+ * Bounds are checked on the device, because the index lists may be device data nobody has read: a pair with src_idx[i]
+ * outside [0, src_cols) or dst_idx[i] outside [0, dst_cols) of a plane copies nothing in that plane and ORs 1 into
+ * *status (status == NULL: it is skipped silently).  No index list, however wrong, makes the call read or write outside a
+ * plane's rows x columns; columns [cols, stride) are never written.
+ * count == 0 launches nothing and returns WEDM_OK.  WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)): planes NULL, n_planes
+ * outside [1, WEDM_COPY_MAX_PLANES], count < 0, a NULL index list with count > 0, an elem_bytes other than 1 / 4 / 8 / 16, a
+ * base pointer that is NULL or not aligned to elem_bytes, rows < 0, a negative column count, a stride smaller than its
+ * column count.
+ * PRECONDITION the call cannot check: where a plane's src and dst are the same memory, no destination index may equal a
+ * source index or another destination index (one source may feed many destinations).  Otherwise the named destination
+ * columns end up holding some source column's old or new value; nothing outside them is touched.                     */
+int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const int32_t* src_idx, const int32_t* dst_idx,
+                          int32_t count, int32_t* status, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

@@ -344,3 +344,15 @@ class TraceDesc(C.Structure):
         ("env_lo", C.c_int32), ("env_count", C.c_int32), ("every", C.c_int32), ("capacity", C.c_int32),
         ("reserved0", C.c_int32),
     ]
+
+
+COPY_MAX_PLANES = 16  # WEDM_COPY_MAX_PLANES
+
+
+class CopyPlane(C.Structure):
+    """``struct wedm_copy_plane``: one block on both sides of `wedm_copy_columns` (strides in elements)."""
+
+    _fields_ = [
+        ("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("elem_bytes", C.c_int32),
+        ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("src_cols", C.c_int32), ("dst_cols", C.c_int32),
+    ]

@@ -28,6 +28,8 @@
 //   wedm_k_regs.h         wedm_step_regs<L> (the headline: the wire in the registers of two lanes per environment),
 //                         wedm_step_regs_wide<L> (4 / 8 / 16 lanes of a DPP row per environment: small batches)
 //                         and, as text (WEDM_REGS_*), what both and wedm_step_regs_served do with the wire around the loop
+//   wedm_copy.h           wedm_copy_columns_kernel: environments' columns between or within caller-owned blocks (snapshot,
+//                         restore, fork); not a step kernel, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -64,6 +66,9 @@ using namespace wedm;
 #include "wedm_k_packed.h"
 #include "wedm_served.h"
 #include "wedm_lanes2.h"
+#if !defined(WEDM_PART) || WEDM_PART == 0
+#include "wedm_copy.h"
+#endif
 
 // ------------------------------------------------------------ the registry of instantiations
 // Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are 317
@@ -1331,6 +1336,49 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
         const int64_t every = ctx->trace.every;
         ctx->trace_count += (ctx->trace_us % every + n_substeps) / every;
         ctx->trace_us += n_substeps;
+    }
+    return WEDM_OK;
+}
+
+// No handle: the text of a refusal goes where wedm_create's goes (wedm_last_error(NULL)).
+int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const int32_t* src_idx, const int32_t* dst_idx,
+                          int32_t count, int32_t* status, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_copy_columns: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!planes || n_planes < 1 || n_planes > WEDM_COPY_MAX_PLANES)
+        return bad("null pointer or n_planes outside [1, " + std::to_string(WEDM_COPY_MAX_PLANES) + "]");
+    if (count < 0 || (count > 0 && (!src_idx || !dst_idx))) return bad("negative count or null index list");
+    wedm_copy_args a;
+    std::memset(&a, 0, sizeof(a));
+    int64_t items = 0;
+    for (int32_t k = 0; k < n_planes; ++k) {
+        const wedm_copy_plane& pl = planes[k];
+        const std::string who = "plane " + std::to_string(k) + ": ";
+        const int32_t w = pl.elem_bytes;
+        if (w != 1 && w != 4 && w != 8 && w != 16) return bad(who + "elem_bytes must be 1, 4, 8 or 16");
+        if (!pl.src || !pl.dst || (uintptr_t)pl.src % (uintptr_t)w || (uintptr_t)pl.dst % (uintptr_t)w)
+            return bad(who + "null base pointer or one not aligned to elem_bytes");
+        if (pl.rows < 0 || pl.src_cols < 0 || pl.dst_cols < 0) return bad(who + "negative rows or column count");
+        if (pl.src_stride < pl.src_cols || pl.dst_stride < pl.dst_cols) return bad(who + "stride smaller than the column count");
+        a.plane[k] = pl;
+        items += (pl.rows + WEDM_COPY_ROWS - 1) / WEDM_COPY_ROWS;
+        if (items > INT32_MAX) return bad("more rows than one call can hold");
+        a.item_end[k] = (int32_t)items;
+    }
+    a.n_planes = n_planes;
+    if (count == 0 || items == 0) return WEDM_OK;
+    const int64_t max_y = 65535;
+    for (int64_t item0 = 0; item0 < items; item0 += max_y) {
+        a.item0 = (int32_t)item0;
+        const dim3 grid((uint32_t)(((int64_t)count + 255) / 256), (uint32_t)std::min(max_y, items - item0));
+        hipLaunchKernelGGL(wedm_copy_columns_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, src_idx, dst_idx, count, status);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            g_create_error = std::string("wedm_copy_columns: launch: ") + hipGetErrorString(e);
+            return WEDM_ERR_HIP;
+        }
     }
     return WEDM_OK;
 }

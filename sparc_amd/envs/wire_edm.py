@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import _abi
+from .. import snapshot as _snapshot
 from ..core import derive
 from ..core import env_params as envp
 from ..core.env_config import EnvironmentConfig
@@ -283,6 +284,7 @@ class WireEDMEnv:
         # ---- geometry: uniform (reference behaviour) or one (h, d) pair per environment
         stride = (self.num_envs + 63) // 64 * 64
         self.per_env_geometry = workpiece_height is not None or wire_diameter is not None or mat_index is not None
+        self._geom_hd = None  # float64 [2, num_envs]: each slot's (height, diameter), where they are not all the same
         if self.per_env_geometry:
             h = np.broadcast_to(np.asarray(self.config.workpiece_height if workpiece_height is None
                                            else _to_numpy(workpiece_height), dtype=np.float64), (self.num_envs,))
@@ -294,6 +296,8 @@ class WireEDMEnv:
             self._geom_f64 = torch.from_numpy(gf).to(self.device)
             self._geom_i32 = torch.from_numpy(gi).to(self.device)
             self.n_segments = n_seg_max
+            if (h != h[0]).any() or (d != d[0]).any():  # slots differ: `fork` / `restore` hold copies to equal pairs
+                self._geom_hd = np.stack([h, d])
             if mat_index is not None:
                 self._init_wire_material(h, d, mat_index, stride)
         else:
@@ -371,6 +375,8 @@ class WireEDMEnv:
         self._valid_modes_dev = torch.tensor([m in VALID_CRATER_MODES for m in range(MAX_MODE + 2)], dtype=torch.bool).to(self.device)
         self._step_out = None
         self._trace = None
+        # status word of `snapshot` / `restore` / `fork` with device-resident indices (sparc_amd.snapshot; `check_errors`)
+        self._copy_status = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._seed = int.from_bytes(os.urandom(8), "little")
         self.steps_since_reset = 0  # host-side count of physics steps since the last reset of ALL environments
         self._backend.reset(None, self._seed, True, fresh=True)  # fresh module objects, whatever `reset_semantics`
@@ -510,6 +516,17 @@ class WireEDMEnv:
             raise ValueError(f"environment {idx}: a current mode that has no crater data was latched / passed in a device "
                              f"tensor (material.py:108-113 raises at the first fresh spark with it). "
                              f"Available modes: {[f'I{m}' for m in VALID_CRATER_MODES]}")
+        status = int(self._copy_status.item())
+        if status:
+            self._copy_status.zero_()
+            what = [text for bit, text in ((_snapshot.STATUS_RANGE, "an environment or snapshot-column index out of range (that "
+                                            "pair was skipped)"),
+                                           (_snapshot.STATUS_OVERLAP, "a destination named twice, or a source among the "
+                                            "destinations (those environments hold one of the states copied into them)"))
+                    if status & bit]
+            raise ValueError("snapshot / restore / fork with indices in a device tensor: " + "; ".join(what)
+                             + ".  The indices were not read back when the copy was launched; this check reports and clears "
+                               "the flag")
 
     def set_kernel(self, variant: int, lanes: int = 0) -> None:
         """0 = auto, 1 = global-memory stencil, 2 = LDS predicated, 3 = LDS fused, 4 = LDS
@@ -685,8 +702,12 @@ class WireEDMEnv:
             if m.shape != (n,):
                 raise ValueError(f"mask must have one entry per environment ({n})")
             idx = torch.where(m, idx, self._wmat_index[:n])
-        cur = self._wmat_index
-        cur[:n].copy_(idx)
+        self._wmat_index[:n].copy_(idx)
+        self._select_wire_material_rows()
+
+    def _select_wire_material_rows(self) -> None:
+        """The geometry and material rows of the current material index, selected from the fixed per-material tables."""
+        n, cur = self.num_envs, self._wmat_index
         cur[n:].copy_(cur[n - 1: n].expand(cur.shape[0] - n))  # padding columns repeat the last environment
         for table, dst in ((self._wmat_geom_table, self._geom_f64), (self._wmat_table, self._wmat_rows)):
             dst.copy_(torch.gather(table, 0, cur.view(1, 1, -1).expand(1, table.shape[1], -1))[0])
@@ -790,6 +811,40 @@ class WireEDMEnv:
             self.set_wire_material(sd["wire_material_index"].numpy())
         self._seed = int(sd["seed"])
         self.steps_since_reset = int(sd["steps_since_reset"])
+
+    # ---- snapshot / restore / fork of environment subsets, on the device (sparc_amd.snapshot) ----
+    def snapshot(self, env_ids=None) -> "_snapshot.EnvSnapshot":
+        """Compact device copies of the state of the environments ``env_ids`` (default: all; a source may be named more
+        than once): their columns of every state block -- ``f64``, ``i32``, ``i8``, ``T``, ``obs``, ``stats``, ``reward``
+        and, where present, ``crater_log``, ``pulse``, ``signal`` -- with ``env_params=`` their parameter values and
+        derived rows, with ``wire_material=`` their material index; one launch, no temporaries.  Not in it: the trace
+        ring, the injected-variate table, ``steps_since_reset`` and the geometry (it belongs to the slot).
+        Indices are a Python sequence, a NumPy array or a tensor.  Host indices are checked here.  A device tensor is not
+        read back (its range is checked by the kernel and reported by `check_errors`), except on an environment whose
+        slots differ in ``(height, diameter)``, where every call reads the indices once (a synchronisation)."""
+        return _snapshot.snapshot(self, env_ids)
+
+    def restore(self, snap, env_ids=None, columns=None) -> None:
+        """Snapshot column ``columns[i]`` into environment ``env_ids[i]``.  Defaults: ``columns`` = ``0 .. len(env_ids) - 1``
+        (all of them without ``env_ids``), ``env_ids`` = the environments those columns were taken from.  Raises
+        ``ValueError`` for a snapshot of another ABI version, shape (segments, observation, crater-log capacity), block
+        set, physics fingerprint or material table, for indices out of range, a destination named twice, and a column
+        whose slot had another ``(height, diameter)`` than its destination.  With ``env_params=`` the parameter rows are
+        written, with ``wire_material=`` the material index, after which the rows are selected as `set_wire_material`
+        does.  A restore into the slot a column came from replays exactly (`fork` on the random stream).  Index forms
+        and their checks: see `snapshot`; for device tensors a duplicate destination is found on the device too."""
+        _snapshot.restore(self, snap, env_ids, columns)
+
+    def fork(self, src_ids, dst_ids) -> None:
+        """Environment ``dst_ids[i]`` becomes a copy of environment ``src_ids[i]``: in place, one launch, no temporaries,
+        the same blocks and rows as `snapshot` followed by `restore`.  One source may feed many destinations and a single
+        ``src_ids`` serves all; sources must not be among the destinations and destinations must be distinct
+        (``ValueError`` for host indices; for device tensors a flag that `check_errors` raises for).
+        The random stream: the Philox key and the episode are state and are copied; the counter also holds the SLOT's
+        global id (``env_id_offset`` + index), which is not.  A fork into another slot therefore continues with that
+        slot's own variates -- an independent sample of the same state, which is what shooting and tree search want --
+        while a restore into the slot the state came from replays bit for bit."""
+        _snapshot.fork(self, src_ids, dst_ids)
 
     def save_checkpoint(self, path) -> None:
         torch.save(self.state_dict(), path)

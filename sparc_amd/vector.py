@@ -159,6 +159,14 @@ class WireEDMVectorEnv:
         info["episode"] = self.episode_count
         return obs.clone(), reward, terminated, truncated, info
 
+    def fork(self, src, dst) -> None:
+        """`WireEDMEnv.fork`, and the adapter's own per-environment state with it: a destination is due for a reset
+        exactly if its source is."""
+        from .snapshot import fork_rows
+
+        self.env.fork(src, dst)
+        fork_rows(self._need_reset, src, dst)
+
     def close(self) -> None:
         self.env.close()
 
