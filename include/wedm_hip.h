@@ -623,6 +623,52 @@ typedef struct wedm_copy_plane {
 int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const int32_t* src_idx, const int32_t* dst_idx,
                           int32_t count, int32_t* status, void* stream);
 
+/* ---------------------------------------------------- the wire's temperature profile, per environment
+ * The wire is the largest piece of an environment's state; the observation carries one scalar of it (its maximum).  This call
+ * reduces every named environment's wire, whatever its geometry, in one launch without temporaries: the mean over the
+ * workpiece zone, the mean and the maximum over the wire, the hottest cell, and the wire pooled into `bins` bins (maximum
+ * and mean of each).  Let n be the environment's n_seg and t[0..n) its cells (t[s] = T[WEDM_T_INDEX(s, stride, env)]):
+ *   every MEAN is the float64 sum of the float32 cells, divided in float64 by the number of cells, rounded once to float32.
+ *     Finite temperatures in [1, 65536) are multiples of 2^-23, and at most 2^11 such values below 2^16 sum exactly in
+ *     float64 (16 + 11 + 23 = 50 bits): over such cells the ORDER OF THE SUM DOES NOT MATTER, every order gives the same
+ *     bits, and the kernel reduces across lanes and waves as it likes.  Outside that range (or past 2^11 cells per mean) the
+ *     order is unspecified;
+ *   ZONE_MEAN  the mean over [az_start, az_end) if 0 <= az_start < az_end <= n, else over the whole wire (wire.py:390-394);
+ *   WIRE_MEAN, WIRE_MAX  over [0, n);
+ *   HOT_CELL   the lowest index that holds the maximum, as float32;
+ *   bin b of B covers the cells [lo, hi), lo = floor(b * n / B), hi = max(lo + 1, floor((b + 1) * n / B)): for n >= B a
+ *     partition of the wire, for n < B nearest-cell replication; a bin is never empty and never reaches past n.
+ * A NaN cell makes the maxima and means it takes part in unspecified; it never makes the call read or write outside its
+ * blocks.  Cells past an environment's own n_seg (up to n_seg_max, and the last quad's padding) and the columns
+ * [num_envs, stride) of T never reach a result.                                                                       */
+#define WEDM_PROFILE_MAX_BINS 64
+enum wedm_profile_field { WEDM_PR_ZONE_MEAN = 0, WEDM_PR_WIRE_MEAN, WEDM_PR_WIRE_MAX, WEDM_PR_HOT_CELL, WEDM_PR_FIXED };
+/* rows of out: the WEDM_PR_FIXED rows, then bins rows BIN_MAX[b], then bins rows BIN_MEAN[b] */
+#define WEDM_PROFILE_ROWS(bins) (WEDM_PR_FIXED + 2 * (bins))
+typedef struct wedm_profile_desc {
+    const float* T;            /* [WEDM_T_QUADS(n_seg_max)][stride][4] */
+    int64_t stride;            /* of T and of geom_i32 */
+    int32_t num_envs, n_seg_max;
+    int32_t n_seg, az_start, az_end;   /* uniform geometry; read when geom_i32 == NULL */
+    const int32_t* geom_i32;   /* [WEDM_GEOM_I32_COUNT][stride] or NULL: rows N_SEG, AZ_START, AZ_END are read */
+    int32_t bins;              /* 0 .. WEDM_PROFILE_MAX_BINS */
+    float* out;                /* [WEDM_PROFILE_ROWS(bins)][out_stride] */
+    int64_t out_stride;
+    int32_t out_cols;          /* columns of out that may be written: count <= out_cols <= out_stride */
+} wedm_profile_desc;
+
+/* Output column i (0 <= i < count) describes environment env_idx[i]; with env_idx == NULL, environment i.  One launch on
+ * `stream`.  Stateless like wedm_copy_columns: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory,
+ * read before the call returns; env_idx and status are device pointers.
+ * Checked on the device (the index list and the geometry rows may be device data nobody has read): an env_idx[i] outside
+ * [0, num_envs) writes nothing to column i and ORs 1 into *status; a geometry row with n_seg outside [1, n_seg_max] writes
+ * nothing to column i and ORs 2 (status == NULL: both are skipped silently).  Columns [count, out_stride) of out are never
+ * written.  count == 0 launches nothing and returns WEDM_OK.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)): desc NULL; T or out NULL, or T not 16-byte aligned; bins outside
+ * [0, WEDM_PROFILE_MAX_BINS]; count < 0 or count > out_cols; out_cols > out_stride; stride < num_envs; num_envs < 1;
+ * n_seg_max < 1; with geom_i32 == NULL an n_seg outside [1, n_seg_max]; env_idx == NULL with count > num_envs.           */
+int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx, int32_t count, int32_t* status, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

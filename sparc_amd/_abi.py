@@ -356,3 +356,34 @@ class CopyPlane(C.Structure):
         ("src", C.c_void_p), ("dst", C.c_void_p), ("rows", C.c_int32), ("elem_bytes", C.c_int32),
         ("src_stride", C.c_int64), ("dst_stride", C.c_int64), ("src_cols", C.c_int32), ("dst_cols", C.c_int32),
     ]
+
+
+PROFILE_MAX_BINS = 64  # WEDM_PROFILE_MAX_BINS
+
+
+class PR(enum.IntEnum):
+    """``enum wedm_profile_field``: the fixed rows of a wire profile; ``bins`` rows BIN_MAX and ``bins`` rows BIN_MEAN follow."""
+
+    ZONE_MEAN = 0
+    WIRE_MEAN = 1
+    WIRE_MAX = 2
+    HOT_CELL = 3
+
+
+PR_FIXED = 4
+
+
+def profile_rows(bins: int) -> int:
+    """``WEDM_PROFILE_ROWS``."""
+    return PR_FIXED + 2 * int(bins)
+
+
+class ProfileDesc(C.Structure):
+    """``struct wedm_profile_desc``: what `wedm_wire_profile` reads and where it writes (strides in elements)."""
+
+    _fields_ = [
+        ("T", C.c_void_p), ("stride", C.c_int64), ("num_envs", C.c_int32), ("n_seg_max", C.c_int32),
+        ("n_seg", C.c_int32), ("az_start", C.c_int32), ("az_end", C.c_int32),
+        ("geom_i32", C.c_void_p), ("bins", C.c_int32), ("out", C.c_void_p), ("out_stride", C.c_int64),
+        ("out_cols", C.c_int32),
+    ]

@@ -92,6 +92,8 @@ def load() -> C.CDLL:
     L.wedm_debug_form_name.restype = C.c_char_p
     L.wedm_copy_columns.argtypes = [C.POINTER(_abi.CopyPlane), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.wedm_copy_columns.restype = C.c_int32
+    L.wedm_wire_profile.argtypes = [C.POINTER(_abi.ProfileDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.wedm_wire_profile.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -102,7 +104,7 @@ EXPORTS = (
     "wedm_abi_version", "wedm_create", "wedm_destroy", "wedm_bind_state", "wedm_bind_geometry",
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
-    "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns",
+    "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
 )
 
 
@@ -231,6 +233,14 @@ class HipBackend:
         arr = (_abi.CopyPlane * len(planes))(*planes)
         with self._on_device():
             rc = self._L.wedm_copy_columns(arr, len(planes), src_idx_ptr, dst_idx_ptr, int(count), status_ptr, self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def wire_profile(self, desc: "_abi.ProfileDesc", env_idx_ptr, count: int, status_ptr=None) -> None:
+        """`wedm_wire_profile` on this backend's device and torch's current stream: ``env_idx_ptr`` is the device address of
+        int32[count] or None (environments ``0 .. count - 1``), ``status_ptr`` the device address of an int32 word or None."""
+        with self._on_device():
+            rc = self._L.wedm_wire_profile(C.byref(desc), env_idx_ptr, int(count), status_ptr, self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

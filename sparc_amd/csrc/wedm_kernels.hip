@@ -30,6 +30,8 @@
 //                         and, as text (WEDM_REGS_*), what both and wedm_step_regs_served do with the wire around the loop
 //   wedm_copy.h           wedm_copy_columns_kernel: environments' columns between or within caller-owned blocks (snapshot,
 //                         restore, fork); not a step kernel, not in the registry
+//   wedm_profile.h        wedm_wire_profile_kernel: every named environment's wire reduced to zone mean, mean, maximum, hottest
+//                         cell and pooled bins; not a step kernel, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -68,6 +70,7 @@ using namespace wedm;
 #include "wedm_lanes2.h"
 #if !defined(WEDM_PART) || WEDM_PART == 0
 #include "wedm_copy.h"
+#include "wedm_profile.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1379,6 +1382,50 @@ int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const
             g_create_error = std::string("wedm_copy_columns: launch: ") + hipGetErrorString(e);
             return WEDM_ERR_HIP;
         }
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx, int32_t count, int32_t* status, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_wire_profile: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_profile_desc& d = *desc;
+    if (!d.T || !d.out || (uintptr_t)d.T % 16) return bad("T or out is null, or T is not 16-byte aligned");
+    if (d.bins < 0 || d.bins > WEDM_PROFILE_MAX_BINS) return bad("bins outside [0, " + std::to_string(WEDM_PROFILE_MAX_BINS) + "]");
+    if (d.num_envs < 1 || d.n_seg_max < 1) return bad("num_envs and n_seg_max must be positive");
+    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
+    if (d.out_cols < 0 || d.out_cols > d.out_stride) return bad("out_cols outside [0, out_stride]");
+    if (count < 0 || count > d.out_cols) return bad("count outside [0, out_cols]");
+    if (!d.geom_i32 && (d.n_seg < 1 || d.n_seg > d.n_seg_max)) return bad("n_seg outside [1, n_seg_max] (uniform geometry)");
+    if (!env_idx && count > d.num_envs) return bad("count exceeds num_envs without an index list");
+    if (count == 0) return WEDM_OK;
+    // waves per block = pieces a wire is cut into: four, and more while the launch has fewer than WEDM_PROFILE_WAVES_PER_SIMD
+    // waves for each of the device's 1024 SIMDs and every piece keeps a whole batch of loads
+    const int32_t quads = WEDM_T_QUADS(d.n_seg_max);
+    const int64_t groups = ((int64_t)count + 63) / 64;
+    int32_t waves = 4;
+    while (waves < WEDM_PROFILE_MAX_WAVES && groups * waves < 1024 * WEDM_PROFILE_WAVES_PER_SIMD &&
+           quads >= 2 * waves * WEDM_PROFILE_LOADS)
+        waves *= 2;
+    wedm_profile_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.d = d;
+    a.count = count;
+    a.chunk = (quads + waves - 1) / waves;
+    a.inv_b = d.bins > 0 ? ((1u << 20) + (uint32_t)d.bins - 1) / (uint32_t)d.bins : 0u;
+    const dim3 grid((uint32_t)groups), block((uint32_t)waves * 64);
+    const size_t lds = WEDM_PROFILE_LDS_BYTES(d.bins);
+    if (d.geom_i32)
+        hipLaunchKernelGGL((wedm_wire_profile_kernel<true>), grid, block, lds, (hipStream_t)stream, a, env_idx, status);
+    else
+        hipLaunchKernelGGL((wedm_wire_profile_kernel<false>), grid, block, lds, (hipStream_t)stream, a, env_idx, status);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_create_error = std::string("wedm_wire_profile: launch: ") + hipGetErrorString(e);
+        return WEDM_ERR_HIP;
     }
     return WEDM_OK;
 }

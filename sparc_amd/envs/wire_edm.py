@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import _abi
+from .. import profile as _profile
 from .. import snapshot as _snapshot
 from ..core import derive
 from ..core import env_params as envp
@@ -209,8 +210,8 @@ class WireEDMEnv:
         parameters, and ``env.wire_material`` (and ``env.wire.wire_material``) keep reporting it: the per-environment
         materials are ``env.wire_materials[env.get_wire_material_index()]``.  Implies per-environment geometry (the
         geometry rows carry the material's conductivity and heat capacity), even with uniform height and diameter: as for
-        any per-environment geometry, ``zone_mean_temperature()`` and the ``wire_average_temperature`` signal are then not
-        available.  Combines with ``workpiece_height`` / ``wire_diameter``, ``env_params``, ``pulse_stats``,
+        any per-environment geometry, ``zone_mean_temperature()`` and the ``wire_average_temperature`` signal then come from
+        `wire_profile` (each environment's own zone).  Combines with ``workpiece_height`` / ``wire_diameter``, ``env_params``, ``pulse_stats``,
         ``stencil_dtype``, ``autoreset`` and ``reward``.  Needs a backend with ``bind_wire_material`` (the HIP library).
         ``wire_material_table``: the materials of ``env.wire_materials`` in a fixed order (names or `WireMaterial`
         objects), so that indices mean the same materials in several environments (the shards of one batch); every
@@ -320,8 +321,7 @@ class WireEDMEnv:
 
         base_flow = float(self.dielectric_params.base_flow_rate)
         self.state.derived["dielectric_flow_rate"] = lambda: dielectric_flow_rate(self.state.flow_rate, base_flow)
-        if not self.per_env_geometry:
-            self.state.derived["wire_average_temperature"] = self.zone_mean_temperature
+        self.state.derived["wire_average_temperature"] = self.zone_mean_temperature
         if backend is None:
             from .._lib import HipBackend
 
@@ -377,6 +377,10 @@ class WireEDMEnv:
         self._trace = None
         # status word of `snapshot` / `restore` / `fork` with device-resident indices (sparc_amd.snapshot; `check_errors`)
         self._copy_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        # `wire_profile` (sparc_amd.profile): its status word for device-resident indices, its output blocks by (bins, count)
+        self._profile_status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._profile_out: Dict[Tuple[int, int], torch.Tensor] = {}
+        self._profile_keep = None
         self._seed = int.from_bytes(os.urandom(8), "little")
         self.steps_since_reset = 0  # host-side count of physics steps since the last reset of ALL environments
         self._backend.reset(None, self._seed, True, fresh=True)  # fresh module objects, whatever `reset_semantics`
@@ -527,6 +531,10 @@ class WireEDMEnv:
             raise ValueError("snapshot / restore / fork with indices in a device tensor: " + "; ".join(what)
                              + ".  The indices were not read back when the copy was launched; this check reports and clears "
                                "the flag")
+        status = int(self._profile_status.item())
+        if status:
+            self._profile_status.zero_()
+            raise ValueError(_profile.status_text(status))
 
     def set_kernel(self, variant: int, lanes: int = 0) -> None:
         """0 = auto, 1 = global-memory stencil, 2 = LDS predicated, 3 = LDS fused, 4 = LDS
@@ -852,10 +860,22 @@ class WireEDMEnv:
     def load_checkpoint(self, path) -> None:
         self.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
 
+    def wire_profile(self, bins: int = 8, env_ids=None) -> Dict[str, torch.Tensor]:
+        """The wire's temperature profile per environment, for any geometry, by one launch on the device: float32 tensors
+        ``zone_mean``, ``wire_mean``, ``wire_max``, ``hot_cell`` of shape ``[count]`` (the mean over the environment's
+        workpiece zone, the mean and maximum over its wire, the lowest index of the hottest cell), ``bin_max`` /
+        ``bin_mean`` of shape ``[bins, count]`` (the wire pooled into ``bins`` bins: bin ``b`` covers the cells
+        ``[b * n // bins, (b + 1) * n // bins)``, at least one), and ``rows``, the ``[4 + 2 * bins, count]`` block they are
+        views of.  Means are float64 sums rounded once.  The tensors are valid until the next call with the same
+        ``(bins, count)``; indices may be a device tensor (never read back, mistakes reach `check_errors`).  See
+        `sparc_amd.profile.wire_profile` and DESIGN.md section 4.12."""
+        return _profile.wire_profile(self, bins, env_ids)
+
     def zone_mean_temperature(self) -> torch.Tensor:
-        """Mean wire temperature over the workpiece zone (wire.py:390-398), per environment."""
+        """Mean wire temperature over the workpiece zone (wire.py:390-398), per environment.  With per-environment geometry
+        (``workpiece_height=`` / ``wire_diameter=`` / ``wire_material=``) every environment's own zone, from `wire_profile`."""
         if self.geometry is None:
-            raise NotImplementedError("zone mean needs uniform geometry")
+            return self.wire_profile(bins=0)["zone_mean"].clone()
         g = self.geometry
         lo, hi = g.az_start, g.az_end
         T = self.state.wire_temperature.tensor().t()  # [segment, env], as the reduction was written for ABI v3

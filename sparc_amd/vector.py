@@ -11,6 +11,7 @@ from __future__ import annotations
 
 from typing import Any, Callable, Dict, Optional, Tuple
 
+import numpy as np
 import torch
 
 from .envs.wire_edm import WireEDMEnv
@@ -70,7 +71,8 @@ class WireEDMVectorEnv:
     a torch expression."""
 
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
-                 reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None):
+                 reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
+                 wire_profile_bins: Optional[int] = None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -84,13 +86,27 @@ class WireEDMVectorEnv:
         ``material_sampler``: the same for the wire material -- ``f(env, reset_mask) -> int64[N] device tensor`` of indices
         into ``env.wire_materials``, applied (`WireEDMEnv.set_wire_material`) where ``reset_mask`` is set, at the same
         point as ``param_sampler``.  The environment must have been built with ``wire_material=[...]`` (see
-        `uniform_material_sampler`)."""
+        `uniform_material_sampler`).
+        ``wire_profile_bins``: with an integer B in [0, 64], `reset()` and `step()` return ``[N, obs_dim + 4 + 2 * B]``: the
+        environment's observation followed by the rows of `WireEDMEnv.wire_profile` (zone mean, wire mean, maximum,
+        hottest cell, B bin maxima, B bin means) of the wire as the launch left it -- one more launch, no host
+        synchronisation; `obs_names` and the observation spaces grow to match."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
         self.single_observation_space = env.single_observation_space
         self.action_space = env.action_space
         self.observation_space = env.observation_space
+        self.wire_profile_bins = None
+        self.obs_names = tuple(env.obs_names)
+        if wire_profile_bins is not None:
+            from .envs.wire_edm import Box
+            from .profile import _check_bins, profile_names
+
+            self.wire_profile_bins = _check_bins(wire_profile_bins)
+            self.obs_names += profile_names(self.wire_profile_bins)
+            self.single_observation_space = Box(-np.inf, np.inf, (len(self.obs_names),), np.float32)
+            self.observation_space = self.single_observation_space
         self.autoreset = bool(autoreset)
         self.max_episode_steps = max_episode_steps
         self._in_kernel_reset = self.autoreset and bool(getattr(env, "autoreset", False))
@@ -119,7 +135,14 @@ class WireEDMVectorEnv:
             self._apply_sampler(mask)
         obs, info = self.env.reset(seed=seed, options=options)
         self._need_reset.zero_()
-        return obs.clone(), info
+        return self._observation(obs), info
+
+    def _observation(self, obs: torch.Tensor) -> torch.Tensor:
+        """What `reset` and `step` hand out: a tensor of the caller's own (the environment reuses its block), with the wire
+        profile's columns behind the environment's where asked for."""
+        if self.wire_profile_bins is None:
+            return obs.clone()
+        return torch.cat([obs, self.env.wire_profile(self.wire_profile_bins)["rows"].t()], dim=1)
 
     def _apply_sampler(self, reset_mask: torch.Tensor) -> None:
         if self._param_sampler is not None:
@@ -157,7 +180,7 @@ class WireEDMVectorEnv:
         self._need_reset = terminated | truncated
         info = dict(info)  # (StepInfo: the copy composes the exact int64 clock)
         info["episode"] = self.episode_count
-        return obs.clone(), reward, terminated, truncated, info
+        return self._observation(obs), reward, terminated, truncated, info
 
     def fork(self, src, dst) -> None:
         """`WireEDMEnv.fork`, and the adapter's own per-environment state with it: a destination is due for a reset
@@ -169,7 +192,3 @@ class WireEDMVectorEnv:
 
     def close(self) -> None:
         self.env.close()
-
-    @property
-    def obs_names(self):
-        return self.env.obs_names
