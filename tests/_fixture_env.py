@@ -148,16 +148,17 @@ def run_fixture_stepwise(env, fx, *, exact_floats, every=1):
     return checked
 
 
-def run_fixture_through_trace(env, fx, *, exact_floats, float_rtol=1e-12, T_atol=1e-4):
+def run_fixture_through_trace(env, fx, *, exact_floats, float_rtol=1e-12, T_atol=1e-4, extra=()):
     """Run the fixture's constant action for its whole length in fused launches and compare the
-    traced trajectory of environment `env_id` with the reference's recording."""
+    traced trajectory of environment `env_id` with the reference's recording.  `extra`: further EDMState names to
+    trace and return (not compared here)."""
     import torch
 
     e = int(fx.meta["env_id"])
     assert len(fx.actions) == 1, "constant-action fixtures only"
     servo, tv, on, off, mode = fx.actions[0]
     act = env.make_action(servo, tv, int(mode), on, off)
-    names = sorted(set(TRACE_INT.values()) | set(TRACE_EXACT.values()) | set(TRACE_CLOSE.values()))
+    names = sorted(set(TRACE_INT.values()) | set(TRACE_EXACT.values()) | set(TRACE_CLOSE.values()) | set(extra))
     keep_stepping = getattr(env, "freeze_terminated", True) is False
     if keep_stepping:
         names = sorted(set(names) | {"done"})

@@ -788,6 +788,45 @@ def test_randomized_parameter_reference_fixtures_on_gpu(golden_dir, k):
     assert "wedm_step_" in env._backend.last_kernel()
 
 
+def _untaken_decisions():
+    from tests.test_oracle_golden import UNTAKEN_DECISIONS
+
+    # a mode below the table stays with the oracle: the batch ABI keeps the negative values of the mode row for
+    # "None" (peak_current in wedm_device.h), and the action space is Box(1, 19) here as in the reference
+    return [name for name in UNTAKEN_DECISIONS if "below_table" not in name]
+
+
+@pytest.mark.parametrize("name", _untaken_decisions())
+def test_untaken_decision_reference_fixtures_on_gpu(golden_dir, name):
+    """F19 on the GPU: the reference runs recorded for the decisions of the scalar physics that no other recording takes
+    (both speed clamps, a crater draw <= 0, debris flushed to 0, density saturated at 1, the sigmoid's cuts at +-500,
+    k rho >= 2, the convection floor, a mode above the table).  Same comparison and tolerances as F11, and the witness
+    of tests/test_oracle_golden.py repeated on the traced GPU trajectory: the kernels took the decision too."""
+    from tests._fixture_env import FLOAT_MAP, INT_MAP, env_from_fixture, run_fixture_through_trace
+    from tests._golden import Fixture
+    from tests.test_oracle_golden import untaken_decision_witness
+
+    fx = Fixture(golden_dir / f"{name}.npz")
+    raised = fx.meta["raised"] is not None
+    env = env_from_fixture(fx, 64, device="cuda:0", **(dict(strict_actions=False) if raised else {}))
+    extra = ("h_eff_base", "dielectric_last_gap", "dielectric_last_density")
+    got = run_fixture_through_trace(env, fx, exact_floats=False, extra=extra)
+    assert "wedm_step_" in env._backend.last_kernel()
+    assert len(got["spark_state"]) == fx.n_steps
+
+    def row(field):
+        return got[FLOAT_MAP[field] if field in FLOAT_MAP else INT_MAP[field]]
+
+    untaken_decision_witness(name, fx, row)
+    e = int(fx.meta["env_id"])
+    assert not bool(env.state.error[e])
+    if raised:   # the step at which the reference raised ValueError: the sticky ERROR row, at the fresh spark
+        servo, tv, on, off, mode = fx.actions[0]
+        env.step_many(env.make_action(servo, tv, int(mode), on, off), 1)
+        assert bool(env.state.error[e]) and int(env.state.spark_state[e]) == 1 and int(env.state.spark_duration[e]) == 0
+        assert float(env.state.current[e]) == 215.0
+
+
 @pytest.mark.parametrize("case", range(int(os.environ.get("WEDM_FUZZ_CASES", "64"))))
 def test_randomized_configurations_all_kernels_bit_exact(case):
     """Fuzz: random parameters in every module, random batch size / control mode / action / kernel

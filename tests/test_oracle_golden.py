@@ -23,6 +23,18 @@ PHILOX = [f"f3_philox_env{i}" for i in (0, 1, 2, 3, 777, 65535)] + ["f3_philox_c
 ] + ["f7_gap_controller_philox_env0", "f7_gap_controller_philox_env9", "f7_gap_controller_velocity_philox_env3",
      "f9_voltage_controller_philox_env2", "f9_voltage_controller_velocity_philox_env5",
      "f10_crater_statistics_philox_env1", "f13_dt2_philox_env4", "f14_copper_wire_philox_env6", "f15_default_mode_philox_env7"] + [f"f11_random_params_{k}" for k in range(8)] + SECOND_EPISODE + PAST_TERMINATION
+# F19: decisions of the scalar physics no earlier recording takes (tools/oracle_census.py); witnesses below
+UNTAKEN_DECISIONS = ["f19_speed_clamp_philox_env3", "f19_zero_crater_philox_env31", "f19_debris_flushed_philox_env5",
+                     "f19_packed_gap_philox_env7", "f19_steep_sigmoid_clean_gap_philox_env9",
+                     "f19_convection_floor_philox_env11", "f19_convection_above_floor_philox_env12",
+                     "f19_mode_above_table_philox_env13", "f19_mode_below_table_philox_env14"]
+PHILOX = PHILOX + UNTAKEN_DECISIONS
+# what test_portable_math_mode_stays_within_stated_tolerance replays in PORTABLE math
+PORTABLE = ["f1_config1_native", "f5_debris_short", "f3_philox_env0", "f7_gap_controller", "f9_voltage_controller_philox_env2",
+            "f10_crater_statistics_philox_env1", "f13_dt2_philox_env4", "f14_copper_wire_philox_env6",
+            "f15_default_mode_philox_env7"] + [f"f11_random_params_{k}" for k in range(8)] + UNTAKEN_DECISIONS
+# recordings that end where the reference raised ValueError
+RAISING = ["f5_invalid_mode", "f19_mode_above_table_philox_env13", "f19_mode_below_table_philox_env14"]
 
 
 @pytest.mark.parametrize("name", NATIVE)
@@ -76,6 +88,96 @@ def test_second_episode_fixtures_really_carry_module_state_over(orc, golden_dir)
     assert set(before_latch_1.tolist()) == {60.0} and len(before_latch_2) and set(before_latch_2.tolist()) != {60.0}
 
 
+def untaken_decision_witness(name, fx, row):
+    """Shows, on a trajectory alone, that fixture `name` really takes the decision it was recorded for.  `row(field)` is
+    the per-microsecond series of a recorded field (float fields of these fixtures are recorded at every step); the
+    parameters come from the fixture's meta.  Used on the reference's recording here and on the traced GPU trajectory
+    in tests/test_gpu_parity.py."""
+    import math
+
+    from tests._golden import config_from_meta
+
+    cfg, mods = config_from_meta(fx.meta), fx.meta["modules"]
+    gap = row("workpiece_position") - row("wire_position")
+    if name.startswith("f19_speed_clamp"):                      # A: mechanics.py:105 in both signs
+        v, vmax = row("wire_velocity"), mods["mechanics"]["max_speed"]
+        assert v[0] == -vmax and (v == vmax).sum() > 50 and np.abs(v).max() == vmax
+    elif name.startswith("f19_zero_crater"):                    # B: material.py:130, dielectric.py:103
+        fresh = (row("spark_state") == 1) & (row("spark_dur") == 0)
+        empty = np.nonzero(fresh & (row("last_crater_volume") == 0))[0]
+        assert len(empty) == 1 and empty[0] > 0 and fresh.sum() > 1
+        k = int(empty[0])
+        assert row("workpiece_position")[k] == row("workpiece_position")[k - 1]
+        assert row("debris_volume")[k] == row("debris_volume")[k - 1]
+        others = np.nonzero(fresh & (row("last_crater_volume") > 0))[0]   # an ordinary spark does both
+        j = int(others[others > 0][0])
+        assert row("workpiece_position")[j] > row("workpiece_position")[j - 1] and row("debris_volume")[j] > row("debris_volume")[j - 1]
+    elif name.startswith("f19_debris_flushed"):                 # C: dielectric.py:158
+        assert fx.meta["module_init"]["dielectric.debris_volume"] > 0.001 and row("debris_volume")[0] == 0.0
+        assert row("flow_rate")[0] > 0.001
+    elif name.startswith("f19_packed_gap"):                     # D, E (below -500), F
+        rho = row("debris_density")
+        assert (rho == 1.0).all() and (row("debris_volume") > row("cavity_volume")).all()
+        crit = np.minimum(cfg.base_critical_density + cfg.gap_coefficient * gap, cfg.max_critical_density)
+        exponent = -cfg.sigmoid_steepness * (rho - crit)      # what the NEXT step's short detection sees
+        assert (exponent < -500).all()
+        k = mods["dielectric"]["debris_obstruction_coeff"]
+        assert k * rho[0] >= 2.0 and row("diel_last_gap")[0] == gap[0] and row("diel_last_density")[0] == rho[0]   # refreshed
+        want = min(1.0, (gap[0] / cfg.reference_gap) ** 3) * math.exp(-k * rho[0])
+        assert abs(row("flow_rate")[0] - want) <= 1e-12 * want   # np.exp, not the Pade form (1 - 1.5) / (1 + 1.5) < 0
+    elif name.startswith("f19_steep_sigmoid"):                  # E (above 500)
+        crit = np.minimum(cfg.base_critical_density + cfg.gap_coefficient * gap, cfg.max_critical_density)
+        exponent = -cfg.sigmoid_steepness * (row("debris_density") - crit)
+        assert (exponent > 500).all() and (row("debris_short_remaining") == 0).all()
+    elif name.startswith("f19_convection"):                     # G: wire.py:355-361
+        base, cvf = mods["wire"]["base_convection_coefficient"], mods["wire"]["convection_velocity_factor"]
+        ve = cvf * fx.meta["state_init"]["wire_unwinding_velocity"]
+        floor = np.float32(0.1 * base)
+        if "above" in name:
+            assert -0.9 < ve < 0 and (row("h_base") == np.float32(base * (1.0 + ve))).all() and np.float32(base * (1.0 + ve)) > floor
+        else:   # 1 + max(-0.9, ve) < 0.1 in float64, so the floor binds whenever the clamp does; float32 tells them apart here
+            assert ve < -0.9 and base * (1.0 + -0.9) < 0.1 * base and np.float32(base * (1.0 + -0.9)) < floor
+            assert (row("h_base") == floor).all()
+    elif name.startswith("f19_mode_"):                          # H: ignition.py:107-110, on either side of the table
+        assert int(fx.actions[0][4]) > 19 if "above" in name else int(fx.actions[0][4]) < 0
+        cur, latch = row("current"), fx.meta["config"]["servo_interval"]
+        before, after = cur[:latch][cur[:latch] > 0], cur[latch:][cur[latch:] > 0]
+        assert set(before.tolist()) == {60.0} and len(after) >= 3
+        assert set(after.tolist()) == {215.0}                   # currents.json I13, the default_current_mode of this run
+    else:
+        raise KeyError(name)
+
+
+@pytest.mark.parametrize("name", UNTAKEN_DECISIONS)
+def test_untaken_decision_fixtures_really_take_their_decision(orc, golden_dir, name):
+    """On the recorded reference data alone (no oracle run): each F19 recording shows the decision it exists for."""
+    fx = Fixture(golden_dir / f"{name}.npz")
+    assert np.array_equal(fx.float_steps, np.arange(fx.n_steps))
+
+    def row(field):
+        return fx.float_row(field) if field in fx.float_fields else fx.int_row(field)
+
+    untaken_decision_witness(name, fx, row)
+    if name.startswith("f19_mode_"):
+        from tests._golden import config_from_meta
+
+        assert orc.new_env(config_from_meta(fx.meta)).c.default_current == 215.0
+
+
+@pytest.mark.parametrize("name,mode", [("f19_mode_above_table_philox_env13", "I21"), ("f19_mode_below_table_philox_env14", "I-3")])
+def test_mode_outside_the_table_flags_where_reference_raises(orc, golden_dir, name, mode):
+    """material.py:108-113 raises for a mode outside the table at the first fresh spark after the latch, like F5's even mode."""
+    from tests._golden import action_for
+
+    fx = Fixture(golden_dir / f"{name}.npz")
+    step_raised, msg = fx.meta["raised"]
+    assert mode in msg and fx.n_steps == step_raised
+    bad, env = replay(fx)
+    assert not bad and env.error == 0
+    orc.step(env, action_for(fx, fx.n_steps - 1))
+    assert env.error & 1 and env.spark_state == 1 and env.spark_dur == 0 and env.current == 215.0
+
+
 def test_known_answers_from_survey(orc, golden_dir):
     """SURVEY.md §8c F1 known answers, recorded independently of this build."""
     fx = Fixture(golden_dir / "f1_config1_native.npz")
@@ -123,9 +225,7 @@ def test_invalid_mode_flags_where_reference_raises(orc, golden_dir):
 def test_portable_math_mode_stays_within_stated_tolerance(orc, golden_dir):
     """PORTABLE math (what the GPU computes) vs the reference: decisions identical,
     float64 state within 1e-12 relative, temperatures within 1e-4 K."""
-    for name in ("f1_config1_native", "f5_debris_short", "f3_philox_env0", "f7_gap_controller", "f9_voltage_controller_philox_env2",
-                 "f10_crater_statistics_philox_env1", "f13_dt2_philox_env4", "f14_copper_wire_philox_env6",
-                 "f15_default_mode_philox_env7") + tuple(f"f11_random_params_{k}" for k in range(8)):
+    for name in PORTABLE:
         fx = Fixture(golden_dir / f"{name}.npz")
         bad, _ = replay(fx, math_mode=orc.MATH_PORTABLE, exact_floats=False, float_rtol=1e-12, T_atol=1e-4)
         assert not bad, name + "\n" + "\n".join(bad[:20])

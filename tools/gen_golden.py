@@ -695,6 +695,66 @@ def main():
                  action=make_action(1.0, 80.0, 5, 3.0, 80.0), stop_on_terminate=False,
                  note="wire > workpiece + 100 -> is_wire_broken by _check_termination, then stepped on")
 
+    # F19 — decisions of the scalar physics that no earlier recording takes (tools/oracle_census.py lists them).  Short
+    # runs, Philox variates, constant actions, environment ids below 64 so that one block of a batch replays them.
+    near = {"workpiece_position": 20.0, "wire_position": 10.0, "target_position": 5000.0}
+    # both speed clamps (mechanics.py:105): the run starts far below -max_speed, then the servo drives it to +max_speed
+    run_scenario("f19_speed_clamp_philox_env3", n_steps=260, seed=1901, rng="philox", env_id=3, control_mode="velocity",
+                 config={"servo_interval": 50},
+                 mechanics={"max_speed": 100.0, "omega_n": 600.0, "max_jerk": 1.0e11, "max_acceleration": 3.0e6},
+                 state_init={**near, "wire_velocity": -5000.0}, action=make_action(50000.0, 80.0, 5, 3.0, 80.0),
+                 note="v < -max_speed at the first step, v > max_speed from about step 130 on")
+    # a crater draw <= 0 (material.py:130 max(0, x); I13 has mean/std 3.02, every other mode above 30).  (seed, env id)
+    # found with the oracle: dense mode-13 sparking (gap 4 um, ON = OFF = 1 us) over seeds 19020..19059 x env ids 0..63,
+    # 250 us each, first spark whose recorded crater volume is 0; this one has it at step 11
+    run_scenario("f19_zero_crater_philox_env31", n_steps=60, seed=19026, rng="philox", env_id=31,
+                 config={"servo_interval": 10},
+                 state_init={"workpiece_position": 14.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action=make_action(0.0, 80.0, 13, 1.0, 1.0),
+                 note="the spark igniting at step 11 draws a crater volume <= 0: no advance, no debris")
+    # debris removal larger than the debris there is (dielectric.py:158 max(0.0, v - removed))
+    run_scenario("f19_debris_flushed_philox_env5", n_steps=40, seed=1903, rng="philox", env_id=5,
+                 dielectric={"debris_removal_efficiency": 1.0, "base_flow_rate": 4000.0},
+                 module_init={"dielectric.debris_volume": 0.0011},
+                 state_init={"workpiece_position": 60.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action=QUICKSTART, note="the first step removes more than the 0.0011 mm^3 present: volume clamps to 0.0")
+    # a gap packed with debris: density saturates at 1 (dielectric.py:111), k*rho = 3 >= 2 takes np.exp
+    # (dielectric.py:124-127), the sigmoid's exponent is below -500 (ignition.py:141)
+    run_scenario("f19_packed_gap_philox_env7", n_steps=120, seed=1904, rng="philox", env_id=7,
+                 ignition={"sigmoid_steepness": 2000.0}, dielectric={"debris_obstruction_coeff": 3.0},
+                 module_init={"dielectric.debris_volume": 0.1}, state_init=near, action=QUICKSTART,
+                 note="debris volume above the cavity volume")
+    # a clean gap under a steep sigmoid: exponent above 500 (ignition.py:139)
+    run_scenario("f19_steep_sigmoid_clean_gap_philox_env9", n_steps=200, seed=1905, rng="philox", env_id=9,
+                 ignition={"sigmoid_steepness": 2000.0},
+                 state_init={"workpiece_position": 25.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action=QUICKSTART, note="density ~0 against a critical density of 0.3 at steepness 2000")
+    # convection under a wire that unwinds against the flow (wire.py:355-361): ve = -1.5 clamps to -0.9 and
+    # base * (1 + -0.9) lies below the floor 0.1 * base.  The two differ by a few float64 ulps only, so the base is
+    # chosen where float32 tells them apart: 0.1 * base rounds up to 1400.0001, base * (1 + -0.9) down to 1400.0
+    run_scenario("f19_convection_floor_philox_env11", n_steps=60, seed=1907, rng="philox", env_id=11,
+                 wire={"convection_velocity_factor": -3.0, "base_convection_coefficient": 14000.000610351564},
+                 state_init={**near, "wire_unwinding_velocity": 0.5}, action=QUICKSTART,
+                 note="ve clamped at -0.9, h floor binding")
+    run_scenario("f19_convection_above_floor_philox_env12", n_steps=60, seed=1907, rng="philox", env_id=12,
+                 wire={"convection_velocity_factor": -3.0, "base_convection_coefficient": 14000.000610351564},
+                 state_init={**near, "wire_unwinding_velocity": 0.29}, action=QUICKSTART,
+                 note="ve = -0.87: neither the clamp nor the floor binds")
+    # a current mode above the table (ignition.py:107-110: the default mode's current; material.py:108-113 raises at the
+    # first fresh spark).  Random shorts make current flow between the latch at step 50 and that spark
+    run_scenario("f19_mode_above_table_philox_env13", n_steps=400, seed=1909, rng="philox", env_id=13,
+                 config={"servo_interval": 50},
+                 ignition={"default_current_mode": "I13", "random_short_max_probability": 0.05, "random_short_duration": 12},
+                 state_init={"workpiece_position": 25.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action=make_action(0.0, 80.0, 21, 3.0, 10.0),
+                 note="mode 21: short pulses carry I13's current after the latch, ValueError at the first fresh spark")
+    run_scenario("f19_mode_below_table_philox_env14", n_steps=400, seed=1911, rng="philox", env_id=14,
+                 config={"servo_interval": 50},
+                 ignition={"default_current_mode": "I13", "random_short_max_probability": 0.05, "random_short_duration": 12},
+                 state_init={"workpiece_position": 25.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action=make_action(0.0, 80.0, -3, 3.0, 10.0),
+                 note="mode -3 ('I-3'): the same on the table's lower side")
+
     # F16 — the reference's own SimulationLogger over its own driver loop and signal list
     if not only or only in "f16_logger_philox_env3":
         run_logger_scenario("f16_logger_philox_env3", n_steps=3300, seed=83, env_id=3,
@@ -732,6 +792,8 @@ def main():
         print("f12_module_getters", len(gaps), "gaps x", len(dens), "densities")
 
     # F4 — geometry table straight from WireModule.__init__
+    if only and only not in "f4_geometry_table":
+        return
     rows = []
     for h in (5.0, 10.0, 12.3, 15.0, 20.0, 25.0, 30.0, 47.7):
         for seg in (0.1, 0.2, 0.25, 0.3, 0.5, 0.625, 1.0):
