@@ -591,7 +591,8 @@ int32_t wedm_last_occupancy(wedm_ctx* ctx);
  * Strides are in elements of elem_bytes.  src_cols / dst_cols are the columns that may be named on either side (num_envs
  * of an environment's block, not its stride: the padding columns are not environments).
  * Not state, and so no plane of any caller in this repository: a bound trace ring, the replay table, the geometry rows
- * (height and diameter belong to the slot, not to what is being simulated in it).                                   */
+ * (height and diameter belong to the slot, not to what is being simulated in it) -- except where the caller redraws the
+ * geometry per episode (wedm_derive_geometry below): there the two geometry blocks are state and travel as planes.     */
 #define WEDM_COPY_MAX_PLANES 16
 typedef struct wedm_copy_plane {
     const void* src;     /* first row of the source block                                   */
@@ -668,6 +669,55 @@ typedef struct wedm_profile_desc {
  * [0, WEDM_PROFILE_MAX_BINS]; count < 0 or count > out_cols; out_cols > out_stride; stride < num_envs; num_envs < 1;
  * n_seg_max < 1; with geom_i32 == NULL an n_seg outside [1, n_seg_max]; env_idx == NULL with count > num_envs.           */
 int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx, int32_t count, int32_t* status, void* stream);
+
+/* ---------------------------------------------------- geometry rows derived on the device (a new workpiece per episode)
+ * The any-geometry step kernels read the geometry rows (wedm_bind_geometry) at the start of every launch, and a reset
+ * re-initialises the whole wire.  An environment whose 8 + 6 rows are rewritten just before the launch that resets it is
+ * therefore a fresh environment of the new geometry.  This call rewrites them from per-environment device arrays, with the
+ * bits the host derivation writes.  The derivation is split:
+ *   what depends on the wire DIAMETER (and the wire material) only comes from the caller's combination table, row
+ *     material_idx * n_diameters + diameter_idx, WEDM_GEOMC_COUNT doubles per row (enum below): the six geometry values that
+ *     do not depend on the height, copied verbatim, and PI_R = pi * (diameter / 2) [mm];
+ *   what depends on the HEIGHT h is computed (float64, no contraction, `//` = Python's float floor-division):
+ *     n    = max(1, (int) trunc(((buffer_len_bottom + h) + buffer_len_top) / segment_len))
+ *     ze   = min(zone_start0 + (int) (h // segment_len), n);     zs = min(zone_start0, ze)
+ *     az_s = min(zs, n - 1);   az_e = min(ze, n)
+ *     ct   = min(n - 1, (int) trunc(((buffer_len_bottom + h) + contact_offset_top) / segment_len));  ct = min(n - 1, max(ct, ze))
+ *     cb   = max(0, min(contact_bottom0, zs - 1))
+ *     rows: HEIGHT = h, CAVITY_COEFF = PI_R * h, KERF_BASE / K_COND / TUF / A_SURF / S_AREA / JOULE_GEOM from the table;
+ *           N_SEG = n, ZONE_START = zs, AZ_START = az_s, AZ_END = az_e, CONTACT_BOTTOM = cb, CONTACT_TOP = ct.
+ *   zone_start0 = int(buffer_len_bottom // segment_len) and contact_bottom0 = max(0, int((buffer_len_bottom -
+ *   contact_offset_bottom) / segment_len)) are the caller's (they do not depend on the environment).                     */
+enum wedm_geomc_field {
+    WEDM_GC_K_COND = 0, WEDM_GC_TUF, WEDM_GC_A_SURF, WEDM_GC_S_AREA, WEDM_GC_JOULE_GEOM, WEDM_GC_KERF_BASE, WEDM_GC_PI_R,
+    WEDM_GEOMC_COUNT
+};
+typedef struct wedm_geom_derive_desc {
+    double segment_len, buffer_len_bottom, buffer_len_top, contact_offset_top;   /* [mm], WireModuleParameters */
+    int32_t zone_start0, contact_bottom0;
+    int32_t num_envs, n_seg_max;   /* n_seg_max: the capacity of the wire block the rows are for */
+    int64_t stride;                /* of geom_f64 and geom_i32 */
+    const double* combo;           /* device, [n_materials * n_diameters][WEDM_GEOMC_COUNT] */
+    int32_t n_diameters, n_materials;
+    double* geom_f64;              /* device, [WEDM_GEOM_F64_COUNT][stride] */
+    int32_t* geom_i32;             /* device, [WEDM_GEOM_I32_COUNT][stride] */
+} wedm_geom_derive_desc;
+
+/* For every environment e < num_envs with mask[e] != 0 (mask == NULL: all) column e of the 14 geometry rows is written as
+ * above from height[e], diameter_idx[e] and material_idx[e] (material_idx == NULL: 0).  One launch on `stream`.  Stateless
+ * like wedm_copy_columns: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory, read before the call
+ * returns; height, diameter_idx, material_idx, mask and status are device pointers with one element per environment (status:
+ * one word).  The mask is a device array because the caller may hold it without ever having read it.
+ * Checked on the device: a height that is NaN, infinite or <= 0 ORs 1 into *status; else a height whose n would exceed
+ * n_seg_max ORs 2 (tested in float64, before the conversion: such a row would send a step kernel past its wire); an index
+ * outside the table ORs 4.  Any of them leaves the 14 values of that column as they were (status == NULL: skipped silently).
+ * Never written: columns [num_envs, stride), unmasked columns, anything outside the two blocks.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)): desc, height, diameter_idx, combo, geom_f64 or geom_i32 NULL; geom_f64,
+ * combo or height not 8-byte aligned; num_envs < 1; stride < num_envs; n_seg_max outside [1, 2^29]; n_diameters or
+ * n_materials < 1; a segment_len that is not finite and positive; a buffer length that is not finite and >= 0; a
+ * contact_offset_top that is not finite; zone_start0 or contact_bottom0 outside [0, 2^29].                              */
+int32_t wedm_derive_geometry(const wedm_geom_derive_desc* desc, const double* height, const int32_t* diameter_idx,
+                             const int32_t* material_idx, const uint8_t* mask, int32_t* status, void* stream);
 
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.

@@ -29,7 +29,7 @@ from .controllers import GapController, VoltageController, run_controlled
 from .snapshot import EnvSnapshot
 from .trace import DeviceTrace
 from .utils.logger import LoggerConfig, SimulationLogger
-from .vector import WireEDMVectorEnv, uniform_material_sampler, uniform_param_sampler
+from .vector import WireEDMVectorEnv, uniform_geometry_sampler, uniform_material_sampler, uniform_param_sampler
 
 EDMState = BatchedEDMState  # the reference's name for the state object
 
@@ -37,7 +37,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -387,3 +387,33 @@ class ProfileDesc(C.Structure):
         ("geom_i32", C.c_void_p), ("bins", C.c_int32), ("out", C.c_void_p), ("out_stride", C.c_int64),
         ("out_cols", C.c_int32),
     ]
+
+
+class GEOMC(enum.IntEnum):
+    """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
+    `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""
+
+    K_COND = 0
+    TUF = 1
+    A_SURF = 2
+    S_AREA = 3
+    JOULE_GEOM = 4
+    KERF_BASE = 5
+    PI_R = 6
+
+
+GEOMC_COUNT = 7
+# status bits of `wedm_derive_geometry`: a height that is NaN, infinite or <= 0; a height over the capacity; an index
+# outside the combination table
+GEOM_STATUS_HEIGHT, GEOM_STATUS_CAPACITY, GEOM_STATUS_INDEX = 1, 2, 4
+
+
+class GeomDeriveDesc(C.Structure):
+    """``struct wedm_geom_derive_desc``: what `wedm_derive_geometry` reads and where it writes (stride in elements)."""
+
+    _fields_ = [
+        ("segment_len", _d), ("buffer_len_bottom", _d), ("buffer_len_top", _d), ("contact_offset_top", _d),
+        ("zone_start0", _i), ("contact_bottom0", _i), ("num_envs", _i), ("n_seg_max", _i),
+        ("stride", C.c_int64), ("combo", C.c_void_p), ("n_diameters", _i), ("n_materials", _i),
+        ("geom_f64", C.c_void_p), ("geom_i32", C.c_void_p),
+    ]

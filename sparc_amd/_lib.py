@@ -94,6 +94,9 @@ def load() -> C.CDLL:
     L.wedm_copy_columns.restype = C.c_int32
     L.wedm_wire_profile.argtypes = [C.POINTER(_abi.ProfileDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.wedm_wire_profile.restype = C.c_int32
+    L.wedm_derive_geometry.argtypes = [C.POINTER(_abi.GeomDeriveDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+    L.wedm_derive_geometry.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -105,6 +108,7 @@ EXPORTS = (
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
+    "wedm_derive_geometry",
 )
 
 
@@ -241,6 +245,17 @@ class HipBackend:
         int32[count] or None (environments ``0 .. count - 1``), ``status_ptr`` the device address of an int32 word or None."""
         with self._on_device():
             rc = self._L.wedm_wire_profile(C.byref(desc), env_idx_ptr, int(count), status_ptr, self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def derive_geometry(self, desc: "_abi.GeomDeriveDesc", height_ptr, diameter_idx_ptr, material_idx_ptr=None, mask_ptr=None,
+                        status_ptr=None) -> None:
+        """`wedm_derive_geometry` on this backend's device and torch's current stream: device addresses of float64[num_envs]
+        heights, int32[num_envs] diameter indices, int32[num_envs] material indices or None (material 0), a uint8[num_envs]
+        mask or None (every environment) and an int32 status word or None."""
+        with self._on_device():
+            rc = self._L.wedm_derive_geometry(C.byref(desc), height_ptr, diameter_idx_ptr, material_idx_ptr, mask_ptr, status_ptr,
+                                              self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

@@ -1,0 +1,84 @@
+// wedm_geometry.h -- wedm_derive_geometry: the geometry rows of masked environments derived from (height, diameter index,
+// material index), on the device.
+//
+// Not a step kernel and not in the registry: no wedm_ctx, no wedm_params, no plan, no form bits.  The any-geometry step kernels
+// read the 8 + 6 geometry rows at the start of every launch, and a reset re-initialises the whole wire, so an environment
+// whose rows are rewritten just before the launch that resets it is a fresh environment of the new geometry.  This kernel
+// rewrites them, bit for bit as `derive_geometry` (sparc_amd/core/derive.py) does on the host in Python floats.
+//
+// What makes that possible is a split of the derivation:
+//   everything that depends on the DIAMETER and the material only -- s_area (a C pow on the host), a_surf, k_cond, tuf,
+//     joule_geom, kerf_base, and pi * r -- is a row of the caller's combination table, [material][diameter], made by the host
+//     derivation itself and copied here verbatim;
+//   everything that depends on the HEIGHT is IEEE add, divide, Python's float floor-division (py_floordiv), one multiply,
+//     float -> int truncation and integer min / max, in the host's operand order.  The translation unit is compiled with
+//     -ffp-contract=off: nothing here may fuse.
+//
+// Shape: one lane per environment, blocks of 256.  Row loads and stores are coalesced (the environment is the column); the
+// table is WEDM_GEOMC_COUNT doubles per combination and comes through the cache.  About 150 bytes per environment: the
+// launch, not the kernel, is what it costs.
+//
+// Refusals (the inputs may be device data nobody has read): a height that is NaN, infinite or <= 0 (status bit 1), a height
+// whose wire would have more than n_seg_max cells (bit 2, tested in float64 BEFORE the conversion to int: a geometry row with
+// n_seg > n_seg_max would send a step kernel past its wire), an index outside the table (bit 4).  A refused environment's 14
+// values stay as they were.  Unmasked environments and the columns [num_envs, stride) are never written.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/wedm_hip.h"
+#include "wedm_device.h"
+
+__global__ void __launch_bounds__(256)
+wedm_derive_geometry_kernel(const wedm_geom_derive_desc d, const double* __restrict__ height,
+                            const int32_t* __restrict__ diameter_idx, const int32_t* __restrict__ material_idx,
+                            const uint8_t* __restrict__ mask, int32_t* status) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= d.num_envs) return;
+    if (mask && !mask[e]) return;
+    const double h = height[e];
+    const int32_t di = diameter_idx[e], mi = material_idx ? material_idx[e] : 0;
+    const double seg = d.segment_len, bb = d.buffer_len_bottom;
+    // wire.py:144-149: total_len / segment_len, still a float (h is NaN, inf or <= 0: not used)
+    const double cells = ((bb + h) + d.buffer_len_top) / seg;
+    int32_t bits = 0;
+    if (!(h > 0.0) || h == __builtin_inf()) bits |= 1;
+    else if (!(cells < (double)d.n_seg_max + 1.0)) bits |= 2;  // int(cells) > n_seg_max
+    if ((uint32_t)di >= (uint32_t)d.n_diameters || (uint32_t)mi >= (uint32_t)d.n_materials) bits |= 4;
+    if (bits) {
+        if (status) atomicOr(status, bits);
+        return;
+    }
+    // 0 < h, cells < n_seg_max + 1 <= 2^29 + 1 and zone_start0 <= 2^29 (the host's bounds): every conversion below is of a
+    // value an int32 holds, and so is the sum zone_start0 + floor(h / seg)
+    const int32_t n = max(1, (int32_t)cells);                                           // wire.py:149
+    const int32_t ze = min(d.zone_start0 + (int32_t)wedm::py_floordiv(h, seg), n);      // wire.py:152-154
+    const int32_t zs = min(d.zone_start0, ze);
+    const int32_t az_s = min(zs, n - 1), az_e = min(ze, n);                             // wire.py:207-208
+    // wire.py:232-236, 250-252; the quotient is bounded in float64 first (contact_offset_top is the caller's)
+    double top = trunc(((bb + h) + d.contact_offset_top) / seg);
+    top = fmin(fmax(top, -1.0), (double)(n - 1));   // (below 0: max(ct, ze) takes ze either way)
+    const int32_t ct = min(n - 1, max((int32_t)top, ze));
+    const int32_t cb = max(0, min(d.contact_bottom0, zs - 1));                          // wire.py:247-249
+
+    const double* c = d.combo + ((int64_t)mi * d.n_diameters + di) * WEDM_GEOMC_COUNT;
+    const int64_t s = d.stride;
+    double* f = d.geom_f64 + e;
+    f[WEDM_G_HEIGHT * s] = h;
+    f[WEDM_G_KERF_BASE * s] = c[WEDM_GC_KERF_BASE];
+    f[WEDM_G_CAVITY_COEFF * s] = c[WEDM_GC_PI_R] * h;                                    // dielectric.py:62
+    f[WEDM_G_K_COND * s] = c[WEDM_GC_K_COND];
+    f[WEDM_G_TUF * s] = c[WEDM_GC_TUF];
+    f[WEDM_G_A_SURF * s] = c[WEDM_GC_A_SURF];
+    f[WEDM_G_S_AREA * s] = c[WEDM_GC_S_AREA];
+    f[WEDM_G_JOULE_GEOM * s] = c[WEDM_GC_JOULE_GEOM];
+    int32_t* g = d.geom_i32 + e;
+    g[WEDM_GI_N_SEG * s] = n;
+    g[WEDM_GI_ZONE_START * s] = zs;
+    g[WEDM_GI_AZ_START * s] = az_s;
+    g[WEDM_GI_AZ_END * s] = az_e;
+    g[WEDM_GI_CONTACT_BOTTOM * s] = cb;
+    g[WEDM_GI_CONTACT_TOP * s] = ct;
+}

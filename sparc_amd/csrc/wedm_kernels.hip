@@ -32,6 +32,8 @@
 //                         restore, fork); not a step kernel, not in the registry
 //   wedm_profile.h        wedm_wire_profile_kernel: every named environment's wire reduced to zone mean, mean, maximum, hottest
 //                         cell and pooled bins; not a step kernel, not in the registry
+//   wedm_geometry.h       wedm_derive_geometry_kernel: masked environments' geometry rows derived from (height, diameter
+//                         index, material index) with the host derivation's bits; not a step kernel, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -71,6 +73,7 @@ using namespace wedm;
 #if !defined(WEDM_PART) || WEDM_PART == 0
 #include "wedm_copy.h"
 #include "wedm_profile.h"
+#include "wedm_geometry.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1425,6 +1428,42 @@ int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx,
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         g_create_error = std::string("wedm_wire_profile: launch: ") + hipGetErrorString(e);
+        return WEDM_ERR_HIP;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_derive_geometry(const wedm_geom_derive_desc* desc, const double* height, const int32_t* diameter_idx,
+                             const int32_t* material_idx, const uint8_t* mask, int32_t* status, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_derive_geometry: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    const auto finite = [](double x) { return x - x == 0.0; };
+    if (!desc) return bad("null descriptor");
+    const wedm_geom_derive_desc& d = *desc;
+    if (!height || !diameter_idx) return bad("null height or diameter index array");
+    if (!d.combo || !d.geom_f64 || !d.geom_i32) return bad("null combination table or geometry block");
+    if ((uintptr_t)d.geom_f64 % 8 || (uintptr_t)d.combo % 8 || (uintptr_t)height % 8 || (uintptr_t)d.geom_i32 % 4 ||
+        (uintptr_t)diameter_idx % 4 || (uintptr_t)material_idx % 4)
+        return bad("a pointer is not aligned to its element");
+    if (d.num_envs < 1) return bad("num_envs must be positive");
+    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
+    if (d.n_seg_max < 1 || d.n_seg_max > (1 << 29)) return bad("n_seg_max outside [1, 2^29]");
+    if (d.n_diameters < 1 || d.n_materials < 1) return bad("n_diameters and n_materials must be positive");
+    if (!finite(d.segment_len) || !(d.segment_len > 0.0)) return bad("segment_len must be finite and positive");
+    if (!finite(d.buffer_len_bottom) || !finite(d.buffer_len_top) || d.buffer_len_bottom < 0.0 || d.buffer_len_top < 0.0)
+        return bad("buffer lengths must be finite and not negative");
+    if (!finite(d.contact_offset_top)) return bad("contact_offset_top must be finite");
+    // (2^29 each: zone_start0 + floor(h / seg) <= 2^29 + n_seg_max stays inside int32 in the kernel)
+    if (d.zone_start0 < 0 || d.zone_start0 > (1 << 29) || d.contact_bottom0 < 0 || d.contact_bottom0 > (1 << 29))
+        return bad("zone_start0 or contact_bottom0 outside [0, 2^29]");
+    const dim3 grid((uint32_t)(((int64_t)d.num_envs + 255) / 256));
+    hipLaunchKernelGGL(wedm_derive_geometry_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, height, diameter_idx,
+                       material_idx, mask, status);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_create_error = std::string("wedm_derive_geometry: launch: ") + hipGetErrorString(e);
         return WEDM_ERR_HIP;
     }
     return WEDM_OK;

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import _abi
+from .. import geometry as _geometry
 from .. import profile as _profile
 from .. import snapshot as _snapshot
 from ..core import derive
@@ -159,6 +160,7 @@ class WireEDMEnv:
         env_params: Optional[Dict[str, Any]] = None,
         wire_material=None,
         wire_material_table=None,
+        dynamic_geometry: Optional[Dict[str, Any]] = None,
         backend: Optional[Callable] = None,
     ):
         """Beyond the reference's keywords (wire_edm.py:22-34):
@@ -215,7 +217,15 @@ class WireEDMEnv:
         ``stencil_dtype``, ``autoreset`` and ``reward``.  Needs a backend with ``bind_wire_material`` (the HIP library).
         ``wire_material_table``: the materials of ``env.wire_materials`` in a fixed order (names or `WireMaterial`
         objects), so that indices mean the same materials in several environments (the shards of one batch); every
-        entry of ``wire_material`` must be one of them."""
+        entry of ``wire_material`` must be one of them.
+        ``dynamic_geometry``: ``{"max_workpiece_height": H, "wire_diameters": (d0, d1, ...)}`` -- a new workpiece height and
+        wire diameter per episode.  Implies per-environment geometry; the wire block is sized for ``H``.  ``workpiece_height``
+        / ``wire_diameter`` give the initial values (heights of at most ``H``, diameters from the list; default:
+        ``config``'s pair, whose diameter must be in the list).  `set_geometry` gives environments new values between
+        launches, derived on the device (`sparc_amd.geometry`), `get_geometry` reads them.  Heights
+        and diameter indices are then state: `snapshot` / `restore` / `fork` carry them and the geometry rows, and
+        `state_dict` saves them.  Combines with ``wire_material`` (whose `set_wire_material` re-derives the rows), ``env_params``
+        and the statistics keywords; runs on the any-geometry kernels (1, 2, 10, 11)."""
         self.render_mode = render_mode
         if mechanics_control_mode not in ["position", "velocity"]:
             raise ValueError(f"mechanics_control_mode must be 'position' or 'velocity', got {mechanics_control_mode}")
@@ -284,20 +294,34 @@ class WireEDMEnv:
 
         # ---- geometry: uniform (reference behaviour) or one (h, d) pair per environment
         stride = (self.num_envs + 63) // 64 * 64
-        self.per_env_geometry = workpiece_height is not None or wire_diameter is not None or mat_index is not None
+        self._dyn = None  # `sparc_amd.geometry.DynamicGeometry` of an environment built with dynamic_geometry=
+        dyn_spec = None if dynamic_geometry is None else _geometry.check_spec(dynamic_geometry)
+        self.per_env_geometry = workpiece_height is not None or wire_diameter is not None or mat_index is not None or \
+            dyn_spec is not None
         self._geom_hd = None  # float64 [2, num_envs]: each slot's (height, diameter), where they are not all the same
         if self.per_env_geometry:
             h = np.broadcast_to(np.asarray(self.config.workpiece_height if workpiece_height is None
                                            else _to_numpy(workpiece_height), dtype=np.float64), (self.num_envs,))
             d = np.broadcast_to(np.asarray(self.config.wire_diameter if wire_diameter is None
                                            else _to_numpy(wire_diameter), dtype=np.float64), (self.num_envs,))
-            gf, gi, n_seg_max = derive.geometry_rows(h, d, self.wire_params, self.wire_material,
-                                                     self.material_params, stride)
+            mats = self.wire_material
+            if dyn_spec is not None:
+                if not (np.isfinite(h).all() and (h > 0).all() and (h <= dyn_spec[0]).all()):
+                    raise ValueError(f"workpiece_height must lie in (0, max_workpiece_height={dyn_spec[0]}] with "
+                                     f"dynamic_geometry, got {float(h[~((h > 0) & (h <= dyn_spec[0]))][0])}")
+                self._dyn = _geometry.DynamicGeometry(self, dyn_spec[0], dyn_spec[1], self.wire_materials or (self.wire_material,),
+                                                      h, _geometry.initial_index(d, dyn_spec[1]), stride)
+                if mat_index is not None:  # (no per-material row table at a fixed height: the rows are derived)
+                    mats = [self.wire_materials[k] for k in mat_index]
+            gf, gi, n_seg_max = derive.geometry_rows(h, d, self.wire_params, mats, self.material_params, stride)
             self.geometry = None
             self._geom_f64 = torch.from_numpy(gf).to(self.device)
             self._geom_i32 = torch.from_numpy(gi).to(self.device)
             self.n_segments = n_seg_max
-            if (h != h[0]).any() or (d != d[0]).any():  # slots differ: `fork` / `restore` hold copies to equal pairs
+            if self._dyn is not None:
+                self.n_segments = self._dyn.n_seg_max  # the capacity: n_seg is monotone in the height
+                self._dyn.bind(self)
+            elif (h != h[0]).any() or (d != d[0]).any():  # slots differ: `fork` / `restore` hold copies to equal pairs
                 self._geom_hd = np.stack([h, d])
             if mat_index is not None:
                 self._init_wire_material(h, d, mat_index, stride)
@@ -535,6 +559,11 @@ class WireEDMEnv:
         if status:
             self._profile_status.zero_()
             raise ValueError(_profile.status_text(status))
+        if self._dyn is not None:
+            status = int(self._dyn.status.item())
+            if status:
+                self._dyn.status.zero_()
+                raise ValueError(_geometry.status_text(status))
 
     def set_kernel(self, variant: int, lanes: int = 0) -> None:
         """0 = auto, 1 = global-memory stencil, 2 = LDS predicated, 3 = LDS fused, 4 = LDS
@@ -668,12 +697,19 @@ class WireEDMEnv:
         ([M, GEOM_F64_COUNT, stride]) and its five material rows ([M, WMAT_COUNT, stride]).  A switch is a device-side
         column select from these tables (`set_wire_material`): exact by construction, no arithmetic."""
         M = len(self.wire_materials)
-        geom = [derive.geometry_rows(h, d, self.wire_params, m, self.material_params, stride)[0] for m in self.wire_materials]
         mats = [derive.material_rows(self.wire_materials, np.full(self.num_envs, k), self.wire_params, stride) for k in range(M)]
-        self._wmat_geom_table = torch.from_numpy(np.stack(geom)).to(self.device)
         self._wmat_table = torch.from_numpy(np.stack(mats)).to(self.device)
         self._wmat_index = torch.zeros(stride, dtype=torch.int64, device=self.device)
         self._wmat_rows = torch.empty((_abi.WMAT_COUNT, stride), dtype=torch.float64, device=self.device)
+        if self._dyn is not None:
+            # dynamic geometry: no row table at a fixed height (it would overwrite the heights); the constructor derived the
+            # geometry rows with each environment's material, later switches re-derive them (`set_wire_material`)
+            self._wmat_geom_table = None
+            self._wmat_index[: self.num_envs].copy_(torch.from_numpy(np.asarray(index, dtype=np.int64)))
+            self._select_wire_material_rows(geometry=False)
+            return
+        geom = [derive.geometry_rows(h, d, self.wire_params, m, self.material_params, stride)[0] for m in self.wire_materials]
+        self._wmat_geom_table = torch.from_numpy(np.stack(geom)).to(self.device)
         self.set_wire_material(index)
 
     def set_wire_material(self, index, mask=None) -> None:
@@ -682,7 +718,9 @@ class WireEDMEnv:
         change to the environments where it is set.  The wire temperatures, and every other state, carry over: a switch
         in mid-episode steps on from the current state with the new material's constants.  Host indices are checked;
         device tensors are applied on the device with no host synchronisation -- an entry outside ``[0,
-        len(wire_materials))`` there leaves its environment's material as it was."""
+        len(wire_materials))`` there leaves its environment's material as it was.  In a ``dynamic_geometry`` environment the
+        geometry rows of the masked environments are derived again from their stored heights and diameter indices with the
+        new material (`sparc_amd.geometry`): the heights survive the switch."""
         if self._wmat_rows is None:
             raise RuntimeError("construct the environment with wire_material=[...] to give environments their own wire material")
         n, M = self.num_envs, len(self.wire_materials)
@@ -711,14 +749,38 @@ class WireEDMEnv:
                 raise ValueError(f"mask must have one entry per environment ({n})")
             idx = torch.where(m, idx, self._wmat_index[:n])
         self._wmat_index[:n].copy_(idx)
-        self._select_wire_material_rows()
+        self._select_wire_material_rows(mask=mask)
 
-    def _select_wire_material_rows(self) -> None:
-        """The geometry and material rows of the current material index, selected from the fixed per-material tables."""
+    def _select_wire_material_rows(self, mask=None, geometry: bool = True) -> None:
+        """The geometry and material rows of the current material index, selected from the fixed per-material tables.  With
+        ``dynamic_geometry`` only the material rows are selected; the geometry rows (of the masked environments) are derived
+        again from the stored heights and diameter indices, unless ``geometry`` is False."""
         n, cur = self.num_envs, self._wmat_index
         cur[n:].copy_(cur[n - 1: n].expand(cur.shape[0] - n))  # padding columns repeat the last environment
-        for table, dst in ((self._wmat_geom_table, self._geom_f64), (self._wmat_table, self._wmat_rows)):
+        tables = ((self._wmat_table, self._wmat_rows),) if self._dyn is not None else \
+            ((self._wmat_geom_table, self._geom_f64), (self._wmat_table, self._wmat_rows))
+        for table, dst in tables:
             dst.copy_(torch.gather(table, 0, cur.view(1, 1, -1).expand(1, table.shape[1], -1))[0])
+        if self._dyn is not None and geometry:
+            _geometry.rederive(self, mask)
+
+    # ---- per-episode workpiece height and wire diameter (sparc_amd.geometry, DESIGN.md section 4.13) ----------
+    def set_geometry(self, workpiece_height=None, wire_diameter_index=None, mask=None, reset: bool = True) -> None:
+        """New workpiece heights [mm] and / or wire diameters (indices into ``dynamic_geometry``'s ``wire_diameters``) for the
+        environments where ``mask`` (bool per environment; default: all) is set.  A value is a scalar, one value per
+        environment (sequence, NumPy array) or a device tensor.  The values are merged under the mask on the device, the
+        geometry rows derived by one launch (`wedm_derive_geometry`) with the bits the host derivation writes, and with
+        ``reset=True`` the masked environments are reset: a new workpiece is a new episode (the wire's length follows the
+        height).  ``reset=False`` is for a caller whose next launch resets exactly those environments itself, as
+        `WireEDMVectorEnv` does; stepping an environment on with rows of another height is not a defined simulation.
+        Nothing is read back: a height that is NaN, infinite, not positive or above ``max_workpiece_height`` and an index
+        outside the list leave that environment's geometry as it was, and `check_errors` raises for them."""
+        _geometry.set_geometry(self, workpiece_height, wire_diameter_index, mask, reset)
+
+    def get_geometry(self) -> Dict[str, torch.Tensor]:
+        """Each environment's current ``workpiece_height`` [mm] (float64), ``wire_diameter`` [mm] (float64) and
+        ``n_segments`` (int32: the cells of its wire), as device copies.  Needs ``dynamic_geometry``."""
+        return _geometry.get_geometry(self)
 
     def get_wire_material_index(self) -> torch.Tensor:
         """Each environment's current material, an index into ``env.wire_materials`` (int64 [num_envs] device copy)."""
@@ -737,7 +799,11 @@ class WireEDMEnv:
         import hashlib
 
         h = hashlib.sha256(ctypes.string_at(ctypes.addressof(self.params), ctypes.sizeof(self.params)))
-        if self.per_env_geometry:
+        if self._dyn is not None:  # capacity, catalogue and table: the current rows change with every episode
+            h.update(self._dyn.fingerprint())
+            if self._wmat_rows is not None:
+                h.update(self._wire_material_fingerprint().encode())
+        elif self.per_env_geometry:
             if self._wmat_rows is not None:
                 h.update(self._wire_material_fingerprint().encode())
             else:
@@ -748,7 +814,8 @@ class WireEDMEnv:
     def _wire_material_fingerprint(self) -> str:
         import hashlib
 
-        h = hashlib.sha256(self._wmat_geom_table.cpu().numpy().tobytes())
+        h = hashlib.sha256(self._dyn.combo_host.tobytes() if self._dyn is not None
+                           else self._wmat_geom_table.cpu().numpy().tobytes())
         h.update(self._wmat_table.cpu().numpy().tobytes())
         return h.hexdigest()
 
@@ -761,7 +828,7 @@ class WireEDMEnv:
                 "n_segments": self.n_segments, "env_id_offset": self.env_id_offset, "pulse_stats": self.pulse_stats,
                 "signal_stats": self.signal_stats,
                 "steps_since_reset": self.steps_since_reset, "physics": self._physics_fingerprint(),
-                **self._env_params_state(), **self._wire_material_state()}
+                **self._env_params_state(), **self._wire_material_state(), **_geometry.state(self)}
 
     def _wire_material_state(self) -> Dict[str, Any]:
         if self._wmat_rows is None:
@@ -799,6 +866,7 @@ class WireEDMEnv:
             raise ValueError(f"checkpoint was taken with per-environment wire materials {theirs_m}, this environment has "
                              f"{mine_m}" + (" (same names, different constants or geometry)" if theirs_m == mine_m else "")
                              + ": the material table differs")
+        _geometry.check_state(self, sd)
         if sd.get("physics") != self._physics_fingerprint():
             raise ValueError("checkpoint was taken with different physics (configuration, module parameters, control "
                              "mode or per-environment geometry): continuing would silently change the trajectory")
@@ -815,6 +883,7 @@ class WireEDMEnv:
         if mine is not None:
             self._envp_src.copy_(sd["env_params_src"])
             self._envp_rows.copy_(sd["env_params_rows"])
+        _geometry.load_state(self, sd)  # heights and indices; the rows are derived from them (below, where materials differ)
         if mine_m is not None:
             self.set_wire_material(sd["wire_material_index"].numpy())
         self._seed = int(sd["seed"])

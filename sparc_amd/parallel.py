@@ -42,6 +42,9 @@ class ShardedWireEDMEnv:
                  workpiece_height=None, wire_diameter=None, env_params=None, wire_material=None, **env_kwargs):
         if not dist.is_initialized():
             raise RuntimeError("ShardedWireEDMEnv needs torch.distributed.init_process_group first")
+        if env_kwargs.get("dynamic_geometry") is not None:
+            raise ValueError("ShardedWireEDMEnv does not offer dynamic_geometry (set_geometry, samplers and checkpoints of a "
+                             "sharded batch are not built: DESIGN.md section 5); build a WireEDMEnv per rank for it")
         self.group = process_group
         self.rank = dist.get_rank(process_group)
         self.world_size = dist.get_world_size(process_group)

@@ -11,7 +11,8 @@ What is copied (`env_blocks`): ``f64``, ``i32``, ``i8``, ``T``, ``obs``, ``stats
 as `WireEDMEnv.set_wire_material` does).  What is not: the trace ring (a recording of a window of slots), the
 injected-variate table (an input keyed by step since the reset, not by state), the host-side ``steps_since_reset``, and
 the geometry rows -- height and diameter belong to the slot, so a copy between slots whose ``(height, diameter)`` differ is
-refused.
+refused.  An environment built with ``dynamic_geometry=`` is the exception: there the two geometry blocks, the height row and
+the diameter-index row are state, join the planes and travel with the copy (`sparc_amd.geometry`).
 
 Without a backend ``copy_columns`` (the CPU oracle backend of the tests) the same plane list is served by plain torch:
 ``index_select`` then ``index_copy_`` block by block, ``T`` through its ``[stride]``-wide 16-byte view.  That path needs
@@ -40,6 +41,10 @@ def env_blocks(env) -> Dict[str, torch.Tensor]:
         out["envp_src"], out["envp_rows"] = env._envp_src, env._envp_rows
     if env._wmat_rows is not None:
         out["wmat_index"] = env._wmat_index.view(1, -1)
+    dyn = getattr(env, "_dyn", None)
+    if dyn is not None:  # dynamic geometry: the rows, the height and the diameter index are state and travel with the copy
+        out["geom_f64"], out["geom_i32"] = env._geom_f64, env._geom_i32
+        out["geom_height"], out["geom_diameter_index"] = dyn.height.view(1, -1), dyn.dia.view(1, -1)
     return out
 
 

@@ -59,6 +59,29 @@ def uniform_material_sampler(generator: Optional[torch.Generator] = None):
     return sample
 
 
+def uniform_geometry_sampler(height: Optional[Tuple[float, float]] = None, diameters: bool = True,
+                             generator: Optional[torch.Generator] = None):
+    """A `geometry_sampler` for `WireEDMVectorEnv`: the workpiece height uniform in ``[low, high)`` [mm] (``height=None``:
+    heights stay) and, with ``diameters=True``, one of the environment's ``dynamic_geometry`` wire diameters uniformly, drawn
+    on the environment's device (``generator`` must live there when given)."""
+    if height is not None:
+        lo, hi = float(height[0]), float(height[1])
+        if not (0.0 < lo <= hi):
+            raise ValueError(f"height range must have 0 < low <= high, got ({lo}, {hi})")
+
+    def sample(env: WireEDMEnv, reset_mask: torch.Tensor) -> Dict[str, torch.Tensor]:
+        out = {}
+        if height is not None:
+            out["workpiece_height"] = lo + (hi - lo) * torch.rand(env.num_envs, generator=generator, device=env.device,
+                                                                  dtype=torch.float64)
+        if diameters:
+            out["wire_diameter_index"] = torch.randint(0, len(env._dyn.diameters), (env.num_envs,), generator=generator,
+                                                       device=env.device, dtype=torch.int64)
+        return out
+
+    return sample
+
+
 class WireEDMVectorEnv:
     """Next-step autoreset (Gymnasium's ``AutoresetMode.NEXT_STEP``): the `step()` after the one that
     reported ``terminated`` / ``truncated`` for an environment starts a new episode for it.
@@ -72,7 +95,7 @@ class WireEDMVectorEnv:
 
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
                  reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
-                 wire_profile_bins: Optional[int] = None):
+                 wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -87,6 +110,11 @@ class WireEDMVectorEnv:
         into ``env.wire_materials``, applied (`WireEDMEnv.set_wire_material`) where ``reset_mask`` is set, at the same
         point as ``param_sampler``.  The environment must have been built with ``wire_material=[...]`` (see
         `uniform_material_sampler`).
+        ``geometry_sampler``: the same for the workpiece height and the wire diameter -- ``f(env, reset_mask) ->
+        {"workpiece_height": float64[N], "wire_diameter_index": int64[N]}`` (device tensors, either key optional), applied
+        (`WireEDMEnv.set_geometry` with ``reset=False``: the reset is this adapter's) where ``reset_mask`` is set, before the
+        other two samplers (the material sampler's re-derivation reads the heights).  The environment must have been built
+        with ``dynamic_geometry={...}`` (see `uniform_geometry_sampler`).
         ``wire_profile_bins``: with an integer B in [0, 64], `reset()` and `step()` return ``[N, obs_dim + 4 + 2 * B]``: the
         environment's observation followed by the rows of `WireEDMEnv.wire_profile` (zone mean, wire mean, maximum,
         hottest cell, B bin maxima, B bin means) of the wire as the launch left it -- one more launch, no host
@@ -124,11 +152,15 @@ class WireEDMVectorEnv:
         self._material_sampler = material_sampler
         if material_sampler is not None and getattr(env, "_wmat_rows", None) is None:
             raise ValueError("material_sampler needs an environment built with wire_material=[...] listing the materials")
+        self._geometry_sampler = geometry_sampler
+        if geometry_sampler is not None and getattr(env, "_dyn", None) is None:
+            raise ValueError("geometry_sampler needs an environment built with dynamic_geometry={...}")
+        self._samples = any(f is not None for f in (param_sampler, material_sampler, geometry_sampler))
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
-        if self._param_sampler is not None or self._material_sampler is not None:
+        if self._samples:
             mask = (options or {}).get("mask")
             mask = torch.ones(self.num_envs, dtype=torch.bool, device=self.env.device) if mask is None else \
                 torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
@@ -145,6 +177,9 @@ class WireEDMVectorEnv:
         return torch.cat([obs, self.env.wire_profile(self.wire_profile_bins)["rows"].t()], dim=1)
 
     def _apply_sampler(self, reset_mask: torch.Tensor) -> None:
+        if self._geometry_sampler is not None:
+            drawn = self._geometry_sampler(self.env, reset_mask)
+            self.env.set_geometry(drawn.get("workpiece_height"), drawn.get("wire_diameter_index"), mask=reset_mask, reset=False)
         if self._param_sampler is not None:
             self.env.set_env_params(self._param_sampler(self.env, reset_mask), mask=reset_mask)
         if self._material_sampler is not None:
@@ -152,7 +187,7 @@ class WireEDMVectorEnv:
 
     def step(self, action):
         """One control interval for every environment (1000 us by default)."""
-        if (self._param_sampler is not None or self._material_sampler is not None) and self.autoreset:
+        if self._samples and self.autoreset:
             self._apply_sampler(self._need_reset)  # environments about to start a new episode draw their physics
         if self.autoreset:
             if self._in_kernel_reset:

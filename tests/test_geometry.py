@@ -1,0 +1,357 @@
+"""Per-episode workpiece height and wire diameter on the GPU: `wedm_derive_geometry` bit for bit
+against the reference table, `derive_geometry` and the NumPy stand-in; its memory contract; and `WireEDMEnv(dynamic_geometry=)`
+/ `WireEDMVectorEnv(geometry_sampler=)` against a twin on the CPU oracle backend that follows the same calls."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from sparc_amd import (EnvironmentConfig, MaterialModuleParameters, WireEDMEnv, WireEDMVectorEnv, WireModuleParameters, _abi,
+                       _lib, uniform_geometry_sampler)
+from sparc_amd.core import derive
+from tests import _geometry_ref as ref
+from tests._compare import assert_blocks_equal
+from tests._oracle_backend import OracleBackend, OracleBackendRows
+from tests.test_env_params import ACTION, prepare
+from tests.test_geometry_host import f4_groups, ROOT
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+N = 100  # neither a multiple of 64 nor of 256
+STRIDES = (100, 128)
+WIRE = WireModuleParameters(buffer_len_bottom=2.0, buffer_len_top=2.0, contact_offset_bottom=1.0, contact_offset_top=1.0)
+DIAMETERS = (0.1, 0.2, 0.25)
+DYN = {"max_workpiece_height": 10.0, "wire_diameters": DIAMETERS}
+MP = MaterialModuleParameters()
+CANARY_F, CANARY_I = -12345.678, -77777
+
+
+def kernel_call(wire, combo, n_dia, n_seg_max, stride, height, dia_idx, mat_idx=None, mask=None):
+    """One `wedm_derive_geometry` into canary-filled blocks with a guard row before and behind each, and the stand-in on a
+    host copy of the same memory: returns ((gf, gi, status) of the device, the same of the stand-in), guards included."""
+    n = len(height)
+    host_f = np.full((_abi.GEOM_F64_COUNT + 2, stride), CANARY_F)
+    host_i = np.full((_abi.GEOM_I32_COUNT + 2, stride), CANARY_I, dtype=np.int32)
+    dev_f, dev_i = torch.from_numpy(host_f).to(DEV), torch.from_numpy(host_i).to(DEV)
+    t_combo = torch.from_numpy(np.ascontiguousarray(combo)).to(DEV)
+    t_h = torch.from_numpy(np.asarray(height, dtype=np.float64)).to(DEV)
+    t_d = torch.from_numpy(np.asarray(dia_idx, dtype=np.int32)).to(DEV)
+    t_m = None if mat_idx is None else torch.from_numpy(np.asarray(mat_idx, dtype=np.int32)).to(DEV)
+    t_k = None if mask is None else torch.from_numpy(np.asarray(mask, dtype=np.uint8)).to(DEV)
+    status = torch.zeros(1, dtype=torch.int32, device=DEV)
+    zs0, cb0 = ref.host_constants(wire)
+    desc = _abi.GeomDeriveDesc(
+        segment_len=wire.segment_len, buffer_len_bottom=wire.buffer_len_bottom, buffer_len_top=wire.buffer_len_top,
+        contact_offset_top=wire.contact_offset_top, zone_start0=zs0, contact_bottom0=cb0, num_envs=n, n_seg_max=n_seg_max,
+        stride=stride, combo=t_combo.data_ptr(), n_diameters=n_dia, n_materials=combo.shape[0] // n_dia,
+        geom_f64=dev_f[1:].data_ptr(), geom_i32=dev_i[1:].data_ptr())
+    L = _lib.load()
+    rc = L.wedm_derive_geometry(C.byref(desc), t_h.data_ptr(), t_d.data_ptr(), None if t_m is None else t_m.data_ptr(),
+                                None if t_k is None else t_k.data_ptr(), status.data_ptr(),
+                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert rc == _abi.OK, L.wedm_last_error(None)
+    torch.cuda.synchronize()
+    want = ref.derive_columns(host_f[1:-1], host_i[1:-1], wire, combo, n_dia, n_seg_max, height, dia_idx, mat_idx, mask)
+    return (dev_f.cpu().numpy(), dev_i.cpu().numpy(), int(status.item())), (host_f, host_i, want)
+
+
+def assert_same(got, want):
+    assert got[2] == want[2], (got[2], want[2])
+    assert got[0].tobytes() == want[0].tobytes(), np.argwhere(got[0].view(np.int64) != want[0].view(np.int64))[:5]
+    assert np.array_equal(got[1], want[1]), np.argwhere(got[1] != want[1])[:5]
+
+
+# ------------------------------------------------------------------------------------------------ 1
+def test_kernel_equals_the_reference_table():
+    """All 672 rows of fixture F4, one call per (seg, buffers, offsets) group: every written value is the fixture's."""
+    groups = f4_groups(ROOT / "tests" / "golden")
+    seen = 0
+    for (seg, bb, bt, cob, cot), rows in groups.items():
+        wire = WireModuleParameters(segment_len=seg, buffer_len_bottom=bb, buffer_len_top=bt, contact_offset_bottom=cob,
+                                    contact_offset_top=cot)
+        dias = sorted({r["d"] for r in rows})
+        combo = ref.combination_table([ref.BRASS], dias, wire, MP)
+        h = np.array([r["h"] for r in rows])
+        di = np.array([dias.index(r["d"]) for r in rows])
+        n_max = int(max(r["n_seg"] for r in rows))
+        got, want = kernel_call(wire, combo, len(dias), n_max, len(rows) + 3, h, di)
+        assert_same(got, want)
+        assert got[2] == 0
+        gf, gi = got[0][1:-1], got[1][1:-1]
+        for e, r in enumerate(rows):
+            for row, name in zip(_abi.GI32, ref.INT_NAMES):
+                assert gi[row, e] == int(r[name]), (name, r)
+            for row, name in ((_abi.GF64.K_COND, "k_cond"), (_abi.GF64.TUF, "tuf"), (_abi.GF64.A_SURF, "a_surf"),
+                              (_abi.GF64.S_AREA, "s_area"), (_abi.GF64.JOULE_GEOM, "joule_geom"),
+                              (_abi.GF64.CAVITY_COEFF, "cavity_coeff"), (_abi.GF64.HEIGHT, "h")):
+                assert gf[row, e] == r[name], (name, r)
+            g = derive.derive_geometry(r["h"], r["d"], wire, ref.BRASS, MP)
+            assert gf[_abi.GF64.KERF_BASE, e] == g.kerf_base
+            seen += 1
+    assert seen == 672
+
+
+# ------------------------------------------------------------------------------------------------ 2
+@pytest.mark.parametrize("seg", [0.2, 0.625])
+def test_kernel_equals_the_stand_in_at_cell_boundaries(seg):
+    """Heights k * seg, one ulp above, just below; a scattered mask; two materials x three diameters."""
+    wire = WireModuleParameters(segment_len=seg)
+    mats = [ref.BRASS, ref.COPPER]
+    combo = ref.combination_table(mats, DIAMETERS, wire, MP)
+    h = ref.boundary_heights(seg)
+    n = len(h)
+    rng = np.random.default_rng(17)
+    di, mi, mask = rng.integers(0, 3, n), rng.integers(0, 2, n), rng.random(n) < 0.7
+    n_max = int(ref.height_part(h, wire)["n_seg"].max())
+    got, want = kernel_call(wire, combo, 3, n_max, n + 5, h, di, mi, mask)
+    assert_same(got, want)
+    assert got[2] == 0 and (got[0][1, :n][~mask] == CANARY_F).all()
+    for e in np.flatnonzero(mask)[:: 7]:  # the stand-in itself is held to `derive_geometry` by the host tests; a sample here
+        g = derive.derive_geometry(float(h[e]), DIAMETERS[di[e]], wire, mats[mi[e]], MP)
+        assert tuple(got[1][1:-1, e]) == (g.n_seg, g.zone_start, g.az_start, g.az_end, g.contact_bottom, g.contact_top)
+        assert got[0][1:-1, e].tobytes() == np.array([g.workpiece_height, g.kerf_base, g.cavity_coeff, g.k_cond, g.tuf,
+                                                       g.a_surf, g.s_area, g.joule_geom]).tobytes()
+
+
+# ------------------------------------------------------------------------------------------------ 3
+def capacity_edge(wire, n_seg_max):
+    """(the largest height whose wire has n_seg_max cells, the next float64: one cell over)."""
+    seg, bb, bt = (np.float64(x) for x in (wire.segment_len, wire.buffer_len_bottom, wire.buffer_len_top))
+    h = np.float64((n_seg_max + 1) * seg - bb - bt) + 1e-12
+    while not ((bb + h) + bt) / seg < n_seg_max + 1.0:
+        h = np.nextafter(h, 0.0)
+    return float(h), float(np.nextafter(h, np.inf))
+
+
+@pytest.mark.parametrize("stride", STRIDES)
+def test_kernel_writes_only_what_it_owns_and_refuses_bad_inputs(stride):
+    """Canaries in the padding columns, the unmasked columns and the guard rows around both blocks; each bad input leaves its
+    column alone and sets exactly its bit, the good columns of the same call are written.  Nothing is provoked: the
+    inputs are refused, not followed."""
+    combo = ref.combination_table([ref.BRASS, ref.COPPER], DIAMETERS, WIRE, MP)
+    fits, over = capacity_edge(WIRE, 70)
+    assert int(ref.height_part(np.array([fits, over]), WIRE)["n_seg"][1]) == 71
+    h0 = np.linspace(1.0, 10.0, N)
+    di0, mi0 = np.arange(N) % 3, (np.arange(N) // 3) % 2
+    mask = np.arange(N) % 5 != 2
+    bad_col = 40  # masked
+    assert mask[bad_col]
+    for what, bit in ((("h", np.nan), 1), (("h", np.inf), 1), (("h", 0.0), 1), (("h", -1.0), 1), (("h", over), 2),
+                      (("d", -1), 4), (("d", 3), 4), (("m", 2), 4), (("h", fits), 0)):
+        h, di, mi = h0.copy(), di0.copy(), mi0.copy()
+        {"h": h, "d": di, "m": mi}[what[0]][bad_col] = what[1]
+        got, want = kernel_call(WIRE, combo, 3, 70, stride, h, di, mi, mask)
+        assert_same(got, want)
+        assert got[2] == bit, (what, got[2])
+        gf, gi = got[:2]
+        assert (gf[[0, -1]] == CANARY_F).all() and (gi[[0, -1]] == CANARY_I).all()                     # guard rows
+        assert (gf[:, N:] == CANARY_F).all() and (gi[:, N:] == CANARY_I).all()                         # padding columns
+        assert (gf[:, :N][:, ~mask] == CANARY_F).all() and (gi[:, :N][:, ~mask] == CANARY_I).all()     # unmasked columns
+        written = mask.copy()
+        written[bad_col] = bit == 0
+        assert (gf[1:-1, :N][:, written] != CANARY_F).all() and (gi[1:-1, :N][:, written] != CANARY_I).all()
+        if bit:
+            assert (gf[:, bad_col] == CANARY_F).all() and (gi[:, bad_col] == CANARY_I).all()
+        else:
+            assert gi[1 + _abi.GI32.N_SEG, bad_col] == 70
+    # an unmasked bad input is not looked at
+    h = h0.copy()
+    h[2] = np.nan
+    got, want = kernel_call(WIRE, combo, 3, 70, stride, h, di0, mi0, mask)
+    assert_same(got, want)
+    assert got[2] == 0
+
+
+# ------------------------------------------------------------------------------------------------ 4 - 6: the environment
+H0 = np.linspace(1.0, 10.0, N)
+D0 = np.resize(DIAMETERS, N)
+THIRD_A, THIRD_B = np.arange(N) % 3 == 0, np.arange(N) % 3 == 1
+H_A, DI_A = np.linspace(9.9, 1.1, N), (np.arange(N) // 3) % 3
+H_B, DI_B = np.linspace(2.05, 8.95, N), (np.arange(N) // 2) % 3
+MATS = [ref.BRASS, ref.COPPER]
+
+
+def make(device, backend=None, **kw):
+    kw.setdefault("config", EnvironmentConfig(target_cutting_distance=5000.0))
+    if backend is not None:
+        kw["backend"] = backend
+    return WireEDMEnv(num_envs=N, device=device, wire_params=WIRE, dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0,
+                      **kw)
+
+
+def on(env, x, dtype=None):
+    """Host values for the twin, device tensors for the GPU environment: both input forms see the same calls."""
+    return torch.as_tensor(x, dtype=dtype).to(env.device) if env.device.type == "cuda" else x
+
+
+def scenario(env, materials=False):
+    """set_geometry on a third, 3 x 300 us, set_geometry on another third (and a material switch), 300 us more."""
+    env.set_geometry(on(env, H_A), on(env, DI_A), mask=on(env, THIRD_A))
+    prepare(env, N)
+    act = env.make_action(*ACTION)
+    for _ in range(3):
+        env.step_many(act, 300)
+    env.set_geometry(on(env, H_B), on(env, DI_B), mask=on(env, THIRD_B))
+    if materials:
+        env.set_wire_material(on(env, 1 - np.arange(N) % 2), mask=on(env, np.arange(N) % 4 < 2))
+    env.step_many(act, 300)
+    if env.device.type == "cuda":
+        torch.cuda.synchronize()
+    env.check_errors()
+    return env
+
+
+_TWINS = {}
+
+
+def twin(materials=False):
+    if materials not in _TWINS:
+        kw = dict(wire_material=[MATS[k] for k in np.arange(N) % 2]) if materials else {}
+        _TWINS[materials] = scenario(make("cpu", OracleBackendRows if materials else OracleBackend, **kw), materials)
+    return _TWINS[materials]
+
+
+def assert_equals_twin(env, t):
+    assert_blocks_equal(env.state.clone_blocks(), t.state.clone_blocks(), N)
+    assert torch.equal(env._geom_f64[:, :N].cpu(), t._geom_f64[:, :N]) and torch.equal(env._geom_i32[:, :N].cpu(), t._geom_i32[:, :N])
+    g, w = env.get_geometry(), t.get_geometry()
+    for k in w:
+        assert torch.equal(g[k].cpu(), w[k]), k
+    h = np.where(THIRD_B, H_B, np.where(THIRD_A, H_A, H0))
+    assert g["workpiece_height"].cpu().numpy().tobytes() == h.tobytes()
+    assert np.array_equal(g["n_segments"].cpu().numpy(), ref.height_part(h, WIRE)["n_seg"])
+    # the profile follows the new n_seg: every environment's own wire and zone
+    assert torch.equal(env.wire_profile(bins=4)["rows"].cpu(), t.wire_profile(bins=4)["rows"])
+    assert torch.equal(env.zone_mean_temperature().cpu(), t.zone_mean_temperature())
+    env.check_errors()
+
+
+def legal_lanes(**kw):
+    env, out = make(DEV, **kw), []
+    for L in (1, 2, 4, 8, 16):
+        env.set_kernel(2, L)
+        try:
+            env.step_many(env.make_action(*ACTION), 1)
+            out.append(L)
+        except _lib.WedmError:  # a lane count whose chunks do not fit
+            pass
+    return out
+
+
+@pytest.mark.parametrize("materials", [False, True], ids=["geometry", "geometry+material"])
+def test_environment_equals_the_oracle_twin_on_every_any_geometry_kernel(materials):
+    kw = dict(wire_material=[MATS[k] for k in np.arange(N) % 2]) if materials else {}
+    t = twin(materials)
+    assert int(t.state.spark_count.sum()) > 0
+    lanes = legal_lanes(**kw)
+    assert lanes, "kernel 2 has no legal lane count here"
+    for kernel, L in [(1, 0)] + [(2, L) for L in lanes]:
+        env = make(DEV, **kw)
+        env.set_kernel(kernel, L)
+        scenario(env, materials)
+        name = env._backend.last_kernel()
+        assert ("wedm_step_global" if kernel == 1 else "wedm_step_lanes_pk") in name, name
+        assert_equals_twin(env, t)
+        if materials:
+            assert torch.equal(env._wmat_rows[:, :N].cpu(), t._wmat_rows[:, :N])
+
+
+def test_fork_carries_the_geometry_into_a_slot_of_another_height():
+    h = H0.copy()
+    h[5], h[60] = 3.0, 9.0
+    envs = []
+    for device, backend in ((DEV, None), ("cpu", OracleBackend)):
+        env = WireEDMEnv(num_envs=N, device=device, wire_params=WIRE, dynamic_geometry=DYN, workpiece_height=h, wire_diameter=D0,
+                         config=EnvironmentConfig(target_cutting_distance=5000.0), **({} if backend is None else {"backend": backend}))
+        prepare(env, N)
+        act = env.make_action(*ACTION)
+        env.step_many(act, 300)
+        env.fork(on(env, [5]), on(env, [60]))
+        assert torch.equal(env._geom_f64[:, 60], env._geom_f64[:, 5]) and torch.equal(env._geom_i32[:, 60], env._geom_i32[:, 5])
+        g = env.get_geometry()
+        assert float(g["workpiece_height"][60]) == 3.0 and float(g["wire_diameter"][60]) == float(g["wire_diameter"][5])
+        assert int(g["n_segments"][60]) == int(g["n_segments"][5]) == 35
+        env.step_many(act, 300)
+        env.check_errors()
+        envs.append(env)
+    torch.cuda.synchronize()
+    assert_blocks_equal(envs[0].state.clone_blocks(), envs[1].state.clone_blocks(), N)
+    assert torch.equal(envs[0]._geom_i32[:, :N].cpu(), envs[1]._geom_i32[:, :N])
+
+
+# ------------------------------------------------------------------------------------------------ 7
+def test_vector_adapter_resamples_without_a_host_synchronisation():
+    env = make(DEV, autoreset=True, reward="progress", config=EnvironmentConfig(target_cutting_distance=50.01))
+    gen = torch.Generator(device=DEV).manual_seed(5)
+    vec = WireEDMVectorEnv(env, geometry_sampler=uniform_geometry_sampler(height=(1.0, 10.0), generator=gen))
+    vec.reset(seed=3)
+    act = env.make_action(0.5, 80.0, 9, 3.0, 30.0)
+    geoms, dues, rows = [env.get_geometry()], [], []
+    torch.cuda.set_sync_debug_mode("error")
+    try:
+        for _ in range(10):
+            dues.append(vec._need_reset.clone())
+            vec.step(act)
+            geoms.append(env.get_geometry())
+            rows.append((env._geom_f64.clone(), env._geom_i32.clone()))
+    finally:
+        torch.cuda.set_sync_debug_mode("default")
+    torch.cuda.synchronize()
+    env.check_errors()
+    total = torch.zeros(N, dtype=torch.bool)
+    for i, due in enumerate(dues):
+        due = due.cpu()
+        total |= due
+        for k in geoms[i]:
+            assert torch.equal(geoms[i][k].cpu()[~due], geoms[i + 1][k].cpu()[~due]), (i, k)  # no reset: geometry kept, bit for bit
+        if i:
+            keep = ~due
+            assert torch.equal(rows[i][0][:, :N].cpu()[:, keep], rows[i - 1][0][:, :N].cpu()[:, keep])
+            assert torch.equal(rows[i][1][:, :N].cpu()[:, keep], rows[i - 1][1][:, :N].cpu()[:, keep])
+        assert (geoms[i]["workpiece_height"].cpu()[due] != geoms[i + 1]["workpiece_height"].cpu()[due]).all()
+        # every environment holds the rows `derive_geometry` gives for what it drew
+        h, d = geoms[i + 1]["workpiece_height"].cpu().numpy(), geoms[i + 1]["wire_diameter"].cpu().numpy()
+        gf, gi = rows[i][0][:, :N].cpu().numpy(), rows[i][1][:, :N].cpu().numpy()
+        for e in np.flatnonzero(due.numpy()):
+            g = derive.derive_geometry(float(h[e]), float(d[e]), WIRE, ref.BRASS, MP)
+            assert tuple(gi[:, e]) == (g.n_seg, g.zone_start, g.az_start, g.az_end, g.contact_bottom, g.contact_top)
+            assert gf[:, e].tobytes() == np.array([g.workpiece_height, g.kerf_base, g.cavity_coeff, g.k_cond, g.tuf, g.a_surf,
+                                                   g.s_area, g.joule_geom]).tobytes()
+    assert total.any() and not total.all(), int(total.sum())
+    assert (1.0 <= geoms[-1]["workpiece_height"]).all() and (geoms[-1]["workpiece_height"] < 10.0).all()
+
+
+# ------------------------------------------------------------------------------------------------ 8
+def test_refused_device_values_reach_check_errors_and_leave_rows_and_stored_values_in_step():
+    """Device tensors are never read back: the kernel refuses, the status word reaches `check_errors`, and the heights and
+    indices the environment stores stay those the rows were derived from: `sparc_amd.geometry.derive_rows` reads the kernel's
+    own decision off the N_SEG row, so they agree at the capacity's edge too, where a torch division by a scalar does not."""
+    env = make(DEV)
+    fits, over = capacity_edge(WIRE, env.n_segments)
+    h, di = np.linspace(1.5, 9.5, N), (np.arange(N) // 4) % 3
+    h[[3, 9, 17, 33, 40, 42]] = [np.nan, np.inf, 0.0, -1.0, over, fits]
+    di[[50, 51]] = [-1, 3]
+    mask = np.arange(N) % 7 != 6
+    assert mask[[3, 9, 17, 33, 40, 42, 50, 51]].all()
+    gf, gi = env._geom_f64.cpu().numpy().copy(), env._geom_i32.cpu().numpy().copy()
+    combo = ref.combination_table([ref.BRASS], DIAMETERS, WIRE, MP)
+    hc, dc = np.where(mask, h, H0), np.where(mask, di, np.resize([0, 1, 2], N))
+    assert ref.derive_columns(gf, gi, WIRE, combo, 3, env.n_segments, hc, dc, None, mask) == 7
+    env.set_geometry(torch.from_numpy(h).to(DEV), torch.from_numpy(di).to(DEV), mask=torch.from_numpy(mask).to(DEV))
+    assert env._geom_f64.cpu().numpy().tobytes() == gf.tobytes() and np.array_equal(env._geom_i32.cpu().numpy(), gi)
+    g = env.get_geometry()
+    assert g["workpiece_height"].cpu().numpy().tobytes() == gf[_abi.GF64.HEIGHT, :N].tobytes()
+    bad = np.zeros(N, dtype=bool)
+    bad[[3, 9, 17, 33, 40, 50, 51]] = True
+    want_d = np.where(mask & ~bad, np.asarray(DIAMETERS)[np.clip(di, 0, 2)], D0)
+    assert np.array_equal(g["wire_diameter"].cpu().numpy(), want_d)
+    assert int(g["n_segments"][42]) == env.n_segments
+    with pytest.raises(ValueError) as exc:
+        env.check_errors()
+    for word in ("NaN, infinite or not positive", "above max_workpiece_height", "outside the catalogue"):
+        assert word in str(exc.value)
+    env.check_errors()

@@ -1,0 +1,297 @@
+"""Per-episode geometry without a GPU: the split derivation of `wedm_derive_geometry`, in its NumPy
+stand-in, against `derive_geometry`; the ABI mirror; and `WireEDMEnv(dynamic_geometry=)` on the CPU oracle backend, where the
+rows come from `derive.geometry_rows` under the same mask and refusals as the kernel's."""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import re
+import subprocess
+from pathlib import Path
+
+import numpy as np
+import pytest
+import torch
+
+from sparc_amd import (EnvironmentConfig, MaterialModuleParameters, WireEDMEnv, WireEDMVectorEnv, WireModuleParameters, _abi,
+                       _lib, uniform_geometry_sampler)
+from sparc_amd.core import derive
+from sparc_amd.core.material_db import get_material_db
+from tests import _geometry_ref as ref
+from tests._compare import assert_blocks_equal
+from tests._oracle_backend import OracleBackend, OracleBackendRows
+
+ROOT = Path(__file__).resolve().parents[1]
+WIRE = WireModuleParameters(buffer_len_bottom=2.0, buffer_len_top=2.0, contact_offset_bottom=1.0, contact_offset_top=1.0)
+DYN = {"max_workpiece_height": 10.0, "wire_diameters": (0.1, 0.2, 0.25)}
+ACTION = (0.1, 80.0, 9, 3.0, 30.0)
+N = 12
+
+
+def against_derive_geometry(heights, diameter, wire, material):
+    """The stand-in's 14 values of every height, bit for bit against `derive_geometry`."""
+    mp = MaterialModuleParameters()
+    combo = ref.combination_table([material], [diameter], wire, mp)
+    n = len(heights)
+    gf, gi = np.full((_abi.GEOM_F64_COUNT, n), np.nan), np.full((_abi.GEOM_I32_COUNT, n), -7, dtype=np.int32)
+    assert ref.derive_columns(gf, gi, wire, combo, 1, 2**30, heights, np.zeros(n, dtype=np.int64)) == 0
+    ints = ref.height_part(heights, wire)
+    for e, h in enumerate(heights):
+        g = derive.derive_geometry(float(h), diameter, wire, material, mp)
+        assert tuple(gi[:, e]) == (g.n_seg, g.zone_start, g.az_start, g.az_end, g.contact_bottom, g.contact_top), (h, diameter)
+        assert int(ints["zone_end"][e]) == g.zone_end
+        want = np.array([g.workpiece_height, g.kerf_base, g.cavity_coeff, g.k_cond, g.tuf, g.a_surf, g.s_area, g.joule_geom])
+        assert gf[:, e].tobytes() == want.tobytes(), (h, diameter)
+
+
+def f4_groups(golden_dir):
+    z = np.load(golden_dir / "f4_geometry_table.npz")
+    cols = json.loads(str(z["columns"]))
+    rows = [dict(zip(cols, r)) for r in z["table"]]
+    groups = {}
+    for r in rows:
+        groups.setdefault((r["seg"], r["buf_bottom"], r["buf_top"], r["off_bottom"], r["off_top"]), []).append(r)
+    return groups
+
+
+@pytest.fixture(scope="module")
+def golden_dir():
+    return ROOT / "tests" / "golden"
+
+
+def test_stand_in_matches_the_reference_table(golden_dir):
+    """All 672 rows of fixture F4 (the reference's own constructors): the stand-in's values equal the fixture's columns
+    and `derive_geometry`."""
+    brass = get_material_db().get_wire_material("brass")
+    groups = f4_groups(golden_dir)
+    assert sum(len(g) for g in groups.values()) == 672
+    mp = MaterialModuleParameters()
+    for (seg, bb, bt, cob, cot), rows in groups.items():
+        wire = WireModuleParameters(segment_len=seg, buffer_len_bottom=bb, buffer_len_top=bt, contact_offset_bottom=cob,
+                                    contact_offset_top=cot)
+        dias = sorted({r["d"] for r in rows})
+        combo = ref.combination_table([brass], dias, wire, mp)
+        h = np.array([r["h"] for r in rows])
+        di = np.array([dias.index(r["d"]) for r in rows])
+        gf, gi = np.zeros((_abi.GEOM_F64_COUNT, len(rows))), np.zeros((_abi.GEOM_I32_COUNT, len(rows)), dtype=np.int32)
+        assert ref.derive_columns(gf, gi, wire, combo, len(dias), 2**30, h, di) == 0
+        for e, r in enumerate(rows):
+            for row, name in zip(_abi.GI32, ref.INT_NAMES):
+                assert gi[row, e] == int(r[name]), (name, r)
+            for row, name in ((_abi.GF64.K_COND, "k_cond"), (_abi.GF64.TUF, "tuf"), (_abi.GF64.A_SURF, "a_surf"),
+                              (_abi.GF64.S_AREA, "s_area"), (_abi.GF64.JOULE_GEOM, "joule_geom"),
+                              (_abi.GF64.CAVITY_COEFF, "cavity_coeff")):
+                assert gf[row, e] == r[name], (name, r)
+        for d in dias:
+            against_derive_geometry(h[di == dias.index(d)], d, wire, brass)
+
+
+@pytest.mark.parametrize("seg", [0.2, 0.625])
+def test_stand_in_matches_derive_geometry_at_cell_boundaries(seg):
+    """Heights k * seg, one ulp above and just below: where trunc and floor-divide change their integer."""
+    wire = WireModuleParameters(segment_len=seg)
+    copper = ref.COPPER
+    against_derive_geometry(ref.boundary_heights(seg), 0.25, wire, copper)
+    against_derive_geometry(ref.boundary_heights(seg, 60), 0.1, WireModuleParameters(
+        segment_len=seg, buffer_len_bottom=2.0, buffer_len_top=2.0, contact_offset_bottom=1.0, contact_offset_top=1.0), copper)
+
+
+def test_header_declares_and_library_exports_the_call():
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "wedm_hip.h").read_text(), flags=re.S)
+    assert re.search(r"\bwedm_derive_geometry\s*\(", text) and "wedm_geom_derive_desc" in text
+    assert "#define WEDM_ABI_VERSION 4" in text
+    assert "wedm_derive_geometry" in _lib.EXPORTS
+    L = _lib.load()
+    assert hasattr(L, "wedm_derive_geometry")
+    assert L.wedm_derive_geometry(None, None, None, None, None, None, None) == _abi.ERR_BAD_ARG
+    assert b"wedm_derive_geometry: null descriptor" in L.wedm_last_error(None)
+    d = _abi.GeomDeriveDesc(segment_len=0.2, buffer_len_bottom=2.0, buffer_len_top=2.0, contact_offset_top=1.0, num_envs=4,
+                            n_seg_max=70, stride=2, combo=8, n_diameters=1, n_materials=1, geom_f64=8, geom_i32=8)
+    assert L.wedm_derive_geometry(C.byref(d), 8, 8, None, None, None, None) == _abi.ERR_BAD_ARG
+    assert b"stride smaller than num_envs" in L.wedm_last_error(None)
+
+
+def test_enum_and_descriptor_mirror_the_header(tmp_path):
+    text = (ROOT / "include" / "wedm_hip.h").read_text()
+    body = re.sub(r"/\*.*?\*/", "", re.search(r"enum wedm_geomc_field \{(.*?)\};", text, flags=re.S).group(1), flags=re.S)
+    names = [n.strip().split("=")[0].strip() for n in body.split(",") if n.strip()]
+    assert names[-1] == "WEDM_GEOMC_COUNT" and len(names) == _abi.GEOMC_COUNT + 1
+    for idx, n in enumerate(names[:-1]):
+        assert _abi.GEOMC[n[len("WEDM_GC_"):]].value == idx
+    cname, mirror = "wedm_geom_derive_desc", _abi.GeomDeriveDesc
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "wedm_hip.h"', "int main(void) {",
+             f'  printf("size %zu\\n", sizeof({cname}));']
+    lines += [f'  printf("{field} %zu\\n", offsetof({cname}, {field}));' for field, _ in mirror._fields_]
+    lines += ["  return 0;", "}"]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(lines))
+    subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", f"-I{ROOT / 'include'}", str(src), "-o", str(exe)],
+                   check=True)
+    out = dict(row.split() for row in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    assert C.sizeof(mirror) == int(out.pop("size"))
+    assert {f: getattr(mirror, f).offset for f, _ in mirror._fields_} == {k: int(v) for k, v in out.items()}
+
+
+# ---------------------------------------------------------------------------------- the environment, on the oracle backend
+def make(n=N, backend=OracleBackend, **kw):
+    kw.setdefault("config", EnvironmentConfig(target_cutting_distance=5000.0))
+    return WireEDMEnv(num_envs=n, device="cpu", backend=backend, wire_params=WIRE, **kw)
+
+
+def start(env, n=N):
+    env.state.workpiece_position = torch.linspace(10.4, 25.0, n, dtype=torch.float64)
+    env.state.wire_position = 10.0
+    env.state.target_position = 5000.0
+
+
+H0 = np.linspace(1.0, 10.0, N)
+D0 = np.resize([0.1, 0.2, 0.25], N)
+MASK = np.arange(N) % 3 == 1
+H1 = np.where(MASK, np.linspace(9.7, 1.3, N), H0)
+DI1 = np.where(MASK, (np.arange(N) // 3) % 3, np.resize([0, 1, 2], N))
+
+
+def test_set_geometry_under_a_mask_equals_an_environment_built_with_the_merged_values():
+    a = make(dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0)
+    assert a.n_segments == 70 and a.per_env_geometry
+    b = make(workpiece_height=H1, wire_diameter=np.asarray(DYN["wire_diameters"])[DI1])  # built as the parent commit builds it
+    a.reset(seed=31)
+    a.set_geometry(workpiece_height=np.linspace(9.7, 1.3, N), wire_diameter_index=(np.arange(N) // 3) % 3, mask=MASK)
+    b.reset(seed=31)
+    b.reset(options={"mask": MASK})
+    assert torch.equal(a._geom_f64[:, :N], b._geom_f64[:, :N]) and torch.equal(a._geom_i32[:, :N], b._geom_i32[:, :N])
+    g = a.get_geometry()
+    assert g["workpiece_height"].numpy().tobytes() == H1.tobytes()
+    assert np.array_equal(g["wire_diameter"].numpy(), np.asarray(DYN["wire_diameters"])[DI1])
+    assert np.array_equal(g["n_segments"].numpy(), ref.height_part(H1, WIRE)["n_seg"])
+    for env in (a, b):
+        start(env)
+        act = env.make_action(*ACTION)
+        for _ in range(3):
+            env.step_many(act, 300)
+    a.check_errors()
+    assert int(a.state.spark_count.sum()) > 0
+    assert_blocks_equal(a.state.clone_blocks(), b.state.clone_blocks(), N, T_rows=b.n_segments)
+    assert torch.equal(a.zone_mean_temperature(), b.zone_mean_temperature())
+
+
+def test_refusals():
+    a = make(dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0)
+    before = (a._geom_f64.clone(), a._geom_i32.clone(), a.get_geometry())
+    for kw, word in ((dict(workpiece_height=10.5), "above max_workpiece_height"),
+                     (dict(workpiece_height=float("nan")), "NaN"), (dict(workpiece_height=0.0), "not positive"),
+                     (dict(wire_diameter_index=3), "outside the catalogue"), (dict(wire_diameter_index=-1), "outside the catalogue")):
+        a.set_geometry(mask=MASK, reset=False, **kw)
+        with pytest.raises(ValueError, match=word):
+            a.check_errors()
+        a.check_errors()  # reported once, then cleared
+        assert torch.equal(a._geom_f64, before[0]) and torch.equal(a._geom_i32, before[1])
+        assert all(torch.equal(v, before[2][k]) for k, v in a.get_geometry().items())
+    # a bad value in one environment does not keep the others from being written
+    h = np.full(N, 4.0)
+    h[2] = 11.0
+    a.set_geometry(workpiece_height=h, reset=False)
+    with pytest.raises(ValueError, match="above max_workpiece_height"):
+        a.check_errors()
+    want = np.where(np.arange(N) == 2, H0, 4.0)
+    assert np.array_equal(a.get_geometry()["workpiece_height"].numpy(), want)
+    assert np.array_equal(a._geom_f64[_abi.GF64.HEIGHT, :N].numpy(), want)
+    # constructor values are host values: checked at once
+    with pytest.raises(ValueError, match="max_workpiece_height"):
+        make(dynamic_geometry=DYN, workpiece_height=10.5, wire_diameter=0.2)
+    with pytest.raises(ValueError, match="not in dynamic_geometry"):
+        make(dynamic_geometry=DYN, workpiece_height=5.0, wire_diameter=0.3)
+    with pytest.raises(ValueError, match="max_workpiece_height"):
+        make(dynamic_geometry=DYN)  # the default is config's pair: its 20 mm do not fit 10
+    # an environment without the keyword
+    plain = make(workpiece_height=H0, wire_diameter=D0)
+    for call in (lambda: plain.set_geometry(workpiece_height=3.0), plain.get_geometry):
+        with pytest.raises(RuntimeError, match="dynamic_geometry"):
+            call()
+    with pytest.raises(ValueError, match="dynamic_geometry"):
+        WireEDMVectorEnv(plain, geometry_sampler=uniform_geometry_sampler(height=(1.0, 10.0)))
+    # checkpoints across capacities
+    small = make(dynamic_geometry=dict(DYN, max_workpiece_height=8.0), workpiece_height=np.minimum(H0, 8.0), wire_diameter=D0)
+    with pytest.raises(ValueError):
+        small.load_state_dict(a.state_dict())
+    other = make(dynamic_geometry=dict(DYN, wire_diameters=(0.1, 0.2, 0.25, 0.3)), workpiece_height=H0, wire_diameter=D0)
+    with pytest.raises(ValueError, match="catalogue"):
+        other.load_state_dict(a.state_dict())
+    with pytest.raises(ValueError):
+        plain.load_state_dict(a.state_dict())
+
+
+def test_snapshot_carries_its_geometry_and_checkpoints_rederive_it():
+    a = make(dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0)
+    a.reset(seed=5)
+    start(a)
+    act = a.make_action(*ACTION)
+    a.step_many(act, 200)
+    snap = a.snapshot([2])       # height 2.6..., 35-ish cells
+    col = {k: v[:, 2].clone() for k, v in (("f", a._geom_f64), ("i", a._geom_i32))}
+    a.restore(snap, [9])         # a slot of another height and diameter
+    assert torch.equal(a._geom_f64[:, 9], col["f"]) and torch.equal(a._geom_i32[:, 9], col["i"])
+    g = a.get_geometry()
+    assert g["workpiece_height"][9] == g["workpiece_height"][2] == H0[2] and g["wire_diameter"][9] == D0[2]
+    assert torch.equal(a.state.f64[:, 9], a.state.f64[:, 2])
+    a.fork([0], [11])
+    assert torch.equal(a._geom_i32[:, 11], a._geom_i32[:, 0]) and a.get_geometry()["workpiece_height"][11] == H0[0]
+    # a checkpoint saves heights and indices; the rows are derived again on load, in an environment that started elsewhere
+    sd = a.state_dict()
+    b = make(dynamic_geometry=DYN, workpiece_height=5.0, wire_diameter=0.2)
+    b.load_state_dict(sd)
+    assert torch.equal(a._geom_f64[:, :N], b._geom_f64[:, :N]) and torch.equal(a._geom_i32[:, :N], b._geom_i32[:, :N])
+    for env in (a, b):
+        env.step_many(env.make_action(*ACTION), 200)
+    assert_blocks_equal(a.state.clone_blocks(), b.state.clone_blocks(), N)
+    # environments without the keyword keep refusing a copy between slots of differing height
+    plain = make(workpiece_height=H0, wire_diameter=D0)
+    with pytest.raises(ValueError, match="geometry belongs to the slot"):
+        plain.fork([0], [11])
+
+
+def test_wire_material_switch_keeps_the_heights():
+    mats = [ref.BRASS, ref.COPPER]
+    a = make(backend=OracleBackendRows, dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0,
+             wire_material=list(np.resize(mats, N)))
+    a.set_geometry(workpiece_height=np.linspace(9.7, 1.3, N), wire_diameter_index=(np.arange(N) // 3) % 3, mask=MASK)
+    flip = np.arange(N) % 4 < 2
+    idx = np.where(flip, 1 - np.arange(N) % 2, np.arange(N) % 2)
+    a.set_wire_material(1 - np.arange(N) % 2, mask=flip)
+    b = make(backend=OracleBackendRows, workpiece_height=H1, wire_diameter=np.asarray(DYN["wire_diameters"])[DI1],
+             wire_material=[mats[k] for k in idx], wire_material_table=mats)
+    assert torch.equal(a._geom_f64[:, :N], b._geom_f64[:, :N]) and torch.equal(a._geom_i32[:, :N], b._geom_i32[:, :N])
+    assert torch.equal(a._wmat_rows[:, :N], b._wmat_rows[:, :N])
+    assert a.get_geometry()["workpiece_height"].numpy().tobytes() == H1.tobytes()
+
+
+def test_vector_adapter_draws_a_geometry_for_every_new_episode():
+    """The adapter's own masked reset (the environment has no in-kernel autoreset): environments due for a reset draw a
+    geometry, the others keep theirs, and every row equals `derive_geometry` of what its environment holds."""
+    env = make(dynamic_geometry=DYN, workpiece_height=H0, wire_diameter=D0,
+               config=EnvironmentConfig(target_cutting_distance=50.01))  # 10 nm past the initial gap: a few control steps
+    gen = torch.Generator().manual_seed(3)
+    vec = WireEDMVectorEnv(env, geometry_sampler=uniform_geometry_sampler(height=(1.0, 10.0), generator=gen))
+    vec.reset(seed=2)
+    assert not torch.equal(env.get_geometry()["workpiece_height"], torch.from_numpy(H0))  # reset() draws for everyone
+    act = env.make_action(0.5, 80.0, 9, 3.0, 30.0)
+    resets = torch.zeros(N, dtype=torch.bool)
+    for _ in range(8):
+        before, due = env.get_geometry(), vec._need_reset.clone()
+        vec.step(act)
+        after = env.get_geometry()
+        for k in before:
+            assert torch.equal(before[k][~due], after[k][~due]), k
+        assert (before["workpiece_height"][due] != after["workpiece_height"][due]).all()
+        resets |= due
+    assert resets.any() and not resets.all()
+    env.check_errors()
+    g = env.get_geometry()
+    for e in range(N):
+        w = derive.derive_geometry(float(g["workpiece_height"][e]), float(g["wire_diameter"][e]), WIRE, ref.BRASS,
+                                   MaterialModuleParameters())
+        assert tuple(env._geom_i32[:, e].tolist()) == (w.n_seg, w.zone_start, w.az_start, w.az_end, w.contact_bottom,
+                                                       w.contact_top)
+        assert env._geom_f64[:, e].numpy().tobytes() == np.array(
+            [w.workpiece_height, w.kerf_base, w.cavity_coeff, w.k_cond, w.tuf, w.a_surf, w.s_area, w.joule_geom]).tobytes()
+        assert int(g["n_segments"][e]) == w.n_seg
