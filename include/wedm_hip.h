@@ -719,6 +719,86 @@ typedef struct wedm_geom_derive_desc {
 int32_t wedm_derive_geometry(const wedm_geom_derive_desc* desc, const double* height, const int32_t* diameter_idx,
                              const int32_t* material_idx, const uint8_t* mask, int32_t* status, void* stream);
 
+/* ------------------------------------------- seeded per-episode domain randomisation, drawn on the device (one launch)
+ * A sampler is a 64-bit seed, a table of WEDM_DRAW_SLOTS slots and one int32 draw_count[stride] device array.  What
+ * environment e, of global id g = env_id_offset + e (mod 2^32), receives for its k-th draw is a pure function of (seed, g, k):
+ * no batch size, rank, launch shape or call history enters it.  With k = draw_count[e] before the call, the variate of slot s
+ * is word (s & 3) -- x, y, z, w in that order -- of
+ *     W(q) = Philox4x32-10(counter = {k, 0, g, 0x80000000 + q}, key = {seed & 0xffffffff, seed >> 32}),   q = s >> 2,
+ * the generator of the step kernels (counter {time, episode, global env id, stream}; multipliers 0xD2511F53 on word 0 and
+ * 0xCD9E8D57 on word 2, Weyl key increments 0x9E3779B9 / 0xBB67AE85, ten rounds).  The physics uses streams 0 .. 64 of that
+ * counter, so a draw never repeats a variate of the physics, whatever the two seeds are.
+ * Slots are fixed: enabling one more never changes another's draw.  Slot s < 15 is user-facing physics parameter s in the
+ * order of enum wedm_draw_slot_id (the row order of envp_src); 15 the wire material; 16 the workpiece height; 17 the index of
+ * the wire diameter.  A slot's kind says what is made of its word w (uint32):
+ *   WEDM_DRAW_NONE     nothing is drawn and nothing is written for that name;
+ *   WEDM_DRAW_UNIFORM  (slots 0 .. 14 and 16) float64, no contraction:  u = ((double) w + 0.5) * 2^-32;  x = lo + span * u
+ *                      (span = hi - lo, computed by the caller);  x = min(max(x, lo), hi).  For WEDM_DS_OMEGA_N the low 27
+ *                      bits of x's mantissa are then cleared, so that x * x is exact and equals C pow(x, 2);
+ *   WEDM_DRAW_CHOICE   (slots 15 and 17) i = (uint32) (((uint64) w * k) >> 32), one of k values; no float is involved.
+ * For every environment e < num_envs with mask[e] != 0 (mask == NULL: all) the call writes, in column e only:
+ *   envp_src[s][e] = x for every drawn slot s < 15, and every row of envp_rows that depends on a drawn name:
+ *     the row of the same meaning = x (WEDM_EP_OMEGA_N too);   DEBRIS_REMOVAL_PER_US = eff * base_flow_rate * 1e-6;
+ *     DAMPING_COEFF = -2.0 * zeta * omega_n (when either is drawn);   STIFFNESS_COEFF = -(omega_n * omega_n);
+ *     MAX_JERK_DT = max_jerk * dt_s  -- left to right, an operand that is not drawn read from envp_src;
+ *   material_index[e] = i of slot 15, the WEDM_WMAT_COUNT rows wmat_rows[r][e] = wmat_table[i][r][e] and, when `dynamic` is
+ *     0, the WEDM_GEOM_F64_COUNT rows geom_f64[r][e] = wmat_geom_table[i][r][e];
+ *   height[e] = x of slot 16, diameter_index[e] = i of slot 17 and, when `dynamic` is 1 and any of the slots 15 .. 17 is
+ *     drawn, the 8 + 6 geometry rows of wedm_derive_geometry (descriptor `geom`) for the environment's height, diameter index
+ *     and material index (drawn or stored; material 0 when material_index == NULL);
+ *   draw_count[e] = k + 1.
+ * Never written: unmasked columns, columns [num_envs, stride), anything outside the named blocks.  No block is gathered
+ * again across the stride.  The ranges are checked on the host so that no derivation can be refused: *geom_status is ORed
+ * only if a STORED height or index is bad (the bits of wedm_derive_geometry).                                             */
+enum wedm_draw_slot_id {
+    WEDM_DS_BASE_CRITICAL_DENSITY = 0, WEDM_DS_GAP_COEFFICIENT, WEDM_DS_MAX_CRITICAL_DENSITY, WEDM_DS_HARD_SHORT_GAP,
+    WEDM_DS_SIGMOID_STEEPNESS, WEDM_DS_SPARK_VOLTAGE_FACTOR, WEDM_DS_DEBRIS_REMOVAL_EFFICIENCY, WEDM_DS_DIELECTRIC_TEMPERATURE,
+    WEDM_DS_PLASMA_EFFICIENCY, WEDM_DS_BASE_CONVECTION_COEFFICIENT, WEDM_DS_OMEGA_N, WEDM_DS_ZETA, WEDM_DS_MAX_ACCELERATION,
+    WEDM_DS_MAX_JERK, WEDM_DS_MAX_SPEED,
+    WEDM_DS_MATERIAL, WEDM_DS_HEIGHT, WEDM_DS_DIAMETER,
+    WEDM_DRAW_SLOTS
+};
+#define WEDM_DRAW_ENVP_SLOTS 15          /* rows of envp_src */
+#define WEDM_DRAW_STREAM0 0x80000000u    /* Philox stream of call q: WEDM_DRAW_STREAM0 + q */
+enum wedm_draw_kind { WEDM_DRAW_NONE = 0, WEDM_DRAW_UNIFORM = 1, WEDM_DRAW_CHOICE = 2 };
+typedef struct wedm_draw_slot {
+    int32_t kind;          /* enum wedm_draw_kind */
+    int32_t k;             /* CHOICE: the number of values (>= 1) */
+    double lo, hi, span;   /* UNIFORM: the bounds and hi - lo */
+} wedm_draw_slot;
+typedef struct wedm_draw_desc {
+    uint64_t seed;
+    uint32_t env_id_offset;        /* global id of environment 0 */
+    int32_t num_envs;
+    int64_t stride;                /* of every per-environment block and array below */
+    wedm_draw_slot slot[WEDM_DRAW_SLOTS];
+    double base_flow_rate, dt_s;   /* the uniform operands of the derived rows */
+    double* envp_src;              /* device, [WEDM_DRAW_ENVP_SLOTS][stride]; needed when a slot < 15 is drawn */
+    double* envp_rows;             /* device, [WEDM_ENVP_COUNT][stride]; the same */
+    int64_t* material_index;       /* device, [stride]; needed when slot 15 is drawn, read otherwise (NULL: material 0) */
+    const double* wmat_table;      /* device, [k of slot 15][WEDM_WMAT_COUNT][stride]; needed when slot 15 is drawn */
+    double* wmat_rows;             /* device, [WEDM_WMAT_COUNT][stride]; the same */
+    const double* wmat_geom_table; /* device, [k of slot 15][WEDM_GEOM_F64_COUNT][stride]; slot 15 drawn and dynamic == 0 */
+    double* geom_f64;              /* device, [WEDM_GEOM_F64_COUNT][stride]; the same (dynamic == 1: geom.geom_f64 is used) */
+    double* height;                /* device, [stride]; dynamic == 1 */
+    int32_t* diameter_index;       /* device, [stride]; dynamic == 1 */
+    int32_t* geom_status;          /* device, one word, or NULL; dynamic == 1 */
+    int32_t dynamic;               /* 1: geometry rows are derived (wedm_derive_geometry's `geom`); 0: selected from the table */
+    int32_t reserved;
+    wedm_geom_derive_desc geom;    /* dynamic == 1; its num_envs and stride must equal this descriptor's */
+} wedm_draw_desc;
+
+/* One launch on `stream`.  Stateless like wedm_derive_geometry: no wedm_ctx, the current device, caller-owned memory.  `desc`
+ * is HOST memory, read before the call returns; mask (uint8 per environment, or NULL) and draw_count are device pointers.
+ * A descriptor with no drawn slot still advances the counts under the mask.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc or draw_count NULL; num_envs < 1; stride < num_envs;
+ * a kind that its slot does not take; a UNIFORM slot whose lo, hi or span is not finite, or lo > hi; a CHOICE slot with
+ * k < 1; a block that a drawn slot needs NULL or not aligned to its element; slots 16 or 17 drawn with dynamic == 0; with
+ * dynamic == 1: a `geom` that wedm_derive_geometry would refuse or whose num_envs / stride differ, k of slot 15 other than
+ * geom.n_materials, k of slot 17 above geom.n_diameters, a height range with lo <= 0 or whose hi has more than n_seg_max
+ * cells.                                                                                                                 */
+int32_t wedm_draw_episode(const wedm_draw_desc* desc, const uint8_t* mask, int32_t* draw_count, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

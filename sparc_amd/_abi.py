@@ -417,3 +417,31 @@ class GeomDeriveDesc(C.Structure):
         ("stride", C.c_int64), ("combo", C.c_void_p), ("n_diameters", _i), ("n_materials", _i),
         ("geom_f64", C.c_void_p), ("geom_i32", C.c_void_p),
     ]
+
+
+# `wedm_draw_episode`: slot s < DRAW_ENVP_SLOTS is name s of `core.env_params.NAMES` (enum wedm_draw_slot_id), then the wire
+# material, the workpiece height and the wire-diameter index; the Philox stream of call q is DRAW_STREAM0 + q
+DRAW_ENVP_SLOTS = 15
+DRAW_SLOT_MATERIAL, DRAW_SLOT_HEIGHT, DRAW_SLOT_DIAMETER = 15, 16, 17
+DRAW_SLOTS = 18
+DRAW_STREAM0 = 0x80000000
+DRAW_NONE, DRAW_UNIFORM, DRAW_CHOICE = 0, 1, 2  # enum wedm_draw_kind
+
+
+class DrawSlot(C.Structure):
+    """``struct wedm_draw_slot``."""
+
+    _fields_ = [("kind", _i), ("k", _i), ("lo", _d), ("hi", _d), ("span", _d)]
+
+
+class DrawDesc(C.Structure):
+    """``struct wedm_draw_desc``: what `wedm_draw_episode` draws and where it writes (stride in elements)."""
+
+    _fields_ = [
+        ("seed", C.c_uint64), ("env_id_offset", C.c_uint32), ("num_envs", _i), ("stride", C.c_int64),
+        ("slot", DrawSlot * DRAW_SLOTS), ("base_flow_rate", _d), ("dt_s", _d),
+        ("envp_src", C.c_void_p), ("envp_rows", C.c_void_p), ("material_index", C.c_void_p), ("wmat_table", C.c_void_p),
+        ("wmat_rows", C.c_void_p), ("wmat_geom_table", C.c_void_p), ("geom_f64", C.c_void_p), ("height", C.c_void_p),
+        ("diameter_index", C.c_void_p), ("geom_status", C.c_void_p), ("dynamic", _i), ("reserved", _i),
+        ("geom", GeomDeriveDesc),
+    ]

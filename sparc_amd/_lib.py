@@ -97,6 +97,8 @@ def load() -> C.CDLL:
     L.wedm_derive_geometry.argtypes = [C.POINTER(_abi.GeomDeriveDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]
     L.wedm_derive_geometry.restype = C.c_int32
+    L.wedm_draw_episode.argtypes = [C.POINTER(_abi.DrawDesc), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wedm_draw_episode.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -108,7 +110,7 @@ EXPORTS = (
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
-    "wedm_derive_geometry",
+    "wedm_derive_geometry", "wedm_draw_episode",
 )
 
 
@@ -256,6 +258,14 @@ class HipBackend:
         with self._on_device():
             rc = self._L.wedm_derive_geometry(C.byref(desc), height_ptr, diameter_idx_ptr, material_idx_ptr, mask_ptr, status_ptr,
                                               self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def draw_episode(self, desc: "_abi.DrawDesc", mask_ptr, draw_count_ptr) -> None:
+        """`wedm_draw_episode` on this backend's device and torch's current stream: device addresses of a uint8[num_envs] mask
+        or None (every environment) and of the sampler's int32[stride] draw counts."""
+        with self._on_device():
+            rc = self._L.wedm_draw_episode(C.byref(desc), mask_ptr, draw_count_ptr, self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

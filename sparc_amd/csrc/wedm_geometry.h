@@ -31,15 +31,10 @@
 #include "../../include/wedm_hip.h"
 #include "wedm_device.h"
 
-__global__ void __launch_bounds__(256)
-wedm_derive_geometry_kernel(const wedm_geom_derive_desc d, const double* __restrict__ height,
-                            const int32_t* __restrict__ diameter_idx, const int32_t* __restrict__ material_idx,
-                            const uint8_t* __restrict__ mask, int32_t* status) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= d.num_envs) return;
-    if (mask && !mask[e]) return;
-    const double h = height[e];
-    const int32_t di = diameter_idx[e], mi = material_idx ? material_idx[e] : 0;
+// Column e of the 14 rows from (h, di, mi), or the refusal.  The whole derivation, once: the kernel below and
+// wedm_draw_episode_kernel (wedm_randomize.h), which draws h, di and mi itself, both end here.
+__device__ __forceinline__ void wedm_derive_geometry_env(const wedm_geom_derive_desc& d, const int64_t e, const double h,
+                                                         const int32_t di, const int32_t mi, int32_t* status) {
     const double seg = d.segment_len, bb = d.buffer_len_bottom;
     // wire.py:144-149: total_len / segment_len, still a float (h is NaN, inf or <= 0: not used)
     const double cells = ((bb + h) + d.buffer_len_top) / seg;
@@ -81,4 +76,14 @@ wedm_derive_geometry_kernel(const wedm_geom_derive_desc d, const double* __restr
     g[WEDM_GI_AZ_END * s] = az_e;
     g[WEDM_GI_CONTACT_BOTTOM * s] = cb;
     g[WEDM_GI_CONTACT_TOP * s] = ct;
+}
+
+__global__ void __launch_bounds__(256)
+wedm_derive_geometry_kernel(const wedm_geom_derive_desc d, const double* __restrict__ height,
+                            const int32_t* __restrict__ diameter_idx, const int32_t* __restrict__ material_idx,
+                            const uint8_t* __restrict__ mask, int32_t* status) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= d.num_envs) return;
+    if (mask && !mask[e]) return;
+    wedm_derive_geometry_env(d, e, height[e], diameter_idx[e], material_idx ? material_idx[e] : 0, status);
 }

@@ -34,6 +34,9 @@
 //                         cell and pooled bins; not a step kernel, not in the registry
 //   wedm_geometry.h       wedm_derive_geometry_kernel: masked environments' geometry rows derived from (height, diameter
 //                         index, material index) with the host derivation's bits; not a step kernel, not in the registry
+//   wedm_randomize.h      wedm_draw_episode_kernel: masked environments' physics parameters, material, height and diameter of
+//                         their next episode drawn from (seed, global id, draw number) and written with every row that depends
+//                         on them; not a step kernel, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -74,6 +77,7 @@ using namespace wedm;
 #include "wedm_copy.h"
 #include "wedm_profile.h"
 #include "wedm_geometry.h"
+#include "wedm_randomize.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1433,37 +1437,109 @@ int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx,
     return WEDM_OK;
 }
 
+static bool finite_f64(double x) { return x - x == 0.0; }
+
+// why a descriptor cannot be followed (wedm_derive_geometry, and wedm_draw_episode for its `geom`), or NULL
+static const char* geom_derive_desc_error(const wedm_geom_derive_desc& d) {
+    if (!d.combo || !d.geom_f64 || !d.geom_i32) return "null combination table or geometry block";
+    if ((uintptr_t)d.geom_f64 % 8 || (uintptr_t)d.combo % 8 || (uintptr_t)d.geom_i32 % 4) return "a pointer is not aligned to its element";
+    if (d.num_envs < 1) return "num_envs must be positive";
+    if (d.stride < d.num_envs) return "stride smaller than num_envs";
+    if (d.n_seg_max < 1 || d.n_seg_max > (1 << 29)) return "n_seg_max outside [1, 2^29]";
+    if (d.n_diameters < 1 || d.n_materials < 1) return "n_diameters and n_materials must be positive";
+    if (!finite_f64(d.segment_len) || !(d.segment_len > 0.0)) return "segment_len must be finite and positive";
+    if (!finite_f64(d.buffer_len_bottom) || !finite_f64(d.buffer_len_top) || d.buffer_len_bottom < 0.0 || d.buffer_len_top < 0.0)
+        return "buffer lengths must be finite and not negative";
+    if (!finite_f64(d.contact_offset_top)) return "contact_offset_top must be finite";
+    // (2^29 each: zone_start0 + floor(h / seg) <= 2^29 + n_seg_max stays inside int32 in the kernel)
+    if (d.zone_start0 < 0 || d.zone_start0 > (1 << 29) || d.contact_bottom0 < 0 || d.contact_bottom0 > (1 << 29))
+        return "zone_start0 or contact_bottom0 outside [0, 2^29]";
+    return nullptr;
+}
+
 int32_t wedm_derive_geometry(const wedm_geom_derive_desc* desc, const double* height, const int32_t* diameter_idx,
                              const int32_t* material_idx, const uint8_t* mask, int32_t* status, void* stream) {
     const auto bad = [](const std::string& msg) {
         g_create_error = "wedm_derive_geometry: " + msg;
         return (int32_t)WEDM_ERR_BAD_ARG;
     };
-    const auto finite = [](double x) { return x - x == 0.0; };
     if (!desc) return bad("null descriptor");
     const wedm_geom_derive_desc& d = *desc;
     if (!height || !diameter_idx) return bad("null height or diameter index array");
-    if (!d.combo || !d.geom_f64 || !d.geom_i32) return bad("null combination table or geometry block");
-    if ((uintptr_t)d.geom_f64 % 8 || (uintptr_t)d.combo % 8 || (uintptr_t)height % 8 || (uintptr_t)d.geom_i32 % 4 ||
-        (uintptr_t)diameter_idx % 4 || (uintptr_t)material_idx % 4)
+    if ((uintptr_t)height % 8 || (uintptr_t)diameter_idx % 4 || (uintptr_t)material_idx % 4)
         return bad("a pointer is not aligned to its element");
-    if (d.num_envs < 1) return bad("num_envs must be positive");
-    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
-    if (d.n_seg_max < 1 || d.n_seg_max > (1 << 29)) return bad("n_seg_max outside [1, 2^29]");
-    if (d.n_diameters < 1 || d.n_materials < 1) return bad("n_diameters and n_materials must be positive");
-    if (!finite(d.segment_len) || !(d.segment_len > 0.0)) return bad("segment_len must be finite and positive");
-    if (!finite(d.buffer_len_bottom) || !finite(d.buffer_len_top) || d.buffer_len_bottom < 0.0 || d.buffer_len_top < 0.0)
-        return bad("buffer lengths must be finite and not negative");
-    if (!finite(d.contact_offset_top)) return bad("contact_offset_top must be finite");
-    // (2^29 each: zone_start0 + floor(h / seg) <= 2^29 + n_seg_max stays inside int32 in the kernel)
-    if (d.zone_start0 < 0 || d.zone_start0 > (1 << 29) || d.contact_bottom0 < 0 || d.contact_bottom0 > (1 << 29))
-        return bad("zone_start0 or contact_bottom0 outside [0, 2^29]");
+    if (const char* why = geom_derive_desc_error(d)) return bad(why);
     const dim3 grid((uint32_t)(((int64_t)d.num_envs + 255) / 256));
     hipLaunchKernelGGL(wedm_derive_geometry_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, height, diameter_idx,
                        material_idx, mask, status);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         g_create_error = std::string("wedm_derive_geometry: launch: ") + hipGetErrorString(e);
+        return WEDM_ERR_HIP;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_draw_episode(const wedm_draw_desc* desc, const uint8_t* mask, int32_t* draw_count, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_draw_episode: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_draw_desc& d = *desc;
+    if (!draw_count || (uintptr_t)draw_count % 4) return bad("draw_count is null or not aligned to its element");
+    if (d.num_envs < 1) return bad("num_envs must be positive");
+    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
+    if (d.dynamic != 0 && d.dynamic != 1) return bad("dynamic must be 0 or 1");
+    bool envp = false;
+    for (int s = 0; s < WEDM_DRAW_SLOTS; ++s) {
+        const wedm_draw_slot& sl = d.slot[s];
+        const bool choice = s == WEDM_DS_MATERIAL || s == WEDM_DS_DIAMETER;
+        const std::string name = "slot " + std::to_string(s);
+        if (sl.kind == WEDM_DRAW_NONE) continue;
+        if (sl.kind != (choice ? WEDM_DRAW_CHOICE : WEDM_DRAW_UNIFORM)) return bad(name + ": a kind this slot does not take");
+        if (choice) {
+            if (sl.k < 1) return bad(name + ": a choice needs k >= 1");
+        } else {
+            if (!finite_f64(sl.lo) || !finite_f64(sl.hi) || !finite_f64(sl.span)) return bad(name + ": bounds must be finite");
+            if (sl.lo > sl.hi) return bad(name + ": lo > hi");
+        }
+        envp |= s < WEDM_DRAW_ENVP_SLOTS;
+    }
+    const auto misplaced = [](const void* p, size_t align) { return !p || (uintptr_t)p % align; };
+    if (envp) {
+        if (misplaced(d.envp_src, 8) || misplaced(d.envp_rows, 8)) return bad("envp_src or envp_rows is null or misaligned");
+        if (!finite_f64(d.base_flow_rate) || !finite_f64(d.dt_s)) return bad("base_flow_rate and dt_s must be finite");
+    }
+    const bool has_mat = d.slot[WEDM_DS_MATERIAL].kind != WEDM_DRAW_NONE, has_h = d.slot[WEDM_DS_HEIGHT].kind != WEDM_DRAW_NONE,
+               has_dia = d.slot[WEDM_DS_DIAMETER].kind != WEDM_DRAW_NONE;
+    if (has_mat) {
+        if (misplaced(d.material_index, 8) || misplaced(d.wmat_table, 8) || misplaced(d.wmat_rows, 8))
+            return bad("material_index, wmat_table or wmat_rows is null or misaligned");
+        if (!d.dynamic && (misplaced(d.wmat_geom_table, 8) || misplaced(d.geom_f64, 8)))
+            return bad("wmat_geom_table or geom_f64 is null or misaligned");
+    }
+    if ((has_h || has_dia) && !d.dynamic) return bad("height and diameter are drawn with dynamic geometry only");
+    if (d.dynamic && (has_mat || has_h || has_dia)) {
+        const wedm_geom_derive_desc& g = d.geom;
+        if (const char* why = geom_derive_desc_error(g)) return bad(std::string("geom: ") + why);
+        if (g.num_envs != d.num_envs || g.stride != d.stride) return bad("geom: num_envs or stride differs from the descriptor's");
+        if (misplaced(d.height, 8) || misplaced(d.diameter_index, 4)) return bad("height or diameter_index is null or misaligned");
+        if ((uintptr_t)d.material_index % 8 || (uintptr_t)d.geom_status % 4) return bad("material_index or geom_status is misaligned");
+        if (has_mat && d.slot[WEDM_DS_MATERIAL].k != g.n_materials) return bad("k of the material slot is not geom.n_materials");
+        if (has_dia && d.slot[WEDM_DS_DIAMETER].k > g.n_diameters) return bad("k of the diameter slot exceeds geom.n_diameters");
+        if (has_h) {  // the kernel's own capacity test on the largest height: cells is monotone in h, so no draw is refused
+            const wedm_draw_slot& sl = d.slot[WEDM_DS_HEIGHT];
+            const double cells = ((g.buffer_len_bottom + sl.hi) + g.buffer_len_top) / g.segment_len;
+            if (!(sl.lo > 0.0)) return bad("height range must have lo > 0");
+            if (!(cells < (double)g.n_seg_max + 1.0)) return bad("height range reaches past n_seg_max cells");
+        }
+    }
+    const dim3 grid((uint32_t)(((int64_t)d.num_envs + 255) / 256));
+    hipLaunchKernelGGL(wedm_draw_episode_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, mask, draw_count);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        g_create_error = std::string("wedm_draw_episode: launch: ") + hipGetErrorString(e);
         return WEDM_ERR_HIP;
     }
     return WEDM_OK;

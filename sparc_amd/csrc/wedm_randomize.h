@@ -1,0 +1,138 @@
+// wedm_randomize.h -- wedm_draw_episode: the physics of masked environments' next episode, drawn on the device from a seed.
+//
+// Not a step kernel and not in the registry: no wedm_ctx, no wedm_params, no plan, no form bits.  Like wedm_derive_geometry
+// it rewrites per-environment rows that the step kernels read at the start of a launch; unlike it, the values do not come
+// from the caller but from Philox4x32-10 on the counter {draw number, 0, global environment id, 0x80000000 + call}
+// (include/wedm_hip.h has the whole contract).  A draw is a pure function of (seed, global id,
+// draw number, slot): the batch size, the rank, the launch shape and what ran before do not enter it.
+//
+// Shape: one lane per environment, blocks of 256.  Every row access is coalesced (the environment is the column); the slot
+// table is kernel-argument memory and every branch on it is wave-uniform, so a launch computes only the Philox calls whose
+// slots are drawn and touches only the rows of drawn names.  The geometry rows are those of wedm_derive_geometry_env
+// (wedm_geometry.h), called here, not restated.  At most ~700 bytes per environment with everything drawn: the launch is what
+// it costs.  The translation unit is compiled with -ffp-contract=off: x = lo + span * u may not fuse.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "../../include/wedm_hip.h"
+#include "wedm_device.h"
+#include "wedm_geometry.h"
+
+namespace wedm {
+
+// device row that holds slot s's value itself, or -1 (sparc_amd/core/env_params.py, _COPY)
+__device__ __forceinline__ constexpr int draw_copy_row(int s) {
+    switch (s) {
+        case WEDM_DS_BASE_CRITICAL_DENSITY: return WEDM_EP_BASE_CRITICAL_DENSITY;
+        case WEDM_DS_GAP_COEFFICIENT: return WEDM_EP_GAP_COEFFICIENT;
+        case WEDM_DS_MAX_CRITICAL_DENSITY: return WEDM_EP_MAX_CRITICAL_DENSITY;
+        case WEDM_DS_HARD_SHORT_GAP: return WEDM_EP_HARD_SHORT_GAP;
+        case WEDM_DS_SIGMOID_STEEPNESS: return WEDM_EP_SIGMOID_STEEPNESS;
+        case WEDM_DS_SPARK_VOLTAGE_FACTOR: return WEDM_EP_SPARK_VOLTAGE_FACTOR;
+        case WEDM_DS_DIELECTRIC_TEMPERATURE: return WEDM_EP_DIELECTRIC_TEMPERATURE;
+        case WEDM_DS_PLASMA_EFFICIENCY: return WEDM_EP_PLASMA_EFFICIENCY;
+        case WEDM_DS_BASE_CONVECTION_COEFFICIENT: return WEDM_EP_BASE_CONVECTION;
+        case WEDM_DS_OMEGA_N: return WEDM_EP_OMEGA_N;
+        case WEDM_DS_MAX_ACCELERATION: return WEDM_EP_MAX_ACCELERATION;
+        case WEDM_DS_MAX_SPEED: return WEDM_EP_MAX_SPEED;
+        default: return -1;
+    }
+}
+
+__device__ __forceinline__ double draw_uniform(const wedm_draw_slot& s, uint32_t w) {
+    const double u = ((double)w + 0.5) * 0x1p-32;
+    const double x = s.lo + s.span * u;
+    return fmin(fmax(x, s.lo), s.hi);
+}
+
+__device__ __forceinline__ int32_t draw_choice(const wedm_draw_slot& s, uint32_t w) {
+    return (int32_t)(uint32_t)(((uint64_t)w * (uint32_t)s.k) >> 32);
+}
+
+__device__ __forceinline__ uint32_t word_of(const W4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; }
+
+}  // namespace wedm
+
+__global__ void __launch_bounds__(256)
+wedm_draw_episode_kernel(const wedm_draw_desc d, const uint8_t* __restrict__ mask, int32_t* __restrict__ draw_count) {
+    using namespace wedm;
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= d.num_envs) return;
+    if (mask && !mask[e]) return;
+    const int32_t k = draw_count[e];
+    const uint32_t gid = d.env_id_offset + (uint32_t)e;
+    const uint32_t key0 = (uint32_t)d.seed, key1 = (uint32_t)(d.seed >> 32);
+    const int64_t st = d.stride;
+
+    // ---- slots 0 .. 14: the physics parameters (calls 0 .. 3); every index below is a constant after unrolling
+    double eff = 0.0, omega = 0.0, zeta = 0.0, jerk = 0.0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        bool any = false;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) any |= 4 * q + i < WEDM_DRAW_ENVP_SLOTS && d.slot[4 * q + i].kind != WEDM_DRAW_NONE;
+        if (!any) continue;
+        const W4 v = philox4(key0, key1, (uint32_t)k, 0u, gid, WEDM_DRAW_STREAM0 + (uint32_t)q);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int s = 4 * q + i;
+            if (s >= WEDM_DRAW_ENVP_SLOTS || d.slot[s].kind == WEDM_DRAW_NONE) continue;
+            double x = draw_uniform(d.slot[s], word_of(v, i));
+            if (s == WEDM_DS_OMEGA_N)  // 26 significant bits: x * x is exact
+                x = __longlong_as_double(__double_as_longlong(x) & ~((1ll << 27) - 1));
+            d.envp_src[s * st + e] = x;
+            if (draw_copy_row(s) >= 0) d.envp_rows[draw_copy_row(s) * st + e] = x;
+            if (s == WEDM_DS_DEBRIS_REMOVAL_EFFICIENCY) eff = x;
+            if (s == WEDM_DS_OMEGA_N) omega = x;
+            if (s == WEDM_DS_ZETA) zeta = x;
+            if (s == WEDM_DS_MAX_JERK) jerk = x;
+        }
+    }
+    // the derived rows, in `env_params.derive_row`'s operand order; an operand that was not drawn is the stored one
+    const bool has_omega = d.slot[WEDM_DS_OMEGA_N].kind != WEDM_DRAW_NONE, has_zeta = d.slot[WEDM_DS_ZETA].kind != WEDM_DRAW_NONE;
+    if (d.slot[WEDM_DS_DEBRIS_REMOVAL_EFFICIENCY].kind != WEDM_DRAW_NONE)
+        d.envp_rows[WEDM_EP_DEBRIS_REMOVAL_PER_US * st + e] = eff * d.base_flow_rate * 1e-6;
+    if (has_omega || has_zeta) {
+        if (!has_omega) omega = d.envp_src[WEDM_DS_OMEGA_N * st + e];
+        if (!has_zeta) zeta = d.envp_src[WEDM_DS_ZETA * st + e];
+        d.envp_rows[WEDM_EP_DAMPING_COEFF * st + e] = -2.0 * zeta * omega;
+    }
+    if (has_omega) d.envp_rows[WEDM_EP_STIFFNESS_COEFF * st + e] = -(omega * omega);
+    if (d.slot[WEDM_DS_MAX_JERK].kind != WEDM_DRAW_NONE) d.envp_rows[WEDM_EP_MAX_JERK_DT * st + e] = jerk * d.dt_s;
+
+    // ---- slots 15 .. 17: material, height, diameter index (calls 3 and 4)
+    const bool has_mat = d.slot[WEDM_DS_MATERIAL].kind != WEDM_DRAW_NONE;
+    const bool has_h = d.slot[WEDM_DS_HEIGHT].kind != WEDM_DRAW_NONE, has_dia = d.slot[WEDM_DS_DIAMETER].kind != WEDM_DRAW_NONE;
+    int32_t mi = 0;
+    if (has_mat) {
+        const W4 v = philox4(key0, key1, (uint32_t)k, 0u, gid, WEDM_DRAW_STREAM0 + (uint32_t)(WEDM_DS_MATERIAL >> 2));
+        mi = draw_choice(d.slot[WEDM_DS_MATERIAL], word_of(v, WEDM_DS_MATERIAL & 3));
+        d.material_index[e] = mi;
+#pragma unroll
+        for (int r = 0; r < WEDM_WMAT_COUNT; ++r) d.wmat_rows[r * st + e] = d.wmat_table[((int64_t)mi * WEDM_WMAT_COUNT + r) * st + e];
+        if (!d.dynamic) {
+#pragma unroll
+            for (int r = 0; r < WEDM_GEOM_F64_COUNT; ++r)
+                d.geom_f64[r * st + e] = d.wmat_geom_table[((int64_t)mi * WEDM_GEOM_F64_COUNT + r) * st + e];
+        }
+    } else if (d.dynamic && d.material_index && (has_h || has_dia)) {
+        mi = (int32_t)d.material_index[e];
+    }
+    if (d.dynamic && (has_mat || has_h || has_dia)) {
+        double h = 0.0;
+        int32_t di = 0;
+        if (has_h || has_dia) {
+            static_assert((WEDM_DS_HEIGHT >> 2) == (WEDM_DS_DIAMETER >> 2), "height and diameter share a Philox call");
+            const W4 v = philox4(key0, key1, (uint32_t)k, 0u, gid, WEDM_DRAW_STREAM0 + (uint32_t)(WEDM_DS_HEIGHT >> 2));
+            if (has_h) d.height[e] = h = draw_uniform(d.slot[WEDM_DS_HEIGHT], word_of(v, WEDM_DS_HEIGHT & 3));
+            if (has_dia) d.diameter_index[e] = di = draw_choice(d.slot[WEDM_DS_DIAMETER], word_of(v, WEDM_DS_DIAMETER & 3));
+        }
+        if (!has_h) h = d.height[e];
+        if (!has_dia) di = d.diameter_index[e];
+        wedm_derive_geometry_env(d.geom, e, h, di, mi, d.geom_status);
+    }
+    draw_count[e] = k + 1;
+}

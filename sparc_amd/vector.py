@@ -95,7 +95,8 @@ class WireEDMVectorEnv:
 
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
                  reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
-                 wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None):
+                 wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None,
+                 episode_sampler=None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -115,6 +116,10 @@ class WireEDMVectorEnv:
         (`WireEDMEnv.set_geometry` with ``reset=False``: the reset is this adapter's) where ``reset_mask`` is set, before the
         other two samplers (the material sampler's re-derivation reads the heights).  The environment must have been built
         with ``dynamic_geometry={...}`` (see `uniform_geometry_sampler`).
+        ``episode_sampler``: a `sparc_amd.randomize.EpisodeSampler` -- seeded domain randomisation of all of the above by one
+        device launch, each draw a pure function of (seed, global environment id, draw number), applied where the three
+        samplers would be.  It excludes them.  ``reset(seed=x)`` reseeds it with ``x``; a seed together with a mask is
+        refused (it would put the unmasked environments' draws on another seed's sequence).
         ``wire_profile_bins``: with an integer B in [0, 64], `reset()` and `step()` return ``[N, obs_dim + 4 + 2 * B]``: the
         environment's observation followed by the rows of `WireEDMEnv.wire_profile` (zone mean, wire mean, maximum,
         hottest cell, B bin maxima, B bin means) of the wire as the launch left it -- one more launch, no host
@@ -156,10 +161,22 @@ class WireEDMVectorEnv:
         if geometry_sampler is not None and getattr(env, "_dyn", None) is None:
             raise ValueError("geometry_sampler needs an environment built with dynamic_geometry={...}")
         self._samples = any(f is not None for f in (param_sampler, material_sampler, geometry_sampler))
+        self._episode_sampler = episode_sampler
+        if episode_sampler is not None:
+            if self._samples:
+                raise ValueError("episode_sampler replaces param_sampler / material_sampler / geometry_sampler: give either")
+            episode_sampler.bind(env)
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
+        if self._episode_sampler is not None:
+            mask = (options or {}).get("mask")
+            if seed is not None:
+                if mask is not None:
+                    raise ValueError("reset(seed=...) reseeds the episode sampler for every environment: no mask with it")
+                self._episode_sampler.reseed(seed)
+            self._episode_sampler.draw(self.env, mask=mask, reset=False)
         if self._samples:
             mask = (options or {}).get("mask")
             mask = torch.ones(self.num_envs, dtype=torch.bool, device=self.env.device) if mask is None else \
@@ -189,6 +206,8 @@ class WireEDMVectorEnv:
         """One control interval for every environment (1000 us by default)."""
         if self._samples and self.autoreset:
             self._apply_sampler(self._need_reset)  # environments about to start a new episode draw their physics
+        if self._episode_sampler is not None and self.autoreset:
+            self._episode_sampler.draw(self.env, mask=self._need_reset, reset=False)
         if self.autoreset:
             if self._in_kernel_reset:
                 # terminated environments are reset by the launch itself; a truncated one is handed to it
@@ -219,7 +238,8 @@ class WireEDMVectorEnv:
 
     def fork(self, src, dst) -> None:
         """`WireEDMEnv.fork`, and the adapter's own per-environment state with it: a destination is due for a reset
-        exactly if its source is."""
+        exactly if its source is.  An episode sampler's draw counts stay: a destination keeps its own stream of draws, as
+        it keeps its own Philox stream in the physics."""
         from .snapshot import fork_rows
 
         self.env.fork(src, dst)
