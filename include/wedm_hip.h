@@ -799,6 +799,99 @@ typedef struct wedm_draw_desc {
  * cells.                                                                                                                 */
 int32_t wedm_draw_episode(const wedm_draw_desc* desc, const uint8_t* mask, int32_t* draw_count, void* stream);
 
+/* ---------------------------------------------------- running observation and reward normalisation, reduced on the device
+ * What a policy is fed: the observation columns standardised by running moments over every environment and every step so
+ * far, the reward scaled by the running deviation of the discounted return, and the episode return / length bookkeeping
+ * (Gymnasium's NormalizeObservation, NormalizeReward and RecordEpisodeStatistics), without leaving the device.  This is the
+ * one reduction ACROSS environments of this ABI, and it is defined so that its bits depend on the values and their global
+ * environment indices alone: not on block size, grid, scheduling, or on how a batch is split over devices.
+ *
+ * COLUMNS.  C = D + 1: the D observation columns (plane 0's rows, then plane 1's), then the discounted return.
+ * MOMENTS.  A triple (n, m, S) of float64: count, mean, sum of squared deviations.  EMPTY = (0, 0, 0); the leaf of a value x
+ *   is (1, (double) x, 0).
+ * MERGE.  merge(a, b), every operation rounded to float64, nothing fused, in this order with these parentheses:
+ *     nb == 0: a;   na == 0: b;   otherwise
+ *     n = na + nb;   d = mb - ma;   m = ma + d * (nb / n);   S = Sa + Sb + d * d * (na * nb / n).
+ *   merge is not commutative in its bits: the left argument is always the node of the lower index.
+ * BATCH MOMENT of a column: the pairwise tree over the leaves by GLOBAL environment index g = 256 * tile_offset + e.  Level 0
+ *   is the leaves (EMPTY for an environment the mask leaves out, and past the batch's end); node j of level k + 1 is
+ *   merge(node 2j, node 2j + 1) of level k; the tree is padded with EMPTY to a power of two.  EMPTY is merge's identity (it
+ *   returns the other argument's bits), so the padding changes nothing.  A TILE is 256 consecutive environments (eight
+ *   levels); tile t's node is partials[t]; the levels above run over the tile index.
+ * RUNNING STATISTICS, per column: stats_out = merge(stats_in, batch); var = S / n.  A fresh normaliser holds (1e-4, 0, 1e-4):
+ *   count 1e-4, mean 0, variance 1.
+ * PER ENVIRONMENT, in a call with WEDM_NORM_STEP, for the environments the mask includes (mask == NULL: all), float64:
+ *     ret = ret * gamma + (double) reward          -- this new ret is the leaf of column D
+ *     ep_return += (double) reward;   ep_length += 1
+ *     where terminated | truncated:  last_return = ep_return;  last_length = ep_length;  ep_count += 1;  finished = 1;
+ *                                    then ep_return = 0, ep_length = 0, ret = 0;      elsewhere finished = 0.
+ *   An environment the mask leaves out keeps every one of these rows.
+ * OUTPUTS, for every environment below num_envs, masked or not, from stats_out:
+ *     obs_out[e][c] = (float) clamp(((double) x - m_c) / sqrt(var_c + eps), -clip_obs, clip_obs); x itself where skip[c] != 0;
+ *     reward_out[e] = (float) clamp((double) reward / sqrt(var_D + eps), -clip_reward, clip_reward)   (WEDM_NORM_STEP only),
+ *   clamp(v, lo, hi) = v < lo ? lo : (v > hi ? hi : v): a clip of +inf clips nothing.  obs_out is row-major [num_envs][D].
+ * FLAGS.
+ *   WEDM_NORM_UPDATE  absent: stats_out = stats_in (evaluation mode); no partial is read or written.
+ *   WEDM_NORM_STEP    absent: observation only, as after a reset: the leaves of column D are EMPTY (its statistics pass
+ *                     through), no reward is written, no per-environment row is read or written.
+ *   WEDM_NORM_REDUCE / WEDM_NORM_APPLY  the two phases of a call; neither set means both, in this order.
+ *                     REDUCE updates ret and writes this batch's tile partials at partials[tile_offset + t], t < ceil(num_envs / 256).
+ *                     APPLY folds all n_tiles_total partials and writes stats_out, the outputs and the episode rows (it reads
+ *                     the ret REDUCE left and zeroes it where an episode ended).  Each phase runs once per shard per step:
+ *                     a sharded batch reduces every shard into its own tiles of one workspace (an all-gather of
+ *                     [tiles][3][C] doubles between devices) and then applies every shard: statistics and outputs carry
+ *                     the bits of the whole-batch call.  A shard that is not the last holds a multiple of 256 environments.
+ * A NaN input makes the numbers it reaches unspecified; it never makes the call touch memory outside its blocks.        */
+#define WEDM_NORM_MAX_COLUMNS 160   /* C = D + 1 <= 160: 16 environment columns + the 132 rows of a 64-bin wire profile fit */
+#define WEDM_NORM_MAX_TILES 4096    /* n_tiles_total <= 4096: 1 048 576 environments over all shards */
+#define WEDM_NORM_TILE 256
+enum wedm_norm_flag { WEDM_NORM_UPDATE = 1, WEDM_NORM_STEP = 2, WEDM_NORM_REDUCE = 4, WEDM_NORM_APPLY = 8 };
+enum wedm_norm_moment { WEDM_NM_COUNT = 0, WEDM_NM_MEAN, WEDM_NM_M2, WEDM_NORM_MOMENTS };
+typedef struct wedm_norm_plane {
+    const float* rows;   /* [n_rows][stride], struct-of-arrays as the environment's obs block and the wire-profile block lie */
+    int32_t n_rows;      /* plane 1 may have 0 rows (rows is then not read) */
+    int32_t reserved;
+    int64_t stride;      /* >= num_envs */
+} wedm_norm_plane;
+typedef struct wedm_norm_desc {
+    wedm_norm_plane plane[2];      /* D = plane[0].n_rows + plane[1].n_rows, in [1, WEDM_NORM_MAX_COLUMNS - 1] */
+    const float* reward;           /* [num_envs]; STEP */
+    const uint8_t* terminated;     /* [num_envs]; STEP */
+    const uint8_t* truncated;      /* [num_envs]; STEP */
+    const uint8_t* mask;           /* [num_envs] or NULL: every environment takes part */
+    const uint8_t* skip;           /* [D] or NULL: no column is skipped */
+    float* obs_out;                /* [num_envs][D] */
+    float* reward_out;             /* [num_envs]; STEP */
+    double* ret;                   /* [num_envs] each; STEP */
+    double* ep_return;
+    double* last_return;
+    int32_t* ep_length;
+    int32_t* last_length;
+    int32_t* ep_count;
+    uint8_t* finished;
+    const double* stats_in;        /* [WEDM_NORM_MOMENTS][C] */
+    double* stats_out;             /* [WEDM_NORM_MOMENTS][C]; must not overlap stats_in */
+    double* partials;              /* [n_tiles_total][WEDM_NORM_MOMENTS][C]; UPDATE */
+    int32_t tile_offset;           /* global index of this batch's tile 0 */
+    int32_t n_tiles_total;         /* tiles of the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= WEDM_NORM_MAX_TILES */
+    double gamma, eps, clip_obs, clip_reward;
+    int32_t flags;                 /* enum wedm_norm_flag */
+    int32_t num_envs;
+} wedm_norm_desc;
+
+/* At most three launches on `stream` (REDUCE: one; APPLY: the fold of the partials into stats_out, then the outputs), none
+ * of which waits for another block: no spin, no cooperative launch, no floating-point atomic.  Stateless like
+ * wedm_wire_profile: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory, read before the call
+ * returns; everything it names is device memory.  Written: obs_out, reward_out, stats_out, partials[tile_offset ..
+ * tile_offset + ceil(num_envs / 256)), elements [0, num_envs) of the per-environment rows -- nothing else, and none of the
+ * source planes, whose columns [num_envs, stride) are not read either.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; a pointer that the flags need NULL (the planes'
+ * rows, obs_out, stats_in, stats_out for APPLY; partials with UPDATE; reward and ret with STEP, and for APPLY with STEP
+ * terminated, truncated, reward_out and the other six per-environment rows); D outside [1, WEDM_NORM_MAX_COLUMNS - 1] or a
+ * negative n_rows; a stride < num_envs; stats_in and stats_out overlapping; tile_offset < 0, n_tiles_total outside
+ * [1, WEDM_NORM_MAX_TILES] or the batch's tiles reaching past it; num_envs < 1; flag bits that are not defined.             */
+int32_t wedm_normalize(const wedm_norm_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

@@ -389,6 +389,37 @@ class ProfileDesc(C.Structure):
     ]
 
 
+# `wedm_normalize` (sparc_amd.normalize): C = D + 1 columns at most, tiles of the partials workspace at most, environments
+# per tile; enum wedm_norm_flag; the rows of a moments block (enum wedm_norm_moment)
+NORM_MAX_COLUMNS = 160  # WEDM_NORM_MAX_COLUMNS
+NORM_MAX_TILES = 4096   # WEDM_NORM_MAX_TILES
+NORM_TILE = 256         # WEDM_NORM_TILE
+NORM_UPDATE, NORM_STEP, NORM_REDUCE, NORM_APPLY = 1, 2, 4, 8
+NM_COUNT, NM_MEAN, NM_M2, NORM_MOMENTS = 0, 1, 2, 3
+
+
+class NormPlane(C.Structure):
+    """``struct wedm_norm_plane``: one struct-of-arrays source block of `wedm_normalize` (stride in elements)."""
+
+    _fields_ = [("rows", C.c_void_p), ("n_rows", C.c_int32), ("reserved", C.c_int32), ("stride", C.c_int64)]
+
+
+class NormDesc(C.Structure):
+    """``struct wedm_norm_desc``: what `wedm_normalize` reads and where it writes."""
+
+    _fields_ = [
+        ("plane", NormPlane * 2),
+        ("reward", C.c_void_p), ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("mask", C.c_void_p), ("skip", C.c_void_p),
+        ("obs_out", C.c_void_p), ("reward_out", C.c_void_p),
+        ("ret", C.c_void_p), ("ep_return", C.c_void_p), ("last_return", C.c_void_p), ("ep_length", C.c_void_p),
+        ("last_length", C.c_void_p), ("ep_count", C.c_void_p), ("finished", C.c_void_p),
+        ("stats_in", C.c_void_p), ("stats_out", C.c_void_p), ("partials", C.c_void_p),
+        ("tile_offset", C.c_int32), ("n_tiles_total", C.c_int32),
+        ("gamma", C.c_double), ("eps", C.c_double), ("clip_obs", C.c_double), ("clip_reward", C.c_double),
+        ("flags", C.c_int32), ("num_envs", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

@@ -99,6 +99,8 @@ def load() -> C.CDLL:
     L.wedm_derive_geometry.restype = C.c_int32
     L.wedm_draw_episode.argtypes = [C.POINTER(_abi.DrawDesc), C.c_void_p, C.c_void_p, C.c_void_p]
     L.wedm_draw_episode.restype = C.c_int32
+    L.wedm_normalize.argtypes = [C.POINTER(_abi.NormDesc), C.c_void_p]
+    L.wedm_normalize.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -110,7 +112,7 @@ EXPORTS = (
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
-    "wedm_derive_geometry", "wedm_draw_episode",
+    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize",
 )
 
 
@@ -266,6 +268,13 @@ class HipBackend:
         or None (every environment) and of the sampler's int32[stride] draw counts."""
         with self._on_device():
             rc = self._L.wedm_draw_episode(C.byref(desc), mask_ptr, draw_count_ptr, self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def normalize(self, desc: "_abi.NormDesc") -> None:
+        """`wedm_normalize` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
+        with self._on_device():
+            rc = self._L.wedm_normalize(C.byref(desc), self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

@@ -37,6 +37,8 @@
 //   wedm_randomize.h      wedm_draw_episode_kernel: masked environments' physics parameters, material, height and diameter of
 //                         their next episode drawn from (seed, global id, draw number) and written with every row that depends
 //                         on them; not a step kernel, not in the registry
+//   wedm_normalize.h      wedm_norm_reduce / _fold / _apply_kernel: running observation and reward normalisation over all
+//                         environments by a fixed pairwise tree, episode statistics; not step kernels, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -78,6 +80,7 @@ using namespace wedm;
 #include "wedm_profile.h"
 #include "wedm_geometry.h"
 #include "wedm_randomize.h"
+#include "wedm_normalize.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1433,6 +1436,73 @@ int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx,
     if (e != hipSuccess) {
         g_create_error = std::string("wedm_wire_profile: launch: ") + hipGetErrorString(e);
         return WEDM_ERR_HIP;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_normalize(const wedm_norm_desc* desc, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_normalize: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_norm_desc& d = *desc;
+    const int32_t all = WEDM_NORM_UPDATE | WEDM_NORM_STEP | WEDM_NORM_REDUCE | WEDM_NORM_APPLY;
+    if (d.flags & ~all) return bad("undefined flag bits");
+    const bool update = d.flags & WEDM_NORM_UPDATE, step = d.flags & WEDM_NORM_STEP;
+    const bool both = !(d.flags & (WEDM_NORM_REDUCE | WEDM_NORM_APPLY));
+    const bool reduce = both || (d.flags & WEDM_NORM_REDUCE), apply = both || (d.flags & WEDM_NORM_APPLY);
+    if (d.num_envs < 1) return bad("num_envs must be positive");
+    if (d.plane[0].n_rows < 0 || d.plane[1].n_rows < 0) return bad("negative n_rows");
+    const int64_t D = (int64_t)d.plane[0].n_rows + d.plane[1].n_rows;
+    if (D < 1 || D > WEDM_NORM_MAX_COLUMNS - 1) return bad("D outside [1, " + std::to_string(WEDM_NORM_MAX_COLUMNS - 1) + "]");
+    for (int k = 0; k < 2; ++k) {
+        if (d.plane[k].n_rows == 0) continue;
+        if (!d.plane[k].rows || (uintptr_t)d.plane[k].rows % 4) return bad("plane " + std::to_string(k) + ": rows is null or misaligned");
+        if (d.plane[k].stride < d.num_envs) return bad("plane " + std::to_string(k) + ": stride smaller than num_envs");
+    }
+    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
+    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
+        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
+                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
+    if (update && (!d.partials || (uintptr_t)d.partials % 8)) return bad("partials is null or misaligned (UPDATE)");
+    if (step && (!d.reward || !d.ret || (uintptr_t)d.reward % 4 || (uintptr_t)d.ret % 8)) return bad("reward or ret is null or misaligned (STEP)");
+    const int64_t C = D + 1;
+    if (apply) {
+        if (!d.obs_out || !d.stats_in || !d.stats_out || (uintptr_t)d.obs_out % 4 || (uintptr_t)d.stats_in % 8 || (uintptr_t)d.stats_out % 8)
+            return bad("obs_out, stats_in or stats_out is null or misaligned (APPLY)");
+        const uintptr_t a = (uintptr_t)d.stats_in, b = (uintptr_t)d.stats_out, bytes = (uintptr_t)(WEDM_NORM_MOMENTS * C * 8);
+        if (a < b + bytes && b < a + bytes) return bad("stats_in and stats_out overlap");
+        if (step) {
+            if (!d.terminated || !d.truncated || !d.reward_out || !d.ep_return || !d.last_return || !d.ep_length || !d.last_length ||
+                !d.ep_count || !d.finished)
+                return bad("terminated, truncated, reward_out or a per-environment row is null (APPLY with STEP)");
+            if ((uintptr_t)d.reward_out % 4 || (uintptr_t)d.ep_return % 8 || (uintptr_t)d.last_return % 8 || (uintptr_t)d.ep_length % 4 ||
+                (uintptr_t)d.last_length % 4 || (uintptr_t)d.ep_count % 4)
+                return bad("reward_out or a per-environment row is not aligned to its element");
+        }
+    }
+    const auto launched = [](const char* what) {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return (int32_t)WEDM_OK;
+        g_create_error = std::string("wedm_normalize: ") + what + " launch: " + hipGetErrorString(e);
+        return (int32_t)WEDM_ERR_HIP;
+    };
+    const dim3 grid((uint32_t)tiles), block(WEDM_NORM_TILE);
+    if (reduce && (update || step)) {
+        // a wave per tile and column group; in evaluation mode one wave per tile, which only moves the return on
+        const int32_t c_first = update ? 0 : (int32_t)D;
+        const dim3 rgrid((uint32_t)tiles, (uint32_t)((C - c_first + WEDM_NORM_GROUP - 1) / WEDM_NORM_GROUP));
+        hipLaunchKernelGGL(wedm_norm_reduce_kernel, rgrid, dim3(64), 0, (hipStream_t)stream, d, (int32_t)D, c_first);
+        if (const int32_t rc = launched("reduce")) return rc;
+    }
+    if (apply) {
+        int32_t per = 1;  // tiles per lane of the fold: the power of two with 256 * per >= n_tiles_total
+        while (256 * per < d.n_tiles_total) per *= 2;
+        hipLaunchKernelGGL(wedm_norm_fold_kernel, dim3((uint32_t)C), dim3(256), 0, (hipStream_t)stream, d, (int32_t)C, per);
+        if (const int32_t rc = launched("fold")) return rc;
+        hipLaunchKernelGGL(wedm_norm_apply_kernel, grid, block, 0, (hipStream_t)stream, d, (int32_t)D);
+        if (const int32_t rc = launched("apply")) return rc;
     }
     return WEDM_OK;
 }

@@ -1,0 +1,386 @@
+"""Running observation and reward normalisation with episode statistics, reduced on the device.
+
+What a policy is fed: every observation column standardised by running moments over all environments and all steps so far,
+the reward scaled by the running deviation of the discounted return, and per-environment episode returns and lengths -- the
+work of Gymnasium's ``NormalizeObservation``, ``NormalizeReward`` and ``RecordEpisodeStatistics``, by `wedm_normalize`
+(include/wedm_hip.h, which holds the definition) in at most three launches without a host synchronisation and without
+temporaries.  The batch moments are a fixed pairwise tree over the global environment index, so the statistics and the
+outputs carry the same bits at every block size, on one device or several, and after a checkpoint.
+
+`torch_normalize` is that definition on host data in NumPy float64: the path of backends without the call (the CPU oracle
+backends of the tests) and what the kernels are checked against, bit for bit.  `Normalizer` owns the statistics, the
+per-environment rows and the cached workspace; `WireEDMVectorEnv(env, normalizer=Normalizer())` is the caller.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Any, Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _abi
+
+UPDATE, STEP, REDUCE, APPLY = _abi.NORM_UPDATE, _abi.NORM_STEP, _abi.NORM_REDUCE, _abi.NORM_APPLY
+TILE = _abi.NORM_TILE
+# the per-environment rows, in the order of the descriptor, and their element types
+ROWS = (("ret", np.float64), ("ep_return", np.float64), ("last_return", np.float64), ("ep_length", np.int32),
+        ("last_length", np.int32), ("ep_count", np.int32), ("finished", np.uint8))
+ROW_NAMES = tuple(name for name, _ in ROWS)
+_TORCH = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}
+RETURN_COLUMN = "discounted_return"  # the name of column D in a state dict's column set
+
+
+def fresh_stats(columns: int) -> np.ndarray:
+    """``[3, C]`` moments of a normaliser that has seen nothing: count 1e-4, mean 0, variance 1 (Gymnasium's ``RunningMeanStd``)."""
+    s = np.zeros((_abi.NORM_MOMENTS, columns), dtype=np.float64)
+    s[_abi.NM_COUNT] = 1e-4
+    s[_abi.NM_M2] = 1e-4
+    return s
+
+
+def fresh_rows(num_envs: int) -> Dict[str, np.ndarray]:
+    return {name: np.zeros(num_envs, dtype=dt) for name, dt in ROWS}
+
+
+def merge(a, b):
+    """``merge(a, b)`` of the definition on ``(n, m, S)`` float64 arrays, element-wise, every operation rounded to float64."""
+    na, ma, Sa = a
+    nb, mb, Sb = b
+    with np.errstate(all="ignore"):
+        n = na + nb
+        d = mb - ma
+        m = ma + d * (nb / n)
+        S = Sa + Sb + d * d * (na * nb / n)
+    ea, eb = na == 0.0, nb == 0.0
+    return tuple(np.where(eb, x, np.where(ea, y, z)) for x, y, z in ((na, nb, n), (ma, mb, m), (Sa, Sb, S)))
+
+
+def tree(n: np.ndarray, m: np.ndarray, S: np.ndarray):
+    """The pairwise tree along axis 0 (its length a power of two): node j of the next level is merge(node 2j, node 2j + 1)."""
+    assert n.shape[0] & (n.shape[0] - 1) == 0 and n.shape[0] > 0
+    while n.shape[0] > 1:
+        n, m, S = merge((n[0::2], m[0::2], S[0::2]), (n[1::2], m[1::2], S[1::2]))
+    return n[0], m[0], S[0]
+
+
+def fold(partials: np.ndarray) -> np.ndarray:
+    """``[T, 3, C]`` tile nodes -> the ``[3, C]`` batch moments: the tree over the tile index, padded with EMPTY."""
+    T = partials.shape[0]
+    P = 1
+    while P < T:
+        P *= 2
+    p = np.zeros((P,) + partials.shape[1:], dtype=np.float64)
+    p[:T] = partials
+    return np.stack(tree(p[:, 0], p[:, 1], p[:, 2]))
+
+
+def _host(x, dtype=None) -> Optional[np.ndarray]:
+    if x is None:
+        return None
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    return a if dtype is None else a.astype(dtype)
+
+
+def _clamp(v: np.ndarray, clip: float) -> np.ndarray:
+    return np.where(v < -clip, -clip, np.where(v > clip, clip, v))
+
+
+def torch_normalize(planes: Sequence, num_envs: int, stats_in, *, reward=None, terminated=None, truncated=None, mask=None,
+                    skip=None, rows: Optional[Dict[str, Any]] = None, partials=None, tile_offset: int = 0,
+                    n_tiles_total: Optional[int] = None, gamma: float = 0.99, eps: float = 1e-8, clip_obs: float = 10.0,
+                    clip_reward: float = 10.0, flags: int = UPDATE | STEP) -> Dict[str, torch.Tensor]:
+    """The definition of `wedm_normalize` on host data.  ``planes``: one or two float32 ``[rows, stride]`` blocks (tensors on
+    any device or arrays) whose columns ``[0, num_envs)`` are read; ``stats_in``: ``[3, C]`` float64; ``rows``: the
+    per-environment rows by name (`ROW_NAMES`; needed with ``STEP``); ``partials``: the ``[n_tiles_total, 3, C]`` workspace
+    (default: one of exactly this batch's tiles, zeroed).  Nothing that is passed in is modified.  Returns CPU tensors:
+    ``partials`` (the workspace after ``REDUCE``), ``stats_out``, ``obs_out`` ``[num_envs, D]``, ``reward_out`` (after
+    ``APPLY``; the reward only with ``STEP``) and every per-environment row that was passed in, as the call leaves it."""
+    N = int(num_envs)
+    blocks = [_host(p) for p in planes if p is not None]
+    assert 1 <= len(blocks) <= 2 and all(b.dtype == np.float32 and b.ndim == 2 and b.shape[1] >= N for b in blocks)
+    x = np.concatenate([b[:, :N] for b in blocks], axis=0)  # [D, N] float32
+    D = x.shape[0]
+    Cn = D + 1
+    if not 1 <= D <= _abi.NORM_MAX_COLUMNS - 1:
+        raise ValueError(f"normalize: {D} observation columns, outside [1, {_abi.NORM_MAX_COLUMNS - 1}]")
+    update, step = bool(flags & UPDATE), bool(flags & STEP)
+    do_reduce = bool(flags & REDUCE) or not flags & (REDUCE | APPLY)
+    do_apply = bool(flags & APPLY) or not flags & (REDUCE | APPLY)
+    tiles = -(-N // TILE)
+    n_tiles_total = tile_offset + tiles if n_tiles_total is None else int(n_tiles_total)
+    if not (tile_offset >= 0 and tile_offset + tiles <= n_tiles_total <= _abi.NORM_MAX_TILES):
+        raise ValueError("normalize: tile range outside the workspace")
+    included = np.ones(N, dtype=bool) if mask is None else _host(mask).reshape(-1)[:N].astype(bool)
+    r = _host(reward, np.float64).reshape(-1)[:N] if step else None
+    out_rows = {k: _host(v).copy() for k, v in (rows or {}).items()}
+    parts = np.zeros((n_tiles_total, _abi.NORM_MOMENTS, Cn), dtype=np.float64) if partials is None else \
+        _host(partials, np.float64).copy()
+    assert parts.shape == (n_tiles_total, _abi.NORM_MOMENTS, Cn)
+    out: Dict[str, Any] = {}
+
+    if do_reduce:
+        if step:
+            ret = out_rows["ret"]
+            ret[included] = (ret * gamma + r)[included]
+        if update:
+            n = np.zeros((tiles * TILE, Cn), dtype=np.float64)
+            m = np.zeros((tiles * TILE, Cn), dtype=np.float64)
+            n[:N, :D] = included[:, None]
+            m[:N, :D] = np.where(included[:, None], x.T.astype(np.float64), 0.0)
+            if step:
+                n[:N, D] = included
+                m[:N, D] = np.where(included, out_rows["ret"], 0.0)
+            shape = (tiles, TILE, Cn)
+            node = tree(*(a.reshape(shape).transpose(1, 0, 2) for a in (n, m, np.zeros_like(n))))
+            parts[tile_offset: tile_offset + tiles] = np.stack(node, axis=1)
+    out["partials"] = torch.from_numpy(parts)
+
+    if do_apply:
+        s_in = _host(stats_in, np.float64)
+        assert s_in.shape == (_abi.NORM_MOMENTS, Cn)
+        s_out = np.stack(merge(tuple(s_in), tuple(fold(parts)))) if update else s_in.copy()
+        with np.errstate(all="ignore"):
+            den = np.sqrt(s_out[_abi.NM_M2] / s_out[_abi.NM_COUNT] + eps)
+            y = _clamp((x.T.astype(np.float64) - s_out[_abi.NM_MEAN, :D]) / den[:D], clip_obs).astype(np.float32)
+            if skip is not None:
+                y = np.where(_host(skip).reshape(-1)[:D].astype(bool)[None, :], x.T, y)
+            out["obs_out"] = torch.from_numpy(np.ascontiguousarray(y))
+            if step:
+                out["reward_out"] = torch.from_numpy(_clamp(r / den[D], clip_reward).astype(np.float32))
+        out["stats_out"] = torch.from_numpy(s_out)
+        if step:
+            done = (_host(terminated).reshape(-1)[:N].astype(bool) | _host(truncated).reshape(-1)[:N].astype(bool))
+            total = out_rows["ep_return"] + r
+            length = out_rows["ep_length"] + 1
+            end, go = included & done, included & ~done
+            out_rows["last_return"][end] = total[end]
+            out_rows["last_length"][end] = length[end]
+            out_rows["ep_count"][end] += 1
+            out_rows["finished"][end] = 1
+            out_rows["finished"][go] = 0
+            out_rows["ep_return"][:] = np.where(end, 0.0, np.where(go, total, out_rows["ep_return"]))
+            out_rows["ep_length"][:] = np.where(end, 0, np.where(go, length, out_rows["ep_length"]))
+            out_rows["ret"][end] = 0.0
+    out.update({k: torch.from_numpy(v) for k, v in out_rows.items()})
+    return out
+
+
+def device_normalize(desc: "_abi.NormDesc", device) -> None:
+    """`wedm_normalize` on ``device`` and torch's current stream, for callers that hold no environment."""
+    from . import _lib
+
+    L = _lib.load()
+    device = torch.device(device)
+    with torch.cuda.device(device):
+        rc = L.wedm_normalize(C.byref(desc), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    if rc != _abi.OK:
+        raise _lib.WedmError(rc, (L.wedm_last_error(None) or b"").decode())
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _as_u8(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A bool / uint8 / int8 per-environment tensor as the bytes the call reads (a view, never a copy)."""
+    if t is None:
+        return None
+    assert t.element_size() == 1 and t.is_contiguous()
+    return t.view(torch.uint8)
+
+
+class Normalizer:
+    """Running normalisation of a `WireEDMVectorEnv`'s observation and reward, and its episode statistics.
+
+    ``obs`` / ``reward``: whether the adapter hands out the normalised observation / reward (the statistics are kept
+    either way).  ``gamma``: discount of the return whose deviation scales the reward.  ``epsilon``: added to a variance
+    before its root.  ``clip_obs`` / ``clip_reward``: bounds of the outputs (``float("inf")``: none).  ``skip``: names of
+    observation columns handed out as they are (a 0 / 1 flag gains nothing from standardising).  ``training=False`` (or
+    `eval`) freezes the statistics: outputs use them, episode rows and the discounted return go on.
+
+    The normaliser is bound to an adapter's column set and batch size by `WireEDMVectorEnv`; ``mean`` / ``var`` /
+    ``count`` are device tensors over the observation columns and the discounted return (the last element)."""
+
+    def __init__(self, obs: bool = True, reward: bool = True, gamma: float = 0.99, epsilon: float = 1e-8,
+                 clip_obs: float = 10.0, clip_reward: float = 10.0, skip: Sequence[str] = ("spark_state",),
+                 training: bool = True):
+        if not (clip_obs > 0.0 and clip_reward > 0.0):
+            raise ValueError("clip_obs and clip_reward must be positive (float('inf'): no clipping)")
+        if not epsilon >= 0.0:
+            raise ValueError("epsilon must not be negative")
+        self.obs, self.reward = bool(obs), bool(reward)
+        self.gamma, self.epsilon = float(gamma), float(epsilon)
+        self.clip_obs, self.clip_reward = float(clip_obs), float(clip_reward)
+        self.skip = tuple(skip)
+        self.training = bool(training)
+        self.columns: Optional[tuple] = None
+        self._pending: Optional[Dict[str, Any]] = None
+
+    # ------------------------------------------------------------------ binding
+    def bind(self, obs_names: Sequence[str], num_envs: int, device, backend=None) -> None:
+        """Allocates everything the calls need, once: two statistics blocks that alternate, the per-environment rows, the
+        partials workspace and the outputs."""
+        if self.columns is not None:
+            raise ValueError("this Normalizer already serves an adapter")
+        names = tuple(obs_names)
+        D = len(names)
+        if not 1 <= D <= _abi.NORM_MAX_COLUMNS - 1:
+            raise ValueError(f"a Normalizer takes 1 to {_abi.NORM_MAX_COLUMNS - 1} observation columns, got {D}")
+        self.columns = names + (RETURN_COLUMN,)
+        self.num_envs, self.device = int(num_envs), torch.device(device)
+        self._native = backend if hasattr(backend, "normalize") else None
+        self._tiles = -(-self.num_envs // TILE)
+        if self._tiles > _abi.NORM_MAX_TILES:
+            raise ValueError(f"a Normalizer serves at most {_abi.NORM_MAX_TILES * TILE} environments")
+        kw = dict(device=self.device)
+        self._stats = torch.from_numpy(np.stack([fresh_stats(D + 1)] * 2)).to(self.device)  # [2][3][C]; _cur names the live one
+        self._cur = 0
+        self.rows = {name: torch.zeros(self.num_envs, dtype=_TORCH[dt], **kw) for name, dt in ROWS}
+        self._partials = torch.zeros((self._tiles, _abi.NORM_MOMENTS, D + 1), dtype=torch.float64, **kw)
+        self._obs_out = torch.zeros((self.num_envs, D), dtype=torch.float32, **kw)
+        self._reward_out = torch.zeros(self.num_envs, dtype=torch.float32, **kw)
+        skip = [1 if (not self.obs or n in self.skip) else 0 for n in names]
+        self._skip = torch.tensor(skip, dtype=torch.uint8).to(self.device)
+        self._desc = _abi.NormDesc(
+            skip=self._skip.data_ptr(), obs_out=self._obs_out.data_ptr(), reward_out=self._reward_out.data_ptr(),
+            partials=self._partials.data_ptr(), tile_offset=0, n_tiles_total=self._tiles, gamma=self.gamma, eps=self.epsilon,
+            clip_obs=self.clip_obs, clip_reward=self.clip_reward, num_envs=self.num_envs,
+            **{name: t.data_ptr() for name, t in self.rows.items()})
+        self._keep = None
+        if self._pending is not None:
+            sd, self._pending = self._pending, None
+            self.load_state_dict(sd)
+
+    def _bound(self) -> None:
+        if self.columns is None:
+            raise ValueError("the Normalizer serves no adapter yet: pass it to WireEDMVectorEnv(env, normalizer=...)")
+
+    # ------------------------------------------------------------------ statistics
+    @property
+    def stats(self) -> torch.Tensor:
+        """The live ``[3, C]`` moments (count, mean, sum of squared deviations): a view, valid until the next call."""
+        self._bound()
+        return self._stats[self._cur]
+
+    @property
+    def count(self) -> torch.Tensor:
+        return self.stats[_abi.NM_COUNT]
+
+    @property
+    def mean(self) -> torch.Tensor:
+        return self.stats[_abi.NM_MEAN]
+
+    @property
+    def var(self) -> torch.Tensor:
+        return self.stats[_abi.NM_M2] / self.stats[_abi.NM_COUNT]
+
+    def train(self, mode: bool = True) -> "Normalizer":
+        self.training = bool(mode)
+        return self
+
+    def eval(self) -> "Normalizer":
+        return self.train(False)
+
+    @property
+    def episode_stats(self) -> Dict[str, torch.Tensor]:
+        """``r`` / ``l``: return and length of each environment's last finished episode; ``count``: episodes it has
+        finished; ``finished``: whether it finished one in the last step.  The live rows: valid until the next step."""
+        self._bound()
+        return {"r": self.rows["last_return"], "l": self.rows["last_length"], "count": self.rows["ep_count"],
+                "finished": self.rows["finished"]}
+
+    # ------------------------------------------------------------------ the call
+    def normalize(self, planes: Sequence[torch.Tensor], *, reward=None, terminated=None, truncated=None, mask=None):
+        """One call: with ``reward`` a step (`WEDM_NORM_STEP`), without it an observation only.  ``planes``: one or two
+        float32 ``[rows, stride]`` blocks on the normaliser's device.  Returns ``(obs_out, reward_out or None)``, the cached
+        output tensors: valid until the next call."""
+        self._bound()
+        planes = [p for p in planes if p is not None]
+        D = len(self.columns) - 1
+        if sum(int(p.shape[0]) for p in planes) != D:
+            raise ValueError(f"normalize: the planes hold {sum(int(p.shape[0]) for p in planes)} rows, the Normalizer {D} columns")
+        step = reward is not None
+        flags = (UPDATE if self.training else 0) | (STEP if step else 0)
+        nxt = 1 - self._cur
+        if self._native is None:
+            out = torch_normalize(planes, self.num_envs, self._stats[self._cur], reward=reward, terminated=terminated,
+                                  truncated=truncated, mask=mask, skip=self._skip, rows=self.rows if step else None,
+                                  gamma=self.gamma, eps=self.epsilon, clip_obs=self.clip_obs, clip_reward=self.clip_reward,
+                                  flags=flags)
+            self._stats[nxt].copy_(out["stats_out"])
+            self._obs_out.copy_(out["obs_out"])
+            if step:
+                self._reward_out.copy_(out["reward_out"])
+                for name in ROW_NAMES:
+                    self.rows[name].copy_(out[name])
+        else:
+            d = self._desc
+            for k in range(2):
+                p = planes[k] if k < len(planes) else None
+                assert p is None or (p.dtype == torch.float32 and p.dim() == 2 and p.stride(1) == 1 and p.device == self.device)
+                d.plane[k].rows = _ptr(p)
+                d.plane[k].n_rows = 0 if p is None else int(p.shape[0])
+                d.plane[k].stride = 0 if p is None else int(p.stride(0))
+            term, trunc, msk = _as_u8(terminated), _as_u8(truncated), _as_u8(mask)
+            d.reward, d.terminated, d.truncated, d.mask = _ptr(reward), _ptr(term), _ptr(trunc), _ptr(msk)
+            d.stats_in, d.stats_out = self._stats[self._cur].data_ptr(), self._stats[nxt].data_ptr()
+            d.flags = flags
+            self._native.normalize(d)
+            self._keep = (planes, reward, term, trunc, msk)  # the launches are asynchronous: their inputs live until the next call
+        self._cur = nxt
+        return self._obs_out, (self._reward_out if step else None)
+
+    def reset_rows(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Zeroes the per-environment rows of the environments ``mask`` names (``None``: all).  The statistics stay."""
+        self._bound()
+        for t in self.rows.values():
+            if mask is None:
+                t.zero_()
+            else:
+                t.masked_fill_(mask, 0)
+
+    def fork(self, src, dst) -> None:
+        """Carries the per-environment rows from environments ``src`` to ``dst`` (`sparc_amd.snapshot.fork_rows`)."""
+        from .snapshot import fork_rows
+
+        self._bound()
+        for t in self.rows.values():
+            fork_rows(t, src, dst)
+
+    # ------------------------------------------------------------------ checkpoints
+    def settings(self) -> Dict[str, Any]:
+        return dict(obs=self.obs, reward=self.reward, gamma=self.gamma, epsilon=self.epsilon, clip_obs=self.clip_obs,
+                    clip_reward=self.clip_reward, skip=self.skip, training=self.training)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """The column set, the statistics, the per-environment rows and the settings, as CPU tensors and plain values."""
+        self._bound()
+        return {"columns": self.columns, "num_envs": self.num_envs, "stats": self.stats.detach().cpu().clone(),
+                "rows": {k: v.detach().cpu().clone() for k, v in self.rows.items()}, "settings": self.settings()}
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Takes over a `state_dict`.  Before the normaliser serves an adapter the dict is kept and checked when it does; a
+        dict of another column set or batch size is refused."""
+        if self.columns is None:
+            self._pending = sd
+            self._load_settings(sd["settings"])
+            return
+        if tuple(sd["columns"]) != self.columns:
+            raise ValueError(f"the state dict normalises the columns {tuple(sd['columns'])}, this Normalizer {self.columns}")
+        if int(sd["num_envs"]) != self.num_envs:
+            raise ValueError(f"the state dict holds {sd['num_envs']} environments, this Normalizer {self.num_envs}")
+        self._load_settings(sd["settings"])
+        self._stats[self._cur].copy_(torch.as_tensor(sd["stats"], dtype=torch.float64))
+        for k, t in self.rows.items():
+            t.copy_(torch.as_tensor(sd["rows"][k]).to(t.dtype))
+        names = self.columns[:-1]
+        self._skip.copy_(torch.tensor([1 if (not self.obs or n in self.skip) else 0 for n in names], dtype=torch.uint8))
+        d = self._desc
+        d.gamma, d.eps, d.clip_obs, d.clip_reward = self.gamma, self.epsilon, self.clip_obs, self.clip_reward
+
+    def _load_settings(self, s: Dict[str, Any]) -> None:
+        self.obs, self.reward = bool(s["obs"]), bool(s["reward"])
+        self.gamma, self.epsilon = float(s["gamma"]), float(s["epsilon"])
+        self.clip_obs, self.clip_reward = float(s["clip_obs"]), float(s["clip_reward"])
+        self.skip, self.training = tuple(s["skip"]), bool(s["training"])

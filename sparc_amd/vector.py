@@ -96,7 +96,7 @@ class WireEDMVectorEnv:
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
                  reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
                  wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None,
-                 episode_sampler=None):
+                 episode_sampler=None, normalizer=None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -123,7 +123,16 @@ class WireEDMVectorEnv:
         ``wire_profile_bins``: with an integer B in [0, 64], `reset()` and `step()` return ``[N, obs_dim + 4 + 2 * B]``: the
         environment's observation followed by the rows of `WireEDMEnv.wire_profile` (zone mean, wire mean, maximum,
         hottest cell, B bin maxima, B bin means) of the wire as the launch left it -- one more launch, no host
-        synchronisation; `obs_names` and the observation spaces grow to match."""
+        synchronisation; `obs_names` and the observation spaces grow to match.
+        ``normalizer``: a `sparc_amd.normalize.Normalizer` -- `reset()` and `step()` return the observation (profile columns
+        included) standardised by running moments over every environment and step, `step()` the reward scaled by the running
+        deviation of the discounted return, by `wedm_normalize` (at most three more launches, no host synchronisation, no
+        allocation after the first call); ``info["episode_stats"]`` holds the return ``r`` and length ``l`` of each
+        environment's last finished episode, its ``count`` of finished episodes and whether it ``finished`` one in this
+        step (device tensors, valid until the next step), ``info["raw_observation"]`` / ``info["raw_reward"]`` the values
+        before normalisation.  The normalised tensors are the normaliser's cached outputs: valid until the next call.
+        Environments that are frozen during a step (done, with ``autoreset=False``) take no part in the statistics and keep
+        their rows; a masked `reset` zeroes the rows of the environments it resets."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
@@ -167,6 +176,9 @@ class WireEDMVectorEnv:
                 raise ValueError("episode_sampler replaces param_sampler / material_sampler / geometry_sampler: give either")
             episode_sampler.bind(env)
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
+        self.normalizer = normalizer
+        if normalizer is not None:
+            normalizer.bind(self.obs_names, self.num_envs, env.device, getattr(env, "_backend", None))
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
@@ -184,7 +196,29 @@ class WireEDMVectorEnv:
             self._apply_sampler(mask)
         obs, info = self.env.reset(seed=seed, options=options)
         self._need_reset.zero_()
+        if self.normalizer is not None:
+            mask = (options or {}).get("mask")
+            if mask is not None:
+                mask = torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
+            self.normalizer.reset_rows(mask)
+            planes = self._planes()
+            out, _ = self.normalizer.normalize(planes, mask=mask)
+            info = dict(info)
+            info["raw_observation"] = self._raw(obs, planes)
+            return out, info
         return self._observation(obs), info
+
+    def _planes(self):
+        """The blocks `wedm_normalize` reads, as they lie: the environment's observation and the wire profile's rows."""
+        obs = self.env.state.obs
+        if self.wire_profile_bins is None:
+            return [obs]
+        return [obs, self.env.wire_profile(self.wire_profile_bins)["rows"]]
+
+    @staticmethod
+    def _raw(obs: torch.Tensor, planes) -> torch.Tensor:
+        """`_observation` from the planes already at hand (no second profile launch)."""
+        return obs.clone() if len(planes) == 1 else torch.cat([obs, planes[1].t()], dim=1)
 
     def _observation(self, obs: torch.Tensor) -> torch.Tensor:
         """What `reset` and `step` hand out: a tensor of the caller's own (the environment reuses its block), with the wire
@@ -217,6 +251,8 @@ class WireEDMVectorEnv:
             elif bool(self._need_reset.any().item()):
                 self.env.reset(options={"mask": self._need_reset})  # same key, next episode stream
             self.episode_count += self._need_reset.to(torch.int64)
+        # environments this step leaves frozen take no part in the normaliser's statistics
+        live = None if self.normalizer is None or self.autoreset else ~self._need_reset
         prev = {"workpiece_position": self.env.state.workpiece_position.clone()} if self._reward_fn is not None else None
         if prev is not None and self._in_kernel_reset:  # what the kernel's reset will make of the marked environments
             prev["workpiece_position"] = torch.where(self._need_reset, torch.full_like(
@@ -234,6 +270,15 @@ class WireEDMVectorEnv:
         self._need_reset = terminated | truncated
         info = dict(info)  # (StepInfo: the copy composes the exact int64 clock)
         info["episode"] = self.episode_count
+        if self.normalizer is not None:
+            norm = self.normalizer
+            reward = reward.contiguous()
+            planes = self._planes()
+            out, scaled = norm.normalize(planes, reward=reward, terminated=terminated, truncated=truncated, mask=live)
+            info["episode_stats"] = norm.episode_stats
+            info["raw_observation"] = self._raw(obs, planes)
+            info["raw_reward"] = reward
+            return out, (scaled if norm.reward else reward), terminated, truncated, info
         return self._observation(obs), reward, terminated, truncated, info
 
     def fork(self, src, dst) -> None:
@@ -244,6 +289,8 @@ class WireEDMVectorEnv:
 
         self.env.fork(src, dst)
         fork_rows(self._need_reset, src, dst)
+        if self.normalizer is not None:
+            self.normalizer.fork(src, dst)
 
     def close(self) -> None:
         self.env.close()
