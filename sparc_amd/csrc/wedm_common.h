@@ -171,13 +171,29 @@ struct GlobalT {
 };
 __device__ __forceinline__ GlobalT global_wire(float* T, int64_t stride, int64_t e) { return GlobalT{T + 4 * e, 4 * stride}; }
 
-// Block-cooperative copy of the wire cells [0, n) of the block's 256 / L environments between the quad-interleaved
+// The LDS images' slot maps: LDS float offset of wire cell i for the block's first environment; one column per thread
+// that walks.
+// Plain (wedm_step_fused, wedm_step_lanes): chunk ci = i / C, cell r = i % C -> lane ci, row r of 256 columns.
+struct ChunkSlot {
+    int C;
+    __device__ int operator()(int i) const { const int ci = i / C; return (i - ci * C) * 256 + ci; }
+};
+// Packed (wedm_step_packed, wedm_step_lanes_pk and the served forms of both): virtual chunk vc = i / Cv, cell r = i % Cv
+// -> lane vc / 2, row 2 r + vc % 2 of CS columns (256, or a served kernel's walker threads).
+template <int CS>
+struct PackedSlot {
+    int Cv;
+    __device__ int operator()(int i) const { const int vc = i / Cv; return (2 * (i - vc * Cv) + (vc & 1)) * CS + (vc >> 1); }
+};
+
+// Block-cooperative copy of the wire cells [0, n) of the block's NT / L environments between the quad-interleaved
 // block in HBM and the kernel's LDS image, 16 bytes per lane and instruction (a wave touches contiguous runs of
-// 64 x 16 B).  `slot(i)` = LDS float offset of wire cell i for the block's first environment (the kernel's own
-// chunk / row mapping); environment slot `sel` adds sel * L.  Cells of the last quad past n are padding: not copied.
-template <int L, bool TO_LDS, class Slot>
+// 64 x 16 B).  NT: the threads that move the wire, the block's first (all 256, or a served kernel's walker threads: the
+// others do not call).  `slot(i)`: one of the maps above; environment slot `sel` adds sel * L.  Cells of the last quad past
+// n are padding: not copied.
+template <int L, bool TO_LDS, int NT = 256, class Slot>
 __device__ __forceinline__ void copy_wire(float* T, int64_t stride, int64_t e0, int num_envs, int n, int tid, float* lds, Slot slot) {
-    constexpr int EPB = 256 / L;
+    constexpr int EPB = NT / L;
     const int qr = tid / EPB, sel = tid % EPB;  // L quads per iteration
     if (e0 + sel >= num_envs) return;
     float* const base = T + 4 * (e0 + sel);

@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
 
     // ---- stage the block's EPB wire columns: 16-byte words of the quad-interleaved block -> LDS
     // wire cell i -> chunk i / C, cell i % C -> LDS [cell][256 lanes], lane = environment slot * L + chunk
-    const auto wire_slot = [C](int i) { const int ci = i / C; return (i - ci * C) * 256 + ci; };
+    const ChunkSlot wire_slot{C};
     copy_wire<L, true>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
     __syncthreads();
 

@@ -7,7 +7,9 @@
 //                         Philox, the portable exp / log / cube, stencil_cell
 //   wedm_env_rows.h       which Env member holds which state row, when it is final, whether a step reads it and whether a
 //                         reference-semantics reset keeps it: the lists load_env / store_env / the trace are expanded from
-//   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors / copy_wire, tile_staged / quad_staged
+//   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors, the LDS images' slot maps (ChunkSlot,
+//                         PackedSlot) and the block copy of the wire that takes them (copy_wire: every LDS kernel, served or
+//                         not), tile_staged / quad_staged
 //   wedm_lifecycle.h      an environment's launch lifecycle, each part written once as text the kernels expand (WEDM_ENV_LOAD /
 //                         _RESET / _START, _END_US / _STEP_DONE, _CLOSE) and the helpers that wrap it (env_open / env_start,
 //                         env_end_us / env_step_done, env_close); launch_hot, stencil_f64_consts (the file's head says who
@@ -24,7 +26,10 @@
 //   wedm_packed_walk.inc  the packed LDS walk itself (per-lane tile flags; one microsecond: halos, tiles, patches), included as
 //                         text by wedm_step_packed and by the walkers of wedm_step_served
 //   wedm_served.h         wedm_step_served<L>: the packed walk on three waves of a block, the scalar physics of the block's
-//                         environments on the fourth, one microsecond ahead (kernel 9: large batches of long wires)
+//                         environments on the fourth, one microsecond ahead (kernel 9: large batches of long wires); the
+//                         LDS mailbox between them and both sides of its protocol, each written once (served_scalar_wave;
+//                         WEDM_SV_BOX_INIT / _WAIT_COEF / _TAKE, sv_give, sv_walker_reinit, sv_stamp_row), which
+//                         wedm_step_lanes_served (wedm_lanes2.h) and wedm_step_regs_served (here) run as well
 //   wedm_k_regs.h         wedm_step_regs<L> (the headline: the wire in the registers of two lanes per environment),
 //                         wedm_step_regs_wide<L> (4 / 8 / 16 lanes of a DPP row per environment: small batches)
 //                         and, as text (WEDM_REGS_*), what both and wedm_step_regs_served do with the wire around the loop

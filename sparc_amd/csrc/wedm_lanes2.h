@@ -211,8 +211,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
     const int Cv = (nmax + 2 * L - 1) / (2 * L);  // cells per virtual chunk
     const int R = 2 * Cv;                          // data rows per lane; rows R and R + 1 are the halo pair
     const int64_t stride = cold->s.stride;
-    // wire cell i -> virtual chunk vc = i / Cv, cell r = i % Cv -> lane vc / 2, row 2 r + vc % 2
-    const auto wire_slot = [Cv](int i) { const int vc = i / Cv; return (2 * (i - vc * Cv) + (vc & 1)) * 256 + (vc >> 1); };
+    const PackedSlot<256> wire_slot{Cv};
     copy_wire<L, true>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
     __syncthreads();
 
@@ -300,8 +299,8 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_lanes
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
     SvStamps svs;
     sv_stamps_begin(svs);
-    unsigned long long* const stamp_row = k.dbg ? k.dbg + ((size_t)blockIdx.x * 4 + (tid >> 6)) * 12 : nullptr;
-    if (tid == 0) { box->cf_seq = 0u; box->tm_seq[0] = 0u; box->tm_seq[1] = 0u; box->tm_seq[2] = 0u; box->tm_seq[3] = 0u; }
+    unsigned long long* const stamp_row = sv_stamp_row<4>(k, tid);
+    WEDM_SV_BOX_INIT()
     if (tid >= NT) {
         served_scalar_wave<EPB, L>(k, cold, box, e0, tid - NT, svs, stamp_row);
         return;
@@ -311,12 +310,12 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_lanes
     const int el = tid / L, c = tid % L, wave = tid >> 6;
     const int64_t e = e0 + el;
     const bool live = e < k.num_envs;
-    const auto wire_slot = [Cv](int i) { const int vc = i / Cv; return (2 * (i - vc * Cv) + (vc & 1)) * NT + (vc >> 1); };
-    copy_wire_nt<L, NT, true>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
+    const PackedSlot<NT> wire_slot{Cv};
+    copy_wire<L, true, NT>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
     Geom g;
     load_geom(k.hot, cold, live ? e : 0, g);  // this lane's environment
     float* col = lds + tid;
-    const bool reinit = live && WEDM_AUTORESET(cold) && cold->s.i8[(int64_t)WEDM_B_DONE * stride + e] != 0;
+    const bool reinit = sv_walker_reinit(cold, stride, e, live);
     __syncthreads();  // (A)
     if (reinit) {
         for (int row = 0; row < R; ++row) col[row * NT] = spool;
@@ -325,6 +324,8 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_lanes
     const int baseA = 2 * c * Cv, baseB = baseA + Cv;
     const int n = g.n_seg;
     if (c == 0) col[0] = spool;  // wire cell 0 is held at the spool temperature
+    // (wedm_step_lanes_pk's LanesPkGeom in this kernel's own wording: a builder, or either kernel's wording in the other,
+    // moved the code of the kernel that took it -- profiles/r13/asm_parent_vs_served_walker.txt)
     const int own_last = (n >= 2) ? ((n - 1 >= baseA && n - 1 < baseA + Cv) ? 1 : (n - 1 >= baseB && n - 1 < baseB + Cv) ? 2 : 0) : 0;
     const bool has_inner = n >= 3;
     const LanesPkGeom pkg{c, Cv, R, n, baseA, baseB, own_last,
@@ -335,26 +336,18 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_lanes
     WEDM_SV_LOOP_START();
     for (int it = 0; it < k.n_substeps; ++it) {
         const int slot = it & 1;
-        { WEDM_SV_WAIT_BEGIN(); sv_wait(&box->cf_seq, (uint32_t)it + 1u); WEDM_SV_WAIT_END(); }
+        { WEDM_SV_WAIT_BEGIN(); WEDM_SV_WAIT_COEF(); WEDM_SV_WAIT_END(); }
         WEDM_SV_PHASE_START();
-        const int32_t fl = box->flags[slot][el];
-        if (fl & SV_STOP) break;  // (block-wide: every lane reads it)
-        const Coef cf{box->jf[slot][el], box->q[slot][el], (fl & SV_JOULE) ? 1 : 0, box->pidx[slot][el]};
-        ps.conv_base = box->conv_base[slot][el];
-        ps.conv_zone = box->conv_zone[slot][el];
-        ps.adv_on = (fl & SV_ADV) ? 1 : 0;
-        const bool keep = live && !(fl & SV_DONE);
+        WEDM_SV_TAKE(cf, frozen)
         WEDM_SV_PHASE(pa);
-        float tmax = lanes_pk_step<L, NT>(col, pkg, keep, g, cf, ps, spool, tref, alpha, tdiel);
+        float tmax = lanes_pk_step<L, NT>(col, pkg, !frozen, g, cf, ps, spool, tref, alpha, tdiel);
         WEDM_SV_PHASE(pb);
         tmax = max_over_env_lanes<L>(tmax);
-        if (c == 0) box->tmax[slot][el] = tmax;
-        asm volatile("" ::: "memory");
-        if ((tid & 63) == 0) box->tm_seq[wave] = (uint32_t)it + 1u;
+        sv_give(box, slot, el, c == 0, tid, wave, it, tmax);
         WEDM_SV_PHASE(pc);
     }
     WEDM_SV_LOOP_END();
     sv_stamps_out(svs, stamp_row);
     __syncthreads();  // (B)
-    copy_wire_nt<L, NT, false>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
+    copy_wire<L, false, NT>(cold->s.T, stride, e0, k.num_envs, nmax, tid, lds, wire_slot);
 }

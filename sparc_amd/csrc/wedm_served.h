@@ -1,6 +1,8 @@
 // wedm_served.h — "served" kernels: the float64 scalar physics of a block's environments on a wave of its own.
 //
-// Included by wedm_kernels.hip (it uses that file's KArgs, WalkTable, copy_wire, tile8_staged, interior_cell ...).
+// Included by wedm_kernels.hip behind wedm_common.h (KArgs, WalkTable, copy_wire, PackedSlot, tile_staged) and wedm_k_regs.h.
+// Here: the mailbox, both sides of its protocol written once each (served_scalar_wave; the walkers' behind sv_wait), and
+// wedm_step_served and wedm_step_regs_served.  The third kernel that runs it, wedm_step_lanes_served, is in wedm_lanes2.h.
 // The walkers of wedm_step_served run the text of wedm_packed_walk.inc (wedm_step_packed's walk, column stride 192, the frozen
 // flag from the mailbox) with this kernel's own tiles and tails; those of wedm_step_regs_served the text of wedm_regs_walk.inc.
 //
@@ -115,6 +117,50 @@ __device__ __forceinline__ void sv_wait_lanes(const volatile uint32_t* p, uint32
 
 }  // namespace wedm
 
+// ------------------------------------------------------------------------------------- the walkers' side of the mailbox
+// Written once for the walkers of the three kernels, which keep their WEDM_SV_WAIT_BEGIN / _END and WEDM_SV_PHASE marks
+// around the pieces.  Functions where a function leaves every kernel's code as it was; text the kernel expands (as
+// wedm_lifecycle.h's, naming the includer's `box`, `tid`, `it`, `slot`, `el`, `live`, `ps`, `s`, `hv`) where a function moved
+// a wave's register allocation: profiles/r13/asm_parent_vs_served_walker.txt.
+// Thread 0 of the block, before barrier (A): nothing is published yet.
+#define WEDM_SV_BOX_INIT() \
+    if (tid == 0) { box->cf_seq = 0u; box->tm_seq[0] = 0u; box->tm_seq[1] = 0u; box->tm_seq[2] = 0u; box->tm_seq[3] = 0u; }
+// this wave's 12 words of the stamp buffer (WAVES per block, the scalar wave included), or null
+template <int WAVES>
+__device__ __forceinline__ unsigned long long* sv_stamp_row(const KArgs& k, int tid) {
+    return k.dbg ? k.dbg + ((size_t)blockIdx.x * WAVES + (tid >> 6)) * 12 : nullptr;
+}
+// next-step autoreset: the environment's wire starts at the spool temperature (the scalar wave re-initialises the state)
+__device__ __forceinline__ bool sv_walker_reinit(const ColdRef cold, int64_t stride, int64_t e, bool live) {
+    return live && WEDM_AUTORESET(cold) && cold->s.i8[(int64_t)WEDM_B_DONE * stride + e] != 0;
+}
+// Step `it`: until its coefficients are published; then take those of environment slot `el`: the step's `cf`, the convection
+// pair and adv_on of `ps`, and `frozen` (no store into this environment's wire: terminated, or past the batch).  SV_STOP:
+// every environment of the block is terminated, the walker leaves its loop (block-wide: every lane reads it).
+#define WEDM_SV_WAIT_COEF() sv_wait(&box->cf_seq, (uint32_t)it + 1u)
+#define WEDM_SV_TAKE(cf, frozen)                                                                                  \
+    const int32_t fl = box->flags[slot][el];                                                                      \
+    if (fl & SV_STOP) break;                                                                                      \
+    Coef cf{box->jf[slot][el], box->q[slot][el], (fl & SV_JOULE) ? 1 : 0, box->pidx[slot][el]};                   \
+    ps.conv_base = box->conv_base[slot][el];                                                                      \
+    ps.conv_zone = box->conv_zone[slot][el];                                                                      \
+    ps.adv_on = (fl & SV_ADV) ? 1 : 0;                                                                            \
+    const bool frozen = !live || (fl & SV_DONE);
+// Give the environment's maximum of step `it` (`first`: the environment's first lane writes it).  The store order is the
+// protocol's: the data word, then the compiler barrier, then the sequence word of this walker wave (by its first lane).
+template <int EPB>
+__device__ __forceinline__ void sv_give(volatile ServedBox<EPB>* box, int slot, int el, bool first, int tid, int wave, int it, float tmax) {
+    if (first) box->tmax[slot][el] = tmax;
+    asm volatile("" ::: "memory");
+    if ((tid & 63) == 0) box->tm_seq[wave] = (uint32_t)it + 1u;
+}
+// The scalar wave applies the temperature monitor (wire.py:376-388) of a step it ran ahead of, when the maximum `tm` is
+// there.  The step was proven not to break the wire: a break here is impossible, and loud (the sticky ERROR flag).
+#define WEDM_SV_APPLY_MONITOR(tm)                                                                                 \
+    s.tcrit = (tm) > hv.tcrit ? s.tcrit + 1 : 0;                                                                  \
+    s.tmax = (tm);                                                                                                \
+    if ((tm) > hv.tbreak) { s.err = 1; s.broken = 1; s.done = hv.done_value; }
+
 // -DWEDM_SV_CALL_GENERAL (tried, slower, kept as a switch): the GENERAL prelude (a lane ignites, a short, a control-step
 // latch: a few per cent of a batch's microseconds) as a real function call.  Inlined, its ~100 temporaries on top of the Env
 // cost the scalar wave 46-62 spilled registers at the 168 registers three blocks per CU leave a wave.  Called, what it takes
@@ -134,35 +180,6 @@ __device__ __attribute__((noinline)) void sv_general_prelude(uint64_t kernarg_ad
     load_geom(hot, cold, e, g);
     out = scalar_prelude(hot, cold, g, e, gid, s, ps, true, qt);
 #endif
-}
-
-// copy_wire() for a block whose first NT threads (NT = L x environments per block) move the wire; LDS rows of NT floats
-template <int L, int NT, bool TO_LDS, class Slot>
-__device__ __forceinline__ void copy_wire_nt(float* T, int64_t stride, int64_t e0, int num_envs, int n, int tid, float* lds, Slot slot) {
-    constexpr int EPB = NT / L;
-    const int qr = tid / EPB, sel = tid % EPB;  // L quads per iteration
-    if (e0 + sel >= num_envs) return;
-    float* const base = T + 4 * (e0 + sel);
-    const int64_t qstride = 4 * stride;
-    const int nq = (n + 3) >> 2;
-    for (int q = qr; q < nq; q += L) {
-        float* const g = base + (int64_t)q * qstride;
-        if (TO_LDS) {
-            const f4v v = *(const f4v*)g;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * q + k < n) lds[slot(4 * q + k) + sel * L] = v[k];
-        } else if (4 * q + 3 < n) {
-            f4v v;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) v[k] = lds[slot(4 * q + k) + sel * L];
-            *(f4v*)g = v;
-        } else {
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * q + k < n) g[k] = lds[slot(4 * q + k) + sel * L];
-        }
-    }
 }
 
 #ifndef WEDM_SERVED_STAGE_W
@@ -272,9 +289,7 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
             { WEDM_SV_WAIT_BEGIN(); sv_wait_lanes(&box->tm_seq[(sl < EPB ? sl * LPE : 0) >> 6], (uint32_t)it); WEDM_SV_WAIT_END(); }
             const float tm = sl < EPB ? box->tmax[slot ^ 1][sl] : spool;
             if (pend_live) {
-                s.tcrit = tm > hv.tcrit ? s.tcrit + 1 : 0;
-                s.tmax = tm;
-                if (tm > hv.tbreak) { s.err = 1; s.broken = 1; s.done = hv.done_value; }  // (proven impossible; loud if it ever is not)
+                WEDM_SV_APPLY_MONITOR(tm)
                 M = tm;
             }
             pending = false;
@@ -321,9 +336,7 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
         sv_wait_lanes(&box->tm_seq[(sl < EPB ? sl * LPE : 0) >> 6], (uint32_t)it);
         const float tm = sl < EPB ? box->tmax[(it - 1) & 1][sl] : spool;
         if (pend_live) {
-            s.tcrit = tm > hv.tcrit ? s.tcrit + 1 : 0;
-            s.tmax = tm;
-            if (tm > hv.tbreak) { s.err = 1; s.broken = 1; s.done = hv.done_value; }
+            WEDM_SV_APPLY_MONITOR(tm)
         }
     }
     WEDM_SV_LOOP_END();
@@ -390,9 +403,9 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
     const bool scalar_wave = tid >= NT;
     SvStamps svs;
     sv_stamps_begin(svs);
-    unsigned long long* const stamp_row = k.dbg ? k.dbg + ((size_t)blockIdx.x * (WW + 1) + (tid >> 6)) * 12 : nullptr;
+    unsigned long long* const stamp_row = sv_stamp_row<WW + 1>(k, tid);
 
-    if (tid == 0) { box->cf_seq = 0u; box->tm_seq[0] = 0u; box->tm_seq[1] = 0u; box->tm_seq[2] = 0u; box->tm_seq[3] = 0u; }
+    WEDM_SV_BOX_INIT()
 
     if (scalar_wave) {
         served_scalar_wave<EPB, L>(k, cold, box, e0, tid - NT, svs, stamp_row);
@@ -407,14 +420,13 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
     const int64_t e = e0 + el;
     const bool live = e < k.num_envs;
     const int wave = tid >> 6;
-    // ---- stage: wire cell i -> virtual chunk vc = i / Cv, cell r = i % Cv -> lane vc/2, row 2r + vc%2
-    const auto wire_slot = [Cv](int i) { const int vc = i / Cv; return (2 * (i - vc * Cv) + (vc & 1)) * NT + (vc >> 1); };
-    copy_wire_nt<L, NT, true>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
+    // ---- stage
+    const PackedSlot<NT> wire_slot{Cv};
+    copy_wire<L, true, NT>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
     Geom g;
     load_geom(k.hot, cold, 0, g);  // uniform geometry
     float* col = lds + tid;
-    // next-step autoreset: the environment's wire starts at the spool temperature (the scalar wave re-initialises the state)
-    const bool reinit = live && WEDM_AUTORESET(cold) && cold->s.i8[(int64_t)WEDM_B_DONE * stride + e] != 0;
+    const bool reinit = sv_walker_reinit(cold, stride, e, live);
     __syncthreads();  // (A)
     if (reinit) {
         for (int row = 0; row < R; ++row) col[row * NT] = spool;
@@ -432,15 +444,9 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
     WEDM_SV_LOOP_START();
     for (int it = 0; it < k.n_substeps; ++it) {
         const int slot = it & 1;
-        { WEDM_SV_WAIT_BEGIN(); sv_wait(&box->cf_seq, (uint32_t)it + 1u); WEDM_SV_WAIT_END(); }
+        { WEDM_SV_WAIT_BEGIN(); WEDM_SV_WAIT_COEF(); WEDM_SV_WAIT_END(); }
         WEDM_SV_PHASE_START();
-        const int32_t fl = box->flags[slot][el];
-        if (fl & SV_STOP) break;  // (block-wide: every lane reads it)
-        Coef cf{box->jf[slot][el], box->q[slot][el], (fl & SV_JOULE) ? 1 : 0, box->pidx[slot][el]};
-        ps.conv_base = box->conv_base[slot][el];
-        ps.conv_zone = box->conv_zone[slot][el];
-        ps.adv_on = (fl & SV_ADV) ? 1 : 0;
-        const bool done = !live || (fl & SV_DONE);
+        WEDM_SV_TAKE(cf, done)
 
         float tmax = spool;
         // a tile with one coefficient change at `split`: the pairs' coefficients are selected group by group, right before
@@ -468,16 +474,14 @@ __global__ void __launch_bounds__(256, WEDM_SERVED_WAVES_PER_EU) wedm_step_serve
 #undef WEDM_PACKED_WALK_MARK_TILES
 #undef WEDM_PACKED_WALK_MARK_PATCHES
         tmax = max_over_env_lanes<L>(tmax);
-        if (c == 0) box->tmax[slot][el] = tmax;
-        asm volatile("" ::: "memory");
-        if ((tid & 63) == 0) box->tm_seq[wave] = (uint32_t)it + 1u;
+        sv_give(box, slot, el, c == 0, tid, wave, it, tmax);
         WEDM_SV_PHASE(pc);  // patches, reduction, publication
     }
 
     WEDM_SV_LOOP_END();
     sv_stamps_out(svs, stamp_row);
     __syncthreads();  // (B)
-    copy_wire_nt<L, NT, false>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
+    copy_wire<L, false, NT>(cold->s.T, stride, e0, k.num_envs, n, tid, lds, wire_slot);
 }
 #undef WEDM_PACKED_WALK_TAILS_FROM_OLD
 #undef WEDM_PACKED_WALK_TAIL_NEW
@@ -507,8 +511,8 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
     const int64_t e0 = (int64_t)blockIdx.x * EPB;
     SvStamps svs;
     sv_stamps_begin(svs);
-    unsigned long long* const stamp_row = k.dbg ? k.dbg + ((size_t)blockIdx.x * 3 + (tid >> 6)) * 12 : nullptr;
-    if (tid == 0) { box->cf_seq = 0u; box->tm_seq[0] = 0u; box->tm_seq[1] = 0u; box->tm_seq[2] = 0u; box->tm_seq[3] = 0u; }
+    unsigned long long* const stamp_row = sv_stamp_row<3>(k, tid);
+    WEDM_SV_BOX_INIT()
     if (tid >= NT) {
         served_scalar_wave<EPB, L>(k, cold, box, e0, tid - NT, svs, stamp_row);
         return;
@@ -526,8 +530,7 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
     WEDM_REGS_LOAD_WIRE()  // (the wire first)
     Geom g;
     load_geom(k.hot, cold, 0, g);  // uniform geometry
-    // next-step autoreset: the environment's wire starts at the spool temperature (the scalar wave re-initialises the state)
-    const bool reinit = live && WEDM_AUTORESET(cold) && cold->s.i8[(int64_t)WEDM_B_DONE * stride + e] != 0;
+    const bool reinit = sv_walker_reinit(cold, stride, e, live);
     WEDM_REGS_WIPE_WIRE()
     // tile flags of this lane's two chunks (bit t: the tile's first cell lies in the workpiece zone / between the contacts)
     const int n_tiles = wt->n_tiles;
@@ -551,15 +554,10 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
     WEDM_SV_LOOP_START();
     for (int it = 0; it < k.n_substeps; ++it) {
         const int slot = it & 1;
-        { WEDM_SV_WAIT_BEGIN(); sv_wait(&box->cf_seq, (uint32_t)it + 1u); WEDM_SV_WAIT_END(); }
+        { WEDM_SV_WAIT_BEGIN(); WEDM_SV_WAIT_COEF(); WEDM_SV_WAIT_END(); }
         WEDM_SV_PHASE_START();
-        const int32_t fl = box->flags[slot][el];
-        if (fl & SV_STOP) break;  // (block-wide: every lane reads it)
-        Coef cf{box->jf[slot][el], box->q[slot][el], (fl & SV_JOULE) ? 1 : 0, box->pidx[slot][el]};
-        ps.conv_base = box->conv_base[slot][el];
-        ps.conv_zone = box->conv_zone[slot][el];
-        ps.adv_on = (fl & SV_ADV) ? 1 : 0;
-        const bool act = live && !(fl & SV_DONE);
+        WEDM_SV_TAKE(cf, frozen)
+        const bool act = !frozen;
 #pragma unroll
         for (int t = 0; t < H / 8; ++t)
             convp[t] = f2{((zoneA >> t) & 1u) ? ps.conv_zone : ps.conv_base, ((zoneB >> t) & 1u) ? ps.conv_zone : ps.conv_base};
@@ -586,9 +584,7 @@ __global__ void __launch_bounds__(192, WEDM_SERVED_WAVES_PER_EU) wedm_step_regs_
 #undef WEDM_REGS_WALK_TILE_FENCE
         WEDM_SV_PHASE(pb);
         tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
-        if (c == 0) box->tmax[slot][el] = tmax;
-        asm volatile("" ::: "memory");
-        if ((tid & 63) == 0) box->tm_seq[wave] = (uint32_t)it + 1u;
+        sv_give(box, slot, el, c == 0, tid, wave, it, tmax);
         WEDM_SV_PHASE(pc);
     }
     WEDM_SV_LOOP_END();
