@@ -892,6 +892,84 @@ typedef struct wedm_norm_desc {
  * [1, WEDM_NORM_MAX_TILES] or the batch's tiles reaching past it; num_envs < 1; flag bits that are not defined.             */
 int32_t wedm_normalize(const wedm_norm_desc* desc, void* stream);
 
+/* ------------------------------------------------- rollout advantages and returns (GAE), computed on the device
+ * What an on-policy trainer (PPO, A2C) makes of T control steps of a batch: generalised advantage estimates, returns, the
+ * mask of the steps that count, and the advantages standardised over the rollout -- in float64 with every rounding fixed
+ * here, so that the bits depend on the values and their global environment indices alone, as wedm_normalize's do.
+ *
+ * BLOCKS.  Struct-of-arrays [T][stride], environment-minor; the inputs share in_stride, the outputs out_stride, both
+ *   >= num_envs; columns [num_envs, stride) are neither read nor written.
+ * NEXT-STEP AUTORESET.  The step after a terminated / truncated one resets and steps in one launch: its stored observation
+ *   (and value) is the FINAL observation of the finished episode -- what a truncated step bootstraps from -- but the step
+ *   itself pairs an observation of episode k with a reward of episode k + 1.  WEDM_GAE_SKIP_AFTER_DONE leaves it out.
+ * PER ENVIRONMENT e, for t = T - 1 down to 0, float64, every operation rounded, nothing fused, parentheses as written:
+ *     done_t  = terminated[t][e] | truncated[t][e]
+ *     before  = t > 0 ? done_{t-1} : prev_done_in[e]                         (prev_done_in == NULL: 0)
+ *     skip_t  = (flags & WEDM_GAE_SKIP_AFTER_DONE) && before
+ *     nv_t    = t == T - 1 ? (double) last_value[e] : (double) value[t+1][e]
+ *     delta_t = ((double) reward[t][e] + (terminated[t][e] ? 0.0 : gamma * nv_t)) - (double) value[t][e]
+ *     A_t     = skip_t ? 0.0 : delta_t + (done_t ? 0.0 : gl * A_{t+1})        gl = gamma * lambda, formed once; A_T = 0
+ *     advantage[t][e] = (float) A_t;  returns[t][e] = (float) (A_t + (double) value[t][e]);  valid[t][e] = !skip_t
+ *     prev_done_out[e] = done_{T-1}
+ *   A truncated step bootstraps from value[t+1], a terminated one from nothing; a skipped step contributes nothing, and the
+ *   done before it has already cut the chain.
+ * MOMENTS (WEDM_GAE_NORMALIZE).  The environment's triple (n, m, S) is Welford over its valid steps in the order of the
+ *   scan (t descending), from EMPTY:   x = (double) advantage[t][e]  (the rounded float: what APPLY reads again);
+ *     n = n + 1;   d = x - m;   m = m + d / n;   S = S + d * (x - m).
+ *   The batch moment is wedm_normalize's pairwise tree of these triples (its merge, the lower index on the left, padded
+ *   with EMPTY) by GLOBAL environment index 256 * tile_offset + e: tile t's node is partials[tile_offset + t], the levels
+ *   above run over the tile index.  Then moments = (n, m, S) and
+ *     advantage_norm[t][e] = valid[t][e] ? (float) (((double) advantage[t][e] - m) / sqrt(S / n + eps)) : 0;
+ *   with n == 0 every advantage_norm is 0 and moments is EMPTY: no NaN.
+ * FLAGS.
+ *   WEDM_GAE_SKIP_AFTER_DONE  absent: no step is skipped, valid is all 1, prev_done_in is not read.
+ *   WEDM_GAE_NORMALIZE        absent: partials, moments and advantage_norm are neither read nor written.
+ *   WEDM_GAE_SCAN / WEDM_GAE_APPLY  the two phases; neither set means both, in this order.  SCAN writes advantage, returns,
+ *                     valid, prev_done_out and (NORMALIZE) this batch's tile partials; APPLY (NORMALIZE only: without it
+ *                     nothing is launched) folds all n_tiles_total partials and writes moments and advantage_norm.  A sharded
+ *                     batch scans every shard into its own tiles of one workspace, then applies every shard; a shard that
+ *                     is not the last holds a multiple of 256 environments.
+ * A NaN input reaches numbers only; it never makes the call touch memory outside its blocks.                            */
+#define WEDM_GAE_MAX_STEPS 65536
+enum wedm_gae_flag { WEDM_GAE_SKIP_AFTER_DONE = 1, WEDM_GAE_NORMALIZE = 2, WEDM_GAE_SCAN = 4, WEDM_GAE_APPLY = 8 };
+typedef struct wedm_gae_desc {
+    const float* reward;           /* [T][in_stride] */
+    const float* value;            /* [T][in_stride] */
+    const float* last_value;       /* [num_envs]: the estimate at the observation after step T - 1 */
+    const uint8_t* terminated;     /* [T][in_stride] */
+    const uint8_t* truncated;      /* [T][in_stride] */
+    const uint8_t* prev_done_in;   /* [num_envs] or NULL (zeros): done of the step before step 0 */
+    float* advantage;              /* [T][out_stride] */
+    float* returns;                /* [T][out_stride] */
+    float* advantage_norm;         /* [T][out_stride]; NORMALIZE */
+    uint8_t* valid;                /* [T][out_stride] */
+    uint8_t* prev_done_out;        /* [num_envs] or NULL; may be prev_done_in */
+    double* partials;              /* [n_tiles_total][WEDM_NORM_MOMENTS]; NORMALIZE */
+    double* moments;               /* [WEDM_NORM_MOMENTS]; NORMALIZE, APPLY */
+    int64_t in_stride;             /* >= num_envs, in elements */
+    int64_t out_stride;            /* >= num_envs, in elements */
+    double gamma, lam, eps;        /* lam: the lambda of the definition */
+    int32_t T;                     /* in [1, WEDM_GAE_MAX_STEPS] */
+    int32_t num_envs;
+    int32_t tile_offset;           /* global index of this batch's tile 0 */
+    int32_t n_tiles_total;         /* tile_offset + ceil(num_envs / 256) <= n_tiles_total <= WEDM_NORM_MAX_TILES */
+    int32_t flags;                 /* enum wedm_gae_flag */
+    int32_t reserved;
+} wedm_gae_desc;
+
+/* At most three launches on `stream` (SCAN: one; APPLY: the fold of the partials into moments, then advantage_norm), none
+ * of which waits for another block: no spin, no cooperative launch, no floating-point atomic.  Stateless like
+ * wedm_normalize: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory, read before the call
+ * returns; everything it names is device memory.  Written: the output blocks' columns [0, num_envs) of rows [0, T),
+ * prev_done_out, partials[tile_offset .. tile_offset + ceil(num_envs / 256)), moments -- nothing else.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; a pointer that the flags need NULL or not
+ * aligned to its element (SCAN: reward, value, last_value, terminated, truncated, advantage, returns, valid, and partials
+ * with NORMALIZE; APPLY with NORMALIZE: advantage, valid, advantage_norm, partials, moments); num_envs < 1; T outside
+ * [1, WEDM_GAE_MAX_STEPS]; a stride < num_envs; tile_offset < 0, n_tiles_total outside [1, WEDM_NORM_MAX_TILES] or the
+ * batch's tiles reaching past it; gamma, lam or eps not finite; flag bits that are not defined; an output block (first
+ * to last byte that the call may write) overlapping an input block, other than prev_done_out with prev_done_in.          */
+int32_t wedm_gae(const wedm_gae_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

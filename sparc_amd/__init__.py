@@ -28,6 +28,7 @@ from .modules.views import DielectricModule, IgnitionModule, MaterialRemovalModu
 from .controllers import GapController, VoltageController, run_controlled
 from .normalize import Normalizer
 from .randomize import EpisodeSampler
+from .rollout import RolloutBuffer
 from .snapshot import EnvSnapshot
 from .trace import DeviceTrace
 from .utils.logger import LoggerConfig, SimulationLogger
@@ -39,7 +40,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "Normalizer",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "Normalizer", "RolloutBuffer",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -420,6 +420,25 @@ class NormDesc(C.Structure):
     ]
 
 
+GAE_SKIP_AFTER_DONE, GAE_NORMALIZE, GAE_SCAN, GAE_APPLY = 1, 2, 4, 8  # enum wedm_gae_flag
+GAE_MAX_STEPS = 65536  # WEDM_GAE_MAX_STEPS
+
+
+class GaeDesc(C.Structure):
+    """``struct wedm_gae_desc``: what `wedm_gae` reads and where it writes (strides in elements; ``lam``: lambda)."""
+
+    _fields_ = [
+        ("reward", C.c_void_p), ("value", C.c_void_p), ("last_value", C.c_void_p), ("terminated", C.c_void_p),
+        ("truncated", C.c_void_p), ("prev_done_in", C.c_void_p),
+        ("advantage", C.c_void_p), ("returns", C.c_void_p), ("advantage_norm", C.c_void_p), ("valid", C.c_void_p),
+        ("prev_done_out", C.c_void_p), ("partials", C.c_void_p), ("moments", C.c_void_p),
+        ("in_stride", C.c_int64), ("out_stride", C.c_int64),
+        ("gamma", C.c_double), ("lam", C.c_double), ("eps", C.c_double),
+        ("T", C.c_int32), ("num_envs", C.c_int32), ("tile_offset", C.c_int32), ("n_tiles_total", C.c_int32),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

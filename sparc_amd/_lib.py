@@ -101,6 +101,8 @@ def load() -> C.CDLL:
     L.wedm_draw_episode.restype = C.c_int32
     L.wedm_normalize.argtypes = [C.POINTER(_abi.NormDesc), C.c_void_p]
     L.wedm_normalize.restype = C.c_int32
+    L.wedm_gae.argtypes = [C.POINTER(_abi.GaeDesc), C.c_void_p]
+    L.wedm_gae.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -112,7 +114,7 @@ EXPORTS = (
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
-    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize",
+    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize", "wedm_gae",
 )
 
 
@@ -275,6 +277,13 @@ class HipBackend:
         """`wedm_normalize` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
         with self._on_device():
             rc = self._L.wedm_normalize(C.byref(desc), self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def gae(self, desc: "_abi.GaeDesc") -> None:
+        """`wedm_gae` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
+        with self._on_device():
+            rc = self._L.wedm_gae(C.byref(desc), self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

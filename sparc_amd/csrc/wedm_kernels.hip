@@ -44,6 +44,8 @@
 //                         on them; not a step kernel, not in the registry
 //   wedm_normalize.h      wedm_norm_reduce / _fold / _apply_kernel: running observation and reward normalisation over all
 //                         environments by a fixed pairwise tree, episode statistics; not step kernels, not in the registry
+//   wedm_gae.h            wedm_gae_scan / _fold / _apply_kernel: a rollout's advantages, returns, valid mask and standardised
+//                         advantages, the time loop in the lane, moments by the same tree; not step kernels, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -86,6 +88,7 @@ using namespace wedm;
 #include "wedm_geometry.h"
 #include "wedm_randomize.h"
 #include "wedm_normalize.h"
+#include "wedm_gae.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1513,6 +1516,81 @@ int32_t wedm_normalize(const wedm_norm_desc* desc, void* stream) {
 }
 
 static bool finite_f64(double x) { return x - x == 0.0; }
+
+int32_t wedm_gae(const wedm_gae_desc* desc, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_gae: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_gae_desc& d = *desc;
+    const int32_t all = WEDM_GAE_SKIP_AFTER_DONE | WEDM_GAE_NORMALIZE | WEDM_GAE_SCAN | WEDM_GAE_APPLY;
+    if (d.flags & ~all) return bad("undefined flag bits");
+    const bool normalize = d.flags & WEDM_GAE_NORMALIZE;
+    const bool both = !(d.flags & (WEDM_GAE_SCAN | WEDM_GAE_APPLY));
+    const bool scan = both || (d.flags & WEDM_GAE_SCAN), apply = (both || (d.flags & WEDM_GAE_APPLY)) && normalize;
+    if (d.num_envs < 1) return bad("num_envs must be positive");
+    if (d.T < 1 || d.T > WEDM_GAE_MAX_STEPS) return bad("T outside [1, " + std::to_string(WEDM_GAE_MAX_STEPS) + "]");
+    if (d.in_stride < d.num_envs || d.out_stride < d.num_envs) return bad("a stride is smaller than num_envs");
+    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
+    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
+        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
+                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
+    if (!finite_f64(d.gamma) || !finite_f64(d.lam) || !finite_f64(d.eps)) return bad("gamma, lam and eps must be finite");
+    // the blocks by name: first byte, one past the last byte the call may touch, element size
+    struct Block {
+        const char* name;
+        uintptr_t lo, bytes, elem;
+        bool needed;
+    };
+    const uintptr_t rows_in = (uintptr_t)((int64_t)(d.T - 1) * d.in_stride + d.num_envs);
+    const uintptr_t rows_out = (uintptr_t)((int64_t)(d.T - 1) * d.out_stride + d.num_envs), n = (uintptr_t)d.num_envs;
+    const Block in[] = {
+        {"reward", (uintptr_t)d.reward, rows_in * 4, 4, scan},       {"value", (uintptr_t)d.value, rows_in * 4, 4, scan},
+        {"last_value", (uintptr_t)d.last_value, n * 4, 4, scan},     {"terminated", (uintptr_t)d.terminated, rows_in, 1, scan},
+        {"truncated", (uintptr_t)d.truncated, rows_in, 1, scan},     {"prev_done_in", (uintptr_t)d.prev_done_in, n, 1, false},
+    };
+    const Block out[] = {
+        {"advantage", (uintptr_t)d.advantage, rows_out * 4, 4, scan || apply},
+        {"returns", (uintptr_t)d.returns, rows_out * 4, 4, scan},
+        {"valid", (uintptr_t)d.valid, rows_out, 1, scan || apply},
+        {"advantage_norm", (uintptr_t)d.advantage_norm, rows_out * 4, 4, apply},
+        {"prev_done_out", (uintptr_t)d.prev_done_out, n, 1, false},
+        {"partials", (uintptr_t)d.partials, (uintptr_t)d.n_tiles_total * WEDM_NORM_MOMENTS * 8, 8, normalize && (scan || apply)},
+        {"moments", (uintptr_t)d.moments, WEDM_NORM_MOMENTS * 8, 8, apply},
+    };
+    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.elem != 0; };
+    for (const Block& b : in)
+        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
+    for (const Block& b : out)
+        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
+    for (const Block& o : out) {
+        for (const Block& i : in) {
+            if (!o.lo || !i.lo || (&o == &out[4] && &i == &in[5])) continue;  // (prev_done_out may be prev_done_in)
+            if (o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(std::string(o.name) + " overlaps " + i.name);
+        }
+    }
+    const auto launched = [](const char* what) {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return (int32_t)WEDM_OK;
+        g_create_error = std::string("wedm_gae: ") + what + " launch: " + hipGetErrorString(e);
+        return (int32_t)WEDM_ERR_HIP;
+    };
+    if (scan) {
+        hipLaunchKernelGGL(wedm_gae_scan_kernel, dim3((uint32_t)tiles), dim3(WEDM_NORM_TILE), 0, (hipStream_t)stream, d);
+        if (const int32_t rc = launched("scan")) return rc;
+    }
+    if (apply) {
+        int32_t per = 1;  // tiles per lane of the fold: the power of two with 256 * per >= n_tiles_total
+        while (256 * per < d.n_tiles_total) per *= 2;
+        hipLaunchKernelGGL(wedm_gae_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d, per);
+        if (const int32_t rc = launched("fold")) return rc;
+        const dim3 grid((uint32_t)tiles, (uint32_t)((d.T + WEDM_GAE_APPLY_ROWS - 1) / WEDM_GAE_APPLY_ROWS));
+        hipLaunchKernelGGL(wedm_gae_apply_kernel, grid, dim3(WEDM_NORM_TILE), 0, (hipStream_t)stream, d);
+        if (const int32_t rc = launched("apply")) return rc;
+    }
+    return WEDM_OK;
+}
 
 // why a descriptor cannot be followed (wedm_derive_geometry, and wedm_draw_episode for its `geom`), or NULL
 static const char* geom_derive_desc_error(const wedm_geom_derive_desc& d) {

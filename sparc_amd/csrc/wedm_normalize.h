@@ -120,48 +120,58 @@ __global__ void __launch_bounds__(64) wedm_norm_reduce_kernel(const wedm_norm_de
 
 #define WEDM_NORM_FOLD_PER 16  // tiles per lane at most: 256 * 16 = WEDM_NORM_MAX_TILES
 
+// the pairwise tree over the tile index, padded with EMPTY, of column c of a [n_tiles_total][WEDM_NORM_MOMENTS][C] workspace,
+// by a block of 256 lanes (see wedm_norm_fold_kernel above).  Every thread must arrive; thread 0 returns the tree's root,
+// the others a node nobody needs.  s_node: four triples of LDS.
+__device__ __forceinline__ wedm_norm_moments wedm_norm_fold_tiles(const double* partials, const int32_t n_tiles_total, const int32_t C,
+                                                                   const int32_t c, const int32_t per,
+                                                                   double (*s_node)[WEDM_NORM_MOMENTS]) {
+    const int32_t tid = (int32_t)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    wedm_norm_moments v[WEDM_NORM_FOLD_PER];
+#pragma unroll
+    for (int j = 0; j < WEDM_NORM_FOLD_PER; ++j) {
+        const int32_t t = tid * per + j;
+        const bool have = j < per && t < n_tiles_total;
+        const double* const p = partials + (int64_t)(have ? t : 0) * WEDM_NORM_MOMENTS * C + c;
+        v[j].n = have ? p[WEDM_NM_COUNT * C] : 0.0;
+        v[j].m = have ? p[WEDM_NM_MEAN * C] : 0.0;
+        v[j].S = have ? p[WEDM_NM_M2 * C] : 0.0;
+    }
+#pragma unroll
+    for (int s = 1; s < WEDM_NORM_FOLD_PER; s <<= 1) {
+#pragma unroll
+        for (int j = 0; j < WEDM_NORM_FOLD_PER; j += 2 * s) v[j] = wedm_norm_merge(v[j], v[j + s]);
+    }
+    wedm_norm_moments node = wedm_norm_wave_tree(v[0]);
+    if (lane == 0) {
+        s_node[w][WEDM_NM_COUNT] = node.n;
+        s_node[w][WEDM_NM_MEAN] = node.m;
+        s_node[w][WEDM_NM_M2] = node.S;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        wedm_norm_moments q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            q[k].n = s_node[k][WEDM_NM_COUNT];
+            q[k].m = s_node[k][WEDM_NM_MEAN];
+            q[k].S = s_node[k][WEDM_NM_M2];
+        }
+        node = wedm_norm_merge(wedm_norm_merge(q[0], q[1]), wedm_norm_merge(q[2], q[3]));
+    }
+    return node;
+}
+
 __global__ void __launch_bounds__(256) wedm_norm_fold_kernel(const wedm_norm_desc d, const int32_t C, const int32_t per) {
     __shared__ double s_node[4][WEDM_NORM_MOMENTS];
-    const int32_t tid = (int32_t)threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int32_t tid = (int32_t)threadIdx.x;
     const int32_t c = (int32_t)blockIdx.x;
     wedm_norm_moments run;
     run.n = d.stats_in[WEDM_NM_COUNT * C + c];
     run.m = d.stats_in[WEDM_NM_MEAN * C + c];
     run.S = d.stats_in[WEDM_NM_M2 * C + c];
-    if (d.flags & WEDM_NORM_UPDATE) {  // (uniform)
-        wedm_norm_moments v[WEDM_NORM_FOLD_PER];
-#pragma unroll
-        for (int j = 0; j < WEDM_NORM_FOLD_PER; ++j) {
-            const int32_t t = tid * per + j;
-            const bool have = j < per && t < d.n_tiles_total;
-            const double* const p = d.partials + (int64_t)(have ? t : 0) * WEDM_NORM_MOMENTS * C + c;
-            v[j].n = have ? p[WEDM_NM_COUNT * C] : 0.0;
-            v[j].m = have ? p[WEDM_NM_MEAN * C] : 0.0;
-            v[j].S = have ? p[WEDM_NM_M2 * C] : 0.0;
-        }
-#pragma unroll
-        for (int s = 1; s < WEDM_NORM_FOLD_PER; s <<= 1) {
-#pragma unroll
-            for (int j = 0; j < WEDM_NORM_FOLD_PER; j += 2 * s) v[j] = wedm_norm_merge(v[j], v[j + s]);
-        }
-        const wedm_norm_moments node = wedm_norm_wave_tree(v[0]);
-        if (lane == 0) {
-            s_node[w][WEDM_NM_COUNT] = node.n;
-            s_node[w][WEDM_NM_MEAN] = node.m;
-            s_node[w][WEDM_NM_M2] = node.S;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            wedm_norm_moments q[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                q[k].n = s_node[k][WEDM_NM_COUNT];
-                q[k].m = s_node[k][WEDM_NM_MEAN];
-                q[k].S = s_node[k][WEDM_NM_M2];
-            }
-            run = wedm_norm_merge(run, wedm_norm_merge(wedm_norm_merge(q[0], q[1]), wedm_norm_merge(q[2], q[3])));
-        }
-    }
+    if (d.flags & WEDM_NORM_UPDATE)  // (uniform)
+        run = wedm_norm_merge(run, wedm_norm_fold_tiles(d.partials, d.n_tiles_total, C, c, per, s_node));  // (thread 0's counts)
     if (tid == 0) {
         d.stats_out[WEDM_NM_COUNT * C + c] = run.n;
         d.stats_out[WEDM_NM_MEAN * C + c] = run.m;
