@@ -970,6 +970,94 @@ typedef struct wedm_gae_desc {
  * to last byte that the call may write) overlapping an input block, other than prev_done_out with prev_done_in.          */
 int32_t wedm_gae(const wedm_gae_desc* desc, void* stream);
 
+/* ------------------------------------------------- policy action head: sample, log-probability, gradient
+ * What stands between a policy network's output row and the environment's action, and what an on-policy update evaluates
+ * again at the stored actions: four bounded continuous leaves (servo, target_voltage, ON_time, OFF_time: a tanh-squashed
+ * Gaussian each, mapped affinely to [lo, hi]) and current_mode, one of M listed modes (a categorical) -- in float64 on
+ * the float32 inputs, every operation rounded, nothing fused, parentheses as written, exp and log the portable ones of the
+ * kernels (IEEE basic operations only: the CPU oracle's wedm_oracle_exp / wedm_oracle_log with MATH_PORTABLE), so that a
+ * sampled action is a pure function of (seed, global environment id, step number t, the row) and its bits do not depend
+ * on the launch, on how a batch is sharded or on the device.
+ *
+ * ROW r: P = 8 + M float32 at params + r * param_stride:  mu_0..3, ls_0..3 (log standard deviations, used as given),
+ *   l_0..M-1 (logits).  The stored action of the row is u_0..3 (float32, the PRE-SQUASH values, u + 4 r) and
+ *   k = mode_index[r], clamped to [0, M - 1] before any use.
+ * CONSTANTS.  LN2 = 0.6931471805599453, HALF_LOG_2PI = 0.9189385332046727, HALF_LOG_2PIE = 1.4189385332046727 (the
+ *   doubles nearest to these decimals).  span_i = hi_i - lo_i, formed on the device; log_span_i is passed in (the host
+ *   computes log(hi_i - lo_i) once; device and host definition use the passed value).
+ * CONTINUOUS COMPONENT i (mu, ls, u: the row's values as doubles):
+ *     sigma = pexp(ls);   z = (u - mu) / sigma
+ *     a = |u|;   e = pexp(-2.0 * a);   s = u >= 0 ? 1.0 / (1.0 + e) : e / (1.0 + e)              (= (tanh(u) + 1) / 2)
+ *     x = lo + span * s;   x = x > lo ? x : lo;   action_i = x < hi ? x : hi            (a NaN becomes lo: always in bounds)
+ *     logjac = ((log_span + LN2) - 2.0 * a) - 2.0 * plog(1.0 + e)                                     (log |d action / d u|)
+ *     c_i = (((-0.5 * z) * z - ls) - HALF_LOG_2PI) - logjac
+ *   pexp = portable_exp; plog(x) = x is NaN ? x : portable_log(x) (portable_log reads its argument's bits).
+ * MODE.
+ *     m = l_0;  for j = 1 .. M - 1: m = l_j > m ? l_j : m                                      (a NaN logit is never taken)
+ *     d_j = l_j - m;   w_j = pexp(d_j);   W = 0.0, S = 0.0;  for j = 0 .. M - 1: W = W + w_j, S = S + w_j * d_j
+ *     logW = plog(W);   logp_j = d_j - logW;   p_j = w_j / W;   H = logW - S / W
+ * OUTPUTS.  f32(x) = x is NaN ? the float32 with bits 0x7FC00000 : (float) x  -- every float32 this call stores goes
+ *   through it, so a NaN carries no sign or payload of the operation that made it.
+ *     log_prob[r] = f32((((c_0 + c_1) + c_2) + c_3) + logp_k)
+ *     entropy[r]  = f32(((((ls_0 + HALF_LOG_2PIE) + (ls_1 + HALF_LOG_2PIE)) + (ls_2 + HALF_LOG_2PIE)) + (ls_3 + HALF_LOG_2PIE)) + H)
+ *   The entropy is that of the base Gaussian plus the categorical's, not of the squashed variable (which has no closed form).
+ * WEDM_HEAD_SAMPLE (rows == the batch's environments; g = env_id_offset + r modulo 2^32).  Philox4x32-10 of the step
+ *   kernels: key {seed & 0xffffffff, seed >> 32}, counter {t & 0xffffffff, t >> 32, g, stream}; t: the caller's 64-bit step
+ *   number.  Streams from 0xC0000000 are the head's (the physics uses 0 .. 64, wedm_draw_episode 0x80000000 ..).
+ *     n_i = the polar method of the step kernels (its 53-bit pairs, v1 * sqrt(-2.0 * portable_log(q) / q) at the first
+ *           attempt j < 64 with 0 < q < 1, else 0.0) on streams 0xC0000000 + 64 i + j
+ *     u_i = f32(mu_i + sigma_i * n_i)         -- everything else (the action, log_prob) is computed from this rounded u_i
+ *     v = ((double) word x of stream 0xC0000000 + 256 + 0.5) * 2^-32;   tau = v * W
+ *     k = the first j with c_j > tau, where c_0 = 0.0 + w_0, c_j = c_{j-1} + w_j;  none: M - 1
+ *   WEDM_HEAD_DETERMINISTIC: u_i = mu_i;  k = 0, b = l_0;  for j = 1 .. M - 1: if (l_j > b) b = l_j, k = j (the first
+ *   largest; none compares greater: 0).  Nothing is drawn.
+ *   Written: action[i][r] = action_i (float64), current_mode[r] = modes[k], u, mode_index[r] = k, log_prob, entropy.
+ * WEDM_HEAD_EVALUATE reads params, u, mode_index; writes log_prob, entropy.
+ * WEDM_HEAD_BACKWARD reads the same, g_log_prob[r] and g_entropy[r] (float32; g_entropy NULL: 0.0) as doubles glp, gen;
+ *   writes grad_params + r * grad_stride, P float32:
+ *     d mu_i = f32(glp * (z / sigma));   d ls_i = f32(glp * (z * z - 1.0) + gen)
+ *     d l_j  = f32(glp * ((j == k ? 1.0 : 0.0) - p_j) - gen * (p_j * (logp_j + H)))
+ * Columns [P, stride) of params and grad_params are neither read nor written.  A NaN or an infinity in a row reaches
+ * numbers only: no index is formed from data without a clamp.                                                           */
+#define WEDM_HEAD_MAX_MODES 19
+#define WEDM_HEAD_STREAM0 0xC0000000u
+enum wedm_head_op { WEDM_HEAD_SAMPLE = 0, WEDM_HEAD_EVALUATE = 1, WEDM_HEAD_BACKWARD = 2 };
+enum wedm_head_flag { WEDM_HEAD_DETERMINISTIC = 1 };
+typedef struct wedm_head_desc {
+    const float* params;           /* [rows][param_stride] */
+    float* u;                      /* [rows][4], 16-byte aligned; SAMPLE writes it, the others read it */
+    int32_t* mode_index;           /* [rows]; SAMPLE writes it, the others read it */
+    double* action[4];             /* [rows] each: servo, target_voltage, ON_time, OFF_time; SAMPLE */
+    int32_t* current_mode;         /* [rows]; SAMPLE */
+    float* log_prob;               /* [rows]; SAMPLE, EVALUATE */
+    float* entropy;                /* [rows]; SAMPLE, EVALUATE */
+    const float* g_log_prob;       /* [rows]; BACKWARD */
+    const float* g_entropy;        /* [rows] or NULL (zeros); BACKWARD */
+    float* grad_params;            /* [rows][grad_stride]; BACKWARD */
+    int64_t param_stride;          /* >= 8 + n_modes, in elements */
+    int64_t grad_stride;           /* >= 8 + n_modes, in elements; BACKWARD */
+    uint64_t seed;                 /* SAMPLE */
+    uint64_t t;                    /* SAMPLE: the step number */
+    double lo[4], hi[4];           /* finite, lo < hi */
+    double log_span[4];            /* log(hi - lo), finite */
+    int32_t modes[WEDM_HEAD_MAX_MODES]; /* the mode numbers, [0, n_modes) used */
+    int32_t n_modes;               /* M, in [1, WEDM_HEAD_MAX_MODES] */
+    int32_t rows;                  /* >= 1 */
+    uint32_t env_id_offset;        /* SAMPLE: global id of row 0 */
+    int32_t op;                    /* enum wedm_head_op */
+    int32_t flags;                 /* enum wedm_head_flag; SAMPLE only */
+} wedm_head_desc;
+
+/* One launch on `stream`, one lane per row, no block waits for another: no atomic, no spin, no cooperative launch.
+ * Stateless like wedm_gae: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory, read before the
+ * call returns; everything it names is device memory.  Written: what the op lists above -- nothing else.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; op not one of the three; flag bits that are
+ * not defined, or a flag with another op than SAMPLE; rows < 1; n_modes outside [1, WEDM_HEAD_MAX_MODES]; a stride that the op
+ * uses below 8 + n_modes; a bound or log_span that is not finite, or hi <= lo; a pointer that the op needs NULL, or any
+ * pointer not aligned to its element (u: to 16 bytes); an output block of the op (first to last byte that the call may
+ * write) overlapping one of its input blocks.                                                                          */
+int32_t wedm_policy_head(const wedm_head_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

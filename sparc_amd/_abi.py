@@ -439,6 +439,27 @@ class GaeDesc(C.Structure):
     ]
 
 
+HEAD_SAMPLE, HEAD_EVALUATE, HEAD_BACKWARD = 0, 1, 2  # enum wedm_head_op
+HEAD_DETERMINISTIC = 1  # enum wedm_head_flag
+HEAD_MAX_MODES = 19  # WEDM_HEAD_MAX_MODES
+HEAD_STREAM0 = 0xC0000000  # WEDM_HEAD_STREAM0
+
+
+class HeadDesc(C.Structure):
+    """``struct wedm_head_desc``: what `wedm_policy_head` reads and where it writes (strides in elements; ``action``: the
+    four float64 leaves servo, target_voltage, ON_time, OFF_time)."""
+
+    _fields_ = [
+        ("params", C.c_void_p), ("u", C.c_void_p), ("mode_index", C.c_void_p), ("action", C.c_void_p * 4),
+        ("current_mode", C.c_void_p), ("log_prob", C.c_void_p), ("entropy", C.c_void_p), ("g_log_prob", C.c_void_p),
+        ("g_entropy", C.c_void_p), ("grad_params", C.c_void_p),
+        ("param_stride", C.c_int64), ("grad_stride", C.c_int64), ("seed", C.c_uint64), ("t", C.c_uint64),
+        ("lo", C.c_double * 4), ("hi", C.c_double * 4), ("log_span", C.c_double * 4),
+        ("modes", C.c_int32 * HEAD_MAX_MODES), ("n_modes", C.c_int32), ("rows", C.c_int32),
+        ("env_id_offset", C.c_uint32), ("op", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

@@ -103,6 +103,8 @@ def load() -> C.CDLL:
     L.wedm_normalize.restype = C.c_int32
     L.wedm_gae.argtypes = [C.POINTER(_abi.GaeDesc), C.c_void_p]
     L.wedm_gae.restype = C.c_int32
+    L.wedm_policy_head.argtypes = [C.POINTER(_abi.HeadDesc), C.c_void_p]
+    L.wedm_policy_head.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -114,7 +116,7 @@ EXPORTS = (
     "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
-    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize", "wedm_gae",
+    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize", "wedm_gae", "wedm_policy_head",
 )
 
 
@@ -284,6 +286,13 @@ class HipBackend:
         """`wedm_gae` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
         with self._on_device():
             rc = self._L.wedm_gae(C.byref(desc), self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def policy_head(self, desc: "_abi.HeadDesc") -> None:
+        """`wedm_policy_head` on this backend's device and torch's current stream (one launch, no synchronisation)."""
+        with self._on_device():
+            rc = self._L.wedm_policy_head(C.byref(desc), self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

@@ -185,11 +185,12 @@ __device__ __forceinline__ U2 philox_pair(uint32_t key0, uint32_t key1, uint32_t
     return u;
 }
 
-// Marsaglia polar method on Philox streams 1, 2, ... (material.py:127's N(0,1))
+// Marsaglia polar method on Philox streams 1, 2, ... (material.py:127's N(0,1)); the policy head draws its normals on
+// streams of its own (stream_base of wedm_head.h)
 __device__ __forceinline__ double philox_std_normal(uint32_t key0, uint32_t key1, uint32_t time,
-                                                    uint32_t episode, uint32_t gid) {
+                                                    uint32_t episode, uint32_t gid, uint32_t stream_base = 1u) {
     for (uint32_t j = 0; j < 64; ++j) {
-        U2 u = philox_pair(key0, key1, time, episode, gid, 1u + j);
+        U2 u = philox_pair(key0, key1, time, episode, gid, stream_base + j);
         double v1 = 2.0 * u.a - 1.0, v2 = 2.0 * u.b - 1.0;
         double s = v1 * v1 + v2 * v2;
         if (s < 1.0 && s != 0.0) return v1 * sqrt(-2.0 * portable_log(s) / s);

@@ -46,6 +46,8 @@
 //                         environments by a fixed pairwise tree, episode statistics; not step kernels, not in the registry
 //   wedm_gae.h            wedm_gae_scan / _fold / _apply_kernel: a rollout's advantages, returns, valid mask and standardised
 //                         advantages, the time loop in the lane, moments by the same tree; not step kernels, not in the registry
+//   wedm_head.h           wedm_head_kernel: a policy's action head (squashed Gaussians and a categorical) -- a seeded draw, its
+//                         log-probability and entropy, their gradient; one lane per row; not a step kernel, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -89,6 +91,7 @@ using namespace wedm;
 #include "wedm_randomize.h"
 #include "wedm_normalize.h"
 #include "wedm_gae.h"
+#include "wedm_head.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1590,6 +1593,90 @@ int32_t wedm_gae(const wedm_gae_desc* desc, void* stream) {
         if (const int32_t rc = launched("apply")) return rc;
     }
     return WEDM_OK;
+}
+
+int32_t wedm_policy_head(const wedm_head_desc* desc, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_policy_head: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_head_desc& d = *desc;
+    if (d.op != WEDM_HEAD_SAMPLE && d.op != WEDM_HEAD_EVALUATE && d.op != WEDM_HEAD_BACKWARD) return bad("undefined op");
+    if (d.flags & ~(int32_t)WEDM_HEAD_DETERMINISTIC) return bad("undefined flag bits");
+    if (d.flags && d.op != WEDM_HEAD_SAMPLE) return bad("a flag with another op than SAMPLE");
+    if (d.rows < 1) return bad("rows must be positive");
+    if (d.n_modes < 1 || d.n_modes > WEDM_HEAD_MAX_MODES) return bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+    const bool sample = d.op == WEDM_HEAD_SAMPLE, backward = d.op == WEDM_HEAD_BACKWARD;
+    const int64_t P = 8 + d.n_modes;
+    if (d.param_stride < P || (backward && d.grad_stride < P)) return bad("a stride is smaller than 8 + n_modes");
+    for (int i = 0; i < 4; ++i) {
+        if (!finite_f64(d.lo[i]) || !finite_f64(d.hi[i]) || !finite_f64(d.log_span[i])) return bad("a bound or log_span is not finite");
+        if (!(d.hi[i] > d.lo[i])) return bad("hi <= lo");
+    }
+    // the blocks by name: first byte, bytes the call may touch, alignment, whether the op needs it
+    struct Block {
+        const char* name;
+        uintptr_t lo, bytes, align;
+        bool needed;
+    };
+    const uintptr_t n = (uintptr_t)d.rows;
+    const uintptr_t row_bytes = (uintptr_t)((int64_t)(d.rows - 1) * d.param_stride + P) * 4;
+    const uintptr_t grad_bytes = backward ? (uintptr_t)((int64_t)(d.rows - 1) * d.grad_stride + P) * 4 : 0;
+    const Block blocks[] = {
+        {"params", (uintptr_t)d.params, row_bytes, 4, true},
+        {"u", (uintptr_t)d.u, n * 16, 16, true},
+        {"mode_index", (uintptr_t)d.mode_index, n * 4, 4, true},
+        {"g_log_prob", (uintptr_t)d.g_log_prob, n * 4, 4, backward},
+        {"g_entropy", (uintptr_t)d.g_entropy, n * 4, 4, false},
+        {"action[0]", (uintptr_t)d.action[0], n * 8, 8, sample},
+        {"action[1]", (uintptr_t)d.action[1], n * 8, 8, sample},
+        {"action[2]", (uintptr_t)d.action[2], n * 8, 8, sample},
+        {"action[3]", (uintptr_t)d.action[3], n * 8, 8, sample},
+        {"current_mode", (uintptr_t)d.current_mode, n * 4, 4, sample},
+        {"log_prob", (uintptr_t)d.log_prob, n * 4, 4, !backward},
+        {"entropy", (uintptr_t)d.entropy, n * 4, 4, !backward},
+        {"grad_params", (uintptr_t)d.grad_params, grad_bytes, 4, backward},
+    };
+    for (const Block& b : blocks)
+        if ((b.needed && !b.lo) || b.lo % b.align != 0) return bad(std::string(b.name) + " is null or not aligned to its element");
+    // what the op reads and what it writes: u and mode_index are SAMPLE's outputs and the others' inputs
+    const auto is_input = [&](const Block& b) {
+        const size_t i = (size_t)(&b - blocks);
+        return i == 0 || (!sample && (i == 1 || i == 2)) || (backward && (i == 3 || i == 4));
+    };
+    const auto is_output = [&](const Block& b) {
+        const size_t i = (size_t)(&b - blocks);
+        return (sample && (i == 1 || i == 2 || (i >= 5 && i <= 9))) || (!backward && (i == 10 || i == 11)) || (backward && i == 12);
+    };
+    for (const Block& o : blocks) {
+        if (!is_output(o) || !o.lo) continue;
+        for (const Block& i : blocks)
+            if (is_input(i) && i.lo && o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes)
+                return bad(std::string(o.name) + " overlaps " + i.name);
+    }
+    const bool in_lds = d.param_stride == P && (uintptr_t)d.params % 16 == 0;
+    const bool out_lds = backward && d.grad_stride == P && (uintptr_t)d.grad_params % 16 == 0;
+    const dim3 grid((uint32_t)(((int64_t)d.rows + WEDM_HEAD_BLOCK - 1) / WEDM_HEAD_BLOCK)), block(WEDM_HEAD_BLOCK);
+    const size_t lds = in_lds || out_lds ? (size_t)WEDM_HEAD_BLOCK * (size_t)head_pitch((int)P) * 4 : 0;
+    const hipStream_t s = (hipStream_t)stream;
+    if (sample) {
+        if (in_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, true, false>), grid, block, lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, false, false>), grid, block, lds, s, d);
+    } else if (!backward) {
+        if (in_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, true, false>), grid, block, lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, false, false>), grid, block, lds, s, d);
+    } else if (in_lds) {
+        if (out_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, true>), grid, block, lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, false>), grid, block, lds, s, d);
+    } else {
+        if (out_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, true>), grid, block, lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, false>), grid, block, lds, s, d);
+    }
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return WEDM_OK;
+    g_create_error = std::string("wedm_policy_head: launch: ") + hipGetErrorString(e);
+    return WEDM_ERR_HIP;
 }
 
 // why a descriptor cannot be followed (wedm_derive_geometry, and wedm_draw_episode for its `geom`), or NULL
