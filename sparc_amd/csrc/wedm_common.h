@@ -584,16 +584,37 @@ __device__ __forceinline__ float rw_cell(int i, int n_seg, float tm1, float tc, 
         if (quiet) { WEDM_STAMP_ACC(); ++cntS; }                                                \
         else { accN += st1 - st0; accB += st2 - st1; accS += st4 - st2; ++cntN; }               \
     } while (0)
+// (rows per wave, the block's wave count from blockDim.x: 4 words, then from word 4 * waves on 6 words)
 #define WEDM_STAMP_OUT()                                                                         \
     do {                                                                                         \
         if (k.dbg && (threadIdx.x & 63) == 0) {                                                  \
-            unsigned long long* o = k.dbg + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;   \
+            const size_t wpb_ = blockDim.x >> 6, wave_ = (size_t)blockIdx.x * wpb_ + (threadIdx.x >> 6); \
+            unsigned long long* o = k.dbg + wave_ * 4;                                           \
             o[0] = acc0; o[1] = acc1; o[2] = acc2; o[3] = acc3;                                  \
-            unsigned long long* o2 = k.dbg + (size_t)gridDim.x * 16 + ((size_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 6; \
+            unsigned long long* o2 = k.dbg + (size_t)gridDim.x * wpb_ * 4 + wave_ * 6;           \
             o2[0] = accN; o2[1] = accB; o2[2] = accS; o2[3] = cntN; o2[4] = cntB; o2[5] = cntS;  \
         }                                                                                        \
     } while (0)
+// The census of a kernel's waves (wedm_step_regs; tools/stamps_regs.py): which SIMD and wave slot a wave ran in (HW_ID,
+// XCC_ID) and when it started and ended, on the 100 MHz clock all XCDs share whatever WEDM_STAMPS_REAL says.  4 words per
+// wave, from word 10 * waves on (behind the rows of WEDM_STAMP_OUT).  BEGIN at the kernel's first line, OUT at its last.
+#define WEDM_STAMP_CENSUS_BEGIN()                                                                \
+    unsigned long long cen_t0 = 0, cen_t1 = 0;                                                   \
+    uint32_t cen_hw = 0, cen_xcc = 0;                                                            \
+    asm volatile("s_getreg_b32 %0, hwreg(4)\n\ts_getreg_b32 %1, hwreg(20)" : "=s"(cen_hw), "=s"(cen_xcc)); \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cen_t0)::"memory")
+#define WEDM_STAMP_CENSUS_OUT()                                                                  \
+    do {                                                                                         \
+        asm volatile("s_waitcnt vmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(cen_t1)::"memory"); \
+        if (k.dbg && (threadIdx.x & 63) == 0) {                                                  \
+            const size_t wpb_ = blockDim.x >> 6, wave_ = (size_t)blockIdx.x * wpb_ + (threadIdx.x >> 6); \
+            unsigned long long* o = k.dbg + (size_t)gridDim.x * wpb_ * 10 + wave_ * 4;           \
+            o[0] = cen_hw; o[1] = cen_xcc; o[2] = cen_t0; o[3] = cen_t1;                         \
+        }                                                                                        \
+    } while (0)
 #else
+#define WEDM_STAMP_CENSUS_BEGIN() do { } while (0)
+#define WEDM_STAMP_CENSUS_OUT() do { } while (0)
 #define WEDM_STAMP(var) do { } while (0)
 #define WEDM_STAMP_DECL do { } while (0)
 #define WEDM_STAMP_ACC() do { } while (0)

@@ -93,6 +93,23 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 #ifndef WEDM_REGS_PAIR_SPLIT
 #define WEDM_REGS_PAIR_SPLIT 1  // two lanes: Philox and the quiet line's two divisions half in each lane (quiet_prelude_t<.., PAIR>)
 #endif
+// ---- the two waves of a SIMD and their phases (two lanes per environment only)
+// A microsecond of the two-lane form is a dependent float64 chain (prelude, epilogue: few instructions, each waiting for
+// the one before) around a walk of independent packed operations that fills the VALU pipe by itself.  Two such waves
+// share a SIMD.  At equal priority the older one wins every arbitration whatever either is doing: it ends the launch a
+// quarter ahead of the younger one, which then runs the rest alone (the census of tools/stamps_regs.py).
+//   WEDM_REGS_PAIR_PHASES     s_setprio by phase: raised in prelude and epilogue (the chain), 0 in the walk.  A wave in its
+//                             chain issues when its operand arrives, and the walking wave fills the slots between.  Only
+//                             a busy walk behind a general prelude keeps the raised priority (measured: the closed loop,
+//                             whose general microseconds mostly walk PLAIN, is 7 % slower with every general walk raised).
+//                             0: the kernel is the text it was without the priority changes.
+#ifndef WEDM_REGS_PAIR_PHASES
+#define WEDM_REGS_PAIR_PHASES 1
+#endif
+#ifndef WEDM_REGS_PAIR_PRIO_HI
+#define WEDM_REGS_PAIR_PRIO_HI 1
+#endif
+
 // F_TRACE: the form with the signal-trace point (a launch into which a sample falls: the reference's logger samples
 // after every step, utils/logger.py:110-160); launches without a sample run the form without it.
 // F_F64: stencil_mode 1 -- the walk in the typing Numba gives wire.py:58-123 (cell_f64 above); everything else is the same kernel.
@@ -109,9 +126,11 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     static_assert(L == 1 || L == 2, "one or two lanes per environment");
     static_assert(H % 8 == 0 && H / 8 <= 16, "whole tiles");
     constexpr int EPB = 256 / L;
+    constexpr bool PRIO = L == 2 && WEDM_REGS_PAIR_PHASES;
     // pairs per stage of the packed walk: a wave that is alone on its SIMD needs the distance between dependent operations
     constexpr int SW = L == 1 ? 4 : WEDM_REGS_SW2;
     constexpr bool kF64 = F64;
+    WEDM_STAMP_CENSUS_BEGIN();
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
     // every-step float64 constants in VGPRs: all of them with 512 registers, the epilogue's and the quiet prelude's with 256
@@ -196,6 +215,7 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
         WEDM_STAMP(st0);
+        if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);  // the chain: few instructions, each one waited for
         e = env_index();
         const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
@@ -236,7 +256,15 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
             halo_r = c == 0 ? got : 0.0f;
         }
         const float rw_h_base = s.h_base, rw_h_zone = s.h_zone;  // (the predicated float64-typed cell reads the entries themselves)
+        // (priority is a scalar instruction that ignores EXEC: under a wave-uniform, scalar condition)
+        if constexpr (PRIO) {
+            // the walk at priority 0, unless the microsecond took the general path AND its walk is busy (the walk's own test
+            // of its entry): that walk is predicated cells and Joule terms behind a long prelude, and keeps the priority
+            const bool busy = __any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f);
+            if (__builtin_amdgcn_readfirstlane((int)(was_quiet || !busy))) __builtin_amdgcn_s_setprio(0);
+        }
 #include "wedm_regs_walk.inc"
+        if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
         WEDM_STAMP(st2);
         if (L == 2) tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
         WEDM_ENV_END_US(hv, tmax, pk, writer, none, WEDM_STAMP(st3))
@@ -255,12 +283,15 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
                              asm volatile("" : "+v"(pa), "+v"(pb));
                          });
     }
+    // (both ways out of the loop come here)
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(0);
     WEDM_STAMP_OUT();
 
     e = env_index();
     Te = cold->s.T + (live ? e : 0) * 4;  // (formed again from the index, like the index: not held through the loop)
     WEDM_REGS_STORE_WIRE()
     if (live && writer) { WEDM_ENV_CLOSE(frozen0) }
+    WEDM_STAMP_CENSUS_OUT();
 }
 
 

@@ -1,12 +1,17 @@
 #!/usr/bin/env python
-"""Phase stamps of the register kernel wedm_step_regs from a -DWEDM_STAMPS build (diagnostic, never the shipped library):
-cycles per wave and microsecond in prelude / walk / reduction / epilogue, for the microseconds the quiet prelude handled
-and, separately, for those that took the general path.
+"""Phase stamps and the wave census of the register kernel wedm_step_regs from a -DWEDM_STAMPS build (diagnostic, never the
+shipped library):
+* cycles per wave and microsecond in prelude / walk / reduction / epilogue, for the microseconds the quiet prelude handled
+  and, separately, for those that took the general path;
+* the census: how the launch's waves pair up on SIMDs, when the first- and the second-arrived wave of a SIMD end (from the
+  start of the kernel, on the 100 MHz clock all XCDs share), and the share of the launch during which a SIMD held one wave only.
 usage: WEDM_HIP_LIB=build/ablate/libwedm_STAMPS.so python tools/stamps_regs.py [lanes] [num_envs] [gap_um] [microseconds]"""
 import ctypes as C
 import sys
+from collections import Counter, defaultdict
 
 sys.path.insert(0, ".")
+import numpy as np
 import torch
 
 from sparc_amd import WireEDMEnv, WireModuleParameters
@@ -31,9 +36,12 @@ buf.zero_()
 env.step_many(act, us)
 torch.cuda.synchronize()
 raw = buf.cpu().numpy()
-nblk = int(env._backend.last_kernel().split("<<<")[1].split(",")[0])
-q = raw[: nblk * 16].reshape(-1, 4).astype(float)              # quiet microseconds: prelude, walk, reduction, epilogue
-g = raw[nblk * 16: nblk * 16 + nblk * 24].reshape(-1, 6).astype(float)   # general: prelude, walk, reduction + epilogue; their number; -; quiet ones
+grid, block = (int(v) for v in env._backend.last_kernel().split("<<<")[1].split(">>>")[0].split(",")[:2])
+wpb = block // 64
+nw = grid * wpb                                              # waves of the launch
+q = raw[: nw * 4].reshape(-1, 4).astype(float)               # quiet microseconds: prelude, walk, reduction, epilogue
+g = raw[nw * 4: nw * 10].reshape(-1, 6).astype(float)        # general: prelude, walk, reduction + epilogue; their number; -; quiet ones
+cen = raw[nw * 10: nw * 14].reshape(-1, 4)                   # census: HW_ID, XCC_ID, start, end (10 ns ticks)
 keep = (g[:, 3] + g[:, 5]) > 0
 q, g = q[keep], g[keep]
 nq, ng = g[:, 5].sum(), g[:, 3].sum()
@@ -43,3 +51,56 @@ print(f"  quiet   wave-us: prelude {m[0]:.0f}  walk {m[1]:.0f}  reduction {m[2]:
 m = g[:, :3].sum(axis=0) / max(ng, 1)
 print(f"  general wave-us: prelude {m[0]:.0f}  walk {m[1]:.0f}  reduction + epilogue {m[2]:.0f}  total {m.sum():.0f} cycles")
 print(f"  all: {(q.sum() + g[:, :3].sum()) / (nq + ng):.0f} cycles per wave-us")
+
+# ---- the census
+if not cen[:, 3].any():
+    sys.exit("  (no census rows: the library's wedm_step_regs writes none)")
+hw, xcc = cen[:, 0], cen[:, 1] & 0xF
+cu = (xcc << 16) | (((hw >> 13) & 7) << 8) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xF)
+simd = (hw >> 4) & 3
+t0, t1 = cen[:, 2].astype(np.float64) / 100.0, cen[:, 3].astype(np.float64) / 100.0   # us
+start, span = t0.min(), t1.max() - t0.min()
+blk = np.arange(nw) // wpb
+on = defaultdict(list)
+for i in range(nw):
+    on[(int(cu[i]), int(simd[i]))].append(i)
+print(f"  census: {nw} waves in blocks of {wpb} on {len(set(cu.tolist()))} CUs, {len(on)} SIMDs; launch span {span:.0f} us")
+sizes = Counter(len(v) for v in on.values())
+print("  waves per SIMD over the launch: " + ", ".join(f"{k}: {sizes[k]} SIMDs" for k in sorted(sizes)))
+same = sum(1 for v in on.values() if len(v) == 2 and blk[v[0]] == blk[v[1]])
+print(f"  SIMDs with exactly two waves: {sizes.get(2, 0)}, both of one block on {same}")
+per_block = Counter()
+for b in range(grid):
+    per_block[tuple(sorted(Counter(simd[b * wpb:(b + 1) * wpb].tolist()).values()))] += 1
+print("  waves per SIMD inside a block: " + ", ".join(f"{k}: {v} blocks" for k, v in sorted(per_block.items())))
+
+
+def dist(x):
+    x = np.asarray(x)
+    return f"min {x.min():.0f}  p10 {np.percentile(x, 10):.0f}  median {np.median(x):.0f}  p90 {np.percentile(x, 90):.0f}  max {x.max():.0f} us"
+
+
+first, second, lone, empty, both = [], [], 0.0, 0.0, 0.0
+for v in on.values():
+    v = sorted(v, key=lambda i: t0[i])
+    first.append(t1[v[0]] - start)
+    if len(v) > 1:
+        second.append(t1[v[1]] - start)
+    ev = sorted([(t0[i], 1) for i in v] + [(t1[i], -1) for i in v])
+    cur, prev = 0, start
+    for t, d in ev:
+        if cur == 0:
+            empty += t - prev
+        elif cur == 1:
+            lone += t - prev
+        else:
+            both += t - prev
+        cur, prev = cur + d, t
+    empty += start + span - prev
+tot = span * len(on)
+print(f"  end of wave - start of kernel, first-arrived wave of a SIMD:  {dist(first)}")
+if second:
+    print(f"  end of wave - start of kernel, second-arrived wave of a SIMD: {dist(second)}")
+print(f"  wave lifetime: {dist(t1 - t0)}")
+print(f"  share of the launch (SIMD-time over {len(on)} SIMDs): two or more waves resident {100 * both / tot:.1f} %, "
+      f"one wave only {100 * lone / tot:.1f} %, none {100 * empty / tot:.1f} %")
