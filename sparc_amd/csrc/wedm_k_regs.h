@@ -109,6 +109,32 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
 #ifndef WEDM_REGS_PAIR_PRIO_HI
 #define WEDM_REGS_PAIR_PRIO_HI 1
 #endif
+//   WEDM_REGS_PAIR_FAIR       a tie-break on top of the phases.  By phase alone both waves hold the same level in the same
+//                             phase, and the hardware breaks every such tie for the older wave.  With a favour bit `fav` the
+//                             chain runs at level 2 + fav and the walk at fav: a chain still beats the partner's walk, and
+//                             fav decides between equal phases only.  fav is made of the pair bit p (WEDM_REGS_PAIR_BIT),
+//                             which differs between the two waves of a SIMD:
+//                               1   by age: fav = p throughout (the younger wave one level up);  -1  its mirror, fav = !p;
+//                               K >= 3   by turns: fav = ((it >> K) & 1) ^ p, the favour changes sides every 2^K microseconds;
+//                               2   by halves: fav = (2 it >= n_substeps) ^ p, one change of sides per launch whatever its
+//                                   length.  Measured: a standing favour costs 5 % (the favoured wave runs away as the older
+//                                   one did before the phases), and turns gain the more the fewer they are (section 4.4);
+//                               0   the kernel is the text it was with the phases alone.
+//                             Two waves with equal p tie as before.  Priority only: no result depends on it.
+//   WEDM_REGS_PAIR_BIT        p: 0 the half of the grid the block lies in (blockIdx.x >= gridDim.x / 2), 1 the lowest bit of
+//                             the wave's slot on its SIMD (HW_ID), read once before the loop
+#ifndef WEDM_REGS_PAIR_FAIR
+#define WEDM_REGS_PAIR_FAIR 2
+#endif
+#ifndef WEDM_REGS_PAIR_BIT
+#define WEDM_REGS_PAIR_BIT 1
+#endif
+// `s_setprio` takes an immediate: a scalar branch over two instructions (fav is wave-uniform, in a scalar register)
+#define WEDM_REGS_SETPRIO_FAV(level, fav)                                                                     \
+    do {                                                                                                      \
+        if (__builtin_amdgcn_readfirstlane(fav)) __builtin_amdgcn_s_setprio((level) + 1);                     \
+        else __builtin_amdgcn_s_setprio(level);                                                               \
+    } while (0)
 
 // F_TRACE: the form with the signal-trace point (a launch into which a sample falls: the reference's logger samples
 // after every step, utils/logger.py:110-160); launches without a sample run the form without it.
@@ -127,10 +153,21 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     static_assert(H % 8 == 0 && H / 8 <= 16, "whole tiles");
     constexpr int EPB = 256 / L;
     constexpr bool PRIO = L == 2 && WEDM_REGS_PAIR_PHASES;
+    // (not the F_PULSE form: with the pair bit held the allocator gives it 84 bytes of scratch and 29 spilled registers
+    // for 68 / 18, with the bit read again at every site 72 / 22; it keeps the phases alone, the text it had)
+    constexpr int FAIR = PRIO && !PULSE ? WEDM_REGS_PAIR_FAIR : 0;
+    constexpr int PRIO_CHAIN = FAIR != 0 ? 2 : WEDM_REGS_PAIR_PRIO_HI;
     // pairs per stage of the packed walk: a wave that is alone on its SIMD needs the distance between dependent operations
     constexpr int SW = L == 1 ? 4 : WEDM_REGS_SW2;
     constexpr bool kF64 = F64;
     WEDM_STAMP_CENSUS_BEGIN();
+    // the pair bit: a scalar the wave forms by itself, different in the two waves that share a SIMD
+    uint32_t pair_bit = 0u;
+    if constexpr (FAIR != 0) {
+        if (WEDM_REGS_PAIR_BIT == 1) asm volatile("s_getreg_b32 %0, hwreg(4, 0, 1)" : "=s"(pair_bit));
+        else pair_bit = blockIdx.x >= gridDim.x / 2 ? 1u : 0u;
+        if (FAIR < 0) pair_bit ^= 1u;
+    }
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
     // every-step float64 constants in VGPRs: all of them with 512 registers, the epilogue's and the quiet prelude's with 256
@@ -215,7 +252,13 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
         WEDM_STAMP(st0);
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);  // the chain: few instructions, each one waited for
+        // whom a tie favours in this microsecond (by turns: the side changes every 2^FAIR microseconds; by halves: once)
+        const uint32_t fav = FAIR >= 3   ? (((uint32_t)it >> (FAIR >= 3 ? FAIR : 0)) & 1u) ^ pair_bit
+                             : FAIR == 2 ? (2 * it >= k.n_substeps ? 1u : 0u) ^ pair_bit
+                                         : pair_bit;
+        // the chain: few instructions, each one waited for
+        if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(PRIO_CHAIN, fav);
+        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
         e = env_index();
         const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
@@ -261,10 +304,14 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
             // the walk at priority 0, unless the microsecond took the general path AND its walk is busy (the walk's own test
             // of its entry): that walk is predicated cells and Joule terms behind a long prelude, and keeps the priority
             const bool busy = __any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f);
-            if (__builtin_amdgcn_readfirstlane((int)(was_quiet || !busy))) __builtin_amdgcn_s_setprio(0);
+            if (__builtin_amdgcn_readfirstlane((int)(was_quiet || !busy))) {
+                if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(0, fav);
+                else __builtin_amdgcn_s_setprio(0);
+            }
         }
 #include "wedm_regs_walk.inc"
-        if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
+        if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(PRIO_CHAIN, fav);
+        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
         WEDM_STAMP(st2);
         if (L == 2) tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
         WEDM_ENV_END_US(hv, tmax, pk, writer, none, WEDM_STAMP(st3))

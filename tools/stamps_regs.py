@@ -4,7 +4,9 @@ shipped library):
 * cycles per wave and microsecond in prelude / walk / reduction / epilogue, for the microseconds the quiet prelude handled
   and, separately, for those that took the general path;
 * the census: how the launch's waves pair up on SIMDs, when the first- and the second-arrived wave of a SIMD end (from the
-  start of the kernel, on the 100 MHz clock all XCDs share), and the share of the launch during which a SIMD held one wave only.
+  start of the kernel, on the 100 MHz clock all XCDs share), and the share of the launch during which a SIMD held one wave only;
+* the candidates for the pair bit of WEDM_REGS_PAIR_FAIR (the grid half, the bits of HW_ID's wave slot): on how many SIMDs
+  the two waves differ in it, and on how many of those the bit is set in the later-arrived wave.
 usage: WEDM_HIP_LIB=build/ablate/libwedm_STAMPS.so python tools/stamps_regs.py [lanes] [num_envs] [gap_um] [microseconds]"""
 import ctypes as C
 import sys
@@ -104,3 +106,20 @@ if second:
 print(f"  wave lifetime: {dist(t1 - t0)}")
 print(f"  share of the launch (SIMD-time over {len(on)} SIMDs): two or more waves resident {100 * both / tot:.1f} %, "
       f"one wave only {100 * lone / tot:.1f} %, none {100 * empty / tot:.1f} %")
+
+# ---- candidates for the pair bit p of WEDM_REGS_PAIR_FAIR: a bit a wave can form by itself that differs between the two
+# waves of a SIMD.  Per candidate: in how many of the SIMDs with exactly two waves p differs, and in how many of those
+# p = 1 is the later-arrived wave.
+pairs = [sorted(v, key=lambda i: t0[i]) for v in on.values() if len(v) == 2]
+cands = {"grid half (blockIdx.x >= gridDim.x / 2)": (blk >= grid // 2).astype(int)}
+for b in range(4):
+    cands[f"HW_ID wave slot bit {b}"] = ((hw >> b) & 1).astype(int)
+print(f"  pair bit candidates over {len(pairs)} SIMDs with exactly two waves:")
+for name, p in cands.items():
+    differ = [(a, z) for a, z in pairs if p[a] != p[z]]
+    late = sum(1 for a, z in differ if p[z] == 1)
+    print(f"    {name}: differs on {len(differ)}, equal on {len(pairs) - len(differ)}; p = 1 is the later-arrived wave on {late} of {len(differ)}")
+slots = Counter((int(hw[a] & 0xF), int(hw[z] & 0xF)) for a, z in pairs)
+print("  wave slots (first-arrived, second-arrived): " + ", ".join(f"{k}: {v}" for k, v in sorted(slots.items())))
+lag = np.array([t0[z] - t0[a] for a, z in pairs]) if pairs else np.zeros(1)
+print(f"  start of the second-arrived wave behind the first: {dist(lag)}")
