@@ -30,30 +30,47 @@ MP = MaterialModuleParameters()
 CANARY_F, CANARY_I = -12345.678, -77777
 
 
+class DeriveCall:
+    """The device side of `wedm_derive_geometry` calls on one set of inputs: the inputs uploaded once, `blocks` gives
+    canary-filled output blocks with a guard row before and behind each (host copies and device), `launch` enqueues one call
+    into such blocks on torch's current stream and synchronises nothing (`kernel_call` below and tests/test_streams.py)."""
+
+    def __init__(self, wire, combo, n_dia, n_seg_max, stride, height, dia_idx, mat_idx=None, mask=None):
+        self.n, self.stride = len(height), stride
+        self.combo = torch.from_numpy(np.ascontiguousarray(combo)).to(DEV)
+        self.height = torch.from_numpy(np.asarray(height, dtype=np.float64)).to(DEV)
+        self.dia = torch.from_numpy(np.asarray(dia_idx, dtype=np.int32)).to(DEV)
+        self.mat = None if mat_idx is None else torch.from_numpy(np.asarray(mat_idx, dtype=np.int32)).to(DEV)
+        self.mask = None if mask is None else torch.from_numpy(np.asarray(mask, dtype=np.uint8)).to(DEV)
+        zs0, cb0 = ref.host_constants(wire)
+        self.kw = dict(
+            segment_len=wire.segment_len, buffer_len_bottom=wire.buffer_len_bottom, buffer_len_top=wire.buffer_len_top,
+            contact_offset_top=wire.contact_offset_top, zone_start0=zs0, contact_bottom0=cb0, num_envs=self.n, n_seg_max=n_seg_max,
+            stride=stride, combo=self.combo.data_ptr(), n_diameters=n_dia, n_materials=combo.shape[0] // n_dia)
+
+    def blocks(self):
+        """(host_f, host_i, dev_f, dev_i, status): the float64 and int32 blocks with their guard rows, and a status word."""
+        host_f = np.full((_abi.GEOM_F64_COUNT + 2, self.stride), CANARY_F)
+        host_i = np.full((_abi.GEOM_I32_COUNT + 2, self.stride), CANARY_I, dtype=np.int32)
+        return host_f, host_i, torch.from_numpy(host_f).to(DEV), torch.from_numpy(host_i).to(DEV), \
+            torch.zeros(1, dtype=torch.int32, device=DEV)
+
+    def launch(self, dev_f, dev_i, status):
+        desc = _abi.GeomDeriveDesc(geom_f64=dev_f[1:].data_ptr(), geom_i32=dev_i[1:].data_ptr(), **self.kw)
+        L = _lib.load()
+        rc = L.wedm_derive_geometry(C.byref(desc), self.height.data_ptr(), self.dia.data_ptr(),
+                                    None if self.mat is None else self.mat.data_ptr(),
+                                    None if self.mask is None else self.mask.data_ptr(), status.data_ptr(),
+                                    C.c_void_p(torch.cuda.current_stream().cuda_stream))
+        assert rc == _abi.OK, L.wedm_last_error(None)
+
+
 def kernel_call(wire, combo, n_dia, n_seg_max, stride, height, dia_idx, mat_idx=None, mask=None):
     """One `wedm_derive_geometry` into canary-filled blocks with a guard row before and behind each, and the stand-in on a
     host copy of the same memory: returns ((gf, gi, status) of the device, the same of the stand-in), guards included."""
-    n = len(height)
-    host_f = np.full((_abi.GEOM_F64_COUNT + 2, stride), CANARY_F)
-    host_i = np.full((_abi.GEOM_I32_COUNT + 2, stride), CANARY_I, dtype=np.int32)
-    dev_f, dev_i = torch.from_numpy(host_f).to(DEV), torch.from_numpy(host_i).to(DEV)
-    t_combo = torch.from_numpy(np.ascontiguousarray(combo)).to(DEV)
-    t_h = torch.from_numpy(np.asarray(height, dtype=np.float64)).to(DEV)
-    t_d = torch.from_numpy(np.asarray(dia_idx, dtype=np.int32)).to(DEV)
-    t_m = None if mat_idx is None else torch.from_numpy(np.asarray(mat_idx, dtype=np.int32)).to(DEV)
-    t_k = None if mask is None else torch.from_numpy(np.asarray(mask, dtype=np.uint8)).to(DEV)
-    status = torch.zeros(1, dtype=torch.int32, device=DEV)
-    zs0, cb0 = ref.host_constants(wire)
-    desc = _abi.GeomDeriveDesc(
-        segment_len=wire.segment_len, buffer_len_bottom=wire.buffer_len_bottom, buffer_len_top=wire.buffer_len_top,
-        contact_offset_top=wire.contact_offset_top, zone_start0=zs0, contact_bottom0=cb0, num_envs=n, n_seg_max=n_seg_max,
-        stride=stride, combo=t_combo.data_ptr(), n_diameters=n_dia, n_materials=combo.shape[0] // n_dia,
-        geom_f64=dev_f[1:].data_ptr(), geom_i32=dev_i[1:].data_ptr())
-    L = _lib.load()
-    rc = L.wedm_derive_geometry(C.byref(desc), t_h.data_ptr(), t_d.data_ptr(), None if t_m is None else t_m.data_ptr(),
-                                None if t_k is None else t_k.data_ptr(), status.data_ptr(),
-                                C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    assert rc == _abi.OK, L.wedm_last_error(None)
+    call = DeriveCall(wire, combo, n_dia, n_seg_max, stride, height, dia_idx, mat_idx, mask)
+    host_f, host_i, dev_f, dev_i, status = call.blocks()
+    call.launch(dev_f, dev_i, status)
     torch.cuda.synchronize()
     want = ref.derive_columns(host_f[1:-1], host_i[1:-1], wire, combo, n_dia, n_seg_max, height, dia_idx, mat_idx, mask)
     return (dev_f.cpu().numpy(), dev_i.cpu().numpy(), int(status.item())), (host_f, host_i, want)

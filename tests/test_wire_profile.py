@@ -83,15 +83,17 @@ class Call:
                                 az_end=int(self.ze[0]) if u else -1, geom_i32=None if u else self.geom.data_ptr(),
                                 bins=bins, out=out.data_ptr(), out_stride=self.out_stride, out_cols=out_cols)
 
-    def run(self, bins, ids=None, out=None, out_cols=None):
-        """The ``[rows][out_stride]`` block after the launch (a fresh one full of SENTINEL unless given)."""
+    def run(self, bins, ids=None, out=None, out_cols=None, sync=True):
+        """The ``[rows][out_stride]`` block after the launch (a fresh one full of SENTINEL unless given).  ``sync=False``
+        only enqueues the launch on torch's current stream (tests/test_streams.py); the caller synchronises."""
         count = self.num_envs if ids is None else len(ids)
         if out is None:
             out = torch.full((_abi.profile_rows(bins), self.out_stride), float(SENTINEL), dtype=torch.float32, device=DEV)
         idx = None if ids is None else torch.from_numpy(np.asarray(ids, dtype=np.int32)).to(DEV)
         self.be.wire_profile(self.desc(bins, out, count if out_cols is None else out_cols),
                              None if idx is None else idx.data_ptr(), count, self.status.data_ptr())
-        torch.cuda.synchronize()
+        if sync:
+            torch.cuda.synchronize()
         return out
 
 
