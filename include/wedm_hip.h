@@ -1058,6 +1058,101 @@ typedef struct wedm_head_desc {
  * write) overlapping one of its input blocks.                                                                          */
 int32_t wedm_policy_head(const wedm_head_desc* desc, void* stream);
 
+/* ------------------------------------------------- PPO clipped loss and its gradient, one call per minibatch
+ * What an on-policy update makes of a minibatch: the clipped surrogate, the value loss (optionally clipped), the entropy
+ * bonus, their means over the rows that count, the diagnostics (approximate KL, clip fraction) and the gradient of the
+ * loss with respect to the policy's parameter rows and the value estimates -- in one pass over the rows, in float64 on
+ * the float32 inputs, every operation rounded, nothing fused, parentheses as written, with wedm_policy_head's pexp, plog
+ * and f32.  The means are a fixed pairwise tree over the row number, so the bits of every output depend on the values
+ * and the rows' order alone: not on the launch, the device or a library's reduction.
+ *
+ * ROWS.  B = rows.  Dense by row r: params + r * param_stride (the head's row [mu x 4, ls x 4, l x M], P = 8 + M) and
+ *   value[r].  STORED inputs are read at src = index ? index[r] : r (index: int64 [B] or NULL): u + 4 src, mode_index[src]
+ *   (clamped to [0, M - 1] as in the head), old_log_prob[src], advantage[src], returns[src], old_value[src] (read only with
+ *   WEDM_PPO_CLIP_VALUE), valid[src] (uint8, or NULL).  n_src is the length of the stored blocks (== rows when index is
+ *   NULL).  A row is LIVE iff 0 <= src < n_src and (valid == NULL or valid[src] != 0).  A src outside [0, n_src) is
+ *   never dereferenced: its row is not live and is BAD.
+ * A LIVE ROW (old, A, v, R, ov: old_log_prob, advantage, value, returns, old_value as doubles):
+ *     lp64, ent64: the unrounded log_prob and entropy of wedm_policy_head's definition
+ *     lp = (double) f32(lp64)       -- the float32 that EVALUATE stores: with old taken from SAMPLE at unchanged parameters
+ *                                      lr is exactly 0 and ratio exactly 1
+ *     lr = lp - old;   ratio = pexp(lr);   lo_c = 1.0 - clip;   hi_c = 1.0 + clip
+ *     rc = ratio < lo_c ? lo_c : (ratio > hi_c ? hi_c : ratio)
+ *     s1 = ratio * A;   s2 = rc * A;   clipped = s2 < s1
+ *     pol = -(clipped ? s2 : s1);   dlp = clipped ? 0.0 : -(A * ratio)
+ *     kl = (ratio - 1.0) - lr;   cf = (ratio < lo_c || ratio > hi_c) ? 1.0 : 0.0
+ *     e = v - R;   vl = e * e;   dv = e
+ *     WEDM_PPO_CLIP_VALUE:  d = v - ov;   dc = d < -clip_value ? -clip_value : (d > clip_value ? clip_value : d)
+ *                           ec = (ov + dc) - R;   vlc = ec * ec;   if (vlc > vl) { vl = vlc;  dv = (dc == d) ? ec : 0.0; }
+ *     vloss = 0.5 * vl
+ *   Every comparison is the chain as written: a NaN falls through it as the text says, not as fmin would have it.
+ * SUMS.  Seven doubles per row, [live, bad, pol, vloss, ent64, kl, cf] (live and bad: 1.0 or 0.0); a row that is not live
+ *   holds +0.0 in all but its bad flag.  Each is added by the pairwise tree over r with plain additions, the lower index on
+ *   the left: rows are padded with +0.0 to tiles of 256; a tile's eight levels come first (tile t's node is
+ *   partials[t][0 .. 7)), then the pairwise tree over the tile index, padded with +0.0 to the smallest power of two that
+ *   holds the tiles.  tiles = ceil(rows / 256) <= WEDM_NORM_MAX_TILES.
+ * STATS.  stats[8] = [n, n_bad, loss, policy_loss, value_loss, entropy, approx_kl, clip_fraction]:  n and n_bad are the
+ *   sums of live and bad;  s = n > 0 ? 1.0 / n : 0.0;  the five means are sum * s;
+ *   loss = (policy_loss + vf_coef * value_loss) - ent_coef * entropy.  With n == 0 everything is 0: no NaN.
+ * GRADIENT of loss (the float32 rounding of lp taken as the identity), written only where the pointer is given:
+ *     live row:  grad_params + r * grad_stride, P float32: WEDM_HEAD_BACKWARD's formulas with glp = dlp * s and
+ *                gen = -ent_coef * s, each entry rounded once through f32;  grad_value[r] = f32((vf_coef * dv) * s)
+ *     other rows: zeros in both.   Columns [P, grad_stride) are not touched.
+ * A NaN is stored in partials and stats as 0x7FF8000000000000 and in a float32 as 0x7FC00000.
+ * PHASES.  s must be known before a gradient is written.  Without valid and without index n == rows and the call is MAIN
+ *   (the rows: partials and the gradient) then FOLD (partials -> stats).  Otherwise COUNT comes first: it zeroes count[0 .. 2)
+ *   and counts the live rows into count[0] and the bad ones into count[1] with integer atomics (order-free), and MAIN
+ *   reads count[0].  WEDM_PPO_COUNT / _MAIN / _FOLD select phases; none set means all, in this order.  COUNT without valid
+ *   and index launches nothing.                                                                                         */
+#define WEDM_PPO_SUMS 7
+#define WEDM_PPO_STATS 8
+#define WEDM_PPO_COUNT_WORDS 2
+enum wedm_ppo_flag { WEDM_PPO_CLIP_VALUE = 1, WEDM_PPO_COUNT = 2, WEDM_PPO_MAIN = 4, WEDM_PPO_FOLD = 8 };
+enum wedm_ppo_sum { WEDM_PS_LIVE = 0, WEDM_PS_BAD, WEDM_PS_POLICY, WEDM_PS_VALUE, WEDM_PS_ENTROPY, WEDM_PS_KL, WEDM_PS_CLIPPED };
+enum wedm_ppo_stat { WEDM_PT_N = 0, WEDM_PT_N_BAD, WEDM_PT_LOSS, WEDM_PT_POLICY, WEDM_PT_VALUE, WEDM_PT_ENTROPY, WEDM_PT_KL,
+                     WEDM_PT_CLIP_FRACTION };
+typedef struct wedm_ppo_desc {
+    const float* params;           /* [rows][param_stride] */
+    const float* value;            /* [rows] */
+    const int64_t* index;          /* [rows] or NULL: src = r */
+    const float* u;                /* [n_src][4], 16-byte aligned */
+    const int32_t* mode_index;     /* [n_src] */
+    const float* old_log_prob;     /* [n_src] */
+    const float* advantage;        /* [n_src] */
+    const float* returns;          /* [n_src] */
+    const float* old_value;        /* [n_src]; CLIP_VALUE */
+    const uint8_t* valid;          /* [n_src] or NULL: every row in range is live */
+    float* grad_params;            /* [rows][grad_stride] or NULL */
+    float* grad_value;             /* [rows] or NULL */
+    double* partials;              /* [ceil(rows / 256)][WEDM_PPO_SUMS]; MAIN writes, FOLD reads */
+    double* stats;                 /* [WEDM_PPO_STATS]; FOLD */
+    int32_t* count;                /* [WEDM_PPO_COUNT_WORDS]: live and bad rows; with valid or index: COUNT writes, MAIN reads */
+    int64_t param_stride;          /* >= 8 + n_modes, in elements */
+    int64_t grad_stride;           /* >= 8 + n_modes, in elements */
+    int64_t n_src;                 /* >= 1 */
+    double clip, vf_coef, ent_coef, clip_value; /* finite; clip >= 0, clip_value >= 0 */
+    double lo[4], hi[4];           /* finite, lo < hi */
+    double log_span[4];            /* log(hi - lo), finite */
+    int32_t n_modes;               /* M, in [1, WEDM_HEAD_MAX_MODES] */
+    int32_t rows;                  /* >= 1, at most WEDM_NORM_MAX_TILES * 256 */
+    int32_t flags;                 /* enum wedm_ppo_flag */
+    int32_t reserved;
+} wedm_ppo_desc;
+
+/* At most four launches on `stream` with valid or index (COUNT: two; MAIN; FOLD) and two without, none of which waits for
+ * another block: no spin, no cooperative launch, no floating-point atomic.  Stateless like wedm_policy_head: no wedm_ctx,
+ * the current device, caller-owned memory.  `desc` is HOST memory, read before the call returns; everything it names is
+ * device memory.  Written: grad_params' columns [0, P) of rows [0, rows), grad_value, partials, stats, count -- each by its
+ * phase, nothing else.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined; rows < 1 or
+ * more than WEDM_NORM_MAX_TILES tiles; n_src < 1; n_modes outside [1, WEDM_HEAD_MAX_MODES]; a stride below 8 + n_modes;
+ * clip, vf_coef, ent_coef, clip_value, a bound or a log_span that is not finite; clip < 0 or clip_value < 0; hi <= lo; a
+ * needed pointer NULL (params, value, u, mode_index, old_log_prob, advantage, returns and partials for MAIN; old_value with
+ * CLIP_VALUE; partials and stats for FOLD; count with valid or index for COUNT and MAIN); a pointer not aligned to its
+ * element (u: 16 bytes; index, partials, stats: 8); an output block (first to last byte that the call may write)
+ * overlapping an input block.                                                                                          */
+int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

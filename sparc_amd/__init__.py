@@ -28,6 +28,7 @@ from .modules.views import DielectricModule, IgnitionModule, MaterialRemovalModu
 from .controllers import GapController, VoltageController, run_controlled
 from .normalize import Normalizer
 from .policy_head import PolicyHead
+from .ppo import PPOLoss
 from .randomize import EpisodeSampler
 from .rollout import RolloutBuffer
 from .snapshot import EnvSnapshot
@@ -41,7 +42,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "Normalizer", "RolloutBuffer", "PolicyHead",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "Normalizer", "RolloutBuffer", "PolicyHead", "PPOLoss",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

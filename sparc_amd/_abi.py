@@ -460,6 +460,28 @@ class HeadDesc(C.Structure):
     ]
 
 
+PPO_CLIP_VALUE, PPO_COUNT, PPO_MAIN, PPO_FOLD = 1, 2, 4, 8  # enum wedm_ppo_flag
+PPO_SUMS, PPO_STATS, PPO_COUNT_WORDS = 7, 8, 2  # WEDM_PPO_SUMS, WEDM_PPO_STATS, WEDM_PPO_COUNT_WORDS
+# enum wedm_ppo_stat: the entries of ``stats``
+PPO_STAT_NAMES = ("n", "n_bad", "loss", "policy_loss", "value_loss", "entropy", "approx_kl", "clip_fraction")
+
+
+class PpoDesc(C.Structure):
+    """``struct wedm_ppo_desc``: what `wedm_ppo_loss` reads and where it writes (strides in elements; ``n_src``: the length
+    of the stored blocks that ``index`` points into)."""
+
+    _fields_ = [
+        ("params", C.c_void_p), ("value", C.c_void_p), ("index", C.c_void_p), ("u", C.c_void_p), ("mode_index", C.c_void_p),
+        ("old_log_prob", C.c_void_p), ("advantage", C.c_void_p), ("returns", C.c_void_p), ("old_value", C.c_void_p),
+        ("valid", C.c_void_p), ("grad_params", C.c_void_p), ("grad_value", C.c_void_p), ("partials", C.c_void_p),
+        ("stats", C.c_void_p), ("count", C.c_void_p),
+        ("param_stride", C.c_int64), ("grad_stride", C.c_int64), ("n_src", C.c_int64),
+        ("clip", C.c_double), ("vf_coef", C.c_double), ("ent_coef", C.c_double), ("clip_value", C.c_double),
+        ("lo", C.c_double * 4), ("hi", C.c_double * 4), ("log_span", C.c_double * 4),
+        ("n_modes", C.c_int32), ("rows", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

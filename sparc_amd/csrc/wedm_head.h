@@ -57,7 +57,9 @@ struct head_component {
     double z, action, c;
 };
 
-__device__ __forceinline__ head_component head_continuous(const wedm_head_desc& d, const int i, const double mu, const double ls,
+// Desc: a descriptor with lo[4], hi[4] and log_span[4] (wedm_head_desc; wedm_ppo_desc of wedm_ppo.h)
+template <class Desc>
+__device__ __forceinline__ head_component head_continuous(const Desc& d, const int i, const double mu, const double ls,
                                                           const double sigma, const double u) {
     head_component out;
     out.z = (u - mu) / sigma;

@@ -48,6 +48,8 @@
 //                         advantages, the time loop in the lane, moments by the same tree; not step kernels, not in the registry
 //   wedm_head.h           wedm_head_kernel: a policy's action head (squashed Gaussians and a categorical) -- a seeded draw, its
 //                         log-probability and entropy, their gradient; one lane per row; not a step kernel, not in the registry
+//   wedm_ppo.h            wedm_ppo_count / _main / _fold_kernel: PPO's clipped loss over a minibatch -- the row's terms, their
+//                         means by a fixed pairwise tree over the row number, the gradient; not step kernels, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -92,6 +94,7 @@ using namespace wedm;
 #include "wedm_normalize.h"
 #include "wedm_gae.h"
 #include "wedm_head.h"
+#include "wedm_ppo.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1677,6 +1680,107 @@ int32_t wedm_policy_head(const wedm_head_desc* desc, void* stream) {
     if (e == hipSuccess) return WEDM_OK;
     g_create_error = std::string("wedm_policy_head: launch: ") + hipGetErrorString(e);
     return WEDM_ERR_HIP;
+}
+
+int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_ppo_loss: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_ppo_desc& d = *desc;
+    if (d.flags & ~(int32_t)(WEDM_PPO_CLIP_VALUE | WEDM_PPO_COUNT | WEDM_PPO_MAIN | WEDM_PPO_FOLD)) return bad("undefined flag bits");
+    if (d.rows < 1) return bad("rows must be positive");
+    const int64_t tiles = ((int64_t)d.rows + WEDM_PPO_BLOCK - 1) / WEDM_PPO_BLOCK;
+    if (tiles > WEDM_NORM_MAX_TILES)
+        return bad("a minibatch holds at most " + std::to_string(WEDM_NORM_MAX_TILES * WEDM_PPO_BLOCK) + " rows (" +
+                   std::to_string(WEDM_NORM_MAX_TILES) + " tiles of 256)");
+    if (d.n_src < 1) return bad("n_src must be positive");
+    if (d.n_modes < 1 || d.n_modes > WEDM_HEAD_MAX_MODES) return bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+    const int64_t P = 8 + d.n_modes;
+    if (d.param_stride < P || d.grad_stride < P) return bad("a stride is smaller than 8 + n_modes");
+    if (!finite_f64(d.clip) || !finite_f64(d.vf_coef) || !finite_f64(d.ent_coef) || !finite_f64(d.clip_value))
+        return bad("clip, vf_coef, ent_coef and clip_value must be finite");
+    if (d.clip < 0.0 || d.clip_value < 0.0) return bad("clip and clip_value must not be negative");
+    for (int i = 0; i < 4; ++i) {
+        if (!finite_f64(d.lo[i]) || !finite_f64(d.hi[i]) || !finite_f64(d.log_span[i])) return bad("a bound or log_span is not finite");
+        if (!(d.hi[i] > d.lo[i])) return bad("hi <= lo");
+    }
+    const bool all = !(d.flags & (WEDM_PPO_COUNT | WEDM_PPO_MAIN | WEDM_PPO_FOLD));
+    const bool counted = d.valid || d.index;  // the number of live rows is not the host's to know
+    const bool count = (all || (d.flags & WEDM_PPO_COUNT)) && counted, rows_pass = all || (d.flags & WEDM_PPO_MAIN);
+    const bool fold = all || (d.flags & WEDM_PPO_FOLD), clip_value = d.flags & WEDM_PPO_CLIP_VALUE;
+    // the blocks by name: first byte, bytes the call may touch, alignment, whether a phase that runs needs it
+    struct Block {
+        const char* name;
+        uintptr_t lo, bytes, align;
+        bool needed;
+    };
+    const uintptr_t n = (uintptr_t)d.rows, ns = (uintptr_t)d.n_src;
+    const Block in[] = {
+        {"params", (uintptr_t)d.params, (uintptr_t)((int64_t)(d.rows - 1) * d.param_stride + P) * 4, 4, rows_pass},
+        {"value", (uintptr_t)d.value, n * 4, 4, rows_pass},
+        {"index", (uintptr_t)d.index, n * 8, 8, false},
+        {"u", (uintptr_t)d.u, ns * 16, 16, rows_pass},
+        {"mode_index", (uintptr_t)d.mode_index, ns * 4, 4, rows_pass},
+        {"old_log_prob", (uintptr_t)d.old_log_prob, ns * 4, 4, rows_pass},
+        {"advantage", (uintptr_t)d.advantage, ns * 4, 4, rows_pass},
+        {"returns", (uintptr_t)d.returns, ns * 4, 4, rows_pass},
+        {"old_value", (uintptr_t)d.old_value, ns * 4, 4, rows_pass && clip_value},
+        {"valid", (uintptr_t)d.valid, ns, 1, false},
+    };
+    const Block out[] = {
+        {"grad_params", (uintptr_t)d.grad_params, (uintptr_t)((int64_t)(d.rows - 1) * d.grad_stride + P) * 4, 4, false},
+        {"grad_value", (uintptr_t)d.grad_value, n * 4, 4, false},
+        {"partials", (uintptr_t)d.partials, (uintptr_t)tiles * WEDM_PPO_SUMS * 8, 8, rows_pass || fold},
+        {"stats", (uintptr_t)d.stats, WEDM_PPO_STATS * 8, 8, fold},
+        {"count", (uintptr_t)d.count, WEDM_PPO_COUNT_WORDS * 4, 4, counted && (count || rows_pass)},
+    };
+    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.align != 0; };
+    for (const Block& b : in)
+        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
+    for (const Block& b : out)
+        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
+    for (const Block& o : out) {
+        for (const Block& i : in)
+            if (o.lo && i.lo && o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(std::string(o.name) + " overlaps " + i.name);
+    }
+    const auto launched = [](const char* what) {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return (int32_t)WEDM_OK;
+        g_create_error = std::string("wedm_ppo_loss: ") + what + " launch: " + hipGetErrorString(e);
+        return (int32_t)WEDM_ERR_HIP;
+    };
+    const hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((uint32_t)tiles), block(WEDM_PPO_BLOCK);
+    if (count) {
+        hipLaunchKernelGGL(wedm_ppo_zero_kernel, dim3(1), dim3(64), 0, s, d);
+        if (const int32_t rc = launched("zero")) return rc;
+        hipLaunchKernelGGL(wedm_ppo_count_kernel, dim3((uint32_t)std::min<int64_t>(tiles, WEDM_PPO_COUNT_BLOCKS)), block, 0, s, d);
+        if (const int32_t rc = launched("count")) return rc;
+    }
+    if (rows_pass) {
+        const bool in_lds = d.param_stride == P && (uintptr_t)d.params % 16 == 0;
+        const bool out_lds = d.grad_params && d.grad_stride == P && (uintptr_t)d.grad_params % 16 == 0;
+        const size_t lds = in_lds || out_lds ? (size_t)WEDM_PPO_BLOCK * (size_t)head_pitch((int)P) * 4 : 0;
+        const int32_t n_known = counted ? -1 : d.rows;
+        if (in_lds) {
+            if (out_lds) hipLaunchKernelGGL((wedm_ppo_main_kernel<true, true>), grid, block, lds, s, d, n_known);
+            else hipLaunchKernelGGL((wedm_ppo_main_kernel<true, false>), grid, block, lds, s, d, n_known);
+        } else {
+            if (out_lds) hipLaunchKernelGGL((wedm_ppo_main_kernel<false, true>), grid, block, lds, s, d, n_known);
+            else hipLaunchKernelGGL((wedm_ppo_main_kernel<false, false>), grid, block, lds, s, d, n_known);
+        }
+        if (const int32_t rc = launched("main")) return rc;
+    }
+    if (fold) {
+        int32_t padded = 1, per = 1;  // the smallest power of two >= tiles; tiles per lane: the power of two with 256 * per >= tiles
+        while (padded < tiles) padded *= 2;
+        while (256 * per < tiles) per *= 2;
+        hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, per);
+        if (const int32_t rc = launched("fold")) return rc;
+    }
+    return WEDM_OK;
 }
 
 // why a descriptor cannot be followed (wedm_derive_geometry, and wedm_draw_episode for its `geom`), or NULL
