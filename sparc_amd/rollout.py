@@ -176,6 +176,7 @@ class RolloutBuffer:
         self._partials = torch.zeros((self._tiles, _abi.NORM_MOMENTS), dtype=torch.float64, **kw)
         self.moments = torch.zeros(_abi.NORM_MOMENTS, dtype=torch.float64, **kw)
         self._slot = 0
+        self._finished = False  # `finish` has run and no `add` since: the computed blocks belong to the stored steps
         self._keep = None
         s, c = self.stored, self.computed
         self._desc = _abi.GaeDesc(
@@ -224,6 +225,7 @@ class RolloutBuffer:
         for name, x in given.items():
             s[name][t].copy_(x)
         self._slot = t + 1
+        self._finished = False
 
     # ------------------------------------------------------------------ the call
     def finish(self, last_value: torch.Tensor) -> Dict[str, torch.Tensor]:
@@ -252,6 +254,7 @@ class RolloutBuffer:
             self._native.gae(self._desc)
             self._keep = last_value  # the launches are asynchronous: their input lives until the next call
         self._slot = 0
+        self._finished = True
         return self._results()
 
     def _results(self) -> Dict[str, torch.Tensor]:
@@ -275,6 +278,7 @@ class RolloutBuffer:
         """Forgets the stored steps and the last done row: call it after ``vec.reset()``."""
         self._prev_done.zero_()
         self._slot = 0
+        self._finished = False
 
     @property
     def prev_done(self) -> torch.Tensor:
@@ -287,11 +291,17 @@ class RolloutBuffer:
                     skip_after_done=self.skip_after_done)
 
     def state_dict(self) -> Dict[str, Any]:
-        """The settings, the slot, ``prev_done`` and the steps stored so far (none right after `finish`), as CPU tensors and
-        plain values."""
-        return {"num_steps": self.num_steps, "num_envs": self.num_envs, "settings": self.settings(), "slot": self._slot,
-                "prev_done": self._prev_done.detach().cpu().clone(),
-                "stored": {k: v[: self._slot].detach().cpu().clone() for k, v in self.stored.items()}}
+        """The settings, the slot, ``prev_done`` and the steps stored so far, as CPU tensors and plain values.  Between `finish`
+        and the next `add` -- where the epochs over the rollout run -- the rollout is whole: every stored step, and under
+        ``"computed"`` what `finish` made of them (``moments`` included), so that `flat` and `minibatches` go on after a load."""
+        rows = self.num_steps if self._finished else self._slot
+        sd = {"num_steps": self.num_steps, "num_envs": self.num_envs, "settings": self.settings(), "slot": self._slot,
+              "prev_done": self._prev_done.detach().cpu().clone(),
+              "stored": {k: v[:rows].detach().cpu().clone() for k, v in self.stored.items()}}
+        if self._finished:
+            sd["computed"] = {**{k: v.detach().cpu().clone() for k, v in self.computed.items()},
+                              "moments": self.moments.detach().cpu().clone()}
+        return sd
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
         """Takes over a `state_dict` of a buffer of the same shape, with the same normalisation block and extras."""
@@ -311,12 +321,19 @@ class RolloutBuffer:
         self.skip_after_done = bool(st["skip_after_done"])
         self._settings_to_desc()
         slot = int(sd["slot"])
-        if self._action_keys is None and slot > 0:
+        computed = sd.get("computed")  # the whole rollout of a dict taken between `finish` and the next `add`
+        rows = self.num_steps if computed is not None else slot
+        if self._action_keys is None and rows > 0:
             for k in actions:
                 self.stored[k] = torch.zeros((self.num_steps,) + tuple(stored[k].shape[1:]), dtype=stored[k].dtype, device=self.device)
             self._action_keys = actions
         for k, v in stored.items():
-            if slot > 0:
-                self.stored[k][:slot].copy_(v)
+            if rows > 0:
+                self.stored[k][:rows].copy_(v)
+        if computed is not None:
+            for k, t in self.computed.items():
+                t.copy_(computed[k])
+            self.moments.copy_(computed["moments"])
         self._prev_done.copy_(torch.as_tensor(sd["prev_done"]).to(torch.uint8))
         self._slot = slot
+        self._finished = computed is not None

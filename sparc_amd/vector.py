@@ -292,5 +292,89 @@ class WireEDMVectorEnv:
         if self.normalizer is not None:
             self.normalizer.fork(src, dst)
 
+    # ---- checkpoints ----
+    def _reward_kind(self) -> str:
+        return "kernel" if self._reward_fn is None else "progress" if self._reward_fn is progress_reward else "callable"
+
+    def _sampler_kinds(self) -> Tuple[str, ...]:
+        present = (("param", self._param_sampler), ("material", self._material_sampler), ("geometry", self._geometry_sampler),
+                   ("episode", self._episode_sampler))
+        return tuple(kind for kind, f in present if f is not None)
+
+    def _settings(self) -> Dict[str, Any]:
+        """What changes what a step does, as plain values."""
+        return {"num_envs": self.num_envs, "autoreset": self.autoreset, "max_episode_steps": self.max_episode_steps,
+                "wire_profile_bins": self.wire_profile_bins, "obs_names": tuple(self.obs_names), "reward": self._reward_kind(),
+                "samplers": self._sampler_kinds()}
+
+    def state_dict(self) -> Dict[str, Any]:
+        """Everything a bit-identical continuation of the adapter needs: which environments start a new episode at the next
+        `step()` (``need_reset``) and their ``episode_count``, the settings that change what a step does (batch size,
+        ``autoreset``, ``max_episode_steps``, ``wire_profile_bins``, ``obs_names``, the kind of reward -- ``"kernel"``,
+        ``"progress"`` or ``"callable"`` -- and the kinds of samplers present), and under ``"env"``, ``"episode_sampler"`` and
+        ``"normalizer"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
+        tuples and lists only: loads with ``weights_only=True``.
+        Not in it: ``param_sampler`` / ``material_sampler`` / ``geometry_sampler`` draw from a ``torch.Generator`` the caller
+        owns, and a callable reward may hold state of its own -- the caller saves those (``generator.get_state()``)."""
+        sd = dict(self._settings())
+        sd["need_reset"] = self._need_reset.detach().cpu().clone()
+        sd["episode_count"] = self.episode_count.detach().cpu().clone()
+        sd["env"] = self.env.state_dict()
+        if self._episode_sampler is not None:
+            sd["episode_sampler"] = self._episode_sampler.state_dict()
+        if self.normalizer is not None:
+            sd["normalizer"] = self.normalizer.state_dict()
+        return sd
+
+    def load_state_dict(self, sd: Dict[str, Any]) -> None:
+        """Takes over a `state_dict`.  A dict taken with another batch size, autoreset mode, ``max_episode_steps``, profile
+        bins, observation columns or kind of reward, or with a sampler or a normaliser on one side only, raises
+        ``ValueError`` naming the difference before anything is written; the nested dicts keep their own refusals (the
+        environment's, the episode sampler's spec and batch, the normaliser's columns and batch), all of them checked
+        before the first byte changes."""
+        mine = self._settings()
+        for key, here in mine.items():
+            if key not in sd:
+                raise ValueError(f"the state dict holds no {key!r}: it is not a WireEDMVectorEnv's")
+            there = sd[key]
+            if isinstance(here, tuple):
+                there = tuple(there)
+            if there != here:
+                raise ValueError(f"the checkpoint was taken with {key}={sd[key]!r}, this adapter has {key}={here!r}")
+        for key, mine_has in (("episode_sampler", self._episode_sampler is not None), ("normalizer", self.normalizer is not None)):
+            if (key in sd) != mine_has:
+                raise ValueError(f"the checkpoint was taken {'with' if key in sd else 'without'} a {key}, this adapter has "
+                                 f"{'one' if mine_has else 'none'}")
+        for key, shape_of in (("need_reset", self._need_reset), ("episode_count", self.episode_count)):
+            if tuple(sd[key].shape) != tuple(shape_of.shape):
+                raise ValueError(f"checkpoint tensor {key!r} has shape {tuple(sd[key].shape)}, expected {tuple(shape_of.shape)}")
+        s, norm = self._episode_sampler, self.normalizer
+        if s is not None:
+            ssd = sd["episode_sampler"]
+            if ssd["fingerprint"] != s.fingerprint():
+                raise ValueError("the checkpoint's EpisodeSampler draws other names or from other ranges than this one")
+            if ssd["draw_count"] is not None and tuple(ssd["draw_count"].shape) != (self.num_envs,):
+                raise ValueError(f"the checkpoint's draw counts are for {ssd['draw_count'].shape[0]} environments, this "
+                                 f"sampler's environment has {self.num_envs}")
+        if norm is not None:
+            nsd = sd["normalizer"]
+            if tuple(nsd["columns"]) != norm.columns:
+                raise ValueError(f"the state dict normalises the columns {tuple(nsd['columns'])}, this Normalizer {norm.columns}")
+            if int(nsd["num_envs"]) != norm.num_envs:
+                raise ValueError(f"the state dict holds {nsd['num_envs']} environments, this Normalizer {norm.num_envs}")
+        self.env.load_state_dict(sd["env"])  # (raises before it writes)
+        if s is not None:
+            s.load_state_dict(sd["episode_sampler"])
+        if norm is not None:
+            norm.load_state_dict(sd["normalizer"])
+        self._need_reset = sd["need_reset"].to(device=self.env.device, dtype=torch.bool).clone()
+        self.episode_count.copy_(sd["episode_count"])
+
+    def save_checkpoint(self, path) -> None:
+        torch.save(self.state_dict(), path)
+
+    def load_checkpoint(self, path) -> None:
+        self.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+
     def close(self) -> None:
         self.env.close()

@@ -240,8 +240,7 @@ def test_state_dict_round_trip_and_another_column_set_is_refused():
     assert same_bits(back["stats"], sd["stats"]) and all(same_bits(back["rows"][k], sd["rows"][k]) for k in ROW_NAMES)
     assert same_bits(b.mean, a.mean) and same_bits(b.var, a.var) and same_bits(b.count, a.count)
     # both go on to the same bits
-    vb.env.load_state_dict(va.env.state_dict())
-    vb._need_reset.copy_(va._need_reset)
+    vb.load_state_dict(va.state_dict())   # the environment, which environments are due for a reset, and the normaliser again
     oa, ob = (v.step(v.env.make_action(0.1, 80.0, 9, 3.0, 30.0)) for v in (va, vb))
     assert same_bits(oa[0], ob[0]) and same_bits(oa[1], ob[1]) and same_bits(a.stats, b.stats)
     other = Normalizer()
