@@ -1153,6 +1153,86 @@ typedef struct wedm_ppo_desc {
  * overlapping an input block.                                                                                          */
 int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream);
 
+/* ------------------------------------------------- the log of finished episodes: an ordered ring, per-episode sums
+ * One call per control step, after the step: every environment whose episode ended in it appends one RECORD to a ring of
+ * `capacity` slots, in the order of the global environment index, without the host learning how many there were.
+ *
+ * PLANES.  A plane is a [n_rows][src_stride] block of elem_bytes 1, 4 or 8 with the environment as the column, and of a kind:
+ *   WEDM_ELOG_LAST      the element as it lies when the episode ends, copied as raw words (a NaN keeps its payload);
+ *                       dst is [n_rows][capacity] of elem_bytes;
+ *   WEDM_ELOG_SUM_F32 / _SUM_F64 / _SUM_I32   the sum over the episode's control steps of a float (elem_bytes 4), a double
+ *                       (8) or an int32_t (4) row, held in the caller's accumulator acc [n_rows][num_envs] of 8 bytes
+ *                       (double; int64_t for SUM_I32); dst is [n_rows][capacity] of 8 bytes of the accumulator's type.
+ *                       float:  acc = acc + (double) x   (one rounding, nothing fused);   int32: int64 addition.
+ * PER ENVIRONMENT e of [0, num_envs), g = 256 * tile_offset + e its GLOBAL index (the tile convention of wedm_normalize):
+ *     live(e)   = mask == NULL || mask[e] != 0
+ *     finish(e) = live(e) && ((terminated[e] | (truncated == NULL ? 0 : truncated[e])) != 0)
+ *   every live environment first adds this step's SUM rows to its accumulators; a finishing one then forms a record:
+ *     k = the number of finishing environments of lower global index in this call
+ *       = tile_counts[0] + ... + tile_counts[tile_offset + e / 256 - 1] + the finishing e' < e of e's own tile,
+ *     n = tile_counts[0] + ... + tile_counts[n_tiles_total - 1]        (all finishing environments of this call),
+ *     a = head[0] + k  (the record's absolute number),   slot = a mod capacity, in [0, capacity),
+ *   and the record is WRITTEN iff k >= n - capacity: a call that finishes more episodes than the ring holds keeps the
+ *   newest `capacity` of them, and no two lanes ever write one slot (the result does not depend on block scheduling).
+ *   A written record holds, at column `slot`: every LAST row's element of column e, every SUM accumulator of e (this step
+ *   included), env_out = env_id_offset + e, stamp_out = stamp.  Every finishing environment's accumulators are then zero,
+ *   whether its record was written or dropped.  After all records: head[0] += n, head[1] = n.
+ *   Never written: a slot no record names, an accumulator of an environment that is not live, columns [num_envs, stride),
+ *   any source plane, tile_counts outside this batch's tiles.
+ * PHASES, as wedm_gae has them; none of the three set means all three, in this order:
+ *   WEDM_ELOG_COUNT    writes tile_counts[tile_offset + t], the finishing environments of this batch's tile t;
+ *   WEDM_ELOG_SCATTER  reads head[0] and tile_counts[0 .. n_tiles_total), updates accumulators and writes records;
+ *   WEDM_ELOG_COMMIT   reads tile_counts[0 .. n_tiles_total) and advances head.
+ *   A sharded batch COUNTs every shard into its own tiles of one workspace, then SCATTERs every shard, then COMMITs once;
+ *   a shard that is not the last holds a multiple of 256 environments.  The log then carries the bytes of the whole-batch
+ *   call.  Every tile of the workspace belongs to some shard of the call: n is the sum over all of them.              */
+#define WEDM_ELOG_MAX_PLANES 32
+#define WEDM_ELOG_MAX_ROWS 96       /* rows of all planes together */
+enum wedm_elog_kind { WEDM_ELOG_LAST = 0, WEDM_ELOG_SUM_F32 = 1, WEDM_ELOG_SUM_F64 = 2, WEDM_ELOG_SUM_I32 = 3 };
+enum wedm_elog_flag { WEDM_ELOG_COUNT = 1, WEDM_ELOG_SCATTER = 2, WEDM_ELOG_COMMIT = 4 };
+typedef struct wedm_elog_plane {
+    const void* src;     /* [n_rows][src_stride] of elem_bytes */
+    void* dst;           /* [n_rows][capacity]: LAST of elem_bytes, SUM of 8 bytes */
+    void* acc;           /* SUM: [n_rows][num_envs] of 8 bytes; LAST: not read */
+    int64_t src_stride;  /* >= num_envs, in elements */
+    int32_t n_rows;      /* >= 1 */
+    int32_t elem_bytes;  /* LAST: 1, 4 or 8; SUM_F32 and SUM_I32: 4; SUM_F64: 8 */
+    int32_t kind;        /* enum wedm_elog_kind */
+    int32_t reserved;
+} wedm_elog_plane;
+typedef struct wedm_elog_desc {
+    wedm_elog_plane plane[WEDM_ELOG_MAX_PLANES];
+    const uint8_t* terminated;     /* [num_envs] */
+    const uint8_t* truncated;      /* [num_envs] or NULL (zeros) */
+    const uint8_t* mask;           /* [num_envs] or NULL: every environment is live */
+    int64_t* env_out;              /* [capacity] */
+    int64_t* stamp_out;            /* [capacity] */
+    int64_t* head;                 /* [2]: records appended so far; records of the last call */
+    int32_t* tile_counts;          /* [n_tiles_total] */
+    int64_t capacity;              /* >= 1 */
+    int64_t env_id_offset;
+    int64_t stamp;
+    int32_t n_planes;              /* in [1, WEDM_ELOG_MAX_PLANES]; the planes' rows together at most WEDM_ELOG_MAX_ROWS */
+    int32_t num_envs;
+    int32_t tile_offset;           /* global index of this batch's tile 0 */
+    int32_t n_tiles_total;         /* tile_offset + ceil(num_envs / 256) <= n_tiles_total <= WEDM_NORM_MAX_TILES */
+    int32_t flags;                 /* enum wedm_elog_flag */
+    int32_t reserved;
+} wedm_elog_desc;
+
+/* At most three launches on `stream` (COUNT, SCATTER, COMMIT: one each), none of which waits for another block: no spin, no
+ * cooperative launch, no atomic of any kind.  Stateless like wedm_gae: no wedm_ctx, the current device, caller-owned memory.
+ * `desc` is HOST memory, read before the call returns; everything it names is device memory.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined; num_envs < 1;
+ * capacity < 1; tile_offset < 0, n_tiles_total outside [1, WEDM_NORM_MAX_TILES] or the batch's tiles reaching past it;
+ * n_planes outside [1, WEDM_ELOG_MAX_PLANES]; a plane with n_rows < 1, a kind that is not defined, an elem_bytes that its
+ * kind does not take (a SUM plane of 1 byte among them), or a stride below num_envs; more than WEDM_ELOG_MAX_ROWS rows in
+ * all; a needed pointer NULL or not aligned to its element (terminated and tile_counts always; head for SCATTER and COMMIT;
+ * env_out, stamp_out and every plane's src and dst for SCATTER, and acc of every SUM plane); an output block (first to last
+ * byte that the call may write: dst, acc, env_out, stamp_out, head, tile_counts) overlapping an input block (src,
+ * terminated, truncated, mask).                                                                                          */
+int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

@@ -26,6 +26,7 @@ from .modules.parameters import (
 from .core.state_utils import get_gap, is_short_circuited
 from .modules.views import DielectricModule, IgnitionModule, MaterialRemovalModule, MechanicsModule, WireModule
 from .controllers import GapController, VoltageController, run_controlled
+from .episode_log import EpisodeLog
 from .normalize import Normalizer
 from .policy_head import PolicyHead
 from .ppo import PPOLoss
@@ -42,7 +43,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "Normalizer", "RolloutBuffer", "PolicyHead", "PPOLoss",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PPOLoss",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -482,6 +482,31 @@ class PpoDesc(C.Structure):
     ]
 
 
+ELOG_MAX_PLANES, ELOG_MAX_ROWS = 32, 96  # WEDM_ELOG_MAX_PLANES, WEDM_ELOG_MAX_ROWS
+ELOG_LAST, ELOG_SUM_F32, ELOG_SUM_F64, ELOG_SUM_I32 = 0, 1, 2, 3  # enum wedm_elog_kind
+ELOG_COUNT, ELOG_SCATTER, ELOG_COMMIT = 1, 2, 4  # enum wedm_elog_flag
+
+
+class ElogPlane(C.Structure):
+    """``struct wedm_elog_plane``: one source block of `wedm_episode_log`, its rows of the ring and (a sum) its accumulators."""
+
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("acc", C.c_void_p), ("src_stride", C.c_int64),
+                ("n_rows", C.c_int32), ("elem_bytes", C.c_int32), ("kind", C.c_int32), ("reserved", C.c_int32)]
+
+
+class ElogDesc(C.Structure):
+    """``struct wedm_elog_desc``: what `wedm_episode_log` reads and where it writes (strides in elements)."""
+
+    _fields_ = [
+        ("plane", ElogPlane * ELOG_MAX_PLANES),
+        ("terminated", C.c_void_p), ("truncated", C.c_void_p), ("mask", C.c_void_p),
+        ("env_out", C.c_void_p), ("stamp_out", C.c_void_p), ("head", C.c_void_p), ("tile_counts", C.c_void_p),
+        ("capacity", C.c_int64), ("env_id_offset", C.c_int64), ("stamp", C.c_int64),
+        ("n_planes", C.c_int32), ("num_envs", C.c_int32), ("tile_offset", C.c_int32), ("n_tiles_total", C.c_int32),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

@@ -107,6 +107,8 @@ def load() -> C.CDLL:
     L.wedm_policy_head.restype = C.c_int32
     L.wedm_ppo_loss.argtypes = [C.POINTER(_abi.PpoDesc), C.c_void_p]
     L.wedm_ppo_loss.restype = C.c_int32
+    L.wedm_episode_log.argtypes = [C.POINTER(_abi.ElogDesc), C.c_void_p]
+    L.wedm_episode_log.restype = C.c_int32
     L.wedm_build_id.argtypes = []
     L.wedm_build_id.restype = C.c_char_p
     _lib = L
@@ -119,7 +121,7 @@ EXPORTS = (
     "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
     "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
     "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize", "wedm_gae", "wedm_policy_head",
-    "wedm_ppo_loss",
+    "wedm_ppo_loss", "wedm_episode_log",
 )
 
 
@@ -303,6 +305,13 @@ class HipBackend:
         """`wedm_ppo_loss` on this backend's device and torch's current stream (at most four launches, no synchronisation)."""
         with self._on_device():
             rc = self._L.wedm_ppo_loss(C.byref(desc), self._stream())
+        if rc != _abi.OK:
+            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+
+    def episode_log(self, desc: "_abi.ElogDesc") -> None:
+        """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
+        with self._on_device():
+            rc = self._L.wedm_episode_log(C.byref(desc), self._stream())
         if rc != _abi.OK:
             raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
 

@@ -50,6 +50,8 @@
 //                         log-probability and entropy, their gradient; one lane per row; not a step kernel, not in the registry
 //   wedm_ppo.h            wedm_ppo_count / _main / _fold_kernel: PPO's clipped loss over a minibatch -- the row's terms, their
 //                         means by a fixed pairwise tree over the row number, the gradient; not step kernels, not in the registry
+//   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
+//                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -95,6 +97,7 @@ using namespace wedm;
 #include "wedm_gae.h"
 #include "wedm_head.h"
 #include "wedm_ppo.h"
+#include "wedm_eplog.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -1779,6 +1782,91 @@ int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
         while (256 * per < tiles) per *= 2;
         hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, per);
         if (const int32_t rc = launched("fold")) return rc;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream) {
+    const auto bad = [](const std::string& msg) {
+        g_create_error = "wedm_episode_log: " + msg;
+        return (int32_t)WEDM_ERR_BAD_ARG;
+    };
+    if (!desc) return bad("null descriptor");
+    const wedm_elog_desc& d = *desc;
+    const int32_t phases = WEDM_ELOG_COUNT | WEDM_ELOG_SCATTER | WEDM_ELOG_COMMIT;
+    if (d.flags & ~phases) return bad("undefined flag bits");
+    const bool every = !(d.flags & phases);
+    const bool count = every || (d.flags & WEDM_ELOG_COUNT), scatter = every || (d.flags & WEDM_ELOG_SCATTER);
+    const bool commit = every || (d.flags & WEDM_ELOG_COMMIT);
+    if (d.num_envs < 1) return bad("num_envs must be positive");
+    if (d.capacity < 1) return bad("capacity must be positive");
+    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
+    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
+        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
+                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
+    if (d.n_planes < 1 || d.n_planes > WEDM_ELOG_MAX_PLANES)
+        return bad("n_planes outside [1, " + std::to_string(WEDM_ELOG_MAX_PLANES) + "]");
+    // the blocks by name: first byte, bytes from there to one past the last the call may touch, element size
+    struct Block {
+        std::string name;
+        uintptr_t lo, bytes, elem;
+        bool needed;
+    };
+    std::vector<Block> in, out;
+    const uintptr_t n = (uintptr_t)d.num_envs, cap = (uintptr_t)d.capacity;
+    int64_t rows_in_all = 0;
+    for (int32_t p = 0; p < d.n_planes; ++p) {
+        const wedm_elog_plane& pl = d.plane[p];
+        const std::string who = "plane " + std::to_string(p);
+        if (pl.n_rows < 1) return bad(who + ": n_rows must be positive");
+        rows_in_all += pl.n_rows;
+        if (pl.kind < WEDM_ELOG_LAST || pl.kind > WEDM_ELOG_SUM_I32) return bad(who + ": kind is not defined");
+        const bool sum = pl.kind != WEDM_ELOG_LAST;
+        if (sum ? pl.elem_bytes != (pl.kind == WEDM_ELOG_SUM_F64 ? 8 : 4) : (pl.elem_bytes != 1 && pl.elem_bytes != 4 && pl.elem_bytes != 8))
+            return bad(who + ": elem_bytes is not one its kind takes (LAST: 1, 4 or 8; SUM_F32 and SUM_I32: 4; SUM_F64: 8)");
+        if (pl.src_stride < d.num_envs) return bad(who + ": stride smaller than num_envs");
+        const uintptr_t eb = (uintptr_t)pl.elem_bytes, r1 = (uintptr_t)(pl.n_rows - 1);
+        in.push_back({who + ".src", (uintptr_t)pl.src, (r1 * (uintptr_t)pl.src_stride + n) * eb, eb, scatter});
+        out.push_back({who + ".dst", (uintptr_t)pl.dst, (r1 * cap + cap) * (sum ? 8 : eb), sum ? 8 : eb, scatter});
+        if (sum) out.push_back({who + ".acc", (uintptr_t)pl.acc, (r1 * n + n) * 8, 8, scatter});
+    }
+    if (rows_in_all > WEDM_ELOG_MAX_ROWS) return bad("more than " + std::to_string(WEDM_ELOG_MAX_ROWS) + " rows in all");
+    in.push_back({"terminated", (uintptr_t)d.terminated, n, 1, count || scatter});
+    in.push_back({"truncated", (uintptr_t)d.truncated, n, 1, false});
+    in.push_back({"mask", (uintptr_t)d.mask, n, 1, false});
+    out.push_back({"env_out", (uintptr_t)d.env_out, cap * 8, 8, scatter});
+    out.push_back({"stamp_out", (uintptr_t)d.stamp_out, cap * 8, 8, scatter});
+    out.push_back({"head", (uintptr_t)d.head, 16, 8, scatter || commit});
+    out.push_back({"tile_counts", (uintptr_t)d.tile_counts, (uintptr_t)d.n_tiles_total * 4, 4, true});
+    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.elem != 0; };
+    for (const Block& b : in)
+        if (unusable(b)) return bad(b.name + " is null or not aligned to its element");
+    for (const Block& b : out)
+        if (unusable(b)) return bad(b.name + " is null or not aligned to its element");
+    for (const Block& o : out) {
+        for (const Block& i : in) {
+            if (!o.lo || !i.lo) continue;
+            if (o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(o.name + " overlaps " + i.name);
+        }
+    }
+    const auto launched = [](const char* what) {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return (int32_t)WEDM_OK;
+        g_create_error = std::string("wedm_episode_log: ") + what + " launch: " + hipGetErrorString(e);
+        return (int32_t)WEDM_ERR_HIP;
+    };
+    const hipStream_t s = (hipStream_t)stream;
+    if (count) {
+        hipLaunchKernelGGL(wedm_elog_count_kernel, dim3((uint32_t)tiles), dim3(WEDM_NORM_TILE), 0, s, d);
+        if (const int32_t rc = launched("count")) return rc;
+    }
+    if (scatter) {
+        hipLaunchKernelGGL(wedm_elog_scatter_kernel, dim3((uint32_t)tiles, (uint32_t)d.n_planes), dim3(WEDM_NORM_TILE), 0, s, d);
+        if (const int32_t rc = launched("scatter")) return rc;
+    }
+    if (commit) {
+        hipLaunchKernelGGL(wedm_elog_commit_kernel, dim3(1), dim3(64), 0, s, d);
+        if (const int32_t rc = launched("commit")) return rc;
     }
     return WEDM_OK;
 }

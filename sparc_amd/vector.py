@@ -96,7 +96,7 @@ class WireEDMVectorEnv:
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
                  reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
                  wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None,
-                 episode_sampler=None, normalizer=None):
+                 episode_sampler=None, normalizer=None, episode_log=None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -132,7 +132,12 @@ class WireEDMVectorEnv:
         step (device tensors, valid until the next step), ``info["raw_observation"]`` / ``info["raw_reward"]`` the values
         before normalisation.  The normalised tensors are the normaliser's cached outputs: valid until the next call.
         Environments that are frozen during a step (done, with ``autoreset=False``) take no part in the statistics and keep
-        their rows; a masked `reset` zeroes the rows of the environments it resets."""
+        their rows; a masked `reset` zeroes the rows of the environments it resets.
+        ``episode_log``: a `sparc_amd.episode_log.EpisodeLog` -- `step()` ends with one `wedm_episode_log` call (at most three
+        more launches, no host synchronisation, no allocation after binding) that appends a record for every environment
+        whose episode ended in the step, in the order of the global environment index, and adds the step to the per-episode
+        sums; ``episode_log.read()`` hands the records out when the user chooses.  A frozen environment (done, with
+        ``autoreset=False``) is logged once; `reset` zeroes the sums of the environments it resets and logs nothing."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
@@ -180,6 +185,9 @@ class WireEDMVectorEnv:
         if normalizer is not None:
             normalizer.bind(self.obs_names, self.num_envs, env.device, getattr(env, "_backend", None))
         self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
+        self.episode_log = episode_log
+        if episode_log is not None:
+            episode_log.bind(self)
 
     def reset(self, *, seed: Optional[int] = None, options: Optional[Dict[str, Any]] = None):
         if self._episode_sampler is not None:
@@ -196,6 +204,11 @@ class WireEDMVectorEnv:
             self._apply_sampler(mask)
         obs, info = self.env.reset(seed=seed, options=options)
         self._need_reset.zero_()
+        if self.episode_log is not None:
+            mask = (options or {}).get("mask")
+            if mask is not None:
+                mask = torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
+            self.episode_log.reset_sums(mask)
         if self.normalizer is not None:
             mask = (options or {}).get("mask")
             if mask is not None:
@@ -251,8 +264,8 @@ class WireEDMVectorEnv:
             elif bool(self._need_reset.any().item()):
                 self.env.reset(options={"mask": self._need_reset})  # same key, next episode stream
             self.episode_count += self._need_reset.to(torch.int64)
-        # environments this step leaves frozen take no part in the normaliser's statistics
-        live = None if self.normalizer is None or self.autoreset else ~self._need_reset
+        # environments this step leaves frozen take no part in the normaliser's statistics or in the episode log
+        live = None if (self.normalizer is None and self.episode_log is None) or self.autoreset else ~self._need_reset
         prev = {"workpiece_position": self.env.state.workpiece_position.clone()} if self._reward_fn is not None else None
         if prev is not None and self._in_kernel_reset:  # what the kernel's reset will make of the marked environments
             prev["workpiece_position"] = torch.where(self._need_reset, torch.full_like(
@@ -278,7 +291,12 @@ class WireEDMVectorEnv:
             info["episode_stats"] = norm.episode_stats
             info["raw_observation"] = self._raw(obs, planes)
             info["raw_reward"] = reward
+            if self.episode_log is not None:
+                self.episode_log.append(reward, terminated, truncated, mask=live)
             return out, (scaled if norm.reward else reward), terminated, truncated, info
+        if self.episode_log is not None:
+            reward = reward.contiguous()
+            self.episode_log.append(reward, terminated, truncated, mask=live)
         return self._observation(obs), reward, terminated, truncated, info
 
     def fork(self, src, dst) -> None:
@@ -291,6 +309,8 @@ class WireEDMVectorEnv:
         fork_rows(self._need_reset, src, dst)
         if self.normalizer is not None:
             self.normalizer.fork(src, dst)
+        if self.episode_log is not None:
+            self.episode_log.fork(src, dst)
 
     # ---- checkpoints ----
     def _reward_kind(self) -> str:
@@ -312,7 +332,7 @@ class WireEDMVectorEnv:
         `step()` (``need_reset``) and their ``episode_count``, the settings that change what a step does (batch size,
         ``autoreset``, ``max_episode_steps``, ``wire_profile_bins``, ``obs_names``, the kind of reward -- ``"kernel"``,
         ``"progress"`` or ``"callable"`` -- and the kinds of samplers present), and under ``"env"``, ``"episode_sampler"`` and
-        ``"normalizer"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
+        ``"normalizer"`` and ``"episode_log"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
         tuples and lists only: loads with ``weights_only=True``.
         Not in it: ``param_sampler`` / ``material_sampler`` / ``geometry_sampler`` draw from a ``torch.Generator`` the caller
         owns, and a callable reward may hold state of its own -- the caller saves those (``generator.get_state()``)."""
@@ -324,6 +344,8 @@ class WireEDMVectorEnv:
             sd["episode_sampler"] = self._episode_sampler.state_dict()
         if self.normalizer is not None:
             sd["normalizer"] = self.normalizer.state_dict()
+        if self.episode_log is not None:
+            sd["episode_log"] = self.episode_log.state_dict()
         return sd
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
@@ -341,7 +363,8 @@ class WireEDMVectorEnv:
                 there = tuple(there)
             if there != here:
                 raise ValueError(f"the checkpoint was taken with {key}={sd[key]!r}, this adapter has {key}={here!r}")
-        for key, mine_has in (("episode_sampler", self._episode_sampler is not None), ("normalizer", self.normalizer is not None)):
+        for key, mine_has in (("episode_sampler", self._episode_sampler is not None), ("normalizer", self.normalizer is not None),
+                              ("episode_log", self.episode_log is not None)):
             if (key in sd) != mine_has:
                 raise ValueError(f"the checkpoint was taken {'with' if key in sd else 'without'} a {key}, this adapter has "
                                  f"{'one' if mine_has else 'none'}")
@@ -362,11 +385,15 @@ class WireEDMVectorEnv:
                 raise ValueError(f"the state dict normalises the columns {tuple(nsd['columns'])}, this Normalizer {norm.columns}")
             if int(nsd["num_envs"]) != norm.num_envs:
                 raise ValueError(f"the state dict holds {nsd['num_envs']} environments, this Normalizer {norm.num_envs}")
+        if self.episode_log is not None:
+            self.episode_log.check_state_dict(sd["episode_log"])
         self.env.load_state_dict(sd["env"])  # (raises before it writes)
         if s is not None:
             s.load_state_dict(sd["episode_sampler"])
         if norm is not None:
             norm.load_state_dict(sd["normalizer"])
+        if self.episode_log is not None:
+            self.episode_log.load_state_dict(sd["episode_log"])
         self._need_reset = sd["need_reset"].to(device=self.env.device, dtype=torch.bool).clone()
         self.episode_count.copy_(sd["episode_count"])
 
