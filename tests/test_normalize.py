@@ -13,6 +13,7 @@ import torch
 
 from sparc_amd import Normalizer, WireEDMVectorEnv, _abi
 from sparc_amd.normalize import APPLY, REDUCE, ROW_NAMES, ROWS, STEP, UPDATE, device_normalize, fresh_stats, torch_normalize
+from tests._gae_common import is_subnormal
 from tests._normalize_common import columns, same_bits
 from tests._snapshot_common import assert_same, everything, make
 
@@ -212,6 +213,30 @@ def test_run_twice_gives_the_same_bits():
         torch.cuda.synchronize()
         got.append({name: b.t.clone() for name, b in p.blocks().items()})
     assert all(same_bits(got[0][name], got[1][name]) for name in got[0])
+
+
+def test_float32_subnormals_are_kept_on_input_and_output():
+    """Three columns of its own planes, 300 environments: 1e-41 x N(0,1) (float32 subnormals on input, and around the
+    smallest normal on output); 1e-33 x N(0,1) on running statistics of variance 1e12, so that the standardised output, 1e-39,
+    is a float32 subnormal made from normal inputs; and a unit normal.  The definition (NumPy, which keeps subnormals on
+    load and on the float64 -> float32 store) and the call agree on every byte: statistics, partials, outputs and rows."""
+    p = Problem(300, 3, seed=46, use_skip=False, clips=(math.inf, math.inf))
+    rng = np.random.default_rng(460)
+    x = np.stack([1e-41 * rng.normal(size=300), 1e-33 * rng.normal(size=300), rng.normal(size=300)]).astype(np.float32)
+    p.planes_h[0][:, :300] = x
+    p.planes[0].t.copy_(torch.from_numpy(p.planes_h[0]))
+    p.stats_h[:, 1] = [100.0, 0.0, 100.0 * 1e12]
+    p.stats[0].t.copy_(torch.from_numpy(p.stats_h))
+    assert is_subnormal(x[0]).all() and not is_subnormal(x[1:]).any()
+    p.call(UPDATE | STEP)
+    p.expect(UPDATE | STEP)
+    blocks = p.blocks()
+    p.flip()
+    assert p.differences() == []
+    assert [name for name, b in blocks.items() if not b.bands_intact()] == []
+    out = is_subnormal(p.obs_h)
+    assert out[:, 0].sum() >= 50 and (~out[:, 0] & (p.obs_h[:, 0] != 0.0)).sum() >= 50, "column 0: outputs on either side of the smallest normal"
+    assert out[:, 1].sum() >= 250 and not out[:, 2].any() and p.stats_h[1, 0] != 0.0 and abs(p.stats_h[1, 0]) < 1e-41
 
 
 # ------------------------------------------------------------------------------------------------ shards in turn

@@ -1,8 +1,10 @@
 """The policy action head on the MI355X (sparc_amd/csrc/wedm_head.h, sparc_amd/policy_head.py):
 `wedm_policy_head` against `policy_head_definition` on every byte of everything it writes -- the action leaves, the mode, the
 stored pre-squash values and mode index, log-probability, entropy and the gradient -- at the wave and block edges, through
-LDS and directly, with its blocks in guard bands; a draw evaluated again; shards against the whole batch; hostile rows; and
-`PolicyHead` through `WireEDMVectorEnv` and `RolloutBuffer`, without a host synchronisation or an allocation per step."""
+LDS and directly, with its blocks in guard bands; every mode count from 1 to 19; a wide regime of parameters and stored
+values (zero probabilities, a saturated tanh, infinities, NaN, subnormals); a draw evaluated again; shards against the
+whole batch; hostile rows; and `PolicyHead` through `WireEDMVectorEnv` and `RolloutBuffer`, without a host synchronisation
+or an allocation per step."""
 from __future__ import annotations
 
 import gc
@@ -13,8 +15,10 @@ import torch
 
 from sparc_amd import PolicyHead, RolloutBuffer, WireEDMVectorEnv, _abi
 from sparc_amd.policy_head import BACKWARD, EVALUATE, SAMPLE, device_policy_head, policy_head_definition
+from tests._gae_common import is_subnormal
 from tests._normalize_common import same_bits
-from tests._policy_head_common import CONSTS, MODES, desc_consts, make_hostile, random_params, random_stored
+from tests._policy_head_common import (ALL_M, CONSTS, MODES, desc_consts, make_hostile, random_params, random_stored, wide_params,
+                                       wide_stored, zero_probability_rows)
 from tests._snapshot_common import make
 from tests.test_rollout import DEV, FILL, Banded, poisoned
 
@@ -29,14 +33,18 @@ class Problem:
     pad_out]``), each between guard bands.  `call` runs `wedm_policy_head`; `differences` names every block -- outputs, and
     inputs, which nothing may change -- that is not what ``want`` (default: what it was) says, on every byte."""
 
-    def __init__(self, rows, M, seed, pad_in=0, pad_out=0, hostile=False, mode_index=None):
+    def __init__(self, rows, M, seed, pad_in=0, pad_out=0, hostile=False, mode_index=None, wide=False):
         self.rows, self.M, self.P, self.si, self.so = rows, M, 8 + M, 8 + M + pad_in, 8 + M + pad_out
         rng = np.random.default_rng(seed)
         h = self.host = {}
-        h["params"] = random_params(rng, rows, M, pad_in)
-        if hostile:
-            h["params"] = make_hostile(rng, h["params"], M)
-        h["u"], h["mode_index"] = random_stored(rng, np.nan_to_num(h["params"], posinf=1.0, neginf=-1.0).clip(-3, 3), M)
+        if wide:   # the wide regime's rows, and stored values that saturate the tanh, are huge, infinite, NaN or subnormal
+            h["params"] = wide_params(rng, rows, M, pad_in)
+            h["u"], h["mode_index"] = wide_stored(rng, h["params"], M)
+        else:
+            h["params"] = random_params(rng, rows, M, pad_in)
+            if hostile:
+                h["params"] = make_hostile(rng, h["params"], M)
+            h["u"], h["mode_index"] = random_stored(rng, np.nan_to_num(h["params"], posinf=1.0, neginf=-1.0).clip(-3, 3), M)
         if mode_index is not None:
             h["mode_index"] = np.resize(np.asarray(mode_index, dtype=np.int32), rows)
         h["g_log_prob"], h["g_entropy"] = rng.normal(size=rows).astype(np.float32), rng.normal(size=rows).astype(np.float32)
@@ -51,6 +59,11 @@ class Problem:
         for name in names:
             self.host[name].view(np.uint8)[...] = FILL
             self.blocks[name].t.copy_(torch.from_numpy(self.host[name]))
+
+    def put(self, name, a):
+        """Other contents for an input block, on the host and the device."""
+        self.host[name] = np.ascontiguousarray(a, dtype=self.host[name].dtype)
+        self.blocks[name].t.copy_(torch.from_numpy(self.host[name]))
 
     def desc(self, op, lo=0, count=None, g_entropy=True, **kw):
         """The descriptor of rows [lo, lo + count): a shard is the same blocks entered ``lo`` rows further on."""
@@ -143,6 +156,100 @@ def test_params_and_grad_params_off_16_bytes_take_the_direct_path():
     p.call(EVALUATE, lo=1)
     p.call(BACKWARD, lo=1)
     assert p.differences(want) == []
+
+
+# ------------------------------------------------------------------------------------------------ 6b. every mode count
+SAMPLE_KW = dict(seed=0x123456789ABCDEF, t=2 ** 32 + 5, env_id_offset=2 ** 32 - 7)
+
+
+@pytest.mark.parametrize("M", ALL_M)
+def test_every_mode_count_equals_the_definition_on_every_byte(M):
+    """Every M the header promises (P = 9..27: odd and even LDS rows, and P divisible by 4 at M = 4, 8, 12, 16, where a
+    float4 never straddles a row) by a lone row, a partial tail block and a full block followed by a one-row block (rows 1,
+    255, 257) by param_stride P (staged), P + 1 and P + 3 (direct) and, for BACKWARD, the same three grad_strides: EVALUATE,
+    SAMPLE drawn and DETERMINISTIC, BACKWARD with g_entropy given and NULL, bands, 0xA5 outputs and NaN padding as in the
+    test above.  The mode lists are `MODES[M]`, in which no entry is its index or its index + 1.  Over the sweep every
+    index in [0, M) is drawn and every listed mode is handed out: at M = 19 that is entries 9..18 of the kept array, of
+    the select chain and of ``modes[19]``."""
+    drawn, handed_out = set(), set()
+    for rows in (1, 255, 257):
+        for pad_in in (0, 1, 3):
+            p = Problem(rows, M, seed=5000 * rows + 10 * M + pad_in, pad_in=pad_in)
+            want = p.expect(p.definition(EVALUATE))
+            p.call(EVALUATE)
+            assert p.differences(want) == [], ("EVALUATE", rows, M, pad_in)
+            for deterministic in (True, False):
+                p.poison(*SAMPLED)
+                want = p.expect(p.definition(SAMPLE, deterministic=deterministic, **SAMPLE_KW))
+                p.call(SAMPLE, flags=_abi.HEAD_DETERMINISTIC if deterministic else 0, **SAMPLE_KW)
+                assert p.differences(want) == [], ("SAMPLE", rows, M, pad_in, deterministic)
+                p.adopt(want)
+            drawn |= set(want["mode_index"].tolist())
+            handed_out |= set(want["current_mode"].tolist())
+            for pad_out in (0, 1, 3):
+                q = Problem(rows, M, seed=6000 * rows + 10 * M + pad_in, pad_in=pad_in, pad_out=pad_out)
+                for g_entropy in (True, False):
+                    q.poison("grad_params")
+                    want = q.expect(q.definition(BACKWARD, g_entropy=q.host["g_entropy"] if g_entropy else None))
+                    q.call(BACKWARD, g_entropy=g_entropy)
+                    assert q.differences(want) == [], ("BACKWARD", rows, M, pad_in, pad_out, g_entropy)
+    assert drawn == set(range(M)), "every mode index is drawn"
+    assert handed_out == set(MODES[M]), "every listed mode is handed out"
+
+
+@pytest.mark.parametrize("M", ALL_M)
+def test_deterministic_takes_the_last_logit_when_it_is_the_largest_and_the_first_of_a_tie(M):
+    """257 rows, staged and direct: the largest logit planted at index M - 1 in the even rows, and in the odd rows an exact
+    tie between index 0 and index M - 1, where the first wins."""
+    for pad_in in (0, 3):
+        p = Problem(257, M, seed=7000 + 10 * M + pad_in, pad_in=pad_in)
+        params = p.host["params"].copy()
+        params[:, 8 + M - 1] = 6.0   # (the others lie in [-5, 5])
+        params[1::2, 8] = 6.0
+        p.put("params", params)
+        p.poison(*SAMPLED)
+        want = p.expect(p.definition(SAMPLE, deterministic=True))
+        k = np.where(np.arange(257) % 2 == 1, 0, M - 1).astype(np.int32)
+        assert np.array_equal(want["mode_index"], k) and np.array_equal(want["current_mode"], np.asarray(MODES[M], dtype=np.int32)[k])
+        p.call(SAMPLE, flags=_abi.HEAD_DETERMINISTIC)
+        assert p.differences(want) == [], (M, pad_in)
+
+
+# ------------------------------------------------------------------------------------------------ 6c. the wide regime
+@pytest.mark.parametrize("M", [3, 8, 19])
+def test_the_wide_regime_equals_the_definition_on_every_byte(M):
+    """257 rows of `wide_params` (log_std in [-6, 2]; logit spreads of up to 1588, so that w_j = exp(l_j - m) is exactly 0
+    and p_j (log p_j + H) is 0 times a large finite number) with a stored ``u`` of `wide_stored`: draws at the parameters,
+    +-20 and +-400 (e underflows, the action clamps to a bound), +-1e30, +-inf, NaN and float32 subnormals.  Every output
+    equals the definition's on every byte (a NaN is 0x7FC00000 in both); what SAMPLE emits stays a listed mode with leaves
+    within bounds."""
+    rows = 257
+    for pad in (0, 3):
+        p = Problem(rows, M, seed=8000 + 10 * M + pad, pad_in=pad, pad_out=pad, wide=True)
+        zero_p = zero_probability_rows(p.host["params"], M)
+        assert zero_p.sum() >= 5 and np.isnan(p.host["u"]).any() and np.isinf(p.host["u"]).any() and is_subnormal(p.host["u"]).any()
+        want = p.expect(p.definition(EVALUATE))
+        want.update(p.expect(p.definition(BACKWARD, g_entropy=p.host["g_entropy"])))
+        p.call(EVALUATE)
+        p.call(BACKWARD)
+        assert p.differences(want) == [], (M, pad)
+        lp, grad = want["log_prob"], want["grad_params"][:, : p.P]
+        assert np.isnan(lp).any() and np.isfinite(lp).any() and np.isfinite(lp[zero_p]).any()
+        assert np.isnan(grad).any() and np.isfinite(grad[zero_p]).all(1).any() and np.isfinite(want["entropy"]).all()
+        p.adopt(want)
+        for deterministic in (False, True):
+            p.poison(*SAMPLED)
+            want = p.expect(p.definition(SAMPLE, seed=92, t=1, deterministic=deterministic))
+            p.call(SAMPLE, seed=92, t=1, flags=_abi.HEAD_DETERMINISTIC if deterministic else 0)
+            assert p.differences(want) == [], (M, pad, deterministic)
+            torch.cuda.synchronize()
+            k, mode = p.blocks["mode_index"].t.cpu().numpy(), p.blocks["current_mode"].t.cpu().numpy()
+            assert k.min() >= 0 and k.max() < M and np.array_equal(mode, np.asarray(MODES[M], dtype=np.int32)[k])
+            for i, name in enumerate(LEAF_BLOCKS):
+                leaf = p.blocks[name].t.cpu().numpy()
+                assert np.all(leaf >= CONSTS["lo"][i]) and np.all(leaf <= CONSTS["hi"][i]), name
+            assert np.isfinite(want["log_prob"]).all()
+            p.adopt(want)
 
 
 # ------------------------------------------------------------------------------------------------ 7. a draw, evaluated again

@@ -1,8 +1,9 @@
 """PPO's loss on the MI355X (sparc_amd/csrc/wedm_ppo.h, sparc_amd/ppo.py): `wedm_ppo_loss` against
 `ppo_loss_definition` on every byte of everything it may write -- the gradient blocks with their padding columns, the tile
 partials, the statistics, the count words, each between guard bands -- at the wave and block edges, through LDS and
-directly, with and without a mask, an index, value clipping and the gradient; the phases apart; hostile rows; `PPOLoss`
-through `WireEDMVectorEnv`, `PolicyHead` and `RolloutBuffer` without a host synchronisation or an allocation; and the call
+directly, with and without a mask, an index, value clipping and the gradient; every mode count from 1 to 19; a wide
+regime (ratios of 0 and +inf, clip = 0, advantages and returns from subnormal to 1e30); the phases apart; hostile rows;
+`PPOLoss` through `WireEDMVectorEnv`, `PolicyHead` and `RolloutBuffer` without a host synchronisation or an allocation; and the call
 on a side stream behind a gate."""
 from __future__ import annotations
 
@@ -14,9 +15,10 @@ import torch
 
 from sparc_amd import PolicyHead, PPOLoss, RolloutBuffer, WireEDMVectorEnv, _abi
 from sparc_amd.ppo import device_ppo_loss, ppo_loss_definition
+from tests._gae_common import is_subnormal
 from tests._normalize_common import same_bits
-from tests._policy_head_common import HI, LO, LOG_SPAN, make_hostile, random_params
-from tests._ppo_common import CLIP_VALUE, COEFS, STORED, definition_kw, draw_minibatch
+from tests._policy_head_common import ALL_M, HI, LO, LOG_SPAN, make_hostile, random_params, zero_probability_rows
+from tests._ppo_common import CLIP_VALUE, COEFS, STORED, definition_kw, draw_minibatch, draw_wide_minibatch
 from tests._snapshot_common import make
 from tests._stream_gate import Gate, check_control, gated, seconds_on
 from tests.test_rollout import DEV, FILL, Banded, poisoned
@@ -34,12 +36,13 @@ class Problem:
     ``index``: None, "perm" (a permutation of the rows) or "wild" (entries of the whole store with repeats, and some outside
     it); ``valid``: None, "some" or "none" (all zero)."""
 
-    def __init__(self, rows, M, seed, pad_in=0, pad_out=0, hostile=False):
+    def __init__(self, rows, M, seed, pad_in=0, pad_out=0, hostile=False, wide=None):
         self.rows, self.M, self.P, self.si, self.so = rows, M, 8 + M, 8 + M + pad_in, 8 + M + pad_out
         self.tiles = -(-rows // 256)
         rng = self.rng = np.random.default_rng(seed)
         n = rows + EXTRA
-        h = self.host = draw_minibatch(rng, n, M, pad_in)
+        # ``wide``: None, or the keywords of `draw_wide_minibatch`
+        h = self.host = draw_minibatch(rng, n, M, pad_in) if wide is None else draw_wide_minibatch(rng, n, M, pad_in, **wide)
         h["params"], h["value"] = h["params"][:rows].copy(), h["value"][:rows].copy()
         if hostile:
             bad = np.array([np.nan, np.inf, -np.inf, 1e30, -1e30], dtype=np.float32)
@@ -144,6 +147,58 @@ def test_the_call_equals_the_definition_on_every_byte(rows):
                 for clip_value in (False, True):
                     for variant in VARIANTS:
                         p.check((rows, M, pad_in, pad_out), clip_value=clip_value, **variant)
+
+
+@pytest.mark.parametrize("M", ALL_M)
+def test_every_mode_count_equals_the_definition_on_every_byte(M):
+    """Every M the header promises (`MODES[M]`; P = 9..27, P divisible by 4 among them) at a lone row and at a full block
+    followed by a one-row block (rows 1 and 257) by the staged and the direct path of params and of grad_params (stride P
+    and P + 3, independently), with a mask and an index (repeats, entries outside the store) and without, with value
+    clipping and without: ``stats``, ``partials``, ``grad_params``, ``grad_value``, ``count``, the bands and the inputs."""
+    for rows in (1, 257):
+        for pad_in in (0, 3):
+            for pad_out in (0, 3):
+                p = Problem(rows, M, seed=3000 * rows + 100 * M + 10 * pad_in + pad_out, pad_in=pad_in, pad_out=pad_out)
+                for clip_value in (False, True):
+                    for variant in (dict(), dict(valid="some", index="wild")):
+                        want = p.check((rows, M, pad_in, pad_out), clip_value=clip_value, **variant)
+                if rows > 1:
+                    assert np.isfinite(want["stats"]).all() and want["stats"][0] > 100 and want["stats"][1] > 0
+
+
+WIDE = {"finite-ratios": dict(hostile_u=False, move=300.0), "ratios-0-and-inf": dict(hostile_u=False, move=800.0),
+        "hostile-u": dict(hostile_u=True, move=800.0)}
+
+
+@pytest.mark.parametrize("regime", list(WIDE))
+@pytest.mark.parametrize("M", [3, 8, 19])
+def test_the_wide_regime_equals_the_definition_on_every_byte(M, regime):
+    """257 rows of `draw_wide_minibatch`: `wide_params` (w_j exactly 0), advantages and returns of the kinds normal / +-0 /
+    tiny 1e-30 / huge 1e30 / subnormal 1e-41, ``clip`` in {0.2, 0}, and ``old_log_prob`` moved in every fourth row by up to
+    +-300 (ratios from 1e-130 to 1e130: every sum stays a number, and the statistics are compared as numbers) or by up to
+    +-800 (ratios of exactly 0 and +inf; +inf times an advantage of 0 is a NaN in the policy loss, times a negative one
+    +inf); and, in the third regime, a stored ``u`` that saturates the tanh, is +-1e30, +-inf, NaN or a subnormal.  Every
+    byte equals the definition's (a NaN is 0x7FC00000 / 0x7FF8000000000000 in both)."""
+    rows = 257
+    for pad in (0, 3):
+        p = Problem(rows, M, seed=4000 + 100 * M + 10 * pad + list(WIDE).index(regime), pad_in=pad, pad_out=pad, wide=WIDE[regime])
+        h = p.host
+        assert zero_probability_rows(h["params"], M).any()
+        assert all(is_subnormal(h[k][:rows]).sum() >= 10 and (h[k][:rows] == 0.0).sum() >= 10 and (np.abs(h[k][:rows]) > 1e28).sum() >= 10
+                   for k in ("advantage", "returns"))
+        for clip in (0.2, 0.0):
+            for variant in (dict(), dict(valid="some", index="wild", clip_value=True)):
+                p.check(("wide", M, pad, clip), clip=clip, **variant)
+                out = p.definition(clip=clip, **variant)
+                live, gp, stats = out["live"], out["grad_params"], out["stats"]
+                assert np.isfinite(gp[live]).all(1).any() and (gp[live] != 0.0).any() and np.isfinite(stats[[4, 5]]).all()
+                if regime == "finite-ratios" and not variant:   # (a wild index pairs a row with another row's stored entry)
+                    assert np.isfinite(stats).all() and np.isfinite(out["partials"]).all()
+                    assert clip != 0.0 or stats[7] >= 1.0 - 1e-15, "clip = 0: every ratio but an exact 1 lies outside"
+                if regime != "finite-ratios" and not variant:
+                    assert (live & (out["ratio"] == 0.0)).any() and (live & np.isposinf(out["ratio"])).any()
+                if regime == "hostile-u":
+                    assert np.isnan(gp[live]).any() and np.isnan(stats[2:]).any()
 
 
 def test_bases_off_16_bytes_take_the_direct_path_and_aligned_ones_the_staged():

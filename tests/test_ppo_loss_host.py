@@ -17,8 +17,9 @@ from sparc_amd import PolicyHead, PPOLoss, RolloutBuffer, WireEDMVectorEnv, _abi
 from sparc_amd.policy_head import BACKWARD, SAMPLE, policy_head_definition
 from sparc_amd.ppo import MAX_ROWS, STAT_NAMES, PPOStats, pairwise_sum, ppo_loss_definition
 from tests._normalize_common import same_bits
-from tests._policy_head_common import CONSTS, HI, LO, LOG_SPAN, MODES, random_params
-from tests._ppo_common import CLIP, CLIP_VALUE, ENT_COEF, STORED, VF_COEF, definition_kw, draw_minibatch
+from tests._policy_head_common import ALL_M, CONSTS, HI, LO, LOG_SPAN, MODES, random_params, zero_probability_rows
+from tests._ppo_common import (CLIP, CLIP_VALUE, ENT_COEF, STORED, VALUE_KINDS, VF_COEF, definition_kw, draw_minibatch,
+                                draw_wide_minibatch)
 from tests._snapshot_common import make
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -229,19 +230,26 @@ SEEN = dict(loss=9.44e-10, policy_loss=3.64e-09, value_loss=ULP, entropy=ULP, ap
             grad_params=8.65e-07, grad_value=ULP)
 
 
-@pytest.mark.parametrize("M", [1, 2, 9])
-@pytest.mark.parametrize("clip_value", [False, True])
-def test_the_definition_against_a_float64_torch_composition(M, clip_value):
-    rows = 4096
-    mb = drawn_without_ties(M, 500 + M)
-    ref = torch_reference(mb, M, clip_value)
-    count, tie = branches(mb, ref)
-    assert not tie.any()
-    assert all(c >= 100 for c in count.values()), count
+# the same in the wide regime (`draw_wide_minibatch` without hostile u, |u| < 9, old_log_prob moved by up to +-300 in every
+# fourth row -- ratios from 1e-130 to 1e130, all finite in float64, which a reference needs --, advantages and returns from
+# +-0 and 1e-41 to 1e30), largest over M in WIDE_M with and without value clipping; the bounds are 8 x these.  What is seen
+# is again the float32 rounding of lp, now of a log_prob of up to 1600 in magnitude (half an ulp there is 6e-5): it reaches
+# the ratio undamped, and a ratio of 1e130 times an advantage of 1e30 is the scale's largest summand itself.
+# Seen: loss and policy_loss 1.00e-6 (M = 3), approx_kl 4.67e-7 (M = 4), grad_params 6.04e-5 (M = 8); value_loss 2.19e-16,
+# entropy 8.8e-17, clip_fraction 0, grad_value 0, which do not pass through lp: one unit in the last place, as above.
+WIDE_SEEN = dict(loss=1.00e-06, policy_loss=1.00e-06, value_loss=ULP, entropy=ULP, approx_kl=4.67e-07, clip_fraction=ULP,
+                 grad_params=6.04e-05, grad_value=ULP)
+WIDE_M = (2, 3, 4, 8, 12, 16, 19)
+
+
+def against_the_torch_composition(M, clip_value, mb, ref):
+    """The largest discrepancy of every statistic and of the two gradients between the definition and the reference ``ref``
+    on the minibatch ``mb``, relative to 1 + the sum of the absolute summands."""
     out = ppo_loss_definition(**mb, **definition_kw(M, clip_value))
     assert np.array_equal(out["live"], mb["valid"] != 0) and out["stats"][0] == ref["stats"][0] and out["stats"][1] == 0
     side = lambda r: np.where(r < 1.0 - CLIP, 0, np.where(r > 1.0 + CLIP, 2, 1))   # noqa: E731
     assert np.array_equal(side(out["ratio"]), side(ref["ratio"])), "no row changes sides through the rounding of lp"
+    assert np.isfinite(out["stats"]).all() and np.isfinite(ref["stats"]).all() and np.isfinite(ref["grad_params"]).all()
     # the scales: 1 + the absolute summands of each quantity
     w = (mb["valid"] != 0).astype(np.float64)
     n = w.sum()
@@ -266,10 +274,51 @@ def test_the_definition_against_a_float64_torch_composition(M, clip_value):
     worst["grad_params"] = (n * np.abs(out["grad_params64"] - ref["grad_params"]) / scale_gp).max()
     worst["grad_value"] = (n * np.abs(out["grad_value64"] - ref["grad_value"]) / scale_gv).max()
     print(M, clip_value, {k: float(f"{x:.3g}") for k, x in worst.items()})
+    assert np.array_equal(out["grad_params"][~out["live"]], np.zeros((int((~out["live"]).sum()), 8 + M), np.float32))
+    with np.errstate(over="ignore"):   # (the wide regime: a gradient of 1e160 is +-inf in float32, in both)
+        assert same_bits(out["grad_params"], out["grad_params64"].astype(np.float32)) and same_bits(out["grad_value"], out["grad_value64"].astype(np.float32))
+    return worst
+
+
+@pytest.mark.parametrize("M", ALL_M)
+@pytest.mark.parametrize("clip_value", [False, True])
+def test_the_definition_against_a_float64_torch_composition(M, clip_value):
+    mb = drawn_without_ties(M, 500 + M)
+    ref = torch_reference(mb, M, clip_value)
+    count, tie = branches(mb, ref)
+    assert not tie.any()
+    assert all(c >= 100 for c in count.values()), count
+    worst = against_the_torch_composition(M, clip_value, mb, ref)
     for name, seen in SEEN.items():
         assert worst[name] <= 8 * seen, (name, worst[name])
-    assert np.array_equal(out["grad_params"][~out["live"]], np.zeros((int((~out["live"]).sum()), 8 + M), np.float32))
-    assert same_bits(out["grad_params"], out["grad_params64"].astype(np.float32)) and same_bits(out["grad_value"], out["grad_value64"].astype(np.float32))
+
+
+@pytest.mark.parametrize("M", WIDE_M)
+@pytest.mark.parametrize("clip_value", [False, True])
+def test_the_definition_in_the_wide_regime_against_a_float64_torch_composition(M, clip_value):
+    """Rows within the float32 rounding of lp of a clip bound (by the reference alone: |ratio - bound| <= 2^-22 (1 + |lp|))
+    get the reference's log-probability as ``old_log_prob`` before either side runs: a ratio of 1, inside the range.  Rows
+    that the value clip moves and whose two losses tie (a return of 1e30 absorbs ``value`` and ``old_value`` alike, so
+    ``vlc == vl``: the header takes the unclipped branch, autograd's ``maximum`` halves the gradient between the two) get
+    ``value`` as ``old_value``: inside the range, where both branches are one function -- the tie rule of `branches`."""
+    rows = 4096
+    mb = draw_wide_minibatch(np.random.default_rng(600 + M), rows, M, hostile_u=False, move=300.0, u_limit=9.0)
+    ref = torch_reference(mb, M, clip_value)
+    near = np.minimum(np.abs(ref["ratio"] - (1.0 - CLIP)), np.abs(ref["ratio"] - (1.0 + CLIP))) <= 2.0 ** -22 * (1.0 + np.abs(ref["lp"]))
+    mb["old_log_prob"] = np.where(near, ref["lp"].astype(np.float32), mb["old_log_prob"])
+    v, ov, R = (mb[k].astype(np.float64) for k in ("value", "old_value", "returns"))
+    tied = (np.abs(v - ov) > CLIP_VALUE) & ((ov + np.clip(v - ov, -CLIP_VALUE, CLIP_VALUE) - R) ** 2 == (v - R) ** 2)
+    assert tied.sum() >= 100
+    mb["old_value"] = np.where(tied, mb["value"], mb["old_value"])
+    ref = torch_reference(mb, M, clip_value)
+    live = mb["valid"] != 0
+    assert (live & (ref["ratio"] < 1e-100)).sum() >= 50 and (live & (ref["ratio"] > 1e100)).sum() >= 50
+    assert zero_probability_rows(mb["params"], M).sum() >= 50
+    kinds = np.arange(rows) % len(VALUE_KINDS)
+    assert all((live & (kinds == i)).sum() >= 100 for i in range(len(VALUE_KINDS)))
+    worst = against_the_torch_composition(M, clip_value, mb, ref)
+    for name, seen in WIDE_SEEN.items():
+        assert worst[name] <= 8 * seen, (name, worst[name])
 
 
 # ------------------------------------------------------------------------------------------------ 3. hand-worked cases

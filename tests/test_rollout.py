@@ -1,7 +1,8 @@
 """Rollout storage and GAE on the MI355X (sparc_amd/csrc/wedm_gae.h, sparc_amd/rollout.py): `wedm_gae`
 against `torch_gae` on every byte of everything it writes -- advantages, returns, valid mask, standardised advantages, tile
 partials, moments and the done row -- at the wave, tile and unroll edges, with its blocks in guard bands; its two phases
-apart and shards in turn against the whole batch; and `RolloutBuffer` through `WireEDMVectorEnv`, without a host
+apart and shards in turn against the whole batch; environments of mixed magnitude down to float32 subnormals, flag bytes
+other than 0 and 1, a long rollout and the fold of a large workspace; and `RolloutBuffer` through `WireEDMVectorEnv`, without a host
 synchronisation or an allocation per rollout."""
 from __future__ import annotations
 
@@ -13,6 +14,7 @@ import torch
 
 from sparc_amd import RolloutBuffer, WireEDMVectorEnv, _abi
 from sparc_amd.rollout import APPLY, NORMALIZE, SCAN, SCAN_UNROLL, SKIP_AFTER_DONE, device_gae, torch_gae
+from tests._gae_common import FLAG_BYTES, GAE_KINDS, PAIRS, draw_mixed, is_subnormal, kinds_of
 from tests._normalize_common import same_bits
 from tests._snapshot_common import make
 
@@ -49,7 +51,8 @@ class Problem:
     in the padding columns, outputs ``[T, N + 3]`` of 0xA5 bytes, dones with probability 0.1 each.  `call` runs `wedm_gae`;
     `expect` builds, from `torch_gae` on the same data, every output block as the call has to leave it, padding included."""
 
-    def __init__(self, N, T, seed, prev="given", n_tiles_total=None, p=0.1, gamma=0.99, lam=0.95, eps=1e-8):
+    def __init__(self, N, T, seed, prev="given", n_tiles_total=None, p=0.1, gamma=0.99, lam=0.95, eps=1e-8, kinds=None):
+        """``kinds``: None (unit normals and flag bytes 0 / 1), or the environments' kinds for `draw_mixed`."""
         self.N, self.T, self.prev_mode = N, T, prev
         rng = np.random.default_rng(seed)
         self.si, self.so = N + 5, N + 3
@@ -65,6 +68,11 @@ class Problem:
             h[name][:, :N] = rng.random((T, N)) < p
         h["last_value"] = rng.normal(size=N).astype(np.float32)
         h["prev_done"] = (rng.random(N) < 0.2).astype(np.uint8)
+        if kinds is not None:
+            x = draw_mixed(rng, T, N, p, kinds)
+            for name in ("reward", "value", "terminated", "truncated"):
+                h[name][:, :N] = x[name]
+            h["last_value"] = x["last_value"]
         self.inputs = {name: Banded(a) for name, a in h.items()}
         self.outputs = {name: Banded(poisoned((T, self.so), dt)) for name, dt in OUTPUTS}
         self.outputs["prev_done_out"] = Banded(poisoned((N,), np.uint8))
@@ -91,13 +99,13 @@ class Problem:
     def call(self, flags, **kw):
         device_gae(self.desc(flags, **kw), DEV)
 
-    def expect(self, flags, partials=None):
+    def expect(self, flags, partials=None, tile_offset=0):
         """Every output block as a whole-batch call with ``flags`` (both phases) has to leave it."""
         h = self.host
         out = torch_gae(h["reward"], h["value"], h["last_value"], h["terminated"], h["truncated"], num_envs=self.N,
                         prev_done=self.prev_host(), partials=poisoned((self.n_tiles_total, 3), np.float64) if partials is None else partials,
-                        n_tiles_total=self.n_tiles_total, gamma=self.kw["gamma"], gae_lambda=self.kw["lam"], eps=self.kw["eps"],
-                        flags=flags)
+                        tile_offset=tile_offset, n_tiles_total=self.n_tiles_total, gamma=self.kw["gamma"], gae_lambda=self.kw["lam"],
+                        eps=self.kw["eps"], flags=flags)
         self.out = out
         want = {}
         for name, dt in OUTPUTS:
@@ -207,6 +215,93 @@ def test_run_twice_gives_the_same_bits():
         torch.cuda.synchronize()
         got.append({name: b.raw.clone() for name, b in p.outputs.items()})
     assert all(same_bits(got[0][name], got[1][name]) for name in got[0])
+
+
+# ------------------------------------------------------------------------------------------------ magnitudes, lengths, folds
+def finite(p):
+    """The condition under which `wedm_gae` is compared on every byte: the definition's outputs (``p.out``, after `expect`)
+    hold no NaN and no infinity -- `wedm_gae` does not canonicalise a NaN, and the header leaves a NaN's numbers unspecified."""
+    return all(bool(torch.isfinite(t.to(torch.float64)).all()) for t in p.out.values())
+
+
+@pytest.mark.parametrize("N", [1, 65, 257, 513])
+def test_mixed_kinds_equal_the_definition_on_every_byte(N):
+    """Environments of `GAE_KINDS` -- normal, offset 1e6 + U(0, 8), constant 293.15, tiny 1e-30, huge 1e30, subnormal 1e-41,
+    signed zeros, independently in ``reward``, ``value`` and ``last_value`` -- with ``terminated`` / ``truncated`` bytes
+    from {0, 1, 2, 0x80, 0xFF} (non-zero means set; ``prev_done_out`` is still exactly 0 or 1), for T in {1, U + 1, 3U + 2}
+    by (gamma, lam) in {(0.99, 0.95), (1, 1), (0, 0.5), (0.97, 0)} by both option flags and none.  Float32 subnormals are
+    read and stored: the definition keeps them, and so must the kernels."""
+    seen_kinds, seen_bytes, subnormal = set(), set(), dict(advantage=0, returns=0, advantage_norm=0)
+    for T in (1, U + 1, 3 * U + 2):
+        for gamma, lam in PAIRS:
+            for flags in (SKIP_AFTER_DONE | NORMALIZE, 0):
+                p = Problem(N, T, seed=7000 * N + 100 * T + 10 * PAIRS.index((gamma, lam)) + flags, gamma=gamma, lam=lam, kinds=GAE_KINDS)
+                want = p.expect(flags)
+                assert finite(p), (N, T, gamma, lam, flags)
+                p.call(flags)
+                assert p.differences(want) == [], (N, T, gamma, lam, flags)
+                assert set(want["prev_done_out"].tolist()) <= {0, 1} and set(want["valid"][:, :N].reshape(-1).tolist()) <= {0, 1}
+                for name in ("terminated", "truncated"):
+                    seen_bytes |= set(p.host[name][:, :N].reshape(-1).tolist())
+                for kinds in kinds_of(N):
+                    seen_kinds |= set(kinds.tolist())
+                for name in subnormal:
+                    if name in p.out:
+                        subnormal[name] += int(is_subnormal(p.out[name].numpy()).sum())
+    if N > 1:   # (one environment is of the first kind, and may never set a flag)
+        assert seen_kinds == set(range(len(GAE_KINDS))) and seen_bytes == set(FLAG_BYTES)
+        assert subnormal["advantage"] > 0 and subnormal["returns"] > 0, subnormal
+
+
+def test_a_long_rollout_equals_the_definition_on_every_byte():
+    """T = 40 U + 3 at N = 65 with normal and offset environments: the pipelined chunk loop runs 39 iterations (the tests
+    above: at most two) before its last chunk and the three steps that fill none."""
+    flags = SKIP_AFTER_DONE | NORMALIZE
+    p = Problem(65, 40 * U + 3, seed=60, p=0.02, kinds=("normal", "offset"))
+    want = p.expect(flags)
+    assert finite(p)
+    p.call(flags)
+    assert p.differences(want) == []
+    assert 0 < int(want["valid"][:, :65].sum()) < 65 * (40 * U + 3) and float(want["moments"][0]) == float(want["valid"][:, :65].sum())
+
+
+@pytest.mark.parametrize("n_tiles_total", [256, 257, 1025, 4096])
+def test_the_fold_of_a_large_workspace(n_tiles_total):
+    """As tests/test_normalize.py's: the fold gives a lane 1, 2, 8 or 16 tiles of the one-column workspace (``per`` of
+    `wedm_norm_fold_tiles`), on other shards' nodes, a third of them EMPTY, around this batch's two tiles; SCAN then APPLY
+    at ``tile_offset = n_tiles_total - 2`` against `torch_gae` given the same workspace."""
+    both = SKIP_AFTER_DONE | NORMALIZE
+    p = Problem(300, U + 1, seed=61, n_tiles_total=n_tiles_total)
+    rng = np.random.default_rng(n_tiles_total)
+    nodes = np.stack([rng.integers(1, 257, n_tiles_total).astype(np.float64), rng.normal(size=n_tiles_total),
+                      rng.uniform(0.0, 50.0, n_tiles_total)], axis=1)
+    nodes[rng.random(n_tiles_total) < 0.33] = 0.0
+    p.outputs["partials"].t.copy_(torch.from_numpy(nodes))
+    offset = n_tiles_total - 2
+    want = p.expect(both, partials=nodes, tile_offset=offset)
+    assert finite(p) and want["moments"][0] > nodes[:offset, 0].sum() > 0
+    assert same_bits(want["partials"][:offset], nodes[:offset]) and not same_bits(want["partials"][offset:], nodes[offset:])
+    p.call(both | SCAN, tile_offset=offset)
+    p.call(both | APPLY, tile_offset=offset)
+    assert p.differences(want) == []
+
+
+@pytest.mark.parametrize("prev_done", [0, 1])
+def test_one_environment_and_one_step(prev_done):
+    """N = 1, T = 1 with the default eps: one valid step gives S exactly 0 and the denominator sqrt(eps), and the one
+    standardised advantage is (A - A) / sqrt(eps) = 0; after a done nothing is valid and the moments are EMPTY."""
+    for flags in (SKIP_AFTER_DONE | NORMALIZE, NORMALIZE, SKIP_AFTER_DONE, 0):
+        p = Problem(1, 1, seed=62 + flags)
+        p.host["prev_done"][:] = prev_done
+        p.inputs["prev_done"].t.fill_(prev_done)
+        want = p.expect(flags)
+        p.call(flags)
+        assert p.differences(want) == [], flags
+        if flags & NORMALIZE:
+            skipped = bool(prev_done and flags & SKIP_AFTER_DONE)
+            a = float(want["advantage"][0, 0])
+            assert want["moments"].tolist() == ([0.0, 0.0, 0.0] if skipped else [1.0, a, 0.0]) and float(want["advantage_norm"][0, 0]) == 0.0
+            assert skipped or a != 0.0
 
 
 # ------------------------------------------------------------------------------------------------ through the adapter

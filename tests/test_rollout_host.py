@@ -16,6 +16,7 @@ import torch
 
 from sparc_amd import RolloutBuffer, WireEDMVectorEnv, _abi, _lib
 from sparc_amd.rollout import APPLY, NORMALIZE, SCAN, SCAN_UNROLL, SKIP_AFTER_DONE, torch_gae
+from tests._gae_common import FLAG_BYTES, GAE_KINDS, PAIRS, draw_mixed, is_subnormal, kinds_of
 from tests._normalize_common import same_bits
 from tests._snapshot_common import make
 
@@ -155,6 +156,34 @@ def test_torch_gae_against_a_textbook_gae():
         assert err.max() <= 1e-12, name
     assert got["valid"].all() and "advantage_norm" not in got and "moments" not in got
     assert x["terminated"].any() and x["truncated"].any() and (x["terminated"] | x["truncated"])[:-1].any()
+
+
+@pytest.mark.parametrize("gamma,lam", PAIRS, ids=[f"gamma{g}-lam{l}" for g, l in PAIRS])
+def test_torch_gae_against_a_textbook_gae_on_mixed_kinds(gamma, lam):
+    """26 x 513 environments of `GAE_KINDS` (normal, offset, constant, tiny, huge, subnormal, zeros, independently in
+    ``reward``, ``value`` and ``last_value``) with flag bytes from {0, 1, 2, 0x80, 0xFF}: the criterion of the test above, 1e-12
+    relative after rounding to float32.  Every output is finite -- the condition under which the device test compares bits
+    -- with NumPy's overflow, invalid and division warnings raised as errors around the textbook's rounding (a subnormal
+    result raises underflow by definition: that one is wanted here), and stored float32 subnormals occur."""
+    T, N = 3 * SCAN_UNROLL + 2, 513
+    x = draw_mixed(np.random.default_rng(11), T, N)
+    for kinds in kinds_of(N):
+        assert set(kinds.tolist()) == set(range(len(GAE_KINDS)))
+    assert all(set(x[k].reshape(-1).tolist()) == set(FLAG_BYTES) for k in ("terminated", "truncated"))
+    got = torch_gae(**x, gamma=gamma, gae_lambda=lam, flags=0)
+    adv, ret = textbook_gae(**x, gamma=gamma, lam=lam)
+    for name, want in (("advantage", adv), ("returns", ret)):
+        with np.errstate(over="raise", invalid="raise", divide="raise"):
+            w32 = want.astype(np.float32)
+        g, w = got[name].numpy().astype(np.float64), w32.astype(np.float64)
+        assert np.isfinite(g).all() and np.isfinite(w).all(), name
+        err = np.abs(g - w) / np.maximum(np.abs(w), 1e-300)
+        print(name, "largest relative difference", err.max(), "subnormals stored", int(is_subnormal(got[name].numpy()).sum()))
+        assert err.max() <= 1e-12, name
+        assert is_subnormal(got[name].numpy()).sum() >= 100, name
+    both = torch_gae(**x, gamma=gamma, gae_lambda=lam, prev_done=x["terminated"][0])
+    assert all(bool(torch.isfinite(both[k].to(torch.float64)).all()) for k in ("advantage", "returns", "advantage_norm", "moments", "partials"))
+    assert set(both["prev_done_out"].tolist()) == {0, 1} and set(both["valid"].reshape(-1).tolist()) == {0, 1}
 
 
 def test_lambda_zero_gives_the_one_step_residual_exactly():
