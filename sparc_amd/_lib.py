@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 from pathlib import Path
 
+import torch
+
 from . import _abi
 
 # WEDM_HIP_LIB lets the profiling scripts load an instrumented build of the SAME library;
@@ -25,6 +27,53 @@ class WedmError(RuntimeError):
 
 _lib = None
 
+_ctx, _p, _i32, _i64, _to = C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.POINTER  # (_p: a device address, a stream)
+_form_out = (_to(C.c_int32), _to(C.c_int32), _to(C.c_uint32))
+# every entry point of include/wedm_hip.h: its result type, then its argument types
+_SIGNATURES = {
+    "wedm_abi_version": (_i32,),
+    "wedm_sizeof_params": (_i64,),
+    "wedm_create": (_i32, _to(_abi.Params), _i32, _i32, _to(_ctx)),
+    "wedm_destroy": (_i32, _ctx),
+    "wedm_bind_state": (_i32, _ctx, _to(_abi.StatePtrs)),
+    "wedm_bind_geometry": (_i32, _ctx, _to(_abi.GeomPtrs)),
+    "wedm_reset": (_i32, _ctx, _p, C.c_uint64, _i32, _p),
+    "wedm_step": (_i32, _ctx, _i32, _to(_abi.ActionPtrs), _p),
+    "wedm_bind_trace": (_i32, _ctx, _to(_abi.TraceDesc)),
+    "wedm_bind_rng_replay": (_i32, _ctx, _p, _i64),
+    "wedm_bind_pulse_stats": (_i32, _ctx, _p),
+    "wedm_bind_signal_stats": (_i32, _ctx, _p),
+    "wedm_bind_env_params": (_i32, _ctx, _p),
+    "wedm_bind_wire_material": (_i32, _ctx, _p),
+    "wedm_trace_samples": (_i64, _ctx),
+    "wedm_set_kernel": (_i32, _ctx, _i32),
+    "wedm_set_lanes": (_i32, _ctx, _i32),
+    "wedm_last_error": (C.c_char_p, _ctx),
+    "wedm_last_kernel": (C.c_char_p, _ctx),
+    "wedm_last_occupancy": (_i32, _ctx),
+    "wedm_debug_math": (_i32, _i32, _p, _p, _p, _i32, _p),
+    "wedm_debug_poison_lds": (_i32, C.c_float, _p),
+    "wedm_debug_registry": (_i32, _i32, *_form_out),
+    "wedm_debug_last_form": (_i32, _ctx, *_form_out),
+    "wedm_debug_form_name": (C.c_char_p, _i32),
+    "wedm_copy_columns": (_i32, _to(_abi.CopyPlane), _i32, _p, _p, _i32, _p, _p),
+    "wedm_wire_profile": (_i32, _to(_abi.ProfileDesc), _p, _i32, _p, _p),
+    "wedm_derive_geometry": (_i32, _to(_abi.GeomDeriveDesc), _p, _p, _p, _p, _p, _p),
+    "wedm_draw_episode": (_i32, _to(_abi.DrawDesc), _p, _p, _p),
+    "wedm_normalize": (_i32, _to(_abi.NormDesc), _p),
+    "wedm_gae": (_i32, _to(_abi.GaeDesc), _p),
+    "wedm_policy_head": (_i32, _to(_abi.HeadDesc), _p),
+    "wedm_ppo_loss": (_i32, _to(_abi.PpoDesc), _p),
+    "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
+    "wedm_build_id": (C.c_char_p,),
+}
+EXPORTS = tuple(_SIGNATURES)
+
+
+def _declare(L: C.CDLL, name: str) -> None:
+    fn = getattr(L, name)
+    fn.restype, *fn.argtypes = _SIGNATURES[name]
+
 
 def load() -> C.CDLL:
     """dlopen the library and declare every entry point of include/wedm_hip.h."""
@@ -37,92 +86,16 @@ def load() -> C.CDLL:
             "(hipcc --offload-arch=gfx950).  sparc_amd has no CPU or PyTorch fallback."
         )
     L = C.CDLL(str(LIB_PATH))
-    L.wedm_abi_version.restype = C.c_int32
-    L.wedm_sizeof_params.restype = C.c_int64
+    for name in ("wedm_abi_version", "wedm_sizeof_params"):
+        _declare(L, name)
     if L.wedm_abi_version() != _abi.ABI_VERSION:
         raise ImportError(f"libwedm_hip.so has ABI {L.wedm_abi_version()}, python expects {_abi.ABI_VERSION}")
     if L.wedm_sizeof_params() != C.sizeof(_abi.Params):
         raise ImportError("struct wedm_params layout mismatch between libwedm_hip.so and sparc_amd._abi")
-    ctx = C.c_void_p
-    L.wedm_create.argtypes = [C.POINTER(_abi.Params), C.c_int32, C.c_int32, C.POINTER(ctx)]
-    L.wedm_create.restype = C.c_int32
-    L.wedm_destroy.argtypes = [ctx]
-    L.wedm_destroy.restype = C.c_int32
-    L.wedm_bind_state.argtypes = [ctx, C.POINTER(_abi.StatePtrs)]
-    L.wedm_bind_state.restype = C.c_int32
-    L.wedm_bind_geometry.argtypes = [ctx, C.POINTER(_abi.GeomPtrs)]
-    L.wedm_bind_geometry.restype = C.c_int32
-    L.wedm_reset.argtypes = [ctx, C.c_void_p, C.c_uint64, C.c_int32, C.c_void_p]
-    L.wedm_reset.restype = C.c_int32
-    L.wedm_step.argtypes = [ctx, C.c_int32, C.POINTER(_abi.ActionPtrs), C.c_void_p]
-    L.wedm_step.restype = C.c_int32
-    L.wedm_bind_trace.argtypes = [ctx, C.POINTER(_abi.TraceDesc)]
-    L.wedm_bind_trace.restype = C.c_int32
-    L.wedm_bind_rng_replay.argtypes = [ctx, C.c_void_p, C.c_int64]
-    L.wedm_bind_rng_replay.restype = C.c_int32
-    L.wedm_bind_pulse_stats.argtypes = [ctx, C.c_void_p]
-    L.wedm_bind_pulse_stats.restype = C.c_int32
-    L.wedm_bind_signal_stats.argtypes = [ctx, C.c_void_p]
-    L.wedm_bind_signal_stats.restype = C.c_int32
-    L.wedm_bind_env_params.argtypes = [ctx, C.c_void_p]
-    L.wedm_bind_env_params.restype = C.c_int32
-    L.wedm_bind_wire_material.argtypes = [ctx, C.c_void_p]
-    L.wedm_bind_wire_material.restype = C.c_int32
-    L.wedm_trace_samples.argtypes = [ctx]
-    L.wedm_trace_samples.restype = C.c_int64
-    L.wedm_set_kernel.argtypes = [ctx, C.c_int32]
-    L.wedm_set_kernel.restype = C.c_int32
-    L.wedm_set_lanes.argtypes = [ctx, C.c_int32]
-    L.wedm_set_lanes.restype = C.c_int32
-    L.wedm_last_error.argtypes = [ctx]
-    L.wedm_last_error.restype = C.c_char_p
-    L.wedm_last_kernel.argtypes = [ctx]
-    L.wedm_last_kernel.restype = C.c_char_p
-    L.wedm_last_occupancy.argtypes = [ctx]
-    L.wedm_last_occupancy.restype = C.c_int32
-    L.wedm_debug_math.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    L.wedm_debug_math.restype = C.c_int32
-    L.wedm_debug_poison_lds.argtypes = [C.c_float, C.c_void_p]
-    L.wedm_debug_poison_lds.restype = C.c_int32
-    L.wedm_debug_registry.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
-    L.wedm_debug_registry.restype = C.c_int32
-    L.wedm_debug_last_form.argtypes = [ctx, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32)]
-    L.wedm_debug_last_form.restype = C.c_int32
-    L.wedm_debug_form_name.argtypes = [C.c_int32]
-    L.wedm_debug_form_name.restype = C.c_char_p
-    L.wedm_copy_columns.argtypes = [C.POINTER(_abi.CopyPlane), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.wedm_copy_columns.restype = C.c_int32
-    L.wedm_wire_profile.argtypes = [C.POINTER(_abi.ProfileDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    L.wedm_wire_profile.restype = C.c_int32
-    L.wedm_derive_geometry.argtypes = [C.POINTER(_abi.GeomDeriveDesc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p]
-    L.wedm_derive_geometry.restype = C.c_int32
-    L.wedm_draw_episode.argtypes = [C.POINTER(_abi.DrawDesc), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.wedm_draw_episode.restype = C.c_int32
-    L.wedm_normalize.argtypes = [C.POINTER(_abi.NormDesc), C.c_void_p]
-    L.wedm_normalize.restype = C.c_int32
-    L.wedm_gae.argtypes = [C.POINTER(_abi.GaeDesc), C.c_void_p]
-    L.wedm_gae.restype = C.c_int32
-    L.wedm_policy_head.argtypes = [C.POINTER(_abi.HeadDesc), C.c_void_p]
-    L.wedm_policy_head.restype = C.c_int32
-    L.wedm_ppo_loss.argtypes = [C.POINTER(_abi.PpoDesc), C.c_void_p]
-    L.wedm_ppo_loss.restype = C.c_int32
-    L.wedm_episode_log.argtypes = [C.POINTER(_abi.ElogDesc), C.c_void_p]
-    L.wedm_episode_log.restype = C.c_int32
-    L.wedm_build_id.argtypes = []
-    L.wedm_build_id.restype = C.c_char_p
+    for name in EXPORTS:
+        _declare(L, name)
     _lib = L
     return L
-
-
-EXPORTS = (
-    "wedm_abi_version", "wedm_create", "wedm_destroy", "wedm_bind_state", "wedm_bind_geometry",
-    "wedm_reset", "wedm_step", "wedm_bind_trace", "wedm_bind_rng_replay", "wedm_bind_pulse_stats", "wedm_bind_env_params", "wedm_bind_wire_material", "wedm_bind_signal_stats", "wedm_trace_samples", "wedm_set_kernel", "wedm_set_lanes", "wedm_last_kernel", "wedm_last_error", "wedm_last_occupancy",
-    "wedm_sizeof_params", "wedm_debug_math", "wedm_debug_poison_lds", "wedm_build_id",
-    "wedm_debug_registry", "wedm_debug_last_form", "wedm_debug_form_name", "wedm_copy_columns", "wedm_wire_profile",
-    "wedm_derive_geometry", "wedm_draw_episode", "wedm_normalize", "wedm_gae", "wedm_policy_head",
-    "wedm_ppo_loss", "wedm_episode_log",
-)
 
 
 def registry() -> list:
@@ -156,6 +129,24 @@ class _NoGuard:
 
 
 _NO_GUARD = _NoGuard()
+
+
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def call_stateless(fn, device: torch.device, *args) -> None:
+    """A call of ``fn``, an entry point that takes no handle and a stream last, on ``device`` and torch's current stream
+    there: the device is made current for the call when it is not (an index of None is the current device), the stream goes
+    as its raw handle (no Stream object is built where the accessor exists), and a refusal raises `WedmError` with the
+    library's text."""
+    current, index = torch.cuda.current_device(), device.index
+    if index is None:
+        index = current
+    with _NO_GUARD if index == current else torch.cuda.device(index):
+        stream = _RAW_STREAM(index) if _RAW_STREAM is not None else torch.cuda.current_stream(index).cuda_stream
+        rc = fn(*args, C.c_void_p(stream))
+    if rc != _abi.OK:
+        raise WedmError(rc, (load().wedm_last_error(None) or b"").decode())
 
 
 class HipBackend:
@@ -248,72 +239,45 @@ class HipBackend:
         `_abi.CopyPlane` (at most `_abi.COPY_MAX_PLANES`), the index lists are device addresses of int32[count], `status_ptr`
         the device address of an int32 word or None."""
         arr = (_abi.CopyPlane * len(planes))(*planes)
-        with self._on_device():
-            rc = self._L.wedm_copy_columns(arr, len(planes), src_idx_ptr, dst_idx_ptr, int(count), status_ptr, self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_copy_columns, self.device, arr, len(planes), src_idx_ptr, dst_idx_ptr, int(count), status_ptr)
 
     def wire_profile(self, desc: "_abi.ProfileDesc", env_idx_ptr, count: int, status_ptr=None) -> None:
         """`wedm_wire_profile` on this backend's device and torch's current stream: ``env_idx_ptr`` is the device address of
         int32[count] or None (environments ``0 .. count - 1``), ``status_ptr`` the device address of an int32 word or None."""
-        with self._on_device():
-            rc = self._L.wedm_wire_profile(C.byref(desc), env_idx_ptr, int(count), status_ptr, self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_wire_profile, self.device, C.byref(desc), env_idx_ptr, int(count), status_ptr)
 
     def derive_geometry(self, desc: "_abi.GeomDeriveDesc", height_ptr, diameter_idx_ptr, material_idx_ptr=None, mask_ptr=None,
                         status_ptr=None) -> None:
         """`wedm_derive_geometry` on this backend's device and torch's current stream: device addresses of float64[num_envs]
         heights, int32[num_envs] diameter indices, int32[num_envs] material indices or None (material 0), a uint8[num_envs]
         mask or None (every environment) and an int32 status word or None."""
-        with self._on_device():
-            rc = self._L.wedm_derive_geometry(C.byref(desc), height_ptr, diameter_idx_ptr, material_idx_ptr, mask_ptr, status_ptr,
-                                              self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_derive_geometry, self.device, C.byref(desc), height_ptr, diameter_idx_ptr, material_idx_ptr,
+                       mask_ptr, status_ptr)
 
     def draw_episode(self, desc: "_abi.DrawDesc", mask_ptr, draw_count_ptr) -> None:
         """`wedm_draw_episode` on this backend's device and torch's current stream: device addresses of a uint8[num_envs] mask
         or None (every environment) and of the sampler's int32[stride] draw counts."""
-        with self._on_device():
-            rc = self._L.wedm_draw_episode(C.byref(desc), mask_ptr, draw_count_ptr, self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_draw_episode, self.device, C.byref(desc), mask_ptr, draw_count_ptr)
 
     def normalize(self, desc: "_abi.NormDesc") -> None:
         """`wedm_normalize` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
-        with self._on_device():
-            rc = self._L.wedm_normalize(C.byref(desc), self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_normalize, self.device, C.byref(desc))
 
     def gae(self, desc: "_abi.GaeDesc") -> None:
         """`wedm_gae` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
-        with self._on_device():
-            rc = self._L.wedm_gae(C.byref(desc), self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_gae, self.device, C.byref(desc))
 
     def policy_head(self, desc: "_abi.HeadDesc") -> None:
         """`wedm_policy_head` on this backend's device and torch's current stream (one launch, no synchronisation)."""
-        with self._on_device():
-            rc = self._L.wedm_policy_head(C.byref(desc), self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_policy_head, self.device, C.byref(desc))
 
     def ppo_loss(self, desc: "_abi.PpoDesc") -> None:
         """`wedm_ppo_loss` on this backend's device and torch's current stream (at most four launches, no synchronisation)."""
-        with self._on_device():
-            rc = self._L.wedm_ppo_loss(C.byref(desc), self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_ppo_loss, self.device, C.byref(desc))
 
     def episode_log(self, desc: "_abi.ElogDesc") -> None:
         """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
-        with self._on_device():
-            rc = self._L.wedm_episode_log(C.byref(desc), self._stream())
-        if rc != _abi.OK:
-            raise WedmError(rc, (self._L.wedm_last_error(None) or b"").decode())
+        call_stateless(self._L.wedm_episode_log, self.device, C.byref(desc))
 
     def trace_samples(self) -> int:
         return int(self._L.wedm_trace_samples(self._ctx))

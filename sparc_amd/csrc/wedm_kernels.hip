@@ -52,6 +52,14 @@
 //                         means by a fixed pairwise tree over the row number, the gradient; not step kernels, not in the registry
 //   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the nine stateless entry
+// points (wedm_copy_columns ... wedm_episode_log) behind what they share, each written once above wedm_copy_columns:
+//   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
+//   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
+//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_episode_log)
+//   tile_range, fold_per  the tile range inside the workspace and its tile count; the tiles per lane of a 256-lane fold
+//   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
+//                         (wedm_policy_head, wedm_ppo_loss)
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
 // segments of one environment moves it with global_load / store_dwordx4, a wavefront still touches contiguous 1-KB runs.
 // Every kernel is a template <int L, uint32_t F> (or <uint32_t F>) over its lanes per environment and a set of form bits (F_*
@@ -1370,16 +1378,105 @@ int32_t wedm_step(wedm_ctx* ctx, int32_t n_substeps, const wedm_action_ptrs* act
     return WEDM_OK;
 }
 
+// ------------------------------------------------------------ the stateless entry points: what they share
 // No handle: the text of a refusal goes where wedm_create's goes (wedm_last_error(NULL)).
+
+// An entry point by name: how it refuses a call and how it reports a launch.
+struct Entry {
+    const char* name;
+    int32_t bad(const std::string& msg) const {
+        g_create_error = std::string(name) + ": " + msg;
+        return WEDM_ERR_BAD_ARG;
+    }
+    // after every launch; `what` names it where the entry point has several
+    int32_t launched(const char* what = nullptr) const {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return WEDM_OK;
+        g_create_error = std::string(name) + ": " + (what ? std::string(what) + " launch: " : "launch: ") + hipGetErrorString(e);
+        return WEDM_ERR_HIP;
+    }
+};
+
+// A block of the caller's memory by name: first byte, bytes from there to one past the last the call may touch (0: the call
+// leaves the block alone, so only its alignment counts), element size, whether NULL is refused; two blocks that `may_alias`
+// may be the same memory; plane >= 0 puts "plane <n>" before the name.
+struct Block {
+    const char* name;
+    uintptr_t lo, bytes, elem;
+    bool needed;
+    bool may_alias = false;
+    int32_t plane = -1;
+    std::string text() const { return plane < 0 ? name : "plane " + std::to_string(plane) + name; }
+};
+
+// The first reason why a call cannot use its blocks: an input, then an output, that is null though needed or not aligned to
+// its element; then an output that overlaps an input (outputs in the outer loop).  WEDM_OK where there is none.
+static int32_t check_blocks(const Entry& E, const Block* in, size_t n_in, const Block* out, size_t n_out) {
+    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.elem != 0; };
+    for (const Block* b = in; b < in + n_in; ++b)
+        if (unusable(*b)) return E.bad(b->text() + " is null or not aligned to its element");
+    for (const Block* b = out; b < out + n_out; ++b)
+        if (unusable(*b)) return E.bad(b->text() + " is null or not aligned to its element");
+    for (const Block* o = out; o < out + n_out; ++o) {
+        for (const Block* i = in; i < in + n_in; ++i) {
+            if (!o->lo || !i->lo || !o->bytes || !i->bytes || (o->may_alias && i->may_alias)) continue;
+            if (o->lo < i->lo + i->bytes && i->lo < o->lo + o->bytes) return E.bad(o->text() + " overlaps " + i->text());
+        }
+    }
+    return WEDM_OK;
+}
+
+// The tiles of a batch of num_envs >= 1 environments, or 0 after refusing a tile range that leaves the workspace.
+static int64_t tile_range(const Entry& E, int32_t num_envs, int32_t tile_offset, int32_t n_tiles_total) {
+    const int64_t tiles = ((int64_t)num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
+    if (tile_offset >= 0 && n_tiles_total >= 1 && n_tiles_total <= WEDM_NORM_MAX_TILES && tile_offset + tiles <= n_tiles_total)
+        return tiles;
+    E.bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
+          std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
+    return 0;
+}
+
+// Tiles per lane of a fold by 256 lanes: the smallest power of two with 256 * per >= n.
+static int32_t fold_per(int64_t n) {
+    int32_t per = 1;
+    while (256 * per < n) per *= 2;
+    return per;
+}
+
+static bool finite_f64(double x) { return x - x == 0.0; }
+
+// What wedm_policy_head and wedm_ppo_loss ask of a head's parameters, in two parts, since the loss checks its coefficients
+// between them: HEAD_SHAPE (n_modes, both strides against 8 + n_modes) and HEAD_BOUNDS (lo, hi, log_span of the four axes).
+enum HeadPart { HEAD_SHAPE = 1, HEAD_BOUNDS = 2 };
+static int32_t check_head_params(const Entry& E, int parts, int32_t n_modes, int64_t param_stride, int64_t grad_stride,
+                                 const double* lo, const double* hi, const double* log_span) {
+    if (parts & HEAD_SHAPE) {
+        if (n_modes < 1 || n_modes > WEDM_HEAD_MAX_MODES) return E.bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+        if (param_stride < 8 + n_modes || grad_stride < 8 + n_modes) return E.bad("a stride is smaller than 8 + n_modes");
+    }
+    for (int i = 0; (parts & HEAD_BOUNDS) && i < 4; ++i) {
+        if (!finite_f64(lo[i]) || !finite_f64(hi[i]) || !finite_f64(log_span[i])) return E.bad("a bound or log_span is not finite");
+        if (!(hi[i] > lo[i])) return E.bad("hi <= lo");
+    }
+    return WEDM_OK;
+}
+
+// Whether a kernel stages the parameter rows (in) and the gradient rows (out; `grad` NULL: there are none) through LDS -- dense
+// rows of P floats from a 16-byte boundary -- and the LDS that takes for a block of `block` rows.
+struct StagedRows {
+    bool in, out;
+    size_t lds;
+    StagedRows(const void* params, int64_t param_stride, const void* grad, int64_t grad_stride, int64_t P, int block)
+        : in(param_stride == P && (uintptr_t)params % 16 == 0), out(grad && grad_stride == P && (uintptr_t)grad % 16 == 0),
+          lds(in || out ? (size_t)block * (size_t)head_pitch((int)P) * 4 : 0) {}
+};
+
 int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const int32_t* src_idx, const int32_t* dst_idx,
                           int32_t count, int32_t* status, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_copy_columns: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
+    const Entry E{"wedm_copy_columns"};
     if (!planes || n_planes < 1 || n_planes > WEDM_COPY_MAX_PLANES)
-        return bad("null pointer or n_planes outside [1, " + std::to_string(WEDM_COPY_MAX_PLANES) + "]");
-    if (count < 0 || (count > 0 && (!src_idx || !dst_idx))) return bad("negative count or null index list");
+        return E.bad("null pointer or n_planes outside [1, " + std::to_string(WEDM_COPY_MAX_PLANES) + "]");
+    if (count < 0 || (count > 0 && (!src_idx || !dst_idx))) return E.bad("negative count or null index list");
     wedm_copy_args a;
     std::memset(&a, 0, sizeof(a));
     int64_t items = 0;
@@ -1387,14 +1484,14 @@ int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const
         const wedm_copy_plane& pl = planes[k];
         const std::string who = "plane " + std::to_string(k) + ": ";
         const int32_t w = pl.elem_bytes;
-        if (w != 1 && w != 4 && w != 8 && w != 16) return bad(who + "elem_bytes must be 1, 4, 8 or 16");
+        if (w != 1 && w != 4 && w != 8 && w != 16) return E.bad(who + "elem_bytes must be 1, 4, 8 or 16");
         if (!pl.src || !pl.dst || (uintptr_t)pl.src % (uintptr_t)w || (uintptr_t)pl.dst % (uintptr_t)w)
-            return bad(who + "null base pointer or one not aligned to elem_bytes");
-        if (pl.rows < 0 || pl.src_cols < 0 || pl.dst_cols < 0) return bad(who + "negative rows or column count");
-        if (pl.src_stride < pl.src_cols || pl.dst_stride < pl.dst_cols) return bad(who + "stride smaller than the column count");
+            return E.bad(who + "null base pointer or one not aligned to elem_bytes");
+        if (pl.rows < 0 || pl.src_cols < 0 || pl.dst_cols < 0) return E.bad(who + "negative rows or column count");
+        if (pl.src_stride < pl.src_cols || pl.dst_stride < pl.dst_cols) return E.bad(who + "stride smaller than the column count");
         a.plane[k] = pl;
         items += (pl.rows + WEDM_COPY_ROWS - 1) / WEDM_COPY_ROWS;
-        if (items > INT32_MAX) return bad("more rows than one call can hold");
+        if (items > INT32_MAX) return E.bad("more rows than one call can hold");
         a.item_end[k] = (int32_t)items;
     }
     a.n_planes = n_planes;
@@ -1404,30 +1501,23 @@ int32_t wedm_copy_columns(const wedm_copy_plane* planes, int32_t n_planes, const
         a.item0 = (int32_t)item0;
         const dim3 grid((uint32_t)(((int64_t)count + 255) / 256), (uint32_t)std::min(max_y, items - item0));
         hipLaunchKernelGGL(wedm_copy_columns_kernel, grid, dim3(256), 0, (hipStream_t)stream, a, src_idx, dst_idx, count, status);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) {
-            g_create_error = std::string("wedm_copy_columns: launch: ") + hipGetErrorString(e);
-            return WEDM_ERR_HIP;
-        }
+        if (const int32_t rc = E.launched()) return rc;
     }
     return WEDM_OK;
 }
 
 int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx, int32_t count, int32_t* status, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_wire_profile: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_wire_profile"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_profile_desc& d = *desc;
-    if (!d.T || !d.out || (uintptr_t)d.T % 16) return bad("T or out is null, or T is not 16-byte aligned");
-    if (d.bins < 0 || d.bins > WEDM_PROFILE_MAX_BINS) return bad("bins outside [0, " + std::to_string(WEDM_PROFILE_MAX_BINS) + "]");
-    if (d.num_envs < 1 || d.n_seg_max < 1) return bad("num_envs and n_seg_max must be positive");
-    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
-    if (d.out_cols < 0 || d.out_cols > d.out_stride) return bad("out_cols outside [0, out_stride]");
-    if (count < 0 || count > d.out_cols) return bad("count outside [0, out_cols]");
-    if (!d.geom_i32 && (d.n_seg < 1 || d.n_seg > d.n_seg_max)) return bad("n_seg outside [1, n_seg_max] (uniform geometry)");
-    if (!env_idx && count > d.num_envs) return bad("count exceeds num_envs without an index list");
+    if (!d.T || !d.out || (uintptr_t)d.T % 16) return E.bad("T or out is null, or T is not 16-byte aligned");
+    if (d.bins < 0 || d.bins > WEDM_PROFILE_MAX_BINS) return E.bad("bins outside [0, " + std::to_string(WEDM_PROFILE_MAX_BINS) + "]");
+    if (d.num_envs < 1 || d.n_seg_max < 1) return E.bad("num_envs and n_seg_max must be positive");
+    if (d.stride < d.num_envs) return E.bad("stride smaller than num_envs");
+    if (d.out_cols < 0 || d.out_cols > d.out_stride) return E.bad("out_cols outside [0, out_stride]");
+    if (count < 0 || count > d.out_cols) return E.bad("count outside [0, out_cols]");
+    if (!d.geom_i32 && (d.n_seg < 1 || d.n_seg > d.n_seg_max)) return E.bad("n_seg outside [1, n_seg_max] (uniform geometry)");
+    if (!env_idx && count > d.num_envs) return E.bad("count exceeds num_envs without an index list");
     if (count == 0) return WEDM_OK;
     // waves per block = pieces a wire is cut into: four, and more while the launch has fewer than WEDM_PROFILE_WAVES_PER_SIMD
     // waves for each of the device's 1024 SIMDs and every piece keeps a whole batch of loads
@@ -1449,276 +1539,185 @@ int32_t wedm_wire_profile(const wedm_profile_desc* desc, const int32_t* env_idx,
         hipLaunchKernelGGL((wedm_wire_profile_kernel<true>), grid, block, lds, (hipStream_t)stream, a, env_idx, status);
     else
         hipLaunchKernelGGL((wedm_wire_profile_kernel<false>), grid, block, lds, (hipStream_t)stream, a, env_idx, status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_create_error = std::string("wedm_wire_profile: launch: ") + hipGetErrorString(e);
-        return WEDM_ERR_HIP;
-    }
-    return WEDM_OK;
+    return E.launched();
 }
 
 int32_t wedm_normalize(const wedm_norm_desc* desc, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_normalize: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_normalize"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_norm_desc& d = *desc;
     const int32_t all = WEDM_NORM_UPDATE | WEDM_NORM_STEP | WEDM_NORM_REDUCE | WEDM_NORM_APPLY;
-    if (d.flags & ~all) return bad("undefined flag bits");
+    if (d.flags & ~all) return E.bad("undefined flag bits");
     const bool update = d.flags & WEDM_NORM_UPDATE, step = d.flags & WEDM_NORM_STEP;
     const bool both = !(d.flags & (WEDM_NORM_REDUCE | WEDM_NORM_APPLY));
     const bool reduce = both || (d.flags & WEDM_NORM_REDUCE), apply = both || (d.flags & WEDM_NORM_APPLY);
-    if (d.num_envs < 1) return bad("num_envs must be positive");
-    if (d.plane[0].n_rows < 0 || d.plane[1].n_rows < 0) return bad("negative n_rows");
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.plane[0].n_rows < 0 || d.plane[1].n_rows < 0) return E.bad("negative n_rows");
     const int64_t D = (int64_t)d.plane[0].n_rows + d.plane[1].n_rows;
-    if (D < 1 || D > WEDM_NORM_MAX_COLUMNS - 1) return bad("D outside [1, " + std::to_string(WEDM_NORM_MAX_COLUMNS - 1) + "]");
+    if (D < 1 || D > WEDM_NORM_MAX_COLUMNS - 1) return E.bad("D outside [1, " + std::to_string(WEDM_NORM_MAX_COLUMNS - 1) + "]");
     for (int k = 0; k < 2; ++k) {
         if (d.plane[k].n_rows == 0) continue;
-        if (!d.plane[k].rows || (uintptr_t)d.plane[k].rows % 4) return bad("plane " + std::to_string(k) + ": rows is null or misaligned");
-        if (d.plane[k].stride < d.num_envs) return bad("plane " + std::to_string(k) + ": stride smaller than num_envs");
+        if (!d.plane[k].rows || (uintptr_t)d.plane[k].rows % 4) return E.bad("plane " + std::to_string(k) + ": rows is null or misaligned");
+        if (d.plane[k].stride < d.num_envs) return E.bad("plane " + std::to_string(k) + ": stride smaller than num_envs");
     }
-    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
-    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
-        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
-                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
-    if (update && (!d.partials || (uintptr_t)d.partials % 8)) return bad("partials is null or misaligned (UPDATE)");
-    if (step && (!d.reward || !d.ret || (uintptr_t)d.reward % 4 || (uintptr_t)d.ret % 8)) return bad("reward or ret is null or misaligned (STEP)");
+    const int64_t tiles = tile_range(E, d.num_envs, d.tile_offset, d.n_tiles_total);
+    if (!tiles) return WEDM_ERR_BAD_ARG;
+    if (update && (!d.partials || (uintptr_t)d.partials % 8)) return E.bad("partials is null or misaligned (UPDATE)");
+    if (step && (!d.reward || !d.ret || (uintptr_t)d.reward % 4 || (uintptr_t)d.ret % 8)) return E.bad("reward or ret is null or misaligned (STEP)");
     const int64_t C = D + 1;
     if (apply) {
         if (!d.obs_out || !d.stats_in || !d.stats_out || (uintptr_t)d.obs_out % 4 || (uintptr_t)d.stats_in % 8 || (uintptr_t)d.stats_out % 8)
-            return bad("obs_out, stats_in or stats_out is null or misaligned (APPLY)");
+            return E.bad("obs_out, stats_in or stats_out is null or misaligned (APPLY)");
         const uintptr_t a = (uintptr_t)d.stats_in, b = (uintptr_t)d.stats_out, bytes = (uintptr_t)(WEDM_NORM_MOMENTS * C * 8);
-        if (a < b + bytes && b < a + bytes) return bad("stats_in and stats_out overlap");
+        if (a < b + bytes && b < a + bytes) return E.bad("stats_in and stats_out overlap");
         if (step) {
             if (!d.terminated || !d.truncated || !d.reward_out || !d.ep_return || !d.last_return || !d.ep_length || !d.last_length ||
                 !d.ep_count || !d.finished)
-                return bad("terminated, truncated, reward_out or a per-environment row is null (APPLY with STEP)");
+                return E.bad("terminated, truncated, reward_out or a per-environment row is null (APPLY with STEP)");
             if ((uintptr_t)d.reward_out % 4 || (uintptr_t)d.ep_return % 8 || (uintptr_t)d.last_return % 8 || (uintptr_t)d.ep_length % 4 ||
                 (uintptr_t)d.last_length % 4 || (uintptr_t)d.ep_count % 4)
-                return bad("reward_out or a per-environment row is not aligned to its element");
+                return E.bad("reward_out or a per-environment row is not aligned to its element");
         }
     }
-    const auto launched = [](const char* what) {
-        const hipError_t e = hipGetLastError();
-        if (e == hipSuccess) return (int32_t)WEDM_OK;
-        g_create_error = std::string("wedm_normalize: ") + what + " launch: " + hipGetErrorString(e);
-        return (int32_t)WEDM_ERR_HIP;
-    };
     const dim3 grid((uint32_t)tiles), block(WEDM_NORM_TILE);
     if (reduce && (update || step)) {
         // a wave per tile and column group; in evaluation mode one wave per tile, which only moves the return on
         const int32_t c_first = update ? 0 : (int32_t)D;
         const dim3 rgrid((uint32_t)tiles, (uint32_t)((C - c_first + WEDM_NORM_GROUP - 1) / WEDM_NORM_GROUP));
         hipLaunchKernelGGL(wedm_norm_reduce_kernel, rgrid, dim3(64), 0, (hipStream_t)stream, d, (int32_t)D, c_first);
-        if (const int32_t rc = launched("reduce")) return rc;
+        if (const int32_t rc = E.launched("reduce")) return rc;
     }
     if (apply) {
-        int32_t per = 1;  // tiles per lane of the fold: the power of two with 256 * per >= n_tiles_total
-        while (256 * per < d.n_tiles_total) per *= 2;
-        hipLaunchKernelGGL(wedm_norm_fold_kernel, dim3((uint32_t)C), dim3(256), 0, (hipStream_t)stream, d, (int32_t)C, per);
-        if (const int32_t rc = launched("fold")) return rc;
+        hipLaunchKernelGGL(wedm_norm_fold_kernel, dim3((uint32_t)C), dim3(256), 0, (hipStream_t)stream, d, (int32_t)C,
+                           fold_per(d.n_tiles_total));
+        if (const int32_t rc = E.launched("fold")) return rc;
         hipLaunchKernelGGL(wedm_norm_apply_kernel, grid, block, 0, (hipStream_t)stream, d, (int32_t)D);
-        if (const int32_t rc = launched("apply")) return rc;
+        if (const int32_t rc = E.launched("apply")) return rc;
     }
     return WEDM_OK;
 }
 
-static bool finite_f64(double x) { return x - x == 0.0; }
-
 int32_t wedm_gae(const wedm_gae_desc* desc, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_gae: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_gae"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_gae_desc& d = *desc;
     const int32_t all = WEDM_GAE_SKIP_AFTER_DONE | WEDM_GAE_NORMALIZE | WEDM_GAE_SCAN | WEDM_GAE_APPLY;
-    if (d.flags & ~all) return bad("undefined flag bits");
+    if (d.flags & ~all) return E.bad("undefined flag bits");
     const bool normalize = d.flags & WEDM_GAE_NORMALIZE;
     const bool both = !(d.flags & (WEDM_GAE_SCAN | WEDM_GAE_APPLY));
     const bool scan = both || (d.flags & WEDM_GAE_SCAN), apply = (both || (d.flags & WEDM_GAE_APPLY)) && normalize;
-    if (d.num_envs < 1) return bad("num_envs must be positive");
-    if (d.T < 1 || d.T > WEDM_GAE_MAX_STEPS) return bad("T outside [1, " + std::to_string(WEDM_GAE_MAX_STEPS) + "]");
-    if (d.in_stride < d.num_envs || d.out_stride < d.num_envs) return bad("a stride is smaller than num_envs");
-    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
-    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
-        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
-                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
-    if (!finite_f64(d.gamma) || !finite_f64(d.lam) || !finite_f64(d.eps)) return bad("gamma, lam and eps must be finite");
-    // the blocks by name: first byte, one past the last byte the call may touch, element size
-    struct Block {
-        const char* name;
-        uintptr_t lo, bytes, elem;
-        bool needed;
-    };
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.T < 1 || d.T > WEDM_GAE_MAX_STEPS) return E.bad("T outside [1, " + std::to_string(WEDM_GAE_MAX_STEPS) + "]");
+    if (d.in_stride < d.num_envs || d.out_stride < d.num_envs) return E.bad("a stride is smaller than num_envs");
+    const int64_t tiles = tile_range(E, d.num_envs, d.tile_offset, d.n_tiles_total);
+    if (!tiles) return WEDM_ERR_BAD_ARG;
+    if (!finite_f64(d.gamma) || !finite_f64(d.lam) || !finite_f64(d.eps)) return E.bad("gamma, lam and eps must be finite");
     const uintptr_t rows_in = (uintptr_t)((int64_t)(d.T - 1) * d.in_stride + d.num_envs);
     const uintptr_t rows_out = (uintptr_t)((int64_t)(d.T - 1) * d.out_stride + d.num_envs), n = (uintptr_t)d.num_envs;
     const Block in[] = {
         {"reward", (uintptr_t)d.reward, rows_in * 4, 4, scan},       {"value", (uintptr_t)d.value, rows_in * 4, 4, scan},
         {"last_value", (uintptr_t)d.last_value, n * 4, 4, scan},     {"terminated", (uintptr_t)d.terminated, rows_in, 1, scan},
-        {"truncated", (uintptr_t)d.truncated, rows_in, 1, scan},     {"prev_done_in", (uintptr_t)d.prev_done_in, n, 1, false},
+        {"truncated", (uintptr_t)d.truncated, rows_in, 1, scan},     {"prev_done_in", (uintptr_t)d.prev_done_in, n, 1, false, true},
     };
     const Block out[] = {
         {"advantage", (uintptr_t)d.advantage, rows_out * 4, 4, scan || apply},
         {"returns", (uintptr_t)d.returns, rows_out * 4, 4, scan},
         {"valid", (uintptr_t)d.valid, rows_out, 1, scan || apply},
         {"advantage_norm", (uintptr_t)d.advantage_norm, rows_out * 4, 4, apply},
-        {"prev_done_out", (uintptr_t)d.prev_done_out, n, 1, false},
+        {"prev_done_out", (uintptr_t)d.prev_done_out, n, 1, false, true},  // (may be prev_done_in)
         {"partials", (uintptr_t)d.partials, (uintptr_t)d.n_tiles_total * WEDM_NORM_MOMENTS * 8, 8, normalize && (scan || apply)},
         {"moments", (uintptr_t)d.moments, WEDM_NORM_MOMENTS * 8, 8, apply},
     };
-    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.elem != 0; };
-    for (const Block& b : in)
-        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
-    for (const Block& b : out)
-        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
-    for (const Block& o : out) {
-        for (const Block& i : in) {
-            if (!o.lo || !i.lo || (&o == &out[4] && &i == &in[5])) continue;  // (prev_done_out may be prev_done_in)
-            if (o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(std::string(o.name) + " overlaps " + i.name);
-        }
-    }
-    const auto launched = [](const char* what) {
-        const hipError_t e = hipGetLastError();
-        if (e == hipSuccess) return (int32_t)WEDM_OK;
-        g_create_error = std::string("wedm_gae: ") + what + " launch: " + hipGetErrorString(e);
-        return (int32_t)WEDM_ERR_HIP;
-    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
     if (scan) {
         hipLaunchKernelGGL(wedm_gae_scan_kernel, dim3((uint32_t)tiles), dim3(WEDM_NORM_TILE), 0, (hipStream_t)stream, d);
-        if (const int32_t rc = launched("scan")) return rc;
+        if (const int32_t rc = E.launched("scan")) return rc;
     }
     if (apply) {
-        int32_t per = 1;  // tiles per lane of the fold: the power of two with 256 * per >= n_tiles_total
-        while (256 * per < d.n_tiles_total) per *= 2;
-        hipLaunchKernelGGL(wedm_gae_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d, per);
-        if (const int32_t rc = launched("fold")) return rc;
+        hipLaunchKernelGGL(wedm_gae_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, d, fold_per(d.n_tiles_total));
+        if (const int32_t rc = E.launched("fold")) return rc;
         const dim3 grid((uint32_t)tiles, (uint32_t)((d.T + WEDM_GAE_APPLY_ROWS - 1) / WEDM_GAE_APPLY_ROWS));
         hipLaunchKernelGGL(wedm_gae_apply_kernel, grid, dim3(WEDM_NORM_TILE), 0, (hipStream_t)stream, d);
-        if (const int32_t rc = launched("apply")) return rc;
+        if (const int32_t rc = E.launched("apply")) return rc;
     }
     return WEDM_OK;
 }
 
 int32_t wedm_policy_head(const wedm_head_desc* desc, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_policy_head: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_policy_head"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_head_desc& d = *desc;
-    if (d.op != WEDM_HEAD_SAMPLE && d.op != WEDM_HEAD_EVALUATE && d.op != WEDM_HEAD_BACKWARD) return bad("undefined op");
-    if (d.flags & ~(int32_t)WEDM_HEAD_DETERMINISTIC) return bad("undefined flag bits");
-    if (d.flags && d.op != WEDM_HEAD_SAMPLE) return bad("a flag with another op than SAMPLE");
-    if (d.rows < 1) return bad("rows must be positive");
-    if (d.n_modes < 1 || d.n_modes > WEDM_HEAD_MAX_MODES) return bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+    if (d.op != WEDM_HEAD_SAMPLE && d.op != WEDM_HEAD_EVALUATE && d.op != WEDM_HEAD_BACKWARD) return E.bad("undefined op");
+    if (d.flags & ~(int32_t)WEDM_HEAD_DETERMINISTIC) return E.bad("undefined flag bits");
+    if (d.flags && d.op != WEDM_HEAD_SAMPLE) return E.bad("a flag with another op than SAMPLE");
+    if (d.rows < 1) return E.bad("rows must be positive");
     const bool sample = d.op == WEDM_HEAD_SAMPLE, backward = d.op == WEDM_HEAD_BACKWARD;
+    if (const int32_t rc = check_head_params(E, HEAD_SHAPE | HEAD_BOUNDS, d.n_modes, d.param_stride,
+                                             backward ? d.grad_stride : d.param_stride, d.lo, d.hi, d.log_span))
+        return rc;
     const int64_t P = 8 + d.n_modes;
-    if (d.param_stride < P || (backward && d.grad_stride < P)) return bad("a stride is smaller than 8 + n_modes");
-    for (int i = 0; i < 4; ++i) {
-        if (!finite_f64(d.lo[i]) || !finite_f64(d.hi[i]) || !finite_f64(d.log_span[i])) return bad("a bound or log_span is not finite");
-        if (!(d.hi[i] > d.lo[i])) return bad("hi <= lo");
-    }
-    // the blocks by name: first byte, bytes the call may touch, alignment, whether the op needs it
-    struct Block {
-        const char* name;
-        uintptr_t lo, bytes, align;
-        bool needed;
-    };
-    const uintptr_t n = (uintptr_t)d.rows;
+    // rows of the blocks only SAMPLE, only BACKWARD, all but BACKWARD touch: none for the other ops, which leave them alone
+    const uintptr_t n = (uintptr_t)d.rows, ns = sample ? n : 0, nb = backward ? n : 0, nf = backward ? 0 : n;
     const uintptr_t row_bytes = (uintptr_t)((int64_t)(d.rows - 1) * d.param_stride + P) * 4;
     const uintptr_t grad_bytes = backward ? (uintptr_t)((int64_t)(d.rows - 1) * d.grad_stride + P) * 4 : 0;
     const Block blocks[] = {
         {"params", (uintptr_t)d.params, row_bytes, 4, true},
         {"u", (uintptr_t)d.u, n * 16, 16, true},
         {"mode_index", (uintptr_t)d.mode_index, n * 4, 4, true},
-        {"g_log_prob", (uintptr_t)d.g_log_prob, n * 4, 4, backward},
-        {"g_entropy", (uintptr_t)d.g_entropy, n * 4, 4, false},
-        {"action[0]", (uintptr_t)d.action[0], n * 8, 8, sample},
-        {"action[1]", (uintptr_t)d.action[1], n * 8, 8, sample},
-        {"action[2]", (uintptr_t)d.action[2], n * 8, 8, sample},
-        {"action[3]", (uintptr_t)d.action[3], n * 8, 8, sample},
-        {"current_mode", (uintptr_t)d.current_mode, n * 4, 4, sample},
-        {"log_prob", (uintptr_t)d.log_prob, n * 4, 4, !backward},
-        {"entropy", (uintptr_t)d.entropy, n * 4, 4, !backward},
+        {"g_log_prob", (uintptr_t)d.g_log_prob, nb * 4, 4, backward},
+        {"g_entropy", (uintptr_t)d.g_entropy, nb * 4, 4, false},
+        {"action[0]", (uintptr_t)d.action[0], ns * 8, 8, sample},
+        {"action[1]", (uintptr_t)d.action[1], ns * 8, 8, sample},
+        {"action[2]", (uintptr_t)d.action[2], ns * 8, 8, sample},
+        {"action[3]", (uintptr_t)d.action[3], ns * 8, 8, sample},
+        {"current_mode", (uintptr_t)d.current_mode, ns * 4, 4, sample},
+        {"log_prob", (uintptr_t)d.log_prob, nf * 4, 4, !backward},
+        {"entropy", (uintptr_t)d.entropy, nf * 4, 4, !backward},
         {"grad_params", (uintptr_t)d.grad_params, grad_bytes, 4, backward},
     };
-    for (const Block& b : blocks)
-        if ((b.needed && !b.lo) || b.lo % b.align != 0) return bad(std::string(b.name) + " is null or not aligned to its element");
-    // what the op reads and what it writes: u and mode_index are SAMPLE's outputs and the others' inputs
-    const auto is_input = [&](const Block& b) {
-        const size_t i = (size_t)(&b - blocks);
-        return i == 0 || (!sample && (i == 1 || i == 2)) || (backward && (i == 3 || i == 4));
-    };
-    const auto is_output = [&](const Block& b) {
-        const size_t i = (size_t)(&b - blocks);
-        return (sample && (i == 1 || i == 2 || (i >= 5 && i <= 9))) || (!backward && (i == 10 || i == 11)) || (backward && i == 12);
-    };
-    for (const Block& o : blocks) {
-        if (!is_output(o) || !o.lo) continue;
-        for (const Block& i : blocks)
-            if (is_input(i) && i.lo && o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes)
-                return bad(std::string(o.name) + " overlaps " + i.name);
-    }
-    const bool in_lds = d.param_stride == P && (uintptr_t)d.params % 16 == 0;
-    const bool out_lds = backward && d.grad_stride == P && (uintptr_t)d.grad_params % 16 == 0;
+    // what the op reads comes first: params; u and mode_index, SAMPLE's outputs, for the others; the two gradients for BACKWARD
+    const size_t n_in = sample ? 1 : backward ? 5 : 3;
+    if (const int32_t rc = check_blocks(E, blocks, n_in, blocks + n_in, std::size(blocks) - n_in)) return rc;
+    const StagedRows staged(d.params, d.param_stride, backward ? d.grad_params : nullptr, d.grad_stride, P, WEDM_HEAD_BLOCK);
     const dim3 grid((uint32_t)(((int64_t)d.rows + WEDM_HEAD_BLOCK - 1) / WEDM_HEAD_BLOCK)), block(WEDM_HEAD_BLOCK);
-    const size_t lds = in_lds || out_lds ? (size_t)WEDM_HEAD_BLOCK * (size_t)head_pitch((int)P) * 4 : 0;
     const hipStream_t s = (hipStream_t)stream;
     if (sample) {
-        if (in_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, true, false>), grid, block, lds, s, d);
-        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, false, false>), grid, block, lds, s, d);
+        if (staged.in) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, true, false>), grid, block, staged.lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_SAMPLE, false, false>), grid, block, staged.lds, s, d);
     } else if (!backward) {
-        if (in_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, true, false>), grid, block, lds, s, d);
-        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, false, false>), grid, block, lds, s, d);
-    } else if (in_lds) {
-        if (out_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, true>), grid, block, lds, s, d);
-        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, false>), grid, block, lds, s, d);
+        if (staged.in) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, true, false>), grid, block, staged.lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_EVALUATE, false, false>), grid, block, staged.lds, s, d);
+    } else if (staged.in) {
+        if (staged.out) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, true>), grid, block, staged.lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, true, false>), grid, block, staged.lds, s, d);
     } else {
-        if (out_lds) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, true>), grid, block, lds, s, d);
-        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, false>), grid, block, lds, s, d);
+        if (staged.out) hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, true>), grid, block, staged.lds, s, d);
+        else hipLaunchKernelGGL((wedm_head_kernel<WEDM_HEAD_BACKWARD, false, false>), grid, block, staged.lds, s, d);
     }
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return WEDM_OK;
-    g_create_error = std::string("wedm_policy_head: launch: ") + hipGetErrorString(e);
-    return WEDM_ERR_HIP;
+    return E.launched();
 }
 
 int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_ppo_loss: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_ppo_loss"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_ppo_desc& d = *desc;
-    if (d.flags & ~(int32_t)(WEDM_PPO_CLIP_VALUE | WEDM_PPO_COUNT | WEDM_PPO_MAIN | WEDM_PPO_FOLD)) return bad("undefined flag bits");
-    if (d.rows < 1) return bad("rows must be positive");
+    if (d.flags & ~(int32_t)(WEDM_PPO_CLIP_VALUE | WEDM_PPO_COUNT | WEDM_PPO_MAIN | WEDM_PPO_FOLD)) return E.bad("undefined flag bits");
+    if (d.rows < 1) return E.bad("rows must be positive");
     const int64_t tiles = ((int64_t)d.rows + WEDM_PPO_BLOCK - 1) / WEDM_PPO_BLOCK;
     if (tiles > WEDM_NORM_MAX_TILES)
-        return bad("a minibatch holds at most " + std::to_string(WEDM_NORM_MAX_TILES * WEDM_PPO_BLOCK) + " rows (" +
-                   std::to_string(WEDM_NORM_MAX_TILES) + " tiles of 256)");
-    if (d.n_src < 1) return bad("n_src must be positive");
-    if (d.n_modes < 1 || d.n_modes > WEDM_HEAD_MAX_MODES) return bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+        return E.bad("a minibatch holds at most " + std::to_string(WEDM_NORM_MAX_TILES * WEDM_PPO_BLOCK) + " rows (" +
+                     std::to_string(WEDM_NORM_MAX_TILES) + " tiles of 256)");
+    if (d.n_src < 1) return E.bad("n_src must be positive");
+    if (const int32_t rc = check_head_params(E, HEAD_SHAPE, d.n_modes, d.param_stride, d.grad_stride, d.lo, d.hi, d.log_span)) return rc;
     const int64_t P = 8 + d.n_modes;
-    if (d.param_stride < P || d.grad_stride < P) return bad("a stride is smaller than 8 + n_modes");
     if (!finite_f64(d.clip) || !finite_f64(d.vf_coef) || !finite_f64(d.ent_coef) || !finite_f64(d.clip_value))
-        return bad("clip, vf_coef, ent_coef and clip_value must be finite");
-    if (d.clip < 0.0 || d.clip_value < 0.0) return bad("clip and clip_value must not be negative");
-    for (int i = 0; i < 4; ++i) {
-        if (!finite_f64(d.lo[i]) || !finite_f64(d.hi[i]) || !finite_f64(d.log_span[i])) return bad("a bound or log_span is not finite");
-        if (!(d.hi[i] > d.lo[i])) return bad("hi <= lo");
-    }
+        return E.bad("clip, vf_coef, ent_coef and clip_value must be finite");
+    if (d.clip < 0.0 || d.clip_value < 0.0) return E.bad("clip and clip_value must not be negative");
+    if (const int32_t rc = check_head_params(E, HEAD_BOUNDS, d.n_modes, d.param_stride, d.grad_stride, d.lo, d.hi, d.log_span)) return rc;
     const bool all = !(d.flags & (WEDM_PPO_COUNT | WEDM_PPO_MAIN | WEDM_PPO_FOLD));
     const bool counted = d.valid || d.index;  // the number of live rows is not the host's to know
     const bool count = (all || (d.flags & WEDM_PPO_COUNT)) && counted, rows_pass = all || (d.flags & WEDM_PPO_MAIN);
     const bool fold = all || (d.flags & WEDM_PPO_FOLD), clip_value = d.flags & WEDM_PPO_CLIP_VALUE;
-    // the blocks by name: first byte, bytes the call may touch, alignment, whether a phase that runs needs it
-    struct Block {
-        const char* name;
-        uintptr_t lo, bytes, align;
-        bool needed;
-    };
     const uintptr_t n = (uintptr_t)d.rows, ns = (uintptr_t)d.n_src;
     const Block in[] = {
         {"params", (uintptr_t)d.params, (uintptr_t)((int64_t)(d.rows - 1) * d.param_stride + P) * 4, 4, rows_pass},
@@ -1739,98 +1738,70 @@ int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
         {"stats", (uintptr_t)d.stats, WEDM_PPO_STATS * 8, 8, fold},
         {"count", (uintptr_t)d.count, WEDM_PPO_COUNT_WORDS * 4, 4, counted && (count || rows_pass)},
     };
-    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.align != 0; };
-    for (const Block& b : in)
-        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
-    for (const Block& b : out)
-        if (unusable(b)) return bad(std::string(b.name) + " is null or not aligned to its element");
-    for (const Block& o : out) {
-        for (const Block& i : in)
-            if (o.lo && i.lo && o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(std::string(o.name) + " overlaps " + i.name);
-    }
-    const auto launched = [](const char* what) {
-        const hipError_t e = hipGetLastError();
-        if (e == hipSuccess) return (int32_t)WEDM_OK;
-        g_create_error = std::string("wedm_ppo_loss: ") + what + " launch: " + hipGetErrorString(e);
-        return (int32_t)WEDM_ERR_HIP;
-    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
     const hipStream_t s = (hipStream_t)stream;
     const dim3 grid((uint32_t)tiles), block(WEDM_PPO_BLOCK);
     if (count) {
         hipLaunchKernelGGL(wedm_ppo_zero_kernel, dim3(1), dim3(64), 0, s, d);
-        if (const int32_t rc = launched("zero")) return rc;
+        if (const int32_t rc = E.launched("zero")) return rc;
         hipLaunchKernelGGL(wedm_ppo_count_kernel, dim3((uint32_t)std::min<int64_t>(tiles, WEDM_PPO_COUNT_BLOCKS)), block, 0, s, d);
-        if (const int32_t rc = launched("count")) return rc;
+        if (const int32_t rc = E.launched("count")) return rc;
     }
     if (rows_pass) {
-        const bool in_lds = d.param_stride == P && (uintptr_t)d.params % 16 == 0;
-        const bool out_lds = d.grad_params && d.grad_stride == P && (uintptr_t)d.grad_params % 16 == 0;
-        const size_t lds = in_lds || out_lds ? (size_t)WEDM_PPO_BLOCK * (size_t)head_pitch((int)P) * 4 : 0;
+        const StagedRows staged(d.params, d.param_stride, d.grad_params, d.grad_stride, P, WEDM_PPO_BLOCK);
         const int32_t n_known = counted ? -1 : d.rows;
-        if (in_lds) {
-            if (out_lds) hipLaunchKernelGGL((wedm_ppo_main_kernel<true, true>), grid, block, lds, s, d, n_known);
-            else hipLaunchKernelGGL((wedm_ppo_main_kernel<true, false>), grid, block, lds, s, d, n_known);
+        if (staged.in) {
+            if (staged.out) hipLaunchKernelGGL((wedm_ppo_main_kernel<true, true>), grid, block, staged.lds, s, d, n_known);
+            else hipLaunchKernelGGL((wedm_ppo_main_kernel<true, false>), grid, block, staged.lds, s, d, n_known);
         } else {
-            if (out_lds) hipLaunchKernelGGL((wedm_ppo_main_kernel<false, true>), grid, block, lds, s, d, n_known);
-            else hipLaunchKernelGGL((wedm_ppo_main_kernel<false, false>), grid, block, lds, s, d, n_known);
+            if (staged.out) hipLaunchKernelGGL((wedm_ppo_main_kernel<false, true>), grid, block, staged.lds, s, d, n_known);
+            else hipLaunchKernelGGL((wedm_ppo_main_kernel<false, false>), grid, block, staged.lds, s, d, n_known);
         }
-        if (const int32_t rc = launched("main")) return rc;
+        if (const int32_t rc = E.launched("main")) return rc;
     }
     if (fold) {
-        int32_t padded = 1, per = 1;  // the smallest power of two >= tiles; tiles per lane: the power of two with 256 * per >= tiles
+        int32_t padded = 1;  // the smallest power of two >= tiles
         while (padded < tiles) padded *= 2;
-        while (256 * per < tiles) per *= 2;
-        hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, per);
-        if (const int32_t rc = launched("fold")) return rc;
+        hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, fold_per(tiles));
+        if (const int32_t rc = E.launched("fold")) return rc;
     }
     return WEDM_OK;
 }
 
 int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_episode_log: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_episode_log"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_elog_desc& d = *desc;
     const int32_t phases = WEDM_ELOG_COUNT | WEDM_ELOG_SCATTER | WEDM_ELOG_COMMIT;
-    if (d.flags & ~phases) return bad("undefined flag bits");
+    if (d.flags & ~phases) return E.bad("undefined flag bits");
     const bool every = !(d.flags & phases);
     const bool count = every || (d.flags & WEDM_ELOG_COUNT), scatter = every || (d.flags & WEDM_ELOG_SCATTER);
     const bool commit = every || (d.flags & WEDM_ELOG_COMMIT);
-    if (d.num_envs < 1) return bad("num_envs must be positive");
-    if (d.capacity < 1) return bad("capacity must be positive");
-    const int64_t tiles = ((int64_t)d.num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
-    if (d.tile_offset < 0 || d.n_tiles_total < 1 || d.n_tiles_total > WEDM_NORM_MAX_TILES || d.tile_offset + tiles > d.n_tiles_total)
-        return bad("tile range outside the workspace: tile_offset + ceil(num_envs / 256) <= n_tiles_total <= " +
-                   std::to_string(WEDM_NORM_MAX_TILES) + " must hold");
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.capacity < 1) return E.bad("capacity must be positive");
+    const int64_t tiles = tile_range(E, d.num_envs, d.tile_offset, d.n_tiles_total);
+    if (!tiles) return WEDM_ERR_BAD_ARG;
     if (d.n_planes < 1 || d.n_planes > WEDM_ELOG_MAX_PLANES)
-        return bad("n_planes outside [1, " + std::to_string(WEDM_ELOG_MAX_PLANES) + "]");
-    // the blocks by name: first byte, bytes from there to one past the last the call may touch, element size
-    struct Block {
-        std::string name;
-        uintptr_t lo, bytes, elem;
-        bool needed;
-    };
+        return E.bad("n_planes outside [1, " + std::to_string(WEDM_ELOG_MAX_PLANES) + "]");
     std::vector<Block> in, out;
     const uintptr_t n = (uintptr_t)d.num_envs, cap = (uintptr_t)d.capacity;
     int64_t rows_in_all = 0;
     for (int32_t p = 0; p < d.n_planes; ++p) {
         const wedm_elog_plane& pl = d.plane[p];
         const std::string who = "plane " + std::to_string(p);
-        if (pl.n_rows < 1) return bad(who + ": n_rows must be positive");
+        if (pl.n_rows < 1) return E.bad(who + ": n_rows must be positive");
         rows_in_all += pl.n_rows;
-        if (pl.kind < WEDM_ELOG_LAST || pl.kind > WEDM_ELOG_SUM_I32) return bad(who + ": kind is not defined");
+        if (pl.kind < WEDM_ELOG_LAST || pl.kind > WEDM_ELOG_SUM_I32) return E.bad(who + ": kind is not defined");
         const bool sum = pl.kind != WEDM_ELOG_LAST;
         if (sum ? pl.elem_bytes != (pl.kind == WEDM_ELOG_SUM_F64 ? 8 : 4) : (pl.elem_bytes != 1 && pl.elem_bytes != 4 && pl.elem_bytes != 8))
-            return bad(who + ": elem_bytes is not one its kind takes (LAST: 1, 4 or 8; SUM_F32 and SUM_I32: 4; SUM_F64: 8)");
-        if (pl.src_stride < d.num_envs) return bad(who + ": stride smaller than num_envs");
+            return E.bad(who + ": elem_bytes is not one its kind takes (LAST: 1, 4 or 8; SUM_F32 and SUM_I32: 4; SUM_F64: 8)");
+        if (pl.src_stride < d.num_envs) return E.bad(who + ": stride smaller than num_envs");
         const uintptr_t eb = (uintptr_t)pl.elem_bytes, r1 = (uintptr_t)(pl.n_rows - 1);
-        in.push_back({who + ".src", (uintptr_t)pl.src, (r1 * (uintptr_t)pl.src_stride + n) * eb, eb, scatter});
-        out.push_back({who + ".dst", (uintptr_t)pl.dst, (r1 * cap + cap) * (sum ? 8 : eb), sum ? 8 : eb, scatter});
-        if (sum) out.push_back({who + ".acc", (uintptr_t)pl.acc, (r1 * n + n) * 8, 8, scatter});
+        in.push_back({".src", (uintptr_t)pl.src, (r1 * (uintptr_t)pl.src_stride + n) * eb, eb, scatter, false, p});
+        out.push_back({".dst", (uintptr_t)pl.dst, (r1 * cap + cap) * (sum ? 8 : eb), sum ? 8 : eb, scatter, false, p});
+        if (sum) out.push_back({".acc", (uintptr_t)pl.acc, (r1 * n + n) * 8, 8, scatter, false, p});
     }
-    if (rows_in_all > WEDM_ELOG_MAX_ROWS) return bad("more than " + std::to_string(WEDM_ELOG_MAX_ROWS) + " rows in all");
+    if (rows_in_all > WEDM_ELOG_MAX_ROWS) return E.bad("more than " + std::to_string(WEDM_ELOG_MAX_ROWS) + " rows in all");
     in.push_back({"terminated", (uintptr_t)d.terminated, n, 1, count || scatter});
     in.push_back({"truncated", (uintptr_t)d.truncated, n, 1, false});
     in.push_back({"mask", (uintptr_t)d.mask, n, 1, false});
@@ -1838,35 +1809,19 @@ int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream) {
     out.push_back({"stamp_out", (uintptr_t)d.stamp_out, cap * 8, 8, scatter});
     out.push_back({"head", (uintptr_t)d.head, 16, 8, scatter || commit});
     out.push_back({"tile_counts", (uintptr_t)d.tile_counts, (uintptr_t)d.n_tiles_total * 4, 4, true});
-    const auto unusable = [](const Block& b) { return (b.needed && !b.lo) || b.lo % b.elem != 0; };
-    for (const Block& b : in)
-        if (unusable(b)) return bad(b.name + " is null or not aligned to its element");
-    for (const Block& b : out)
-        if (unusable(b)) return bad(b.name + " is null or not aligned to its element");
-    for (const Block& o : out) {
-        for (const Block& i : in) {
-            if (!o.lo || !i.lo) continue;
-            if (o.lo < i.lo + i.bytes && i.lo < o.lo + o.bytes) return bad(o.name + " overlaps " + i.name);
-        }
-    }
-    const auto launched = [](const char* what) {
-        const hipError_t e = hipGetLastError();
-        if (e == hipSuccess) return (int32_t)WEDM_OK;
-        g_create_error = std::string("wedm_episode_log: ") + what + " launch: " + hipGetErrorString(e);
-        return (int32_t)WEDM_ERR_HIP;
-    };
+    if (const int32_t rc = check_blocks(E, in.data(), in.size(), out.data(), out.size())) return rc;
     const hipStream_t s = (hipStream_t)stream;
     if (count) {
         hipLaunchKernelGGL(wedm_elog_count_kernel, dim3((uint32_t)tiles), dim3(WEDM_NORM_TILE), 0, s, d);
-        if (const int32_t rc = launched("count")) return rc;
+        if (const int32_t rc = E.launched("count")) return rc;
     }
     if (scatter) {
         hipLaunchKernelGGL(wedm_elog_scatter_kernel, dim3((uint32_t)tiles, (uint32_t)d.n_planes), dim3(WEDM_NORM_TILE), 0, s, d);
-        if (const int32_t rc = launched("scatter")) return rc;
+        if (const int32_t rc = E.launched("scatter")) return rc;
     }
     if (commit) {
         hipLaunchKernelGGL(wedm_elog_commit_kernel, dim3(1), dim3(64), 0, s, d);
-        if (const int32_t rc = launched("commit")) return rc;
+        if (const int32_t rc = E.launched("commit")) return rc;
     }
     return WEDM_OK;
 }
@@ -1891,90 +1846,74 @@ static const char* geom_derive_desc_error(const wedm_geom_derive_desc& d) {
 
 int32_t wedm_derive_geometry(const wedm_geom_derive_desc* desc, const double* height, const int32_t* diameter_idx,
                              const int32_t* material_idx, const uint8_t* mask, int32_t* status, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_derive_geometry: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_derive_geometry"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_geom_derive_desc& d = *desc;
-    if (!height || !diameter_idx) return bad("null height or diameter index array");
+    if (!height || !diameter_idx) return E.bad("null height or diameter index array");
     if ((uintptr_t)height % 8 || (uintptr_t)diameter_idx % 4 || (uintptr_t)material_idx % 4)
-        return bad("a pointer is not aligned to its element");
-    if (const char* why = geom_derive_desc_error(d)) return bad(why);
+        return E.bad("a pointer is not aligned to its element");
+    if (const char* why = geom_derive_desc_error(d)) return E.bad(why);
     const dim3 grid((uint32_t)(((int64_t)d.num_envs + 255) / 256));
     hipLaunchKernelGGL(wedm_derive_geometry_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, height, diameter_idx,
                        material_idx, mask, status);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_create_error = std::string("wedm_derive_geometry: launch: ") + hipGetErrorString(e);
-        return WEDM_ERR_HIP;
-    }
-    return WEDM_OK;
+    return E.launched();
 }
 
 int32_t wedm_draw_episode(const wedm_draw_desc* desc, const uint8_t* mask, int32_t* draw_count, void* stream) {
-    const auto bad = [](const std::string& msg) {
-        g_create_error = "wedm_draw_episode: " + msg;
-        return (int32_t)WEDM_ERR_BAD_ARG;
-    };
-    if (!desc) return bad("null descriptor");
+    const Entry E{"wedm_draw_episode"};
+    if (!desc) return E.bad("null descriptor");
     const wedm_draw_desc& d = *desc;
-    if (!draw_count || (uintptr_t)draw_count % 4) return bad("draw_count is null or not aligned to its element");
-    if (d.num_envs < 1) return bad("num_envs must be positive");
-    if (d.stride < d.num_envs) return bad("stride smaller than num_envs");
-    if (d.dynamic != 0 && d.dynamic != 1) return bad("dynamic must be 0 or 1");
+    if (!draw_count || (uintptr_t)draw_count % 4) return E.bad("draw_count is null or not aligned to its element");
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.stride < d.num_envs) return E.bad("stride smaller than num_envs");
+    if (d.dynamic != 0 && d.dynamic != 1) return E.bad("dynamic must be 0 or 1");
     bool envp = false;
     for (int s = 0; s < WEDM_DRAW_SLOTS; ++s) {
         const wedm_draw_slot& sl = d.slot[s];
         const bool choice = s == WEDM_DS_MATERIAL || s == WEDM_DS_DIAMETER;
         const std::string name = "slot " + std::to_string(s);
         if (sl.kind == WEDM_DRAW_NONE) continue;
-        if (sl.kind != (choice ? WEDM_DRAW_CHOICE : WEDM_DRAW_UNIFORM)) return bad(name + ": a kind this slot does not take");
+        if (sl.kind != (choice ? WEDM_DRAW_CHOICE : WEDM_DRAW_UNIFORM)) return E.bad(name + ": a kind this slot does not take");
         if (choice) {
-            if (sl.k < 1) return bad(name + ": a choice needs k >= 1");
+            if (sl.k < 1) return E.bad(name + ": a choice needs k >= 1");
         } else {
-            if (!finite_f64(sl.lo) || !finite_f64(sl.hi) || !finite_f64(sl.span)) return bad(name + ": bounds must be finite");
-            if (sl.lo > sl.hi) return bad(name + ": lo > hi");
+            if (!finite_f64(sl.lo) || !finite_f64(sl.hi) || !finite_f64(sl.span)) return E.bad(name + ": bounds must be finite");
+            if (sl.lo > sl.hi) return E.bad(name + ": lo > hi");
         }
         envp |= s < WEDM_DRAW_ENVP_SLOTS;
     }
     const auto misplaced = [](const void* p, size_t align) { return !p || (uintptr_t)p % align; };
     if (envp) {
-        if (misplaced(d.envp_src, 8) || misplaced(d.envp_rows, 8)) return bad("envp_src or envp_rows is null or misaligned");
-        if (!finite_f64(d.base_flow_rate) || !finite_f64(d.dt_s)) return bad("base_flow_rate and dt_s must be finite");
+        if (misplaced(d.envp_src, 8) || misplaced(d.envp_rows, 8)) return E.bad("envp_src or envp_rows is null or misaligned");
+        if (!finite_f64(d.base_flow_rate) || !finite_f64(d.dt_s)) return E.bad("base_flow_rate and dt_s must be finite");
     }
     const bool has_mat = d.slot[WEDM_DS_MATERIAL].kind != WEDM_DRAW_NONE, has_h = d.slot[WEDM_DS_HEIGHT].kind != WEDM_DRAW_NONE,
                has_dia = d.slot[WEDM_DS_DIAMETER].kind != WEDM_DRAW_NONE;
     if (has_mat) {
         if (misplaced(d.material_index, 8) || misplaced(d.wmat_table, 8) || misplaced(d.wmat_rows, 8))
-            return bad("material_index, wmat_table or wmat_rows is null or misaligned");
+            return E.bad("material_index, wmat_table or wmat_rows is null or misaligned");
         if (!d.dynamic && (misplaced(d.wmat_geom_table, 8) || misplaced(d.geom_f64, 8)))
-            return bad("wmat_geom_table or geom_f64 is null or misaligned");
+            return E.bad("wmat_geom_table or geom_f64 is null or misaligned");
     }
-    if ((has_h || has_dia) && !d.dynamic) return bad("height and diameter are drawn with dynamic geometry only");
+    if ((has_h || has_dia) && !d.dynamic) return E.bad("height and diameter are drawn with dynamic geometry only");
     if (d.dynamic && (has_mat || has_h || has_dia)) {
         const wedm_geom_derive_desc& g = d.geom;
-        if (const char* why = geom_derive_desc_error(g)) return bad(std::string("geom: ") + why);
-        if (g.num_envs != d.num_envs || g.stride != d.stride) return bad("geom: num_envs or stride differs from the descriptor's");
-        if (misplaced(d.height, 8) || misplaced(d.diameter_index, 4)) return bad("height or diameter_index is null or misaligned");
-        if ((uintptr_t)d.material_index % 8 || (uintptr_t)d.geom_status % 4) return bad("material_index or geom_status is misaligned");
-        if (has_mat && d.slot[WEDM_DS_MATERIAL].k != g.n_materials) return bad("k of the material slot is not geom.n_materials");
-        if (has_dia && d.slot[WEDM_DS_DIAMETER].k > g.n_diameters) return bad("k of the diameter slot exceeds geom.n_diameters");
+        if (const char* why = geom_derive_desc_error(g)) return E.bad(std::string("geom: ") + why);
+        if (g.num_envs != d.num_envs || g.stride != d.stride) return E.bad("geom: num_envs or stride differs from the descriptor's");
+        if (misplaced(d.height, 8) || misplaced(d.diameter_index, 4)) return E.bad("height or diameter_index is null or misaligned");
+        if ((uintptr_t)d.material_index % 8 || (uintptr_t)d.geom_status % 4) return E.bad("material_index or geom_status is misaligned");
+        if (has_mat && d.slot[WEDM_DS_MATERIAL].k != g.n_materials) return E.bad("k of the material slot is not geom.n_materials");
+        if (has_dia && d.slot[WEDM_DS_DIAMETER].k > g.n_diameters) return E.bad("k of the diameter slot exceeds geom.n_diameters");
         if (has_h) {  // the kernel's own capacity test on the largest height: cells is monotone in h, so no draw is refused
             const wedm_draw_slot& sl = d.slot[WEDM_DS_HEIGHT];
             const double cells = ((g.buffer_len_bottom + sl.hi) + g.buffer_len_top) / g.segment_len;
-            if (!(sl.lo > 0.0)) return bad("height range must have lo > 0");
-            if (!(cells < (double)g.n_seg_max + 1.0)) return bad("height range reaches past n_seg_max cells");
+            if (!(sl.lo > 0.0)) return E.bad("height range must have lo > 0");
+            if (!(cells < (double)g.n_seg_max + 1.0)) return E.bad("height range reaches past n_seg_max cells");
         }
     }
     const dim3 grid((uint32_t)(((int64_t)d.num_envs + 255) / 256));
     hipLaunchKernelGGL(wedm_draw_episode_kernel, grid, dim3(256), 0, (hipStream_t)stream, d, mask, draw_count);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        g_create_error = std::string("wedm_draw_episode: launch: ") + hipGetErrorString(e);
-        return WEDM_ERR_HIP;
-    }
-    return WEDM_OK;
+    return E.launched();
 }
 
 int32_t wedm_debug_registry(int32_t index, int32_t* kernel, int32_t* lanes, uint32_t* forms) {

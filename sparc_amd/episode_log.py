@@ -96,12 +96,7 @@ def device_episode_log(desc: "_abi.ElogDesc", device) -> None:
 
     from . import _lib
 
-    L = _lib.load()
-    device = torch.device(device)
-    with torch.cuda.device(device):
-        rc = L.wedm_episode_log(C.byref(desc), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != _abi.OK:
-        raise _lib.WedmError(rc, (L.wedm_last_error(None) or b"").decode())
+    _lib.call_stateless(_lib.load().wedm_episode_log, torch.device(device), C.byref(desc))
 
 
 def _np(t: torch.Tensor) -> np.ndarray:

@@ -234,12 +234,7 @@ def device_policy_head(desc: "_abi.HeadDesc", device) -> None:
     """`wedm_policy_head` on ``device`` and torch's current stream, for callers that hold no environment."""
     from . import _lib
 
-    L = _lib.load()
-    device = torch.device(device)
-    with torch.cuda.device(device):
-        rc = L.wedm_policy_head(C.byref(desc), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != _abi.OK:
-        raise _lib.WedmError(rc, (L.wedm_last_error(None) or b"").decode())
+    _lib.call_stateless(_lib.load().wedm_policy_head, torch.device(device), C.byref(desc))
 
 
 # ------------------------------------------------------------------------------------------------ the head

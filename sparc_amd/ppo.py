@@ -157,12 +157,7 @@ def device_ppo_loss(desc: "_abi.PpoDesc", device) -> None:
     """`wedm_ppo_loss` on ``device`` and torch's current stream, for callers that hold no environment."""
     from . import _lib
 
-    L = _lib.load()
-    device = torch.device(device)
-    with torch.cuda.device(device):
-        rc = L.wedm_ppo_loss(C.byref(desc), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != _abi.OK:
-        raise _lib.WedmError(rc, (L.wedm_last_error(None) or b"").decode())
+    _lib.call_stateless(_lib.load().wedm_ppo_loss, torch.device(device), C.byref(desc))
 
 
 class PPOStats:

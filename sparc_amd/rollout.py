@@ -107,12 +107,7 @@ def device_gae(desc: "_abi.GaeDesc", device) -> None:
     """`wedm_gae` on ``device`` and torch's current stream, for callers that hold no environment."""
     from . import _lib
 
-    L = _lib.load()
-    device = torch.device(device)
-    with torch.cuda.device(device):
-        rc = L.wedm_gae(C.byref(desc), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != _abi.OK:
-        raise _lib.WedmError(rc, (L.wedm_last_error(None) or b"").decode())
+    _lib.call_stateless(_lib.load().wedm_gae, torch.device(device), C.byref(desc))
 
 
 def _leaves(action, path: str = "action") -> List[Tuple[str, torch.Tensor]]:

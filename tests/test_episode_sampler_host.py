@@ -407,6 +407,36 @@ def test_header_declares_and_library_exports_the_call():
     assert (ref.SLOT_MATERIAL, ref.SLOT_HEIGHT, ref.SLOT_DIAMETER) == (15, 16, 17)
 
 
+def test_bad_arguments_are_refused_before_anything_is_launched():
+    """Every pointer below is an address nobody owns: each case returns WEDM_ERR_BAD_ARG with exactly this text."""
+    L = _lib.load()
+    uniform, choice = _abi.DRAW_UNIFORM, _abi.DRAW_CHOICE
+
+    def answer(draw_count=8, slots={}, **kw):
+        d = _abi.DrawDesc(**dict(dict(num_envs=4, stride=4), **kw))
+        for s, fields in slots.items():
+            for name, value in fields.items():
+                setattr(d.slot[s], name, value)
+        rc = L.wedm_draw_episode(C.byref(d), None, draw_count, None)
+        return rc, L.wedm_last_error(None).decode()
+
+    unit = dict(kind=uniform, lo=0.0, hi=1.0, span=1.0)
+    for kw, text in ((dict(draw_count=None), "draw_count is null or not aligned to its element"),
+                     (dict(draw_count=6), "draw_count is null or not aligned to its element"),
+                     (dict(num_envs=0), "num_envs must be positive"),
+                     (dict(dynamic=2), "dynamic must be 0 or 1"),
+                     (dict(slots={0: dict(kind=choice, k=2)}), "slot 0: a kind this slot does not take"),
+                     (dict(slots={15: dict(kind=choice, k=0)}), "slot 15: a choice needs k >= 1"),
+                     (dict(slots={3: dict(unit, lo=float("inf"))}), "slot 3: bounds must be finite"),
+                     (dict(slots={3: dict(unit, lo=2.0)}), "slot 3: lo > hi"),
+                     (dict(slots={0: unit}), "envp_src or envp_rows is null or misaligned"),
+                     (dict(slots={0: unit}, envp_src=8, envp_rows=8, dt_s=float("nan")), "base_flow_rate and dt_s must be finite"),
+                     (dict(slots={15: dict(kind=choice, k=2)}), "material_index, wmat_table or wmat_rows is null or misaligned"),
+                     (dict(slots={16: unit}), "height and diameter are drawn with dynamic geometry only"),
+                     (dict(slots={16: unit}, dynamic=1), "geom: null combination table or geometry block")):
+        assert answer(**kw) == (_abi.ERR_BAD_ARG, "wedm_draw_episode: " + text), kw
+
+
 def test_descriptor_mirrors_the_header(tmp_path):
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "wedm_hip.h"', "int main(void) {"]
     for cname, mirror in (("wedm_draw_slot", _abi.DrawSlot), ("wedm_draw_desc", _abi.DrawDesc)):

@@ -111,6 +111,33 @@ def test_header_declares_and_library_exports_the_call():
     assert b"stride smaller than num_envs" in L.wedm_last_error(None)
 
 
+def test_bad_arguments_are_refused_before_anything_is_launched():
+    """Every pointer below is an address nobody owns: each case returns WEDM_ERR_BAD_ARG with exactly this text."""
+    L = _lib.load()
+
+    def answer(height=8, diameter_idx=8, material_idx=None, **kw):
+        f = dict(segment_len=0.2, buffer_len_bottom=2.0, buffer_len_top=2.0, contact_offset_top=1.0, num_envs=4, n_seg_max=70,
+                 stride=4, combo=8, n_diameters=1, n_materials=1, geom_f64=8, geom_i32=8)
+        f.update(kw)
+        rc = L.wedm_derive_geometry(C.byref(_abi.GeomDeriveDesc(**f)), height, diameter_idx, material_idx, None, None, None)
+        return rc, L.wedm_last_error(None).decode()
+
+    for kw, text in ((dict(height=None), "null height or diameter index array"),
+                     (dict(diameter_idx=None), "null height or diameter index array"),
+                     (dict(height=9), "a pointer is not aligned to its element"),
+                     (dict(material_idx=6), "a pointer is not aligned to its element"),
+                     (dict(combo=None), "null combination table or geometry block"),
+                     (dict(geom_i32=10), "a pointer is not aligned to its element"),
+                     (dict(num_envs=0), "num_envs must be positive"),
+                     (dict(n_seg_max=0), "n_seg_max outside [1, 2^29]"),
+                     (dict(n_materials=0), "n_diameters and n_materials must be positive"),
+                     (dict(segment_len=0.0), "segment_len must be finite and positive"),
+                     (dict(buffer_len_top=-1.0), "buffer lengths must be finite and not negative"),
+                     (dict(contact_offset_top=float("inf")), "contact_offset_top must be finite"),
+                     (dict(zone_start0=-1), "zone_start0 or contact_bottom0 outside [0, 2^29]")):
+        assert answer(**kw) == (_abi.ERR_BAD_ARG, "wedm_derive_geometry: " + text), kw
+
+
 def test_enum_and_descriptor_mirror_the_header(tmp_path):
     text = (ROOT / "include" / "wedm_hip.h").read_text()
     body = re.sub(r"/\*.*?\*/", "", re.search(r"enum wedm_geomc_field \{(.*?)\};", text, flags=re.S).group(1), flags=re.S)
