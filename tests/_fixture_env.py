@@ -148,30 +148,49 @@ def run_fixture_stepwise(env, fx, *, exact_floats, every=1):
     return checked
 
 
-def run_fixture_through_trace(env, fx, *, exact_floats, float_rtol=1e-12, T_atol=1e-4, extra=()):
-    """Run the fixture's constant action for its whole length in fused launches and compare the
+def fixture_launches(fx, lo, hi, interval):
+    """[(row of fx.actions, steps)] covering steps lo ... hi - 1: launches of at most `interval` steps that never span a
+    step at which the reference's driver handed `step()` another action (a constant-action fixture: chunks of `interval`)."""
+    out, pos = [], lo
+    while pos < hi:
+        row = int(fx.action_idx[pos])
+        end = pos + 1
+        while end < hi and end - pos < interval and int(fx.action_idx[end]) == row:
+            end += 1
+        out.append((row, end - pos))
+        pos = end
+    return out
+
+
+def run_fixture_through_trace(env, fx, *, exact_floats, float_rtol=1e-12, T_atol=1e-4, extra=(), run=None):
+    """Run the fixture's recorded actions for its whole length in fused launches and compare the
     traced trajectory of environment `env_id` with the reference's recording.  `extra`: further EDMState names to
-    trace and return (not compared here)."""
+    trace and return (not compared here).  `run`: a driver `run(env)` that advances the environment by the fixture's
+    steps itself (a controller under `run_controlled`) in place of the recorded actions."""
     import torch
 
     e = int(fx.meta["env_id"])
-    assert len(fx.actions) == 1, "constant-action fixtures only"
-    servo, tv, on, off, mode = fx.actions[0]
-    act = env.make_action(servo, tv, int(mode), on, off)
     names = sorted(set(TRACE_INT.values()) | set(TRACE_EXACT.values()) | set(TRACE_CLOSE.values()) | set(extra))
     keep_stepping = getattr(env, "freeze_terminated", True) is False
     if keep_stepping:
         names = sorted(set(names) | {"done"})
     trace = env.bind_trace(names, every=1, capacity=fx.n_steps, envs=(e, 1))
-    interval = env.servo_interval // env.dt
+    # physics steps between two latches: the latch tests `time_since_servo >= servo_interval`, so an interval that is no
+    # multiple of dt takes ceil(servo_interval / dt) steps (100 us at dt = 3: 34, not 33)
+    interval = -(-env.servo_interval // env.dt)
     for lo, hi, reset in fixture_segments(fx):   # (one segment unless the fixture holds a second episode)
         if reset is not None:
             apply_fixture_reset(env, reset)
-        left = hi - lo
-        while left > 0:
-            k = min(interval, left)
-            env.step_many(act, k)
-            left -= k
+        if run is not None:
+            assert (lo, hi) == (0, fx.n_steps), "a driver runs a fixture of one episode"
+            run(env)
+            continue
+        acts = {}
+        for row, k in fixture_launches(fx, lo, hi, interval):
+            if row not in acts:
+                servo, tv, on, off, mode = fx.actions[row]
+                acts[row] = env.make_action(servo, tv, int(mode), on, off)
+            env.step_many(acts[row], k)
     got = {k: v[:, 0].cpu().numpy() for k, v in trace.read().items()}
     if keep_stepping:  # WEDM_B_DONE = `terminated` as the reference's step() returns it, at every microsecond
         assert np.array_equal(got["done"].astype(np.int64), fx.int_row("terminated").astype(np.int64)), "terminated"

@@ -25,6 +25,44 @@ TRACE_EVERY = 8       # after the bind: the single microsecond (us 1) holds no s
 TRACE_CAPACITY = 64
 WIDE_AUTO_MAX_LANES = 65536   # WEDM_WIDE_AUTO_MAX_LANES
 
+# The time grids every recipe runs on: name -> (config.dt [us], config.servo_interval [us]).  On g0 the recipes' 597 steps end
+# before the first control step; on g1 and g2 the environments start at staggered `time_since_servo` (`stagger`) and every
+# launch gets an action of its own (`action_leaves`), so every launch of every recipe holds control steps.  `plan_launch`
+# reads neither value: `Recipe.expected` is the same on every grid.
+GRIDS = {"g0": (1, 1000), "g1": (1, 100), "g2": (3, 100)}
+ON_TIMES = (2.0, 2.5, 3.0, 4.0)
+
+
+def steps_per_interval(grid: str) -> int:
+    """Physics steps between two latches: the latch tests `time_since_servo >= servo_interval` (wire_edm.py:117)."""
+    dt, interval = GRIDS[grid]
+    return -(-interval // dt)
+
+
+def stagger(grid: str, seq: str, n_envs: int):
+    """int[n_envs]: `time_since_servo` after the reset, so that environment e first latches in step number
+    phase(e) = 7 e mod span of the handle (counted from 0), span = min(steps of the handle's launches, steps between two
+    latches): servo_interval - dt * phase, plus e mod dt where dt > 1 (the latch then sees values past the interval).
+    Phase 0 starts AT the interval.  Neighbouring lanes of a wave are 7 steps apart: latching and non-latching lanes mix."""
+    dt, interval = GRIDS[grid]
+    span = min(sum(us for us, _ in SEQS[seq]), steps_per_interval(grid))
+    return [interval - dt * ((7 * e) % span) + e % dt for e in range(n_envs)]
+
+
+def action_leaves(modes, launch: int, n_envs: int):
+    """(servo, target voltage, current mode, ON, OFF) of launch number `launch`, one value per environment in every leaf;
+    for every environment every leaf differs from its value in the launch before and in launch 0 (ON: four values, the
+    offsets 1, 2, 3 in turn; the other leaves differ between any two of a handle's launches, at most 7).
+    `modes`: the current modes with crater data."""
+    e = range(n_envs)
+    servo = [0.05 + 0.002 * ((3 * k + 5 * launch) % 41) + 0.0001 * launch for k in e]
+    volt = [70.0 + 0.25 * ((11 * k + 17 * launch) % 120) + 0.01 * launch for k in e]
+    mode = [modes[(3 * k + launch) % len(modes)] for k in e]
+    on = [ON_TIMES[(k + (1 + (launch - 1) % 3 if launch else 0)) % 4] for k in e]
+    off = [10.0 + 0.125 * ((13 * k + 29 * launch) % 160) + 0.01 * launch for k in e]
+    return servo, volt, mode, on, off
+
+
 # launches per handle: (microseconds, trace bound?)
 SEQS = {
     "plain": ((1, False), (1, False), (7, False), (290, False), (1, True), (7, True), (290, True)),

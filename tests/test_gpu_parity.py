@@ -947,12 +947,35 @@ def test_clock_high_word_across_the_32_bit_wrap_matches_oracle(variant, lanes):
     """`state.time` past 2**31 and 2**32 us: the kernels carry the low word (also the Philox counter word) through the
     launch and bump row TIME_HI when it wrapped inside it; every kernel == the oracle on every byte, in fused and in
     single-microsecond launches, with autoreset (a re-initialised environment starts again at 0 / 0)."""
+    _clock_wrap(variant, lanes, 1, [2**31 - 300, 2**32 - 300, 2**32 - 1, 5 * 2**32 - 40])
+
+
+# starts from which the clock's low word steps OVER 2**31 and 2**32 (never landing on them): in the first launch of one
+# step, inside the fused launch of 298 steps and in the last launch
+CLOCK_STARTS = {3: [2**31 - 301, 2**32 - 899, 2**32 - 1, 2**32 - 2, 2**32 - 3002, 5 * 2**32 - 40],
+                7: [2**31 - 300, 2**32 - 1000, 2**32 - 1, 2**32 - 6, 2**32 - 4000, 5 * 2**32 - 40]}
+
+
+@pytest.mark.parametrize("dt", [3, 7])
+@pytest.mark.parametrize("variant,lanes", [(1, 0), (2, 4), (3, 8), (4, 4), (5, 0), (6, 8), (7, 0), (9, 8)])
+def test_clock_high_word_across_the_32_bit_wrap_at_other_physics_steps(variant, lanes, dt):
+    """The same with config.dt = 3 and 7: the low word passes 2**32 without ever being 0 (2**32 - 1 -> 2**32 + 2), so a
+    wrap test on `time == 0`, or one that assumes a step of 1 us, misses it."""
+    for s in CLOCK_STARTS[dt]:
+        for edge in (2**31, 2**32, 5 * 2**32):
+            assert (edge - s) % dt != 0 or edge < s or edge - s > 1502 * dt, (s, edge)
+        assert any(s < edge <= s + 1502 * dt for edge in (2**31, 2**32, 5 * 2**32)), s
+    _clock_wrap(variant, lanes, dt, CLOCK_STARTS[dt])
+
+
+def _clock_wrap(variant, lanes, dt, starts):
     n = 192
-    kw = dict(autoreset=True, config=EnvironmentConfig(target_cutting_distance=5000.0))
+    kw = dict(autoreset=True, config=EnvironmentConfig(target_cutting_distance=5000.0) if dt == 1 else
+              EnvironmentConfig(target_cutting_distance=5000.0, dt=dt))
     if variant == 7:   # (the register kernel holds wires of at most 128 segments)
         kw["wire_params"] = WireModuleParameters(segment_len=0.625)
     gpu, cpu = make_pair(n, **kw)
-    start = torch.tensor([2**31 - 300, 2**32 - 300, 2**32 - 1, 5 * 2**32 - 40] * (n // 4))
+    start = torch.tensor(starts * (n // len(starts)))
     for env in (gpu, cpu):
         env.reset(seed=5)
         close_gap(env, 22.0, 10.0)
@@ -968,8 +991,8 @@ def test_clock_high_word_across_the_32_bit_wrap_matches_oracle(variant, lanes):
     t = gpu.state.time.cpu()
     alive = gpu.state.episode.cpu() == 0
     assert alive.sum() > n // 2 and (~alive).sum() > 0
-    assert torch.equal(t[alive], (start + 1502)[alive]) and int(t[~alive].max()) < 1502
-    assert (gpu.state.time_high32.cpu()[alive] == ((start + 1502) >> 32)[alive]).all()
+    assert torch.equal(t[alive], (start + 1502 * dt)[alive]) and int(t[~alive].max()) < 1502 * dt
+    assert (gpu.state.time_high32.cpu()[alive] == ((start + 1502 * dt) >> 32)[alive]).all()
 
 
 def test_float64_stencil_on_the_tile_walk_over_wire_lengths_and_lane_counts():
@@ -1335,6 +1358,22 @@ def test_two_microsecond_physics_step_fixture_on_gpu(golden_dir):
     env = env_from_fixture(fx, 64, device="cuda:0")
     got = run_fixture_through_trace(env, fx, exact_floats=False)
     assert got["time"][:3].tolist() == [2, 4, 6]
+
+
+@pytest.mark.parametrize("name", ["f20_dt3_gap_controller_philox_env5", "f20_dt7_schedule_velocity_philox_env6",
+                                  "f20_dt3_voltage_controller_philox_env3"])
+def test_off_grid_fixtures_on_gpu(golden_dir, name):
+    """F20: dt = 3 / servo_interval = 100 and dt = 7 / servo_interval = 50 (latches at time_since_servo = 102 and 56), the
+    recorded action rows handed to launches of at most one control interval."""
+    from tests._fixture_env import env_from_fixture, run_fixture_through_trace
+    from tests._golden import Fixture
+
+    fx = Fixture(golden_dir / f"{name}.npz")
+    env = env_from_fixture(fx, 64, device="cuda:0")
+    got = run_fixture_through_trace(env, fx, exact_floats=False)
+    steps = -(-env.servo_interval // env.dt)
+    assert got["time"][:3].tolist() == [env.dt, 2 * env.dt, 3 * env.dt] and got["time_since_servo"].max() == steps * env.dt
+    assert (got["spark_state"] == 1).sum() >= 15
 
 
 def test_custom_wire_material_fixture_on_gpu(golden_dir):

@@ -242,6 +242,25 @@ def test_the_clock_is_64_bit_and_no_launch_count_limits_a_run():
         long_dt.step_many(long_dt.make_action(), 2**29)
 
 
+def test_a_launch_of_2_to_the_31_microseconds_is_refused_in_steps_of_dt():
+    """The limit is on n_substeps * dt, not on n_substeps: at dt = 7 the first refused launch is one of ceil(2**31 / 7)
+    steps, and the one a step shorter reaches the backend."""
+    env = WireEDMEnv(num_envs=2, device="cpu", backend=OracleBackend, config=EnvironmentConfig(dt=7, servo_interval=50))
+    env.reset(seed=1)
+    act = env.make_action()
+    first_refused = -(-2**31 // 7)
+    assert (first_refused - 1) * 7 < 2**31 <= first_refused * 7 and first_refused < 2**31 // 4
+    for n in (first_refused, first_refused + 1, 2**31 // 4):
+        with pytest.raises(ValueError) as exc:
+            env.step_many(act, n)
+        assert str(exc.value) == f"one launch may advance an environment by less than 2**31 us (asked: {n} x 7 us)"
+    assert env.steps_since_reset == 0 and env.state.time.tolist() == [0, 0]      # a refused launch leaves everything as it was
+    asked = []
+    env._backend.step = lambda n, ptrs: asked.append(n)                           # (not run: 2**31 us of oracle steps)
+    env.step_many(act, first_refused - 1)
+    assert asked == [first_refused - 1]
+
+
 def terminating_pair(n, backend, device="cpu", **kw):
     """Two identical batches whose environments reach their cutting target at different moments."""
     envs = []

@@ -29,10 +29,14 @@ UNTAKEN_DECISIONS = ["f19_speed_clamp_philox_env3", "f19_zero_crater_philox_env3
                      "f19_convection_floor_philox_env11", "f19_convection_above_floor_philox_env12",
                      "f19_mode_above_table_philox_env13", "f19_mode_below_table_philox_env14"]
 PHILOX = PHILOX + UNTAKEN_DECISIONS
+# F20: grids whose servo interval is no multiple of the physics step (dt, servo_interval, steps between two latches); witnesses below
+OFF_GRID = {"f20_dt3_gap_controller_philox_env5": (3, 100, 34), "f20_dt7_schedule_velocity_philox_env6": (7, 50, 8),
+            "f20_dt3_voltage_controller_philox_env3": (3, 100, 34)}
+PHILOX = PHILOX + list(OFF_GRID)
 # what test_portable_math_mode_stays_within_stated_tolerance replays in PORTABLE math
 PORTABLE = ["f1_config1_native", "f5_debris_short", "f3_philox_env0", "f7_gap_controller", "f9_voltage_controller_philox_env2",
             "f10_crater_statistics_philox_env1", "f13_dt2_philox_env4", "f14_copper_wire_philox_env6",
-            "f15_default_mode_philox_env7"] + [f"f11_random_params_{k}" for k in range(8)] + UNTAKEN_DECISIONS
+            "f15_default_mode_philox_env7"] + [f"f11_random_params_{k}" for k in range(8)] + UNTAKEN_DECISIONS + list(OFF_GRID)
 # recordings that end where the reference raised ValueError
 RAISING = ["f5_invalid_mode", "f19_mode_above_table_philox_env13", "f19_mode_below_table_philox_env14"]
 
@@ -162,6 +166,41 @@ def test_untaken_decision_fixtures_really_take_their_decision(orc, golden_dir, n
         from tests._golden import config_from_meta
 
         assert orc.new_env(config_from_meta(fx.meta)).c.default_current == 215.0
+
+
+@pytest.mark.parametrize("name", list(OFF_GRID))
+def test_off_grid_fixtures_really_step_over_the_servo_interval(golden_dir, name):
+    """On the recorded reference data alone: every latch (wire_edm.py:117 `time_since_servo >= servo_interval`) follows a
+    step that left `time_since_servo` past the interval without ever equalling it (102 at dt = 3, 56 at dt = 7), the
+    action the driver hands over changes between latches, and in the dt = 7 run a spark's ON phase ends with
+    `time_since_spark_ignition` past the latched ON time without ever equalling it."""
+    fx = Fixture(golden_dir / f"{name}.npz")
+    dt, interval, steps = OFF_GRID[name]
+    assert (fx.meta["config"]["dt"], fx.meta["config"]["servo_interval"]) == (dt, interval) and interval % dt
+    past = steps * dt
+    assert past > interval and past in (102, 56)
+    ctrl, tss = fx.int_row("ctrl_step"), fx.int_row("time_since_servo")
+    latches = np.nonzero(ctrl)[0]
+    assert latches.tolist() == list(range(steps, fx.n_steps, steps)) and len(latches) >= 70
+    assert set(tss[latches - 1].tolist()) == {past} and set(tss[latches].tolist()) == {dt}
+    assert not (tss == interval).any()
+    assert np.array_equal(fx.int_row("time"), dt * np.arange(1, fx.n_steps + 1))
+    latched = fx.actions[fx.action_idx[latches]]          # the action rows the latches read
+    assert int((latched[1:] != latched[:-1]).any(axis=1).sum()) >= 20   # latches that read another row than the one before
+    if dt == 7:
+        assert fx.meta["control_mode"] == "velocity" and len(set(latched[:, 4].tolist())) >= 3      # the current mode changes
+        state, tsi = fx.int_row("spark_state"), fx.int_row("time_since_spark_ignition")
+        ends = np.nonzero((state[1:] == -2) & (state[:-1] == 1))[0] + 1
+        stepped_over = 0
+        for e in ends[ends > latches[0]]:
+            on = float(fx.actions[fx.action_idx[latches[latches <= e][-1]], 2])   # ON_time as latched when the phase ended
+            first = e - 1
+            while state[first - 1] == 1:
+                first -= 1
+            phase = tsi[first:e]
+            assert on % 7 and not (phase == on).any()
+            stepped_over += int(phase[-1] > on)
+        assert stepped_over >= 10
 
 
 @pytest.mark.parametrize("name,mode", [("f19_mode_above_table_philox_env13", "I21"), ("f19_mode_below_table_philox_env14", "I-3")])

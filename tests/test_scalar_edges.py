@@ -333,16 +333,54 @@ def voltage_fallback(k):
                 decision=tv != 0.0, expect=eff, row=("f64", F.VOLTAGE), middle_only=True)
 
 
-def latch(interval):
+def latch(interval, dt=1):
     def ladder(k):
         tss = interval + k
         ctrl = tss >= interval
         return dict(rows={("i32", I.SINCE_SERVO): tss.astype(np.int32), ("f64", F.WORKPIECE_POS): 1000.0, ("f64", F.LAST_GAP): 990.0},
                     decision=ctrl, expect=np.where(ctrl, 0.125, 0.0), row=("f64", F.TARGET_DELTA), servo=0.125,
-                    kw={"config": {"servo_interval": interval}})
-    ladder.__name__ = f"latch_interval_{interval}"
+                    kw={"config": {"servo_interval": interval} if dt == 1 else {"servo_interval": interval, "dt": dt}})
+    ladder.__name__ = f"latch_interval_{interval}" + (f"_dt{dt}" if dt != 1 else "")
     ladder.__doc__ = f"wire_edm.py:117 `time_since_servo >= servo_interval` at interval {interval}: the servo command is latched or not."
     return ladder
+
+
+# ---- config.dt = 3.  The clocks advance by 3 us per step (wire_edm.py:135-144); the generator's ON and OFF times are compared
+# with `spark_status[2]`, which counts STEPS whatever dt is (ignition.py:272-275,304-309).  The ladders below sit on the step
+# count's threshold while `time_since_spark_ignition` / `time_since_spark_end` (3 us per step) are already past it: a
+# kernel that read ON or OFF against a clock in microseconds decides every rung the other way.  In the launches of 1, 7 and
+# 50 steps that follow, `time_since_servo` steps over intervals 1, 4 and 100 without landing on them.
+DT3 = {"config": {"dt": 3}}
+
+
+def on_time_end_dt3(total):
+    def ladder(k):
+        on = ulps(float(total), k)
+        end = float(total - 1 + 1) >= on
+        return dict(rows={**BURNING, ("i32", I.SPARK_DUR): total - 1, ("i32", I.SINCE_IGNITION): 3 * (total - 1),
+                          ("f64", F.ON_TIME): on, ("f64", F.OFF_TIME): 30.0},
+                    decision=end, expect=np.where(end, -2, 1).astype(np.int8), row=("i8", B.SPARK_STATE), kw=DT3)
+    ladder.__name__ = f"on_time_end_{total}_dt3"
+    ladder.__doc__ = (f"ignition.py:274 `duration >= ON_time` at dt = 3: a spark in step {total} of ON = {total} +- k ulp, "
+                      f"time_since_spark_ignition = {3 * (total - 1)} us.")
+    return ladder
+
+
+def rest_end_dt3(total):
+    def ladder(k):
+        off = ulps(float(total - 3), k)
+        end = float(total - 1 + 1) >= 3.0 + off
+        return dict(rows={**RESTING, ("i32", I.SPARK_DUR): total - 1, ("i32", I.SINCE_SPARK_END): 3 * (total - 3),
+                          ("f64", F.ON_TIME): 3.0, ("f64", F.OFF_TIME): off},
+                    decision=end, expect=np.where(end, 0, -2).astype(np.int8), row=("i8", B.SPARK_STATE), kw=DT3)
+    ladder.__name__ = f"rest_end_{total}_dt3"
+    ladder.__doc__ = (f"ignition.py:306-308 `duration >= ON_time + OFF_time` at dt = 3: resting in step {total} of ON 3 + OFF = "
+                      f"{total - 3} +- k ulp, time_since_spark_end = {3 * (total - 3)} us.")
+    return ladder
+
+
+DT3_LADDERS = [latch(1, 3), latch(3, 3), latch(4, 3), latch(100, 3), on_time_end_dt3(2), on_time_end_dt3(3), on_time_end_dt3(4),
+               rest_end_dt3(8), rest_end_dt3(9), rest_end_dt3(10)]
 
 
 # mechanics.py:69-114 at the default parameters, position mode, before the first latch (target_delta = 0)
@@ -527,10 +565,12 @@ def check_observable(ladder, spec, blocks):
     assert set(e[d].tolist()) - set(e[~d].tolist()) or set(e[~d].tolist()) - set(e[d].tolist()), (ladder.__name__, e)
 
 
-@pytest.mark.parametrize("ladder", LADDERS + REPLAY_LADDERS, ids=lambda f: f.__name__)
+@pytest.mark.parametrize("ladder", LADDERS + DT3_LADDERS + REPLAY_LADDERS, ids=lambda f: f.__name__)
 def test_oracle_decides_each_rung_like_the_reference_line(ladder):
     spec, blocks = oracle_run(ladder)
     check_observable(ladder, spec, blocks)
+    if ladder in DT3_LADDERS:   # the clock of these runs: 3 us per step
+        assert blocks[-1]["i32"][int(I.TIME), :N].tolist() == [3 * sum(LAUNCHES)] * N
 
 
 def test_cavity_coefficient_restatement():
@@ -583,7 +623,7 @@ def gpu_against(ladder, spec, refs, kernels):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("ladder", LADDERS, ids=lambda f: f.__name__)
+@pytest.mark.parametrize("ladder", LADDERS + DT3_LADDERS, ids=lambda f: f.__name__)
 def test_every_kernel_decides_the_threshold_at_its_edge(ladder):
     spec, refs = oracle_run(ladder)
     check_observable(ladder, spec, refs)

@@ -119,6 +119,7 @@ def test_terminated_environments_keep_being_sampled():
     ("f9_voltage_controller_servo500_philox_env6", 8, False),   # the 1 ms window spans two control intervals
     ("f9_voltage_controller_philox_env2", 4, True),             # the per-microsecond ring kept as a fallback
     ("f9_voltage_controller_dt2_philox_env4", 6, True),
+    ("f20_dt3_voltage_controller_philox_env3", 5, True),        # dt = 3, servo_interval = 100: 334-sample window, latches at 102 us
 ])
 def test_voltage_controller_reproduces_the_reference_driver(golden_dir, name, n, use_ring):
     """run_simulation.py's loop with the reference's OWN `create_voltage_controller` (fixture
@@ -311,6 +312,80 @@ def test_two_microsecond_physics_step_fixture(golden_dir):
     env = env_from_fixture(fx, 8, device="cpu", backend=LibmOracleBackend)
     got = run_fixture_through_trace(env, fx, exact_floats=True)
     assert got["time"][:3].tolist() == [2, 4, 6] and (got["spark_state"] == 1).sum() > 30
+
+
+OFF_GRID_FIXTURES = ["f20_dt3_gap_controller_philox_env5", "f20_dt7_schedule_velocity_philox_env6",
+                     "f20_dt3_voltage_controller_philox_env3"]
+
+
+@pytest.mark.parametrize("name", OFF_GRID_FIXTURES)
+def test_off_grid_fixtures_on_the_batched_environment(golden_dir, name):
+    """F20: servo intervals that are no multiple of config.dt (`time_since_servo` 99 -> 102 at dt = 3, 49 -> 56 at dt = 7)
+    and an action that changes from latch to latch, the recorded action rows handed to fused launches: whole
+    trajectory, bit for bit."""
+    from tests._fixture_env import env_from_fixture, fixture_launches, run_fixture_through_trace
+
+    fx = Fixture(golden_dir / f"{name}.npz")
+    env = env_from_fixture(fx, 8, device="cpu", backend=LibmOracleBackend)
+    steps = -(-env.servo_interval // env.dt)
+    assert steps * env.dt > env.servo_interval and len(fx.actions) > 20
+    launches = fixture_launches(fx, 0, fx.n_steps, steps)
+    assert sum(k for _, k in launches) == fx.n_steps and max(k for _, k in launches) == steps
+    got = run_fixture_through_trace(env, fx, exact_floats=True)
+    assert got["time"][:3].tolist() == [env.dt, 2 * env.dt, 3 * env.dt] and (got["spark_state"] == 1).sum() >= 15
+    assert got["time_since_servo"].max() == steps * env.dt
+
+
+def test_run_controlled_reproduces_the_gap_controller_off_the_grid(golden_dir):
+    """F20, first recording: `run_controlled` with the on-device `GapController` at dt = 3, servo_interval = 100 (launches
+    of 35, then 34 steps: ceil(100 / 3), each ending on the step that latched at time_since_servo = 102)."""
+    from tests._fixture_env import env_from_fixture, run_fixture_through_trace
+
+    fx = Fixture(golden_dir / "f20_dt3_gap_controller_philox_env5.npz")
+    env = env_from_fixture(fx, 8, device="cpu", backend=LibmOracleBackend)
+    launches, commands = [], []
+
+    class Recording(GapController):
+        def __call__(self, env):
+            action = super().__call__(env)
+            launches.append(env.steps_since_reset)
+            commands.append(float(action.servo[5]))
+            return action
+
+    def run(env):
+        assert run_controlled(env, Recording(), fx.n_steps) == fx.n_steps
+
+    run_fixture_through_trace(env, fx, exact_floats=True, run=run)
+    latches = np.nonzero(fx.int_row("ctrl_step"))[0]
+    assert launches == [0] + (latches + 1).tolist()          # one controller call right after every control step
+    # ... and the float32 servo leaf the reference's driver computed there
+    assert commands == [float(fx.actions[fx.action_idx[min(k, fx.n_steps - 1)], 0]) for k in launches]
+
+
+def test_control_interval_that_dt_does_not_divide_on_the_host_layer():
+    """`step_control` advances ceil(servo_interval / dt) physics steps (the latch tests `time_since_servo >=
+    servo_interval`), and the VoltageController's running-sum form refuses a control period that does not divide its
+    1000-us window."""
+    from sparc_amd import EnvironmentConfig
+
+    for dt, interval, steps in ((3, 100, 34), (7, 50, 8), (2, 1, 1), (3, 3, 1), (3, 4, 2)):
+        env = WireEDMEnv(num_envs=3, device="cpu", backend=OracleBackend, config=EnvironmentConfig(dt=dt, servo_interval=interval))
+        env.reset(seed=3)
+        act = env.make_action()
+        env.step_control(act)
+        assert env.steps_since_reset == steps and env.state.time.tolist() == [steps * dt] * 3
+        assert env.state.time_since_servo.tolist() == [steps * dt] * 3 and not bool(env.state.control_step.any())
+        env.step(act)                                         # the latch: the step after the interval has run out
+        assert bool(env.state.control_step.all()) and env.state.time_since_servo.tolist() == [dt] * 3
+        env.step_control(act)
+        assert env.state.time_since_servo.tolist() == [dt] * 3 and bool(env.state.control_step.all())   # ends on the next latch
+        assert env.steps_since_reset == 2 * steps + 1
+    env = WireEDMEnv(num_envs=3, device="cpu", backend=OracleBackend, config=EnvironmentConfig(dt=3, servo_interval=100))
+    env.reset(seed=3)
+    with pytest.raises(ValueError, match=r"the control period \(102 us\) does not divide the 1000-us averaging window: "
+                                         r"use VoltageController\(use_ring=True\)"):
+        VoltageController(30.0).bind(env)
+    assert VoltageController(30.0, use_ring=True).bind(env)._window == 334   # samples with time >= time - 1000 on this grid
 
 
 def test_custom_wire_material_fixture(golden_dir):

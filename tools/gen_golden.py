@@ -630,6 +630,26 @@ def main():
                  action=make_action(0.1, 80.0, 9, 3.0, 30.0), t_snap_every=2500, float_stride=7,
                  note="config.dt = 2 us")
 
+    # F20 — grids on which the servo interval is no multiple of the physics step: `time_since_servo` steps over the
+    # interval (99 -> 102 at dt = 3, 49 -> 56 at dt = 7) and the action latched there changes from latch to latch
+    run_scenario("f20_dt3_gap_controller_philox_env5", n_steps=2500, seed=93, rng="philox", env_id=5,
+                 config={"dt": 3, "servo_interval": 100}, controller=gap_controller(),
+                 state_init={"workpiece_position": 26.0, "wire_position": 10.0, "target_position": 5000.0},
+                 t_snap_every=2500, float_stride=7, note="config.dt = 3 us, servo_interval = 100 us: gap controller, position mode")
+    on_off = ((2.5, 10.0, 9), (4.0, 33.0, 13), (2.5, 33.0, 5), (4.0, 10.0, 17))   # ON, OFF (no multiples of 7), current mode
+    run_scenario("f20_dt7_schedule_velocity_philox_env6", n_steps=2500, seed=94, rng="philox", env_id=6,
+                 control_mode="velocity", config={"dt": 7, "servo_interval": 50},
+                 state_init={"workpiece_position": 24.0, "wire_position": 10.0, "target_position": 5000.0},
+                 action_schedule=[(at, make_action((150.0, -80.0, 220.0)[k % 3], (80.0, 95.0)[k % 2], on_off[k % 4][2],
+                                                   on_off[k % 4][0], on_off[k % 4][1]))
+                                  for k, at in enumerate(range(0, 2500, 61))],
+                 t_snap_every=2500, float_stride=7,
+                 note="config.dt = 7 us, servo_interval = 50 us: scripted actions every 61 steps, velocity mode")
+    run_scenario("f20_dt3_voltage_controller_philox_env3", n_steps=2500, seed=95, rng="philox", env_id=3,
+                 config={"dt": 3, "servo_interval": 100}, controller=VoltageDriver(30.0),
+                 state_init={"workpiece_position": 30.0, "wire_position": 10.0, "target_position": 5000.0},
+                 t_snap_every=2500, float_stride=7, note="config.dt = 3 us, servo_interval = 100 us: voltage controller (334-sample window)")
+
     # F14 — a wire material other than the built-in brass, registered in the material database
     copper = dict(density=8960, specific_heat=385, thermal_conductivity=401, electrical_resistivity=1.68e-8,
                   temperature_coefficient=0.00393, melting_point=1358, breaking_temperature=1600)
