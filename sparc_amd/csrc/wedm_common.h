@@ -8,36 +8,15 @@
 
 
 // Which kernels let their wave-uniform fast path also carry burning / ending sparks (quiet_prelude_t<true>), A/B-timed
-// on the MI355X (tools/r2_run13.sh, r2_run14.sh): the packed kernel gains everywhere (bench workload +1.3 %, 15 um gap
-// +4.1 %, closed loop +3.6 %), the unpacked fused and the predicated kernels lose 1-4 % on every workload (registers).
-#ifndef WEDM_PACKED_DENSE
-#define WEDM_PACKED_DENSE true
-#endif
-#ifndef WEDM_FUSED_DENSE
-#define WEDM_FUSED_DENSE false
-#endif
-// the fused kernel's F_N1 form requests a tile's LDS rows one tile ahead (see PREFETCH there)
+// on the MI355X: the packed kernel gains everywhere (bench workload +1.3 %, 15 um gap +4.1 %, closed loop +3.6 %), the
+// unpacked fused and the predicated kernels lose 1-4 % on every workload (registers).
+constexpr bool kPackedDense = true;   // the packed-type walks: packed, lanes_pk, served, regs, wide
+constexpr bool kFusedDense = false;   // the one-chunk and predicated walks: fused, lanes
 #ifndef WEDM_FUSED_MIN_BLOCKS
 #define WEDM_FUSED_MIN_BLOCKS 2
 #endif
 #ifndef WEDM_PACKED_MIN_BLOCKS
 #define WEDM_PACKED_MIN_BLOCKS 2
-#endif
-#ifndef WEDM_STREAM_PAIRED_LOADS
-#define WEDM_STREAM_PAIRED_LOADS 1
-#endif
-// the stream kernel walks a launch of ONE microsecond out of the registers the wire was loaded into (see rest_single)
-#ifndef WEDM_STREAM_DENSE_QUIET
-#define WEDM_STREAM_DENSE_QUIET 1
-#endif
-#ifndef WEDM_STREAM_REGWALK
-#define WEDM_STREAM_REGWALK 1
-#endif
-#ifndef WEDM_PIN_STAGE
-#define WEDM_PIN_STAGE 0
-#endif
-#ifndef WEDM_PREFETCH_N1
-#define WEDM_PREFETCH_N1 0
 #endif
 
 // Wave-uniform description of one step's walk over a chunk of C cells (see build_walk()).
@@ -370,11 +349,6 @@ __device__ __forceinline__ void tile_staged(const V (&old)[10], V (&tn)[8], cons
         e[u] = (PERCELL ? conv[o + u] : conv[0]) * e[u];
         f[u] = adv * f[u];
         if (JOULE) r[u] = alpha * r[u];
-#if WEDM_PIN_STAGE
-        // (the optimiser otherwise sinks this product down to its only use, `a - e`, where it folds the negation into the
-        // multiply and leaves a three-deep dependent chain with wait states in the stage that was meant to be one add)
-        asm volatile("" : "+v"(e[u]));
-#endif
     }
     WEDM_STAGE_FENCE();
 #pragma unroll
@@ -529,13 +503,8 @@ __device__ __forceinline__ void quad_f64(const f2 (&tm)[4], const f2 (&tc)[4], c
             jA = (JOULE && jfl[u].x != 0.0f) ? jf64 : 0.0; jB = (JOULE && jfl[u].y != 0.0f) ? jf64 : 0.0;
         }
         tn[u].x = cell_f64<JOULE>(tm[u].x, tc[u].x, tp[u].x, g.k64, g.tuf64, cA, h.tdiel, ps.adv64, jA, h.alpha, h.tref);
-#if WEDM_REGS_F64_FENCE < 0
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         tn[u].y = cell_f64<JOULE>(tm[u].y, tc[u].y, tp[u].y, g.k64, g.tuf64, cB, h.tdiel, ps.adv64, jB, h.alpha, h.tref);
-#if WEDM_REGS_F64_FENCE < 0
-        __builtin_amdgcn_sched_barrier(0);
-#elif WEDM_REGS_F64_FENCE > 0
+#if WEDM_REGS_F64_FENCE > 0
         if ((u + 1) % WEDM_REGS_F64_FENCE == 0) __builtin_amdgcn_sched_barrier(0);  // (cells in flight: 2 per pair between fences)
 #endif
     }

@@ -576,7 +576,7 @@ __device__ __forceinline__ void load_env_inputs_paired_finish(const PairRaw& r, 
 }
 
 // Rows that are final once the scalar prelude has run (stored while the wire is being walked).
-// `quiet_only`: every step of the launch took quiet_prelude() for the whole wave, which never assigns the
+// `quiet_only`: every step of the launch took quiet_prelude_t for the whole wave, which never assigns the
 // second group (workpiece position, dielectric / convection caches, latched action, short timers,
 // spark count, error flag): those rows are left alone.
 __device__ __forceinline__ void store_env_after_prelude(const ColdRef cold, int64_t e, const Env& v, bool quiet_only) {
@@ -744,7 +744,7 @@ __device__ __forceinline__ void crater_stats_update(double* st, int64_t sd, doub
 
 // `writer`: the one lane of an environment's L lanes that updates per-environment global memory
 // beyond the state blocks (the running statistics).
-struct QuietTry {  // what a failed quiet_prelude() hands on: the step's Philox words, if it drew them (wave-uniform flag)
+struct QuietTry {  // what a failed quiet_prelude_t hands on: the step's Philox words, if it drew them (wave-uniform flag)
     W4 w;
     bool have_w;
 };
@@ -1050,24 +1050,16 @@ __device__ __forceinline__ double pair_from_b(double x) {
 // Both run   m = mul X;  t = hi(m) ^ lo;  lo = lo(m);  X = partner(t) ^ k;  k += weyl
 // -- one 64-bit multiply and two xors (the partner's t as the DPP operand of the second) instead of two and four.
 // After the tenth round A holds (c0, c3) and B holds (c2, c1).
-// WEDM_PAIR_KEYS_HOISTED 0: one running key per lane, opaque per call, advanced by an add per round; 1: the compiler is
-// free to keep the ten round keys of a launch in registers (what it does for philox4 in a microsecond loop).
-#ifndef WEDM_PAIR_KEYS_HOISTED
-#define WEDM_PAIR_KEYS_HOISTED 0
-#endif
-#ifndef WEDM_PAIR_DIV
-#define WEDM_PAIR_DIV 1
-#endif
+// One running key per lane, advanced by an add per round (ten round keys of a launch kept in registers, what the compiler
+// does for philox4 in a microsecond loop, measured 10 % slower here: DESIGN.md section 4.4).
 struct PhiloxHalf { uint32_t X, lo; };
 __device__ __forceinline__ PhiloxHalf philox4_pair(bool lane_b, uint32_t key0, uint32_t key1, uint32_t time, uint32_t episode,
                                                    uint32_t gid, uint32_t stream) {
-#if !WEDM_PAIR_KEYS_HOISTED
     // (the lane's choice among launch constants -- key, episode, environment -- made opaque per call: hoisted out of a
     // microsecond loop the selected values are registers the loop does not have, and come back as scratch loads)
     uint32_t odd = lane_b ? 1u : 0u;
     asm volatile("" : "+v"(odd));
     lane_b = odd != 0u;
-#endif
     const uint32_t mul = lane_b ? 0xCD9E8D57u : 0xD2511F53u, weyl = lane_b ? 0xBB67AE85u : 0x9E3779B9u;
     uint32_t X = lane_b ? gid : time, lo = lane_b ? episode : stream, k = lane_b ? key1 : key0;
 #pragma unroll
@@ -1128,7 +1120,7 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
     const double cavity = g.cavity_coeff * (d0 * 0.001);
     double rho = 0.0;
     double lam_pair = 0.0;
-    if (PAIR && WEDM_PAIR_DIV) {
+    if (PAIR) {
         const bool lane_b = pair_lane_b();
         const double den = p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c;
         const double quot = (lane_b ? p.ln2 : s.debris) / (lane_b ? den : cavity);
@@ -1148,25 +1140,18 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
     if (__any(idle && live)) {
         if (PAIR) {
             wh = philox4_pair(pair_lane_b(), s.key0, s.key1, (uint32_t)s.time, (uint32_t)s.episode, gid, 0u);
-            if (!WEDM_PAIR_DIV) lam_pair = p.ln2 / (p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c);
             ign = idle && live && (u32_to_unit(pair_from_b(wh.X)) < lam_pair);   // w.z is the odd lane's X
         } else {
             const double lam = p.ln2 / (p.ignition_a * (d0 * d0) + p.ignition_b * d0 + p.ignition_c);
             const W4 w = philox4(s.key0, s.key1, (uint32_t)s.time, (uint32_t)s.episode, gid, 0u);
             ign = idle && live && (u32_to_unit(w.z) < lam);
-#ifndef WEDM_NO_PHILOX_REUSE
             qt.w = w;      // every lane of the wave computed its words: the general path need not repeat them
-#endif
         }
-#ifndef WEDM_NO_PHILOX_REUSE
         qt.have_w = true;
-#endif
     }
     if (__any(ign)) {
-#ifndef WEDM_NO_PHILOX_REUSE
         // (the general path wants all four words: exchanged here, off the quiet line, still with every lane active)
         if (PAIR) qt.w = philox4_pair_words(wh);
-#endif
         return false;
     }
     bool burning = false;
@@ -1220,16 +1205,6 @@ __device__ __forceinline__ bool quiet_prelude_t(const Hot& p, const ColdRef cold
         }
     }
     return true;
-}
-
-__device__ __forceinline__ bool quiet_prelude(const Hot& p, const Geom& g, uint32_t gid, Env& s, QuietTry& qt) {
-    Coef unused{0.0f, 0.0f, 0, -1};
-    return quiet_prelude_t<false>(p, ColdRef{nullptr}, g, 0, gid, s, qt, unused);
-}
-
-__device__ __forceinline__ bool quiet_prelude(const Hot& p, const Geom& g, uint32_t gid, Env& s) {
-    QuietTry qt;
-    return quiet_prelude(p, g, gid, s, qt);
 }
 
 // a - 2*b exactly as the reference rounds it: 2*b is exact in binary floating point, so

@@ -11,7 +11,7 @@
 //         hold float32 values of float64 rows, key0 / key1 are the uint32 view of their rows, int8 rows sit in int32 registers.
 // stage   which store of a single-microsecond launch has the row final (store_env_after_*, wedm_k_stream.h):
 //           PRE_QUIET    after the scalar prelude, whichever prelude ran
-//           PRE_GENERAL  after the scalar prelude, unless the whole wave took quiet_prelude(), which never assigns these
+//           PRE_GENERAL  after the scalar prelude, unless the whole wave took quiet_prelude_t, which never assigns these
 //           EPILOGUE     after the scalar epilogue
 //           NEVER        no step assigns the member and store_env() does not write the row: the resets and the caller do
 // role    what a microsecond does with the value it finds in the row (load_env_inputs): IN reads it; OUT assigns it before

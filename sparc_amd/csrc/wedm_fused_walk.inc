@@ -2,10 +2,9 @@
 // the right halo), tiles of 8 cells advanced in float registers.  One microsecond of it, from the halos to the trace point.
 // Textually included where it runs: in the microsecond loop of wedm_step_fused (wedm_k_fused.h) and in `rest` of
 // wedm_step_stream (wedm_k_stream.h), behind freeze_wire(s).
-// Names it expects in scope: L, F, FROZEN_OK, PREFETCH, kWalkTiles (compile time: lanes per environment; the kernel's forms;
+// Names it expects in scope: L, F, FROZEN_OK, kWalkTiles (compile time: lanes per environment; the kernel's forms;
 // the tile code has a copy in which frozen lanes do not store -- false sends a wave with a frozen lane down the predicated
-// path; the next tile's rows are requested into a second buffer before this tile is computed; false in an ablation build only:
-// no tiles); k, hv, cold, e, it; c, col (= lds + tid), C, cbase (= c C), n, n_tiles, wt; s, g, cf, ps; spool, tref, alpha,
+// path; false in an ablation build only: no tiles); k, hv, cold, e, it; c, col (= lds + tid), C, cbase (= c C), n, n_tiles, wt; s, g, cf, ps; spool, tref, alpha,
 // tdiel; the lane's tile flags zone_lo, joule_lo, zone_hi, joule_hi and split_pack; the wave-uniform tile masks kind_n,
 // kind_s, kind_ne, kind_nj; owns_last, t_last; and what the two kernels really do differently, as macros that expand here (a
 // lambda in their place changes the order in which the compiler inlines and, with it, the registers and the schedule of the
@@ -72,7 +71,7 @@
             const float jf_lane = (cf.joule_on && !s.done) ? cf.jf : 0.0f;
             const bool joule_wave = __any(jf_lane != 0.0f);
 
-            // tile t covers cells j = 8t..8t+7; cur[u] = OLD T[j+1+u]; `nxt` is loaded one tile ahead
+            // tile t covers cells j = 8t..8t+7; cur[u] = OLD T[j+1+u], loaded at the head of the tile
             // CLAMP = false: all eight rows exist (j + 8 <= C), one base address + immediate offsets
             auto load8 = [&](auto clamp, float (&dst)[8], int j) {
 #pragma unroll
@@ -82,14 +81,10 @@
                     dst[u] = col[row * 256];
                 }
             };
-            auto tile = [&](auto frozen, int t, float (&cur)[8], float (&nxt)[8]) {
+            auto tile = [&](auto frozen, int t, float (&cur)[8]) {
                 constexpr bool FROZEN = decltype(frozen)::value;  // the copy for a wave with frozen lanes: they do not store
                 const int j = 8 * t;
-                // PREFETCH (a lone wave per SIMD: nothing else hides the LDS round trip): the NEXT tile's eight rows are
-                // requested before this tile is computed -- rows this tile does not store (it stores j .. j + 7, they are
-                // j + 9 .. j + 16), so they are still the old values the explicit scheme needs
-                if (PREFETCH) { if (t + 1 < n_walk) load8(std::true_type{}, nxt, j + 8); }
-                else load8(std::true_type{}, cur, j);  // (an unclamped variant for full tiles pays in the packed kernel only)
+                load8(std::true_type{}, cur, j);  // (an unclamped variant for full tiles pays in the packed kernel only)
                 const float conv_lo = ((zone_lo >> t) & 1u) ? ps.conv_zone : ps.conv_base;
                 const float jfe_lo = ((joule_lo >> t) & 1u) ? jf_lane : 0.0f;
                 WEDM_FUSED_WALK_TILE_BEGIN;
@@ -194,7 +189,7 @@
                         }
                         tm1 = tc;
                         tc = tp1;
-                        // rotate the prefetch window (this fallback is rare; keep its code small)
+                        // rotate the tile's window (this fallback is rare; keep its code small)
                         float* w = const_cast<float*>(&cur[0]);
                         float first = w[0];
 #pragma unroll
@@ -205,24 +200,10 @@
                 WEDM_FUSED_WALK_TILE_END;
             };
             float bufA[8];
-            if (PREFETCH) {
-                float bufB[8];
-                load8(std::true_type{}, bufA, 0);
-                if (!FROZEN_OK || !frozen_wave) {
-                    for (int t = 0; t < n_walk; t += 2) {
-                        tile(std::false_type{}, t, bufA, bufB);
-                        if (t + 1 < n_walk) tile(std::false_type{}, t + 1, bufB, bufA);
-                    }
-                } else {
-                    for (int t = 0; t < n_walk; t += 2) {
-                        tile(std::true_type{}, t, bufA, bufB);
-                        if (t + 1 < n_walk) tile(std::true_type{}, t + 1, bufB, bufA);
-                    }
-                }
-            } else if (!FROZEN_OK || !frozen_wave) {
-                for (int t = 0; t < n_walk; ++t) tile(std::false_type{}, t, bufA, bufA);
+            if (!FROZEN_OK || !frozen_wave) {
+                for (int t = 0; t < n_walk; ++t) tile(std::false_type{}, t, bufA);
             } else {
-                for (int t = 0; t < n_walk; ++t) tile(std::true_type{}, t, bufA, bufA);
+                for (int t = 0; t < n_walk; ++t) tile(std::true_type{}, t, bufA);
             }
         }
         // ---- patches (after every store of the walk): boundary condition, last cell, plasma cell

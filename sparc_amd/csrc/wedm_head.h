@@ -16,7 +16,7 @@
 //   u, mode_index, the action leaves, log_prob, entropy, the upstream gradients are indexed by the row: coalesced as they
 //       are, u as one 16-byte access per lane.
 //   the softmax  M is a kernel argument, so the loops over the logits are wave-uniform.  w_j = exp(l_j - m) is needed
-//       twice by BACKWARD (in W, then in p_j).  It KEEPS them (WEDM_HEAD_KEEP_W): an array indexed by a loop counter would
+//       twice by BACKWARD (in W, then in p_j).  It KEEPS them (KEEP below): an array indexed by a loop counter would
 //       live in scratch, so both passes are unrolled over all 19 possible logits under the uniform j < M, every index is
 //       a constant and the 19 doubles are registers -- 86 VGPRs and no scratch, against 101 for the form that computes
 //       them again (DESIGN.md section 4.17 has both measured: keeping saves a quarter of BACKWARD at M = 9).  Either way
@@ -35,9 +35,6 @@
 #include "wedm_device.h"
 
 #define WEDM_HEAD_BLOCK 256
-#ifndef WEDM_HEAD_KEEP_W  // 1: BACKWARD keeps w_j = exp(l_j - m) in registers between its two passes; 0: it computes them again
-#define WEDM_HEAD_KEEP_W 1  // (-D: tools/build_variant.py, for measuring the other choice)
-#endif
 
 namespace wedm {
 
@@ -80,7 +77,7 @@ struct head_softmax {
 };
 
 // KEEP: also leaves w_j in `kept` -- a loop unrolled over all WEDM_HEAD_MAX_MODES under the uniform j < M, so that every index
-// is a constant and the array lives in registers (WEDM_HEAD_KEEP_W below); the operations and their order are the same
+// is a constant and the array lives in registers; the operations and their order are the same
 template <bool KEEP>
 __device__ __forceinline__ head_softmax head_mode_stats(const float* l, const int M, double (&kept)[KEEP ? WEDM_HEAD_MAX_MODES : 1]) {
     head_softmax s;
@@ -213,7 +210,7 @@ __global__ void __launch_bounds__(WEDM_HEAD_BLOCK) wedm_head_kernel(const wedm_h
         head_component c[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) c[i] = head_continuous(d, i, mu[i], ls[i], sigma[i], u[i]);
-        constexpr bool KEEP = OP == WEDM_HEAD_BACKWARD && WEDM_HEAD_KEEP_W;
+        constexpr bool KEEP = OP == WEDM_HEAD_BACKWARD;  // BACKWARD keeps w_j = exp(l_j - m) in registers between its two passes
         double w[KEEP ? WEDM_HEAD_MAX_MODES : 1];
         const head_softmax s = head_mode_stats<KEEP>(l, M, w);
         if (OP == WEDM_HEAD_SAMPLE) {

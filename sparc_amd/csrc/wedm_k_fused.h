@@ -96,8 +96,6 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
     static_assert((F & ~(F_TRACE | F_FROZEN_OK | F_N1 | F_F64)) == 0, "forms of wedm_step_fused");
     constexpr bool TRACE = (F & F_TRACE) != 0, FROZEN_OK = (F & F_FROZEN_OK) != 0, N1 = (F & F_N1) != 0, F64 = (F & F_F64) != 0;
     constexpr bool kFrozenOk = FROZEN_OK;
-    // (the N1 form serves small batches with one wave per SIMD: 4 096 x 400 over 16 lanes)
-    constexpr bool PREFETCH = N1 && !F64 && WEDM_PREFETCH_N1;
 #ifdef WEDM_ABL_NO_STENCIL
     constexpr bool kWalkTiles = false;
 #else
@@ -201,7 +199,7 @@ __global__ void __launch_bounds__(256, WEDM_FUSED_MIN_BLOCKS) wedm_step_fused(co
         WEDM_STAMP(st0);
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        if (!quiet_prelude_t<WEDM_FUSED_DENSE>(hv, cold, g, e, gid, s, qt, cf) && !s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, c == 0, qt);
+        if (!quiet_prelude_t<kFusedDense>(hv, cold, g, e, gid, s, qt, cf) && !s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, c == 0, qt);
         WEDM_STAMP(st1);
         freeze_wire(s);
 

@@ -14,12 +14,8 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
     constexpr bool TRACE = (F & F_TRACE) != 0, F64 = (F & F_F64) != 0;
     constexpr bool kFrozenOk = true;  // (predicated cells: a frozen lane costs this kernel nothing extra)
     const ColdRef cold = kernarg_cold();
-#ifndef WEDM_NO_PIN_LANES
     Hot hv = k.hot;
     pin_hot_in_vgprs(hv);
-#else
-    const Hot& hv = k.hot;
-#endif
     extern __shared__ __attribute__((aligned(16))) float lds[];
     constexpr int EPB = 256 / L;
     const int tid = threadIdx.x;
@@ -58,12 +54,11 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
         if (__all(s.done) && !tracing) break;
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        if (!quiet_prelude_t<WEDM_FUSED_DENSE>(hv, cold, g, e, gid, s, qt, cf) && !s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, c == 0, qt);
+        if (!quiet_prelude_t<kFusedDense>(hv, cold, g, e, gid, s, qt, cf) && !s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, c == 0, qt);
         freeze_wire(s);
         const float halo_l = (c > 0) ? col[(C - 1) * 256 - 1] : spool;
         const float halo_r = (c < L - 1) ? col[1] : 0.0f;
         float tmax = spool, tm1 = halo_l, tc = col[0];
-#ifndef WEDM_LANES_PREDICATED_ONLY
         // Fast walk (float32 stencil, no negative plasma heat in the wave): every cell of the chunk takes the interior
         // formula, stage-major, eight at a time, with ITS OWN coefficients (two range tests against this lane's zone and
         // contact indices per cell); the cells the interior formula is wrong for -- wire cell 0, the last cell, the plasma
@@ -129,31 +124,31 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes(const KArgs k) {
             if (c == 0 && keep) col[0] = spool;
             if (owns_last) { col[(n - 1 - cbase) * 256] = tlast; tmax = fmax_gt(tmax, tlast); }
             if (owns_pl) { col[(cf.pidx - cbase) * 256] = tpl; tmax = fmax_gt(tmax, tpl); }
-        } else
-#endif
-        for (int j0 = 0; j0 < C; j0 += 8) {
-            float nx[8];
+        } else {
+            for (int j0 = 0; j0 < C; j0 += 8) {
+                float nx[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int row = j0 + 1 + u;
-                nx[u] = row < C ? col[row * 256] : halo_r;
-            }
+                for (int u = 0; u < 8; ++u) {
+                    const int row = j0 + 1 + u;
+                    nx[u] = row < C ? col[row * 256] : halo_r;
+                }
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int j = j0 + u;
-                if (j < C) {
-                    const int i = cbase + j;
-                    if (i < n && !s.done) {
-                        float tn = spool;
-                        if (i >= 1) {
-                            if (F64) tn = stencil_cell_f64(i, n, (i == 1) ? spool : tm1, tc, nx[u], g, cf, ps, f64c, s.h_base, s.h_zone);
-                            else tn = stencil_cell(i, n, (i == 1) ? spool : tm1, tc, nx[u], g, cf, ps, tref, alpha, tdiel);
+                for (int u = 0; u < 8; ++u) {
+                    const int j = j0 + u;
+                    if (j < C) {
+                        const int i = cbase + j;
+                        if (i < n && !s.done) {
+                            float tn = spool;
+                            if (i >= 1) {
+                                if (F64) tn = stencil_cell_f64(i, n, (i == 1) ? spool : tm1, tc, nx[u], g, cf, ps, f64c, s.h_base, s.h_zone);
+                                else tn = stencil_cell(i, n, (i == 1) ? spool : tm1, tc, nx[u], g, cf, ps, tref, alpha, tdiel);
+                            }
+                            col[j * 256] = tn;
+                            tmax = fmax_gt(tmax, tn);
                         }
-                        col[j * 256] = tn;
-                        tmax = fmax_gt(tmax, tn);
+                        tm1 = tc;
+                        tc = nx[u];
                     }
-                    tm1 = tc;
-                    tc = nx[u];
                 }
             }
         }

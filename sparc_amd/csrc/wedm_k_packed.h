@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(256, WEDM_PACKED_MIN_BLOCKS) wedm_step_packed(
         WEDM_STAMP(st0);
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE>(hv, cold, g, e, gid, s, qt, cf);
+        const bool was_quiet = quiet_prelude_t<kPackedDense>(hv, cold, g, e, gid, s, qt, cf);
         if (!was_quiet && !s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, c == 0, qt);
         freeze_wire(s);
         WEDM_STAMP(st1);

@@ -81,54 +81,29 @@ __device__ __forceinline__ float max3_raw(float a, float b, float c) {
         }                                                                                                     \
     }
 
-#ifndef WEDM_REGS_DENSE
-#define WEDM_REGS_DENSE WEDM_PACKED_DENSE  // the quiet line also carries sparks that keep burning or end (see WEDM_PACKED_DENSE)
-#endif
 #ifndef WEDM_REGS_SW2
 #define WEDM_REGS_SW2 2
 #endif
-#ifndef WEDM_REGS_PIN2
-#define WEDM_REGS_PIN2 1
-#endif
-#ifndef WEDM_REGS_PAIR_SPLIT
-#define WEDM_REGS_PAIR_SPLIT 1  // two lanes: Philox and the quiet line's two divisions half in each lane (quiet_prelude_t<.., PAIR>)
-#endif
-// ---- the two waves of a SIMD and their phases (two lanes per environment only)
+// ---- the two waves of a SIMD and their phases (two lanes per environment only; DESIGN.md section 4.4 has the table of the
+// variants that were measured)
 // A microsecond of the two-lane form is a dependent float64 chain (prelude, epilogue: few instructions, each waiting for
 // the one before) around a walk of independent packed operations that fills the VALU pipe by itself.  Two such waves
 // share a SIMD.  At equal priority the older one wins every arbitration whatever either is doing: it ends the launch a
 // quarter ahead of the younger one, which then runs the rest alone (the census of tools/stamps_regs.py).
-//   WEDM_REGS_PAIR_PHASES     s_setprio by phase: raised in prelude and epilogue (the chain), 0 in the walk.  A wave in its
-//                             chain issues when its operand arrives, and the walking wave fills the slots between.  Only
-//                             a busy walk behind a general prelude keeps the raised priority (measured: the closed loop,
-//                             whose general microseconds mostly walk PLAIN, is 7 % slower with every general walk raised).
-//                             0: the kernel is the text it was without the priority changes.
-#ifndef WEDM_REGS_PAIR_PHASES
-#define WEDM_REGS_PAIR_PHASES 1
-#endif
-#ifndef WEDM_REGS_PAIR_PRIO_HI
-#define WEDM_REGS_PAIR_PRIO_HI 1
-#endif
-//   WEDM_REGS_PAIR_FAIR       a tie-break on top of the phases.  By phase alone both waves hold the same level in the same
-//                             phase, and the hardware breaks every such tie for the older wave.  With a favour bit `fav` the
-//                             chain runs at level 2 + fav and the walk at fav: a chain still beats the partner's walk, and
-//                             fav decides between equal phases only.  fav is made of the pair bit p (WEDM_REGS_PAIR_BIT),
-//                             which differs between the two waves of a SIMD:
-//                               1   by age: fav = p throughout (the younger wave one level up);  -1  its mirror, fav = !p;
-//                               K >= 3   by turns: fav = ((it >> K) & 1) ^ p, the favour changes sides every 2^K microseconds;
-//                               2   by halves: fav = (2 it >= n_substeps) ^ p, one change of sides per launch whatever its
-//                                   length.  Measured: a standing favour costs 5 % (the favoured wave runs away as the older
-//                                   one did before the phases), and turns gain the more the fewer they are (section 4.4);
-//                               0   the kernel is the text it was with the phases alone.
-//                             Two waves with equal p tie as before.  Priority only: no result depends on it.
-//   WEDM_REGS_PAIR_BIT        p: 0 the half of the grid the block lies in (blockIdx.x >= gridDim.x / 2), 1 the lowest bit of
-//                             the wave's slot on its SIMD (HW_ID), read once before the loop
-#ifndef WEDM_REGS_PAIR_FAIR
-#define WEDM_REGS_PAIR_FAIR 2
-#endif
-#ifndef WEDM_REGS_PAIR_BIT
-#define WEDM_REGS_PAIR_BIT 1
-#endif
+//   * s_setprio by phase: raised in prelude and epilogue (the chain), low in the walk.  A wave in its chain issues when
+//     its operand arrives, and the walking wave fills the slots between.  Only a busy walk behind a general prelude keeps
+//     the raised priority (measured: the closed loop, whose general microseconds mostly walk PLAIN, is 7 % slower with
+//     every general walk raised).
+//   * a tie-break on top of the phases.  By phase alone both waves hold the same level in the same phase, and the hardware
+//     breaks every such tie for the older wave.  With a favour bit `fav` the chain runs at level 2 + fav and the walk at
+//     fav: a chain still beats the partner's walk, and fav decides between equal phases only.  fav is
+//     (2 it >= n_substeps) ^ p: one change of sides per launch whatever its length.  The pair bit p is the lowest bit of
+//     the wave's slot on its SIMD (HW_ID), read once before the loop; it differs between the two waves of a SIMD (two
+//     waves with equal p tie as before).  A standing favour, fav = p or !p, loses 5 %: the favoured wave runs away as
+//     the older one did before the phases; and turns gain the more the fewer they are.
+//   * the F_PULSE form keeps the phases alone, chain at 1 and walk at 0: with the pair bit held the allocator gives it
+//     84 bytes of scratch and 29 spilled registers for 68 / 18 (with the bit read again at every site 72 / 22).
+// Priority only: no result depends on it.
 // `s_setprio` takes an immediate: a scalar branch over two instructions (fav is wave-uniform, in a scalar register)
 #define WEDM_REGS_SETPRIO_FAV(level, fav)                                                                     \
     do {                                                                                                      \
@@ -152,28 +127,21 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     static_assert(L == 1 || L == 2, "one or two lanes per environment");
     static_assert(H % 8 == 0 && H / 8 <= 16, "whole tiles");
     constexpr int EPB = 256 / L;
-    constexpr bool PRIO = L == 2 && WEDM_REGS_PAIR_PHASES;
-    // (not the F_PULSE form: with the pair bit held the allocator gives it 84 bytes of scratch and 29 spilled registers
-    // for 68 / 18, with the bit read again at every site 72 / 22; it keeps the phases alone, the text it had)
-    constexpr int FAIR = PRIO && !PULSE ? WEDM_REGS_PAIR_FAIR : 0;
-    constexpr int PRIO_CHAIN = FAIR != 0 ? 2 : WEDM_REGS_PAIR_PRIO_HI;
+    constexpr bool PRIO = L == 2;         // priority by phase
+    constexpr bool FAIR = PRIO && !PULSE;  // ... with the tie-break: the chain at 2 + fav and the walk at fav, else at 1 and 0
     // pairs per stage of the packed walk: a wave that is alone on its SIMD needs the distance between dependent operations
     constexpr int SW = L == 1 ? 4 : WEDM_REGS_SW2;
     constexpr bool kF64 = F64;
     WEDM_STAMP_CENSUS_BEGIN();
     // the pair bit: a scalar the wave forms by itself, different in the two waves that share a SIMD
     uint32_t pair_bit = 0u;
-    if constexpr (FAIR != 0) {
-        if (WEDM_REGS_PAIR_BIT == 1) asm volatile("s_getreg_b32 %0, hwreg(4, 0, 1)" : "=s"(pair_bit));
-        else pair_bit = blockIdx.x >= gridDim.x / 2 ? 1u : 0u;
-        if (FAIR < 0) pair_bit ^= 1u;
-    }
+    if constexpr (FAIR) asm volatile("s_getreg_b32 %0, hwreg(4, 0, 1)" : "=s"(pair_bit));
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
     // every-step float64 constants in VGPRs: all of them with 512 registers, the epilogue's and the quiet prelude's with 256
-    if (L == 1 || WEDM_REGS_PIN2 == 2) {
+    if (L == 1) {
         pin_hot_in_vgprs(hv);
-    } else if (WEDM_REGS_PIN2 == 1) {
+    } else {
         pin_mechanics_in_vgprs(hv);
         pin_quiet_in_vgprs(hv);
     }
@@ -252,19 +220,18 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
     for (int it = 0; it < k.n_substeps; ++it) {
         if (__all(s.done) && !tracing) break;  // (terminated environments keep being sampled: their frozen state)
         WEDM_STAMP(st0);
-        // whom a tie favours in this microsecond (by turns: the side changes every 2^FAIR microseconds; by halves: once)
-        const uint32_t fav = FAIR >= 3   ? (((uint32_t)it >> (FAIR >= 3 ? FAIR : 0)) & 1u) ^ pair_bit
-                             : FAIR == 2 ? (2 * it >= k.n_substeps ? 1u : 0u) ^ pair_bit
-                                         : pair_bit;
+        // whom a tie favours in this microsecond: the side changes once, half way through the launch (FAIR only)
+        const uint32_t fav = (2 * it >= k.n_substeps ? 1u : 0u) ^ pair_bit;
         // the chain: few instructions, each one waited for
-        if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(PRIO_CHAIN, fav);
-        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
+        if constexpr (FAIR) WEDM_REGS_SETPRIO_FAV(2, fav);
+        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
         e = env_index();
         const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_REGS_DENSE, 0u, L == 2 && WEDM_REGS_PAIR_SPLIT>(hv, cold, g, e, gid, s, qt, cf);
+        // (two lanes: Philox and the quiet line's two divisions half in each lane, quiet_prelude_t<.., PAIR>)
+        const bool was_quiet = quiet_prelude_t<kPackedDense, 0u, L == 2>(hv, cold, g, e, gid, s, qt, cf);
         if (!was_quiet) {
             if (!s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, writer, qt);
             build_conv();
@@ -305,13 +272,13 @@ __global__ void __launch_bounds__(256, L) wedm_step_regs(const KArgs k) {
             // of its entry): that walk is predicated cells and Joule terms behind a long prelude, and keeps the priority
             const bool busy = __any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f);
             if (__builtin_amdgcn_readfirstlane((int)(was_quiet || !busy))) {
-                if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(0, fav);
+                if constexpr (FAIR) WEDM_REGS_SETPRIO_FAV(0, fav);
                 else __builtin_amdgcn_s_setprio(0);
             }
         }
 #include "wedm_regs_walk.inc"
-        if constexpr (FAIR != 0) WEDM_REGS_SETPRIO_FAV(PRIO_CHAIN, fav);
-        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(WEDM_REGS_PAIR_PRIO_HI);
+        if constexpr (FAIR) WEDM_REGS_SETPRIO_FAV(2, fav);
+        else if constexpr (PRIO) __builtin_amdgcn_s_setprio(1);
         WEDM_STAMP(st2);
         if (L == 2) tmax = fmax_gt(tmax, __int_as_float(swap_with_neighbour(__float_as_int(tmax))));
         WEDM_ENV_END_US(hv, tmax, pk, writer, none, WEDM_STAMP(st3))
@@ -377,9 +344,6 @@ __device__ __forceinline__ float dpp_perm(float x) {
 
 #ifndef WEDM_WIDE_SW
 #define WEDM_WIDE_SW 2  // pairs per stage (4 096 x 400: 1.883e9 with 2, 1.862e9 with 4)
-#endif
-#ifndef WEDM_WIDE_DENSE
-#define WEDM_WIDE_DENSE WEDM_REGS_DENSE
 #endif
 #ifndef WEDM_WIDE_AUTO_MAX_LANES
 #define WEDM_WIDE_AUTO_MAX_LANES 65536  // one block per CU: 4 096 environments x 16 lanes, 16 384 x 4
@@ -479,7 +443,7 @@ __global__ void __launch_bounds__(256, wide_min_blocks(F)) wedm_step_regs_wide(c
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_WIDE_DENSE>(hv, cold, g, e, gid, s, qt, cf);
+        const bool was_quiet = quiet_prelude_t<kPackedDense>(hv, cold, g, e, gid, s, qt, cf);
         if (!was_quiet) {
             if (!s.done) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, writer, qt);
             build_conv();

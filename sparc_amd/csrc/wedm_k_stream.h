@@ -32,7 +32,7 @@
 #define WEDM_LDS __attribute__((address_space(3)))
 #define WEDM_GLOBAL __attribute__((address_space(1)))
 // This kernel's pieces of the walk, expanded by wedm_fused_walk.inc where it uses them (its head says what each has to do).
-// No frozen-lane copy of the tile code, no one-change tiles, no second buffer, no tail cells: a frozen lane makes the wave
+// No frozen-lane copy of the tile code, no one-change tiles, no tail cells: a frozen lane makes the wave
 // all_slow, and in the float64 typing every tile is walked cell by cell (this path is the rare one there).
 #define WEDM_FUSED_WALK_CELLWISE (all_slow || F64)
 #define WEDM_FUSED_WALK_FULL_CELL(i, tm, tc, tp) rw_cell<F64>(i, n, tm, tc, tp, g, cf, ps, tref, alpha, tdiel, f64c, s.h_base, s.h_zone)
@@ -91,7 +91,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     static_assert((F & ~(F_TRACE | F_ONE | F_CMAX104 | F_F64)) == 0, "forms of wedm_step_stream");
     constexpr bool TRACE = (F & F_TRACE) != 0, ONE = (F & F_ONE) != 0, F64 = (F & F_F64) != 0;
     constexpr int CMAX = (F & F_CMAX104) ? 104 : 64;
-    constexpr bool FROZEN_OK = false, PREFETCH = false, kWalkTiles = true;  // (what wedm_fused_walk.inc asks of its includer)
+    constexpr bool FROZEN_OK = false, kWalkTiles = true;  // (what wedm_fused_walk.inc asks of its includer)
     static_assert(!F64 || (ONE && !TRACE), "the float64 typing exists for the single-microsecond instantiation only");
     const ColdRef cold = kernarg_cold();
     Hot hv = k.hot;
@@ -130,7 +130,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     WEDM_S2_STAMP(11);  // geometry constants here (two dependent scalar loads)
     double h64[2] = {0.0, 0.0};  // convection coefficients as loaded; converted after the wire rows are requested
     // with an even number of lanes per environment the two lanes of a pair each request ONE row of a pair of rows
-    constexpr bool PAIRED = !TRACE && (L % 2 == 0) && WEDM_STREAM_PAIRED_LOADS;
+    constexpr bool PAIRED = !TRACE && (L % 2 == 0);
     PairRaw raw;
     if (live) {
         if (TRACE) load_env(cold, e, s);  // frozen environments are sampled too: every row
@@ -150,7 +150,6 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     // reads word 0): every load is unconditional and from a valid address, so the compiler can count them and waits
     // for each word only where it is used.  CMAX / 4 loads where ABI v3's T[seg][env] needed CMAX.
     static_assert(CMAX % 4 == 0, "whole 16-byte words");
-#ifndef WEDM_STREAM_NO_STATE_WAIT
     // The state rows land BEFORE the wire words are requested.  All 2 048 waves of a launch start together, and when a
     // wave queues its wire words right behind its state rows the memory system serves the chip's whole request stream
     // interleaved: a wave's state (23 MB chip-wide) then arrives only while the 33 MB of wire stream in, ~5 us after the
@@ -162,7 +161,6 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
         else { env_loaded_here(s); asm volatile("" : "+v"(h64[0]), "+v"(h64[1])); }
         __builtin_amdgcn_sched_barrier(0);
     }
-#endif
     WEDM_S2_STAMP(9);  // state rows landed
     const char* const Tb = (const char*)cold->s.T;
     const uint32_t rowb = (uint32_t)stride * 16u;                                                         // bytes per row of words
@@ -200,9 +198,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
             init_persist<true>(k.hot, cold, e, s, ps);
         }
     }
-#ifndef WEDM_STREAM_NO_PIN
     pin_hot_in_vgprs(hv);
-#endif
     const uint32_t gid = k.hot.env_id_offset + (uint32_t)e;
 
     const float spool = k.hot.spool, tref = k.hot.tref, alpha = k.hot.alpha, tdiel = k.hot.tdiel;
@@ -231,19 +227,13 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     // prelude runs BEFORE the chunk is dropped into LDS: the wire's rows are still in flight then.
     auto prelude = [&](Coef& cf) {
         QuietTry qt;
-#if WEDM_STREAM_DENSE_QUIET
         // (the quiet line also carries sparks that ignited earlier and keep burning or end now: only ignitions, shorts and
         // control-step latches take the general path -- and the issue priority)
         if (!quiet_prelude_t<ONE>(hv, cold, g, e, gid, s, qt, cf)) {
-#else
-        if (!quiet_prelude(hv, g, gid, s, qt)) {
-#endif
-#ifndef WEDM_STREAM_NO_SETPRIO
             // A launch ends with its slowest wave, and the slowest waves are the ~2 % whose prelude is the general one (a lane
             // ignites: crater normal, a dozen float64 divisions).  Such a wave takes the issue priority over the other wave of
             // its SIMD, which is not on the launch's critical path, for the rest of its life.
             __builtin_amdgcn_s_setprio(3);
-#endif
             quiet_only = false;
             // the crater-table entries of every lane's mode (None / unknown -> I1, material.py:104-113) and of I1, read across
             // lanes from the registers that hold the tables (every lane of the wave is here: the quiet test is wave-uniform)
@@ -264,7 +254,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_stream(const KArgs k) {
     // move each), every tile stored to global memory where it is computed.  The OLD chunk still goes to LDS -- one
     // 16-byte write per word -- for the few cells read by a DYNAMIC index: the halos and the neighbours of the patched
     // cells (plasma cell, last cell).
-    constexpr bool REGWALK = ONE && !TRACE && CMAX <= 64 && WEDM_STREAM_REGWALK;
+    constexpr bool REGWALK = ONE && !TRACE && CMAX <= 64;
     auto rest_single = [&](Coef& cf) {
         if (__any(reinit)) {
 #pragma unroll

@@ -746,7 +746,7 @@ static int32_t choose_kernel(wedm_ctx* ctx, bool single, bool tr, Choice& out) {
     const int stream_C = slanes ? walk_of(ctx, W_STREAM, slanes)->C : 0;
     const bool stream_auto = slanes && stream_C <= 64 && (long)blocks(ctx->num_envs, 256 / slanes) * 4 <= 2048;
     // the stream kernel under stencil_mode 1: its single-microsecond instantiation only (chunks of at most 64 cells, no trace sample)
-    const bool stream_f64_ok = slanes && single && !tr && WEDM_STREAM_REGWALK && stream_C <= 64;
+    const bool stream_f64_ok = slanes && single && !tr && stream_C <= 64;
     // kernel 8 by itself for a batch that one round of blocks covers at one wave per SIMD: such a launch is one wave's
     // dependent chain per microsecond whatever the kernel, and this one's is the shortest (measured, 4 096 x 400 and
     // 16 384 x 128: DESIGN.md 4.1b).  (stencil_mode 1, a short wire in a tiny batch: 256 waves of this kernel over 4 lanes
@@ -942,7 +942,7 @@ static int32_t plan_launch(wedm_ctx* ctx, bool single, bool tr, bool frozen_ok, 
             // over 8) or 104 (400 over 4)
             w = walk_of(ctx, W_STREAM, L);
             fl = stream_lds(ctx, L);
-            const bool one = WEDM_STREAM_REGWALK && single && !tr && w->C <= 64;
+            const bool one = single && !tr && w->C <= 64;
             F = (one || f64) ? F_ONE | (F & F_F64) : F | (w->C > 64 ? F_CMAX104 : 0u);
             break;
         }

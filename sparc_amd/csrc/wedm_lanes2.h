@@ -255,7 +255,7 @@ __global__ void __launch_bounds__(256, 2) wedm_step_lanes_pk(const KArgs k) {
         const int32_t pk = PULSE ? pulse_kind(s) : 0;  // the previous sample's pulse (pulse statistics)
         Coef cf{0.0f, 0.0f, 0, -1};
         QuietTry qt;
-        const bool was_quiet = quiet_prelude_t<WEDM_PACKED_DENSE, F>(hv, cold, g, e, gid, s, qt, cf);
+        const bool was_quiet = quiet_prelude_t<kPackedDense, F>(hv, cold, g, e, gid, s, qt, cf);
         if (!was_quiet && !s.done) cf = scalar_prelude<F>(hv, cold, g, e, gid, s, ps, c == 0, qt);
         freeze_wire(s);
         const bool keep = !s.done;

@@ -19,10 +19,7 @@
             float jf_lane = 0.0f;
             int pcell = -1;
             uint32_t ptiles = 0u;
-#ifndef WEDM_REGS_WALK_NO_PLAIN  // (A/B: every microsecond on the busy entry, the walk as it was before the PLAIN one)
-            if (__any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f))
-#endif
-            {
+            if (__any(cf.joule_on != 0 || cf.pidx >= 0 || cf.q != 0.0f)) {
                 // a wave with a negative plasma heat walks every cell on the predicated formula (identical results, slower)
                 all_slow = __any(cf.q < 0.0f);
                 // regular tiles of THIS microsecond: a contact-flag change inside a tile only matters while current flows

@@ -161,32 +161,8 @@ __device__ __forceinline__ void sv_give(volatile ServedBox<EPB>* box, int slot, 
     s.tmax = (tm);                                                                                                \
     if ((tm) > hv.tbreak) { s.err = 1; s.broken = 1; s.done = hv.done_value; }
 
-// -DWEDM_SV_CALL_GENERAL (tried, slower, kept as a switch): the GENERAL prelude (a lane ignites, a short, a control-step
-// latch: a few per cent of a batch's microseconds) as a real function call.  Inlined, its ~100 temporaries on top of the Env
-// cost the scalar wave 46-62 spilled registers at the 168 registers three blocks per CU leave a wave.  Called, what it takes
-// by reference lives in the stack frame around the call only -- but every other value that lives across the call is spilled
-// around it, in the hot loop too, and the chain of the scalar wave got longer, not shorter.
-// (Arguments of a function are vector registers: what is uniform -- the every-step parameters, the pointer block, the
-// geometry -- is read again from the kernel-argument segment inside, into scalar registers, as the kernels read it.  The
-// segment's address is handed over by the caller: in a function __builtin_amdgcn_kernarg_segment_ptr() is a NULL pointer.)
-__device__ __attribute__((noinline)) void sv_general_prelude(uint64_t kernarg_addr, int64_t e, uint32_t gid, Env& s, Persist& ps,
-                                                             const QuietTry& qt, Coef& out) {
-#if defined(__HIP_DEVICE_COMPILE__)  // (the host pass of hipcc cannot copy a struct out of the constant address space)
-    const uint32_t ka_lo = __builtin_amdgcn_readfirstlane((uint32_t)kernarg_addr), ka_hi = __builtin_amdgcn_readfirstlane((uint32_t)(kernarg_addr >> 32));
-    const WEDM_AS4 KArgs* const ka = (const WEDM_AS4 KArgs*)(((uint64_t)ka_hi << 32) | ka_lo);
-    const Hot hot = ka->hot;
-    const ColdRef cold{(ColdPtr)((const WEDM_AS4 char*)ka + offsetof(KArgs, cold))};
-    Geom g;
-    load_geom(hot, cold, e, g);
-    out = scalar_prelude(hot, cold, g, e, gid, s, ps, true, qt);
-#endif
-}
-
 #ifndef WEDM_SERVED_STAGE_W
 #define WEDM_SERVED_STAGE_W 2  // pairs per stage of the packed walk
-#endif
-#ifndef WEDM_SERVED_DENSE
-#define WEDM_SERVED_DENSE WEDM_PACKED_DENSE  // the quiet line also carries sparks that keep burning or end
 #endif
 #ifndef WEDM_SERVED_WAVES_PER_EU
 #define WEDM_SERVED_WAVES_PER_EU 3
@@ -202,14 +178,8 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
 #ifdef WEDM_SV_NO_SCALAR  // (register-pressure probes of the two roles: tools/kernel_resources.py -DWEDM_SV_NO_...)
     return;
 #endif
-#ifndef WEDM_SV_NO_PRIO
     __builtin_amdgcn_s_setprio(3);  // its chain is on the critical path of four walker waves
-#endif
-    Hot hv = k.hot;
-#ifdef WEDM_SV_PIN  // (no pinned constants: the scalar wave's 168 registers hold an Env and a prelude's temporaries, nothing to spare)
-    pin_mechanics_in_vgprs(hv);
-    pin_quiet_in_vgprs(hv);
-#endif
+    Hot hv = k.hot;  // (no pinned constants: the scalar wave's 168 registers hold an Env and a prelude's temporaries, nothing to spare)
     const int64_t e = e0 + (sl < EPB ? sl : 0);
     const bool live = sl < EPB && e0 + sl < k.num_envs;
     Env s;
@@ -253,28 +223,11 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
         const bool was_quiet = true;
         qt.have_w = false;
 #else
-        const bool was_quiet = quiet_prelude_t<WEDM_SERVED_DENSE>(hv, cold, g, e, gid, s, qt, cf);
+        const bool was_quiet = quiet_prelude_t<kPackedDense>(hv, cold, g, e, gid, s, qt, cf);
 #endif
-#ifndef WEDM_SV_NO_GENERAL
-#ifndef WEDM_SV_CALL_GENERAL
+        // (inlined: as a real function call the general prelude measured 9.8 ms against 8.3 ms at 32 768 x 400 -- the values
+        // that live across the call are spilled around it in the hot loop too)
         if (__builtin_expect(!was_quiet && !s.done, 0)) cf = scalar_prelude(hv, cold, g, e, gid, s, ps, true, qt);
-#else
-        // (measured: 32 768 x 400 9.8 ms with the call against 8.3 ms inlined -- the values that live across the call are
-        // spilled around it in the hot loop too; kept as a switch)
-        if (__builtin_expect(!was_quiet && !s.done, 0)) {
-            // through COPIES: an object whose address goes to a call lives in memory for its whole life -- handing `s` itself
-            // over put every access of the hot loop into scratch (no "spill" in the statistics, 10 000 cycles per step)
-            Env s_mem = s;
-            Persist ps_mem = ps;
-            QuietTry qt_mem = qt;
-            Coef cf_mem{0.0f, 0.0f, 0, -1};
-            sv_general_prelude((uint64_t)(const WEDM_AS4 char*)__builtin_amdgcn_kernarg_segment_ptr(), e, gid, s_mem, ps_mem, qt_mem, cf_mem);
-            s = s_mem;
-            ps = ps_mem;
-            cf = cf_mem;
-        }
-#endif
-#endif
         const float jf_eff = (cf.joule_on && !s.done) ? cf.jf : 0.0f;
         if (sl < EPB) {
             box->jf[slot][sl] = cf.jf; box->q[slot][sl] = cf.q; box->pidx[slot][sl] = cf.pidx;
@@ -306,11 +259,7 @@ __device__ __forceinline__ void served_scalar_wave(const KArgs& k, const ColdRef
                                ps.adv >= 0.0f && jf_eff >= 0.0f && tuf * (2.0f * kf + conv_max + ps.adv) <= 1.0f;
         const float rise = tuf * (jf_eff * (1.0f + alpha * (Mb - tref)) + fmaxf(cf.q, 0.0f));
         const bool safe = s.done || (scheme_ok && !s.ctrl && Mb + rise + 1.0f < hv.tbreak);  // (a NaN anywhere: not safe)
-#ifdef WEDM_SV_NO_SPEC  // (ablation: never ahead -- every step waits for its maximum, as an unserved kernel does)
-        if (false) {
-#else
         if (have_m && __all(safe)) {
-#endif
             // proven: no lane's wire breaks in this step -> the rest of the epilogue now, the monitor when the maximum arrives
             pend_live = !s.done;
             WEDM_SV_COUNT_SPEC();

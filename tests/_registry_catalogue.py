@@ -137,7 +137,7 @@ class Recipe:
             assert not sample, "if (v == K_SERVED && tr) v = packed_ok ? K_PACKED : ..."
             f |= self.geom & F.EXTRA   # "F |= walk_extra(w) ? F_EXTRA : 0u;"
         elif k == K.STREAM:
-            # "const bool one = WEDM_STREAM_REGWALK && single && !tr && w->C <= 64;"
+            # "const bool one = single && !tr && w->C <= 64;"
             # "F = (one || f64) ? F_ONE | (F & F_F64) : F | (w->C > 64 ? F_CMAX104 : 0u);"
             one = single and not sample and not (self.geom & F.CMAX104)
             assert one or "f64" not in b, "under stencil_mode 1 the stream kernel runs launches of one microsecond without a trace sample"

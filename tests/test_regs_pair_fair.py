@@ -1,6 +1,6 @@
-"""The two waves of a SIMD in wedm_step_regs<2, *> take turns in issue priority (WEDM_REGS_PAIR_FAIR in
-sparc_amd/csrc/wedm_k_regs.h): every microsecond passes scalar branches over `s_setprio`, under a bit the wave forms by itself
-and, for the variants by turns, the loop's counter.  Priority cannot change a result; a branch written wrongly can.  Kernel 7
+"""The two waves of a SIMD in wedm_step_regs<2, *> take turns in issue priority (sparc_amd/csrc/wedm_k_regs.h: the favour
+changes sides once, half way through a launch): every microsecond passes scalar branches over `s_setprio`, under a bit the
+wave forms by itself and the loop's counter.  Priority cannot change a result; a branch written wrongly can.  Kernel 7
 with two lanes per environment runs against the CPU oracle, every state block bit for bit, after each launch of 1, 7, 8, 9,
 63, 65 and 400 microseconds in sequence (slices of 8 and of 64 microseconds end inside launches and between them), on
 

@@ -588,7 +588,7 @@ KERNELS = [(1, 0), (5, 0), (6, 0), (6, 4), (6, 16), (2, 0), (3, 1), (3, 2), (3, 
 SERVED = [(9, 4), (9, 8)]
 ALL = KERNELS + SERVED + [(7, 1), (7, 2), (8, 0), (0, 0)]   # (0, 0): the automatic plan
 # families whose fast path is the instantiation that also carries burning sparks (quiet_prelude_t<true>, a compile-time
-# property of the family: WEDM_PACKED_DENSE and the macros derived from it), and those that run the plain one
+# property of the family: kPackedDense in wedm_common.h), and those that run the plain one
 DENSE_QUIET = {int(_abi.KERNEL.PACKED), int(_abi.KERNEL.SERVED), int(_abi.KERNEL.REGS), int(_abi.KERNEL.WIDE)}
 
 

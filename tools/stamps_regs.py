@@ -5,8 +5,8 @@ shipped library):
   and, separately, for those that took the general path;
 * the census: how the launch's waves pair up on SIMDs, when the first- and the second-arrived wave of a SIMD end (from the
   start of the kernel, on the 100 MHz clock all XCDs share), and the share of the launch during which a SIMD held one wave only;
-* the candidates for the pair bit of WEDM_REGS_PAIR_FAIR (the grid half, the bits of HW_ID's wave slot): on how many SIMDs
-  the two waves differ in it, and on how many of those the bit is set in the later-arrived wave.
+* the candidates for the pair bit of wedm_step_regs<2, *>'s priority tie-break (the grid half, the bits of HW_ID's wave
+  slot): on how many SIMDs the two waves differ in it, and on how many of those the bit is set in the later-arrived wave.
 usage: WEDM_HIP_LIB=build/ablate/libwedm_STAMPS.so python tools/stamps_regs.py [lanes] [num_envs] [gap_um] [microseconds]"""
 import ctypes as C
 import sys
@@ -107,8 +107,8 @@ print(f"  wave lifetime: {dist(t1 - t0)}")
 print(f"  share of the launch (SIMD-time over {len(on)} SIMDs): two or more waves resident {100 * both / tot:.1f} %, "
       f"one wave only {100 * lone / tot:.1f} %, none {100 * empty / tot:.1f} %")
 
-# ---- candidates for the pair bit p of WEDM_REGS_PAIR_FAIR: a bit a wave can form by itself that differs between the two
-# waves of a SIMD.  Per candidate: in how many of the SIMDs with exactly two waves p differs, and in how many of those
+# ---- candidates for the pair bit p of the two-lane register kernel's priority tie-break: a bit a wave can form by itself
+# that differs between the two waves of a SIMD.  Per candidate: in how many of the SIMDs with exactly two waves p differs, and in how many of those
 # p = 1 is the later-arrived wave.
 pairs = [sorted(v, key=lambda i: t0[i]) for v in on.values() if len(v) == 2]
 cands = {"grid half (blockIdx.x >= gridDim.x / 2)": (blk >= grid // 2).astype(int)}
