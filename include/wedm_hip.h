@@ -1153,6 +1153,94 @@ typedef struct wedm_ppo_desc {
  * overlapping an input block.                                                                                          */
 int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream);
 
+/* ------------------------------------------------- the actor-critic network: forward and backward, defined to the bit
+ * A two-hidden-layer MLP between an observation row and the head's parameter row plus a value estimate.  Every value is a
+ * float32, every fma below is ONE IEEE float32 fused multiply-add, every other operation is a float32 operation rounded
+ * once, parentheses as written.  The definition is a set of k-ordered fma chains, which is what gfx950's float32 matrix
+ * instructions compute and what a CPU reproduces: the bits of every output depend on the values and the rows' order alone.
+ *
+ * SHAPES.  D observation columns, 1 <= D <= WEDM_NORM_MAX_COLUMNS;  H1, H2 multiples of 16 in [16, WEDM_NET_MAX_HIDDEN];
+ *   P = 8 + n_modes;  O = P + 1 in [10, 28].
+ * PARAMETERS.  theta is one flat block without padding: W1[D][H1], b1[H1], W2[H1][H2], b2[H2], W3[H2][O], b3[O], matrices
+ *   row-major with the input index k outermost.  n_theta = (D + 1) H1 + (H1 + 1) H2 + (H2 + 1) O.  A gradient has the
+ *   same layout.
+ * ROWS.  src = index ? index[r] : r.  A src outside [0, n_src) is never dereferenced: the row's inputs x_k are +0.0 and its
+ *   incoming gradient go_j is +0.0; the chains run as written for such a row.
+ * INPUT.  o = obs[src * obs_stride + k];   x_k = (o != o) ? +0.0 : (o < -FLT_MAX ? -FLT_MAX : (o > FLT_MAX ? FLT_MAX : o))
+ * LAYER (in[K], W[K][N], b[N]) -> a[N]:   a_j = b_j;  for k = 0 .. K - 1:  a_j = fma(in_k, W[k][j], a_j)
+ *   h1 = act(layer(x, W1, b1));   h2 = act(layer(h1, W2, b2));   out = layer(h2, W3, b3)
+ *   params[r * param_stride + j] = out_j for j < P;   value[r] = out_P.
+ * ACTIVATION (descriptor field `activation`).
+ *   WEDM_NET_RELU:  act(a) = a > 0 ? a : +0.0;   act'(h) = h > 0 ? 1.0f : 0.0f
+ *   WEDM_NET_TANH:  act'(h) = fma(-h, h, 1.0f), and act(a) is, with u(x) the bits of x and f(b) the float of bits b:
+ *     m  = f(u(a) & 0x7FFFFFFF);           z = m + m
+ *     t  = fma(z, 0x1.715476p+0f, 12582912.0f);   n = t - 12582912.0f       -- n = round(z log2 e), its integer in t's bits
+ *     r  = fma(n, -0x1.62e400p-1f, z);     r = fma(n, -0x1.7f7d1cp-20f, r)  -- z - n ln 2, ln 2 in two parts
+ *     p  = fma(r, 0x1.a01a02p-16f, 0x1.a01a02p-13f)                         -- 1/40320, 1/5040
+ *     p  = fma(r, p, 0x1.6c16c2p-10f);  p = fma(r, p, 0x1.111112p-7f);  p = fma(r, p, 0x1.555556p-5f)  -- 1/720 1/120 1/24
+ *     p  = fma(r, p, 0x1.555556p-3f);   p = fma(r, p, 0.5f)                                          -- 1/6, 1/2
+ *     q  = fma(r * r, p, r)                                                 -- expm1(r)
+ *     s  = f((u(t) << 23) + 0x3F800000)                                     -- 2^n (32-bit wrap-around arithmetic)
+ *     e  = fma(s, q, s - 1.0f);            d = e + 2.0f                     -- expm1(2 m)
+ *     g  = m < 0.5f ? e / d : 1.0f - 2.0f / d;      g = m > 10.0f ? 1.0f : g
+ *     act(a) = f(u(g) | (u(a) & 0x80000000))
+ *   It is odd, |act(a)| <= 1, act(+-0) = +-0, it saturates to +-1 beyond |a| = 10 and a NaN gives a NaN (every comparison
+ *   is false for it).  The division is the correctly rounded float32 division.
+ * BACKWARD.  go[r][0 .. O) = the P entries at grad_params + r * grad_stride, then grad_value[r].  h1, h2 are recomputed by
+ *   the forward definition.
+ *     dh2_k = chain from +0.0 over j = 0 .. O - 1 of fma(go_j, W3[k][j], .);    da2_k = dh2_k * act'(h2_k)
+ *     dh1_k = chain from +0.0 over j = 0 .. H2 - 1 of fma(da2_j, W2[k][j], .);  da1_k = dh1_k * act'(h1_k)
+ *     dW3[k][j] = SUM_r (h2[r][k], go[r][j]);   dW2[k][j] = SUM_r (h1[r][k], da2[r][j]);   dW1[k][j] = SUM_r (x[r][k], da1[r][j])
+ *     db3[j] = SUM_r (1.0f, go[r][j]);          db2[j] = SUM_r (1.0f, da2[r][j]);          db1[j] = SUM_r (1.0f, da1[r][j])
+ * ROW SUM.  SUM_r (u_r, v_r):  rows [64 c, 64 c + 64) form chunk c, whose node is the chain from +0.0 over r ascending of
+ *   fma(u_r, v_r, .); rows at or past `rows` are absent from it.  Chunk nodes are added with plain float32 additions, the
+ *   lower index on the left, by wedm_ppo_loss's pairwise tree: two levels inside a tile of 256 rows (four chunks) give
+ *   partials[tile][n_theta], then the tree over the tile index, padded to the smallest power of two that holds the tiles.
+ *   At every level a node whose right child holds no row is its left child unchanged (no +0.0 is added, which would turn
+ *   a -0.0 into +0.0).  tiles = ceil(rows / 256) <= WEDM_NORM_MAX_TILES.
+ * NaN.  Every float32 the call stores (params, value, partials, grad_theta) holds a NaN as 0x7FC00000.
+ * PHASES.  WEDM_NET_FORWARD: one launch, writes params' columns [0, P) and value.  WEDM_NET_BACKWARD: MAIN, one launch,
+ *   rows -> partials.  WEDM_NET_FOLD: one launch, partials -> grad_theta; with WEDM_NET_ACCUMULATE
+ *   grad_theta[e] = grad_theta[e] + root[e], one float32 addition, else grad_theta[e] = root[e].  At least one of the
+ *   three must be set; they run in this order.                                                                          */
+#define WEDM_NET_MAX_HIDDEN 128
+enum wedm_net_flag { WEDM_NET_FORWARD = 1, WEDM_NET_BACKWARD = 2, WEDM_NET_FOLD = 4, WEDM_NET_ACCUMULATE = 8 };
+enum wedm_net_activation { WEDM_NET_RELU = 0, WEDM_NET_TANH = 1 };
+typedef struct wedm_net_desc {
+    const float* theta;            /* [n_theta]; FORWARD, BACKWARD */
+    const float* obs;              /* [n_src][obs_stride]; FORWARD, BACKWARD */
+    const int64_t* index;          /* [rows] or NULL: src = r */
+    float* params;                 /* [rows][param_stride]; FORWARD writes */
+    float* value;                  /* [rows]; FORWARD writes */
+    const float* grad_params;      /* [rows][grad_stride]; BACKWARD reads */
+    const float* grad_value;       /* [rows]; BACKWARD reads */
+    float* partials;               /* [ceil(rows / 256)][n_theta]; BACKWARD writes, FOLD reads */
+    float* grad_theta;             /* [n_theta]; FOLD writes (ACCUMULATE: reads and writes) */
+    int64_t obs_stride;            /* >= obs_dim, in elements */
+    int64_t param_stride;          /* >= 8 + n_modes, in elements */
+    int64_t grad_stride;           /* >= 8 + n_modes, in elements */
+    int64_t n_src;                 /* >= 1: the rows of obs */
+    int32_t obs_dim;               /* D, in [1, WEDM_NORM_MAX_COLUMNS] */
+    int32_t hidden1, hidden2;      /* H1, H2: multiples of 16 in [16, WEDM_NET_MAX_HIDDEN] */
+    int32_t n_modes;               /* M, in [1, WEDM_HEAD_MAX_MODES] */
+    int32_t activation;            /* enum wedm_net_activation */
+    int32_t rows;                  /* >= 1, at most WEDM_NORM_MAX_TILES * 256 */
+    int32_t flags;                 /* enum wedm_net_flag */
+    int32_t reserved;
+} wedm_net_desc;
+
+/* At most three launches on `stream` (FORWARD; BACKWARD's MAIN; FOLD), none of which waits for another block: no spin, no
+ * cooperative launch, no atomic.  Stateless like wedm_ppo_loss: no wedm_ctx, the current device, caller-owned memory.
+ * `desc` is HOST memory, read before the call returns; everything it names is device memory.  Written: params' columns
+ * [0, P) of rows [0, rows), value, partials, grad_theta -- each by its phase, nothing else.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined or no phase;
+ * rows < 1 or more than WEDM_NORM_MAX_TILES tiles; n_src < 1; obs_dim, hidden1, hidden2, n_modes or activation out of
+ * range; a stride below its row's length; a needed pointer NULL (theta, obs for FORWARD and BACKWARD; params, value for
+ * FORWARD; grad_params, grad_value for BACKWARD; partials for BACKWARD and FOLD; grad_theta for FOLD); a pointer not
+ * aligned to its element (index: 8); an output block (first to last byte that the call may write) overlapping an input
+ * block.                                                                                                               */
+int32_t wedm_policy_net(const wedm_net_desc* desc, void* stream);
+
 /* ------------------------------------------------- the log of finished episodes: an ordered ring, per-episode sums
  * One call per control step, after the step: every environment whose episode ended in it appends one RECORD to a ring of
  * `capacity` slots, in the order of the global environment index, without the host learning how many there were.

@@ -29,6 +29,7 @@ from .controllers import GapController, VoltageController, run_controlled
 from .episode_log import EpisodeLog
 from .normalize import Normalizer
 from .policy_head import PolicyHead
+from .policy_net import PolicyNet
 from .ppo import PPOLoss
 from .randomize import EpisodeSampler
 from .rollout import RolloutBuffer
@@ -43,7 +44,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PPOLoss",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

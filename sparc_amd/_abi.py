@@ -482,6 +482,25 @@ class PpoDesc(C.Structure):
     ]
 
 
+NET_FORWARD, NET_BACKWARD, NET_FOLD, NET_ACCUMULATE = 1, 2, 4, 8  # enum wedm_net_flag
+NET_RELU, NET_TANH = 0, 1  # enum wedm_net_activation
+NET_MAX_HIDDEN = 128  # WEDM_NET_MAX_HIDDEN
+NET_ACTIVATIONS = ("relu", "tanh")  # by enum value
+
+
+class NetDesc(C.Structure):
+    """``struct wedm_net_desc``: what `wedm_policy_net` reads and where it writes (strides in elements; ``n_src``: the rows
+    of ``obs`` that ``index`` points into)."""
+
+    _fields_ = [
+        ("theta", C.c_void_p), ("obs", C.c_void_p), ("index", C.c_void_p), ("params", C.c_void_p), ("value", C.c_void_p),
+        ("grad_params", C.c_void_p), ("grad_value", C.c_void_p), ("partials", C.c_void_p), ("grad_theta", C.c_void_p),
+        ("obs_stride", C.c_int64), ("param_stride", C.c_int64), ("grad_stride", C.c_int64), ("n_src", C.c_int64),
+        ("obs_dim", C.c_int32), ("hidden1", C.c_int32), ("hidden2", C.c_int32), ("n_modes", C.c_int32),
+        ("activation", C.c_int32), ("rows", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 ELOG_MAX_PLANES, ELOG_MAX_ROWS = 32, 96  # WEDM_ELOG_MAX_PLANES, WEDM_ELOG_MAX_ROWS
 ELOG_LAST, ELOG_SUM_F32, ELOG_SUM_F64, ELOG_SUM_I32 = 0, 1, 2, 3  # enum wedm_elog_kind
 ELOG_COUNT, ELOG_SCATTER, ELOG_COMMIT = 1, 2, 4  # enum wedm_elog_flag

@@ -64,6 +64,7 @@ _SIGNATURES = {
     "wedm_gae": (_i32, _to(_abi.GaeDesc), _p),
     "wedm_policy_head": (_i32, _to(_abi.HeadDesc), _p),
     "wedm_ppo_loss": (_i32, _to(_abi.PpoDesc), _p),
+    "wedm_policy_net": (_i32, _to(_abi.NetDesc), _p),
     "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
     "wedm_build_id": (C.c_char_p,),
 }
@@ -274,6 +275,10 @@ class HipBackend:
     def ppo_loss(self, desc: "_abi.PpoDesc") -> None:
         """`wedm_ppo_loss` on this backend's device and torch's current stream (at most four launches, no synchronisation)."""
         call_stateless(self._L.wedm_ppo_loss, self.device, C.byref(desc))
+
+    def policy_net(self, desc: "_abi.NetDesc") -> None:
+        """`wedm_policy_net` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
+        call_stateless(self._L.wedm_policy_net, self.device, C.byref(desc))
 
     def episode_log(self, desc: "_abi.ElogDesc") -> None:
         """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""

@@ -50,13 +50,15 @@
 //                         log-probability and entropy, their gradient; one lane per row; not a step kernel, not in the registry
 //   wedm_ppo.h            wedm_ppo_count / _main / _fold_kernel: PPO's clipped loss over a minibatch -- the row's terms, their
 //                         means by a fixed pairwise tree over the row number, the gradient; not step kernels, not in the registry
+//   wedm_policy_net.h     wedm_net_kernel / wedm_net_fold_kernel: a two-hidden-layer actor-critic MLP, forward and backward as
+//                         k-ordered fma chains on the float32 MFMA, the gradient's row sum by the same tree; not in the registry
 //   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
-// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the nine stateless entry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the ten stateless entry
 // points (wedm_copy_columns ... wedm_episode_log) behind what they share, each written once above wedm_copy_columns:
 //   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
 //   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
-//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_episode_log)
+//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_episode_log)
 //   tile_range, fold_per  the tile range inside the workspace and its tile count; the tiles per lane of a 256-lane fold
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
 //                         (wedm_policy_head, wedm_ppo_loss)
@@ -105,6 +107,7 @@ using namespace wedm;
 #include "wedm_gae.h"
 #include "wedm_head.h"
 #include "wedm_ppo.h"
+#include "wedm_policy_net.h"
 #include "wedm_eplog.h"
 #endif
 
@@ -1763,6 +1766,74 @@ int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
         int32_t padded = 1;  // the smallest power of two >= tiles
         while (padded < tiles) padded *= 2;
         hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, fold_per(tiles));
+        if (const int32_t rc = E.launched("fold")) return rc;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_policy_net(const wedm_net_desc* desc, void* stream) {
+    const Entry E{"wedm_policy_net"};
+    if (!desc) return E.bad("null descriptor");
+    const wedm_net_desc& d = *desc;
+    const int32_t phases = WEDM_NET_FORWARD | WEDM_NET_BACKWARD | WEDM_NET_FOLD;
+    if (d.flags & ~(int32_t)(phases | WEDM_NET_ACCUMULATE)) return E.bad("undefined flag bits");
+    if (!(d.flags & phases)) return E.bad("no phase: FORWARD, BACKWARD or FOLD must be set");
+    if (d.rows < 1) return E.bad("rows must be positive");
+    const int64_t tiles = ((int64_t)d.rows + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
+    if (tiles > WEDM_NORM_MAX_TILES)
+        return E.bad("a minibatch holds at most " + std::to_string(WEDM_NORM_MAX_TILES * WEDM_NORM_TILE) + " rows (" +
+                     std::to_string(WEDM_NORM_MAX_TILES) + " tiles of 256)");
+    if (d.n_src < 1) return E.bad("n_src must be positive");
+    if (d.obs_dim < 1 || d.obs_dim > WEDM_NORM_MAX_COLUMNS) return E.bad("obs_dim outside [1, " + std::to_string(WEDM_NORM_MAX_COLUMNS) + "]");
+    for (const int32_t h : {d.hidden1, d.hidden2})
+        if (h < 16 || h > WEDM_NET_MAX_HIDDEN || h % 16) return E.bad("a hidden width is not a multiple of 16 in [16, " + std::to_string(WEDM_NET_MAX_HIDDEN) + "]");
+    if (d.n_modes < 1 || d.n_modes > WEDM_HEAD_MAX_MODES) return E.bad("n_modes outside [1, " + std::to_string(WEDM_HEAD_MAX_MODES) + "]");
+    if (d.activation != WEDM_NET_RELU && d.activation != WEDM_NET_TANH) return E.bad("activation is neither WEDM_NET_RELU nor WEDM_NET_TANH");
+    const bool fwd = d.flags & WEDM_NET_FORWARD, bwd = d.flags & WEDM_NET_BACKWARD, fold = d.flags & WEDM_NET_FOLD;
+    const int64_t P = 8 + d.n_modes;
+    if ((fwd || bwd) && d.obs_stride < d.obs_dim) return E.bad("obs_stride is smaller than obs_dim");
+    if ((fwd && d.param_stride < P) || (bwd && d.grad_stride < P)) return E.bad("a stride is smaller than 8 + n_modes");
+    const net_shape F = net_make_shape(d.obs_dim, d.hidden1, d.hidden2, (int)P + 1, false);
+    const net_shape B = net_make_shape(d.obs_dim, d.hidden1, d.hidden2, (int)P + 1, true);
+    const uintptr_t n = (uintptr_t)d.rows, nt = (uintptr_t)F.n_theta;
+    const Block in[] = {
+        {"theta", (uintptr_t)d.theta, nt * 4, 4, fwd || bwd},
+        {"obs", (uintptr_t)d.obs, (fwd || bwd) ? (uintptr_t)((d.n_src - 1) * d.obs_stride + d.obs_dim) * 4 : 0, 4, fwd || bwd},
+        {"index", (uintptr_t)d.index, n * 8, 8, false},
+        {"grad_params", (uintptr_t)d.grad_params, bwd ? (uintptr_t)((int64_t)(d.rows - 1) * d.grad_stride + P) * 4 : 0, 4, bwd},
+        {"grad_value", (uintptr_t)d.grad_value, bwd ? n * 4 : 0, 4, bwd},
+    };
+    const Block out[] = {
+        {"params", (uintptr_t)d.params, fwd ? (uintptr_t)((int64_t)(d.rows - 1) * d.param_stride + P) * 4 : 0, 4, fwd},
+        {"value", (uintptr_t)d.value, fwd ? n * 4 : 0, 4, fwd},
+        {"partials", (uintptr_t)d.partials, (bwd || fold) ? (uintptr_t)tiles * nt * 4 : 0, 4, bwd || fold},
+        {"grad_theta", (uintptr_t)d.grad_theta, fold ? nt * 4 : 0, 4, fold},
+    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool tanh_act = d.activation == WEDM_NET_TANH;
+    const auto lds_ok = [&](const void* fn, size_t bytes) {  // a block's LDS above the default limit has to be asked for
+        return bytes <= 64 * 1024 || hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, WEDM_NET_LDS_LIMIT) == hipSuccess;
+    };
+    const auto launch = [&](auto bwd_tag, const net_shape& S, const dim3 grid, const char* what) -> int32_t {
+        constexpr bool BWD = decltype(bwd_tag)::value;
+        const size_t lds = (size_t)S.lds_floats * 4;
+        void (*fn)(const wedm_net_desc) =
+            S.wts >= 0 ? (tanh_act ? wedm_net_kernel<BWD, true, true> : wedm_net_kernel<BWD, false, true>)
+                       : (tanh_act ? wedm_net_kernel<BWD, true, false> : wedm_net_kernel<BWD, false, false>);
+        if (!lds_ok((const void*)fn, lds)) return E.launched(what);
+        hipLaunchKernelGGL(fn, grid, dim3(WEDM_NET_BLOCK), lds, s, d);
+        return E.launched(what);
+    };
+    if (fwd)
+        if (const int32_t rc = launch(std::false_type{}, F, dim3((uint32_t)(((int64_t)d.rows + WEDM_NET_PASS - 1) / WEDM_NET_PASS)), "forward")) return rc;
+    if (bwd)
+        if (const int32_t rc = launch(std::true_type{}, B, dim3((uint32_t)tiles), "main")) return rc;
+    if (fold) {
+        int32_t padded = 1;  // the smallest power of two >= tiles
+        while (padded < tiles) padded *= 2;
+        hipLaunchKernelGGL(wedm_net_fold_kernel, dim3((uint32_t)((F.n_theta + WEDM_NET_FOLD_PARAMS - 1) / WEDM_NET_FOLD_PARAMS)), dim3(256), 0, s, d,
+                           (int32_t)F.n_theta, (int32_t)tiles, std::max(padded / 8, 1), (int32_t)((d.flags & WEDM_NET_ACCUMULATE) != 0));
         if (const int32_t rc = E.launched("fold")) return rc;
     }
     return WEDM_OK;
