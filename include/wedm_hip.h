@@ -1241,6 +1241,98 @@ typedef struct wedm_net_desc {
  * block.                                                                                                               */
 int32_t wedm_policy_net(const wedm_net_desc* desc, void* stream);
 
+/* ------------------------------------------------- Adam with gradient clipping and a KL gate, one call per minibatch
+ * The step from a gradient to the next parameters: the gradient's global norm by wedm_ppo_loss's pairwise tree, the clipping
+ * factor, the decision whether this minibatch is applied at all (a gradient that is not finite, or an approximate KL over
+ * its limit, which closes a latch for the rest of the update), Adam's moments and the decoupled weight decay of AdamW --
+ * without the host ever reading a device value.  All arithmetic is float64 on the float32 inputs, every operation rounded
+ * once, nothing fused, parentheses as written; f32 is wedm_policy_head's; sqrt and / are the correctly rounded float64 ones.
+ * The bits of every output depend on the values and the elements' order alone.
+ *
+ * BLOCKS.  theta[n], m[n], v[n]: float32, read and written.  grad[n]: float32, read only.  partials[ceil(n / 256)]: double,
+ *   written.  state[WEDM_OPT_STATE]: double, read and written: [B1POW, B2POW, T, SKIPPED_NONFINITE, SKIPPED_KL, LATCH, 0, 0]
+ *   (enum wedm_opt_state); a fresh state is [1, 1, 0, 0, 0, 0, 0, 0].  info[WEDM_OPT_INFO]: double, written:
+ *   [SUMSQ, NORM, SCALE, LR, APPLIED, KL, BC1, BC2] (enum wedm_opt_info).  kl: ONE double, read only, only with
+ *   WEDM_OPT_KL_GATE (in practice &stats[WEDM_PT_KL] of wedm_ppo_loss).  1 <= n <= WEDM_NORM_MAX_TILES * 256.
+ * NORM.  q_e = (double) grad[e] * (double) grad[e], which is exact.  S is the pairwise tree over e with plain additions, the
+ *   lower index on the left: elements are padded with +0.0 to tiles of 256, a tile's eight levels give partials[t], then the
+ *   tree over the tile index, padded with +0.0 to the smallest power of two that holds the tiles.  Every leaf is >= +0.0 or a
+ *   NaN, and the sum cannot overflow a double: S < +inf holds exactly when every gradient entry is finite.
+ * DECIDE, one decision per call (CLIP, KL_GATE, NEW_UPDATE: the flag is set):
+ *     latch = state[LATCH];   if (NEW_UPDATE) latch = 0.0
+ *     klv   = KL_GATE ? kl[0] : 0.0
+ *     if (KL_GATE && latch == 0.0 && !(klv <= kl_limit)) latch = 1.0         -- a NaN closes the gate too
+ *     finite = S < +inf                                                       -- false for a NaN
+ *     norm = sqrt(S);   c = 1.0;   if (CLIP) { c = max_norm / (norm + 1e-6);  if (!(c < 1.0)) c = 1.0; }
+ *     if (latch != 0.0)   SKIPPED_KL += 1.0
+ *     else if (!finite)   SKIPPED_NONFINITE += 1.0
+ *     else              { T += 1.0;  B1POW = B1POW * beta1;  B2POW = B2POW * beta2; }
+ *     applied = (latch == 0.0 && finite) ? 1.0 : 0.0
+ *     bc1 = 1.0 - B1POW;   bc2 = 1.0 - B2POW                                  -- from the state after the decision
+ *     info = [S, norm, c, lr, applied, klv, bc1, bc2];   state[LATCH] = latch;   state[6] = state[7] = 0.0
+ *   The bias corrections are running products held in the state: no pow.  The latch stays closed until a call carries
+ *   NEW_UPDATE: "stop this update's remaining minibatches and epochs" without the host looking.
+ * APPLY reads SCALE (c), APPLIED, BC1 and BC2 from info and the other scalars from the descriptor.  It runs only when
+ *   info[APPLIED] == 1.0; otherwise no byte of theta, m, v is written.  Per element:
+ *     g = (double) grad[e] * c;     p = (double) theta[e]
+ *     if (weight_decay != 0.0) p = p - (lr * weight_decay) * p                -- decoupled, as AdamW
+ *     mf = f32(beta1 * (double) m[e] + (1.0 - beta1) * g)
+ *     vf = f32(beta2 * (double) v[e] + (1.0 - beta2) * (g * g))
+ *     mh = (double) mf / bc1;    vh = (double) vf / bc2
+ *     p  = p - lr * (mh / (sqrt(vh) + eps))
+ *     theta[e] = f32(p);   m[e] = mf;   v[e] = vf
+ *   The moments that are used are the float32 values that are stored: a resumed run sees what the uninterrupted one saw.  A
+ *   gradient near FLT_MAX makes vf +inf, which stays: mh / inf = 0 and theta stands still.
+ * A NaN is stored in partials, state and info as 0x7FF8000000000000 and in a float32 as 0x7FC00000.
+ * PHASES.  WEDM_OPT_NORM (grad -> partials), WEDM_OPT_DECIDE (partials, kl, state -> state, info), WEDM_OPT_APPLY; none of
+ *   the three set means all three, in this order.  Without a phase bit and with n <= WEDM_OPT_ONE_BLOCK_MAX the call is ONE
+ *   launch of one block that does all three; any phase bit selects the launches per phase.  Both give the same bytes in every
+ *   block, partials included.                                                                                             */
+#define WEDM_OPT_STATE 8
+#define WEDM_OPT_INFO 8
+/* One block against three launches is a pure speed choice (the bytes are the same).  Measured on an MI355X, back-to-back
+ * calls (tools/optimizer_cost.py): one block takes 4.0 / 5.5 / 8.5 / 12.2 / 14.4 / 25.8 / 94 us at
+ * n = 1 024 / 2 048 / 4 096 / 6 418 / 8 192 / 16 384 / 65 536, the three launches 8.6 to 14 us at every one of them: one
+ * block wins up to 4 096 and not from 6 418 on.  A diagnostic build may define another value, at most 65 536.            */
+#ifndef WEDM_OPT_ONE_BLOCK_MAX
+#define WEDM_OPT_ONE_BLOCK_MAX 4096
+#endif
+enum wedm_opt_flag { WEDM_OPT_CLIP = 1, WEDM_OPT_KL_GATE = 2, WEDM_OPT_NEW_UPDATE = 4, WEDM_OPT_NORM = 8, WEDM_OPT_DECIDE = 16,
+                     WEDM_OPT_APPLY = 32 };
+enum wedm_opt_state { WEDM_OS_B1POW = 0, WEDM_OS_B2POW, WEDM_OS_T, WEDM_OS_SKIPPED_NONFINITE, WEDM_OS_SKIPPED_KL, WEDM_OS_LATCH };
+enum wedm_opt_info { WEDM_OI_SUMSQ = 0, WEDM_OI_NORM, WEDM_OI_SCALE, WEDM_OI_LR, WEDM_OI_APPLIED, WEDM_OI_KL, WEDM_OI_BC1,
+                     WEDM_OI_BC2 };
+typedef struct wedm_opt_desc {
+    float* theta;                  /* [n]; APPLY reads and writes */
+    float* m;                      /* [n]; APPLY reads and writes */
+    float* v;                      /* [n]; APPLY reads and writes */
+    const float* grad;             /* [n]; NORM, APPLY */
+    double* partials;              /* [ceil(n / 256)]; NORM writes, DECIDE reads */
+    double* state;                 /* [WEDM_OPT_STATE]; DECIDE reads and writes */
+    double* info;                  /* [WEDM_OPT_INFO]; DECIDE writes, APPLY reads */
+    const double* kl;              /* one double; DECIDE with KL_GATE */
+    double lr;                     /* finite, >= 0 */
+    double beta1, beta2;           /* in [0, 1) */
+    double eps;                    /* finite, > 0 */
+    double weight_decay;           /* finite, >= 0 */
+    double max_norm;               /* finite, > 0; CLIP */
+    double kl_limit;               /* finite, >= 0; KL_GATE */
+    int32_t n;                     /* >= 1, at most WEDM_NORM_MAX_TILES * 256 */
+    int32_t flags;                 /* enum wedm_opt_flag */
+} wedm_opt_desc;
+
+/* One launch on `stream`, or at most three (NORM, DECIDE, APPLY: one each), none of which waits for another block: no spin,
+ * no cooperative launch, no atomic.  Stateless like wedm_ppo_loss: no wedm_ctx, the current device, caller-owned memory.
+ * `desc` is HOST memory, read before the call returns; everything it names is device memory.  Written: theta, m, v,
+ * partials, state, info -- each by its phase, nothing else.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined; n < 1 or more
+ * than WEDM_NORM_MAX_TILES tiles; lr, eps or weight_decay not finite, lr < 0, eps <= 0, weight_decay < 0; beta1 or beta2
+ * outside [0, 1); with CLIP a max_norm that is not finite or <= 0; with KL_GATE a kl_limit that is not finite or < 0; a needed
+ * pointer NULL (grad, partials for NORM; partials, state, info for DECIDE, and kl with KL_GATE; theta, m, v, grad, info for
+ * APPLY); a pointer not aligned to its element (partials, state, info, kl: 8); an output block (theta, m, v, partials,
+ * state, info: first to last byte that the call may touch) overlapping an input block (grad, kl) or another output block. */
+int32_t wedm_adam(const wedm_opt_desc* desc, void* stream);
+
 /* ------------------------------------------------- the log of finished episodes: an ordered ring, per-episode sums
  * One call per control step, after the step: every environment whose episode ended in it appends one RECORD to a ring of
  * `capacity` slots, in the order of the global environment index, without the host learning how many there were.

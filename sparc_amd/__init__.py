@@ -28,6 +28,7 @@ from .modules.views import DielectricModule, IgnitionModule, MaterialRemovalModu
 from .controllers import GapController, VoltageController, run_controlled
 from .episode_log import EpisodeLog
 from .normalize import Normalizer
+from .optimizer import Adam
 from .policy_head import PolicyHead
 from .policy_net import PolicyNet
 from .ppo import PPOLoss
@@ -44,7 +45,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss", "Adam",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -501,6 +501,26 @@ class NetDesc(C.Structure):
     ]
 
 
+OPT_CLIP, OPT_KL_GATE, OPT_NEW_UPDATE, OPT_NORM, OPT_DECIDE, OPT_APPLY = 1, 2, 4, 8, 16, 32  # enum wedm_opt_flag
+OPT_STATE, OPT_INFO = 8, 8  # WEDM_OPT_STATE, WEDM_OPT_INFO
+OPT_ONE_BLOCK_MAX = 4096  # WEDM_OPT_ONE_BLOCK_MAX: the largest n that one block takes when no phase bit is set
+# enum wedm_opt_state and enum wedm_opt_info: the entries of ``state`` (the last two are zero) and of ``info``
+OPT_STATE_NAMES = ("b1pow", "b2pow", "t", "skipped_nonfinite", "skipped_kl", "latch")
+OPT_INFO_NAMES = ("sumsq", "norm", "scale", "lr", "applied", "kl", "bc1", "bc2")
+
+
+class OptDesc(C.Structure):
+    """``struct wedm_opt_desc``: what `wedm_adam` reads and where it writes."""
+
+    _fields_ = [
+        ("theta", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("grad", C.c_void_p), ("partials", C.c_void_p),
+        ("state", C.c_void_p), ("info", C.c_void_p), ("kl", C.c_void_p),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+        ("max_norm", C.c_double), ("kl_limit", C.c_double),
+        ("n", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
 ELOG_MAX_PLANES, ELOG_MAX_ROWS = 32, 96  # WEDM_ELOG_MAX_PLANES, WEDM_ELOG_MAX_ROWS
 ELOG_LAST, ELOG_SUM_F32, ELOG_SUM_F64, ELOG_SUM_I32 = 0, 1, 2, 3  # enum wedm_elog_kind
 ELOG_COUNT, ELOG_SCATTER, ELOG_COMMIT = 1, 2, 4  # enum wedm_elog_flag

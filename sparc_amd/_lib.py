@@ -65,6 +65,7 @@ _SIGNATURES = {
     "wedm_policy_head": (_i32, _to(_abi.HeadDesc), _p),
     "wedm_ppo_loss": (_i32, _to(_abi.PpoDesc), _p),
     "wedm_policy_net": (_i32, _to(_abi.NetDesc), _p),
+    "wedm_adam": (_i32, _to(_abi.OptDesc), _p),
     "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
     "wedm_build_id": (C.c_char_p,),
 }
@@ -279,6 +280,10 @@ class HipBackend:
     def policy_net(self, desc: "_abi.NetDesc") -> None:
         """`wedm_policy_net` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
         call_stateless(self._L.wedm_policy_net, self.device, C.byref(desc))
+
+    def adam(self, desc: "_abi.OptDesc") -> None:
+        """`wedm_adam` on this backend's device and torch's current stream (one launch or at most three, no synchronisation)."""
+        call_stateless(self._L.wedm_adam, self.device, C.byref(desc))
 
     def episode_log(self, desc: "_abi.ElogDesc") -> None:
         """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""

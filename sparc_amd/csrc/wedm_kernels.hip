@@ -52,13 +52,15 @@
 //                         means by a fixed pairwise tree over the row number, the gradient; not step kernels, not in the registry
 //   wedm_policy_net.h     wedm_net_kernel / wedm_net_fold_kernel: a two-hidden-layer actor-critic MLP, forward and backward as
 //                         k-ordered fma chains on the float32 MFMA, the gradient's row sum by the same tree; not in the registry
+//   wedm_adam.h           wedm_adam_norm / _decide / _apply_kernel and wedm_adam_one_kernel: Adam with global-norm clipping and a
+//                         KL gate over one flat parameter block, the norm by the same tree; not step kernels, not in the registry
 //   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
-// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the ten stateless entry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the eleven stateless entry
 // points (wedm_copy_columns ... wedm_episode_log) behind what they share, each written once above wedm_copy_columns:
 //   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
 //   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
-//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_episode_log)
+//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_episode_log)
 //   tile_range, fold_per  the tile range inside the workspace and its tile count; the tiles per lane of a 256-lane fold
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
 //                         (wedm_policy_head, wedm_ppo_loss)
@@ -108,6 +110,7 @@ using namespace wedm;
 #include "wedm_head.h"
 #include "wedm_ppo.h"
 #include "wedm_policy_net.h"
+#include "wedm_adam.h"
 #include "wedm_eplog.h"
 #endif
 
@@ -1835,6 +1838,67 @@ int32_t wedm_policy_net(const wedm_net_desc* desc, void* stream) {
         hipLaunchKernelGGL(wedm_net_fold_kernel, dim3((uint32_t)((F.n_theta + WEDM_NET_FOLD_PARAMS - 1) / WEDM_NET_FOLD_PARAMS)), dim3(256), 0, s, d,
                            (int32_t)F.n_theta, (int32_t)tiles, std::max(padded / 8, 1), (int32_t)((d.flags & WEDM_NET_ACCUMULATE) != 0));
         if (const int32_t rc = E.launched("fold")) return rc;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_adam(const wedm_opt_desc* desc, void* stream) {
+    const Entry E{"wedm_adam"};
+    if (!desc) return E.bad("null descriptor");
+    const wedm_opt_desc& d = *desc;
+    const int32_t phases = WEDM_OPT_NORM | WEDM_OPT_DECIDE | WEDM_OPT_APPLY;
+    if (d.flags & ~(int32_t)(phases | WEDM_OPT_CLIP | WEDM_OPT_KL_GATE | WEDM_OPT_NEW_UPDATE)) return E.bad("undefined flag bits");
+    if (d.n < 1) return E.bad("n must be positive");
+    const int64_t tiles = ((int64_t)d.n + WEDM_ADAM_BLOCK - 1) / WEDM_ADAM_BLOCK;
+    if (tiles > WEDM_NORM_MAX_TILES)
+        return E.bad("a parameter block holds at most " + std::to_string(WEDM_NORM_MAX_TILES * WEDM_ADAM_BLOCK) + " entries (" +
+                     std::to_string(WEDM_NORM_MAX_TILES) + " tiles of 256)");
+    const bool clip = d.flags & WEDM_OPT_CLIP, gate = d.flags & WEDM_OPT_KL_GATE;
+    if (!finite_f64(d.lr) || d.lr < 0.0) return E.bad("lr must be finite and not negative");
+    if (!(d.beta1 >= 0.0 && d.beta1 < 1.0) || !(d.beta2 >= 0.0 && d.beta2 < 1.0)) return E.bad("beta1 and beta2 must lie in [0, 1)");
+    if (!finite_f64(d.eps) || !(d.eps > 0.0)) return E.bad("eps must be finite and positive");
+    if (!finite_f64(d.weight_decay) || d.weight_decay < 0.0) return E.bad("weight_decay must be finite and not negative");
+    if (clip && (!finite_f64(d.max_norm) || !(d.max_norm > 0.0))) return E.bad("max_norm must be finite and positive");
+    if (gate && (!finite_f64(d.kl_limit) || d.kl_limit < 0.0)) return E.bad("kl_limit must be finite and not negative");
+    const bool all = !(d.flags & phases);
+    const bool norm = all || (d.flags & WEDM_OPT_NORM), decide = all || (d.flags & WEDM_OPT_DECIDE), apply = all || (d.flags & WEDM_OPT_APPLY);
+    const uintptr_t n = (uintptr_t)d.n;
+    const Block in[] = {
+        {"grad", (uintptr_t)d.grad, (norm || apply) ? n * 4 : 0, 4, norm || apply},
+        {"kl", (uintptr_t)d.kl, (uintptr_t)((decide && gate) ? 8 : 0), 8, decide && gate},
+    };
+    const Block out[] = {
+        {"theta", (uintptr_t)d.theta, apply ? n * 4 : 0, 4, apply},
+        {"m", (uintptr_t)d.m, apply ? n * 4 : 0, 4, apply},
+        {"v", (uintptr_t)d.v, apply ? n * 4 : 0, 4, apply},
+        {"partials", (uintptr_t)d.partials, (norm || decide) ? (uintptr_t)tiles * 8 : 0, 8, norm || decide},
+        {"state", (uintptr_t)d.state, (uintptr_t)(decide ? WEDM_OPT_STATE * 8 : 0), 8, decide},
+        {"info", (uintptr_t)d.info, (uintptr_t)((decide || apply) ? WEDM_OPT_INFO * 8 : 0), 8, decide || apply},
+    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
+    for (const Block* a = out; a < out + std::size(out); ++a)  // every block that is written, against every other one
+        for (const Block* b = a + 1; b < out + std::size(out); ++b)
+            if (a->lo && b->lo && a->bytes && b->bytes && a->lo < b->lo + b->bytes && b->lo < a->lo + a->bytes)
+                return E.bad(b->text() + " overlaps " + a->text());
+    const hipStream_t s = (hipStream_t)stream;
+    int32_t padded = 1;  // the smallest power of two >= tiles
+    while (padded < tiles) padded *= 2;
+    if (all && d.n <= WEDM_OPT_ONE_BLOCK_MAX) {
+        const uint32_t lanes = (uint32_t)std::min<int64_t>(tiles * WEDM_ADAM_BLOCK, WEDM_ADAM_ONE_BLOCK);
+        hipLaunchKernelGGL(wedm_adam_one_kernel, dim3(1), dim3(lanes), 0, s, d, (int32_t)tiles, padded);
+        return E.launched("one-block");
+    }
+    if (norm) {
+        hipLaunchKernelGGL(wedm_adam_norm_kernel, dim3((uint32_t)tiles), dim3(WEDM_ADAM_BLOCK), 0, s, d);
+        if (const int32_t rc = E.launched("norm")) return rc;
+    }
+    if (decide) {
+        hipLaunchKernelGGL(wedm_adam_decide_kernel, dim3(1), dim3(64), 0, s, d, (int32_t)tiles, padded);
+        if (const int32_t rc = E.launched("decide")) return rc;
+    }
+    if (apply) {
+        hipLaunchKernelGGL(wedm_adam_apply_kernel, dim3((uint32_t)tiles), dim3(WEDM_ADAM_BLOCK), 0, s, d);
+        if (const int32_t rc = E.launched("apply")) return rc;
     }
     return WEDM_OK;
 }
