@@ -1333,6 +1333,68 @@ typedef struct wedm_opt_desc {
  * state, info: first to last byte that the call may touch) overlapping an input block (grad, kl) or another output block. */
 int32_t wedm_adam(const wedm_opt_desc* desc, void* stream);
 
+/* ------------------------------------------------- the rows of a rollout dealt into minibatches: a seeded permutation
+ * Which rows go into which minibatch of an epoch, as a function of (valid, n_parts, seed, draw) alone: the same bits on every
+ * device, nothing a checkpoint has to carry but three integers, the live rows spread evenly over the parts.  Integers only.
+ * This is NOT a uniformly random permutation: it is a keyed bijection (a balanced Feistel network over the bits of the live
+ * count, walked back into range), good enough to shuffle minibatches; the tests hold it to a chi-square of the row-by-part
+ * membership counts that a uniform shuffle meets.
+ *
+ * BLOCKS.  valid[rows]: uint8, read only, a row is LIVE iff its byte is not zero; NULL: every row is live.  index[rows]: int64,
+ *   written.  count[2]: int64, written: {V, rows - V}.  tile_counts[tiles], tile_base[tiles]: int32, the workspace, with
+ *   tiles = ceil(rows / WEDM_MB_TILE).  1 <= rows <= WEDM_MB_MAX_ROWS, 1 <= n_parts <= min(rows, WEDM_MB_MAX_PARTS).
+ * RANKS.  V is the number of live rows.  k(r), for a live row r, is the number of live rows below r; q(r), for a dead row r,
+ *   the number of dead rows below r.
+ * KEYS.  K[4 c + i], c = 0, 1, is word i of Philox4x32-10 with key (seed lo, seed hi) and counter (draw lo, draw hi, 0,
+ *   WEDM_MB_STREAM0 + c).
+ * E, a bijection of [0, 2^b), where b is the bit length of V - 1 (b = 0 for V <= 1): hl = b >> 1, hh = b - hl,
+ *   lo = x & (2^hl - 1), hi = x >> hl; rounds i = 0 ... 7, an even one hi ^= mix(lo ^ K[i]) & (2^hh - 1), an odd one
+ *   lo ^= mix(hi ^ K[i]) & (2^hl - 1); E(x) = hi << hl | lo.  mix is the 32-bit finaliser
+ *     x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16.
+ *   Every round is an xor of one half with a function of the other: a bijection for every b, odd widths and b = 1 included.
+ * PI, the permutation of [0, V) by cycle walking: PI(k) is the first of E(k), E(E(k)), ... that is below V.  The walk ends
+ *   (k lies on its own cycle and k < V), and since 2^b < 2 V it takes under two applications on average.
+ * PLACE.  The list position of row r is j(r) = PI(k(r)) for a live row and V + q(r) for a dead one.  Positions are dealt
+ *   round-robin: part p = j mod n_parts, slot s = j div n_parts.  Part p holds cnt_p = ceil((rows - p) / n_parts) rows from
+ *   off_p = p * (rows div n_parts) + min(p, rows mod n_parts) on -- sizes and offsets of a split of `rows` entries into
+ *   n_parts as even as they go, the larger ones first, which the host knows without reading anything --, and
+ *   index[off_p + s] = r.  So index is a permutation of [0, rows), in every part the live rows come first, and part p holds
+ *   ceil((V - p) / n_parts) of them (zero for p >= V): the parts' live counts differ by at most one.
+ * WORKSPACE.  tile_counts[t] is the number of live rows among rows [1024 t, 1024 t + 1024); tile_base[t] the sum of the
+ *   counts below t.
+ * PHASES.  WEDM_MB_COUNT (valid -> tile_counts), WEDM_MB_OFFSETS (tile_counts -> tile_base, count), WEDM_MB_SCATTER (valid,
+ *   tile_base, count -> index); none of the three set means all three, in this order.  A SCATTER over a workspace that no
+ *   COUNT and OFFSETS of the same `valid` wrote stores nothing outside index and ends: a row whose rank or position falls
+ *   outside what count[0], clamped to [0, rows], allows is left out.                                                     */
+#define WEDM_MB_STREAM0 0xE0000000u     /* clear of WEDM_DRAW_STREAM0 + q and WEDM_HEAD_STREAM0 + ... */
+#define WEDM_MB_TILE 1024
+#define WEDM_MB_MAX_ROWS (1 << 26)
+#define WEDM_MB_MAX_PARTS 4096
+enum wedm_mb_flag { WEDM_MB_COUNT = 1, WEDM_MB_OFFSETS = 2, WEDM_MB_SCATTER = 4 };
+typedef struct wedm_mb_desc {
+    const uint8_t* valid;          /* [rows] or NULL (every row live); COUNT, SCATTER */
+    int64_t* index;                /* [rows]; SCATTER writes */
+    int64_t* count;                /* [2]; OFFSETS writes, SCATTER reads */
+    int32_t* tile_counts;          /* [ceil(rows / 1024)]; COUNT writes, OFFSETS reads */
+    int32_t* tile_base;            /* [ceil(rows / 1024)]; OFFSETS writes, SCATTER reads */
+    uint64_t seed;                 /* the Philox key */
+    uint64_t draw;                 /* the number of this permutation */
+    int32_t rows;                  /* in [1, WEDM_MB_MAX_ROWS] */
+    int32_t n_parts;               /* in [1, min(rows, WEDM_MB_MAX_PARTS)] */
+    int32_t flags;                 /* enum wedm_mb_flag */
+} wedm_mb_desc;
+
+/* At most three launches on `stream` (COUNT, OFFSETS, SCATTER: one each), none of which waits for another block: no spin, no
+ * cooperative launch, no atomic.  Stateless like wedm_adam: no wedm_ctx, the current device, caller-owned memory.  `desc` is
+ * HOST memory, read before the call returns; everything it names is device memory.  Written: index, count, tile_counts,
+ * tile_base -- each by its phase, nothing else; `valid` is never written.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined; rows outside
+ * [1, WEDM_MB_MAX_ROWS]; n_parts outside [1, min(rows, WEDM_MB_MAX_PARTS)]; a needed pointer NULL (tile_counts for COUNT;
+ * tile_counts, tile_base, count for OFFSETS; tile_base, count, index for SCATTER); a pointer not aligned to its element (index,
+ * count: 8; tile_counts, tile_base: 4; valid: any address); a block that is written or part of the workspace (index, count,
+ * tile_counts, tile_base: first to last byte that the call may touch) overlapping valid or another such block.            */
+int32_t wedm_minibatch_index(const wedm_mb_desc* desc, void* stream);
+
 /* ------------------------------------------------- the log of finished episodes: an ordered ring, per-episode sums
  * One call per control step, after the step: every environment whose episode ended in it appends one RECORD to a ring of
  * `capacity` slots, in the order of the global environment index, without the host learning how many there were.

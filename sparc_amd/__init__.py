@@ -27,6 +27,7 @@ from .core.state_utils import get_gap, is_short_circuited
 from .modules.views import DielectricModule, IgnitionModule, MaterialRemovalModule, MechanicsModule, WireModule
 from .controllers import GapController, VoltageController, run_controlled
 from .episode_log import EpisodeLog
+from .minibatch import MinibatchSampler
 from .normalize import Normalizer
 from .optimizer import Adam
 from .policy_head import PolicyHead
@@ -45,7 +46,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss", "Adam",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss", "Adam", "MinibatchSampler",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -521,6 +521,21 @@ class OptDesc(C.Structure):
     ]
 
 
+MB_COUNT, MB_OFFSETS, MB_SCATTER = 1, 2, 4  # enum wedm_mb_flag
+MB_STREAM0 = 0xE0000000  # WEDM_MB_STREAM0: the Philox stream of key block c is MB_STREAM0 + c
+MB_TILE, MB_MAX_ROWS, MB_MAX_PARTS = 1024, 1 << 26, 4096  # WEDM_MB_TILE, WEDM_MB_MAX_ROWS, WEDM_MB_MAX_PARTS
+
+
+class MbDesc(C.Structure):
+    """``struct wedm_mb_desc``: what `wedm_minibatch_index` reads and where it writes."""
+
+    _fields_ = [
+        ("valid", C.c_void_p), ("index", C.c_void_p), ("count", C.c_void_p), ("tile_counts", C.c_void_p), ("tile_base", C.c_void_p),
+        ("seed", C.c_uint64), ("draw", C.c_uint64),
+        ("rows", C.c_int32), ("n_parts", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
 ELOG_MAX_PLANES, ELOG_MAX_ROWS = 32, 96  # WEDM_ELOG_MAX_PLANES, WEDM_ELOG_MAX_ROWS
 ELOG_LAST, ELOG_SUM_F32, ELOG_SUM_F64, ELOG_SUM_I32 = 0, 1, 2, 3  # enum wedm_elog_kind
 ELOG_COUNT, ELOG_SCATTER, ELOG_COMMIT = 1, 2, 4  # enum wedm_elog_flag

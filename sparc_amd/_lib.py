@@ -66,6 +66,7 @@ _SIGNATURES = {
     "wedm_ppo_loss": (_i32, _to(_abi.PpoDesc), _p),
     "wedm_policy_net": (_i32, _to(_abi.NetDesc), _p),
     "wedm_adam": (_i32, _to(_abi.OptDesc), _p),
+    "wedm_minibatch_index": (_i32, _to(_abi.MbDesc), _p),
     "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
     "wedm_build_id": (C.c_char_p,),
 }
@@ -284,6 +285,10 @@ class HipBackend:
     def adam(self, desc: "_abi.OptDesc") -> None:
         """`wedm_adam` on this backend's device and torch's current stream (one launch or at most three, no synchronisation)."""
         call_stateless(self._L.wedm_adam, self.device, C.byref(desc))
+
+    def minibatch_index(self, desc: "_abi.MbDesc") -> None:
+        """`wedm_minibatch_index` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
+        call_stateless(self._L.wedm_minibatch_index, self.device, C.byref(desc))
 
     def episode_log(self, desc: "_abi.ElogDesc") -> None:
         """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""

@@ -54,13 +54,17 @@
 //                         k-ordered fma chains on the float32 MFMA, the gradient's row sum by the same tree; not in the registry
 //   wedm_adam.h           wedm_adam_norm / _decide / _apply_kernel and wedm_adam_one_kernel: Adam with global-norm clipping and a
 //                         KL gate over one flat parameter block, the norm by the same tree; not step kernels, not in the registry
+//   wedm_minibatch.h      wedm_mb_count / _offsets / _scatter_kernel: a rollout's rows dealt into minibatches by a seeded keyed
+//                         bijection of the live rows' ranks, dead rows last in every part; not step kernels, not in the registry
 //   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
-// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the eleven stateless entry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the twelve stateless entry
 // points (wedm_copy_columns ... wedm_episode_log) behind what they share, each written once above wedm_copy_columns:
 //   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
 //   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
-//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_episode_log)
+//                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_minibatch_index,
+//                         wedm_episode_log); check_apart: every written block against every other one (wedm_adam,
+//                         wedm_minibatch_index)
 //   tile_range, fold_per  the tile range inside the workspace and its tile count; the tiles per lane of a 256-lane fold
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
 //                         (wedm_policy_head, wedm_ppo_loss)
@@ -111,6 +115,7 @@ using namespace wedm;
 #include "wedm_ppo.h"
 #include "wedm_policy_net.h"
 #include "wedm_adam.h"
+#include "wedm_minibatch.h"
 #include "wedm_eplog.h"
 #endif
 
@@ -1432,6 +1437,15 @@ static int32_t check_blocks(const Entry& E, const Block* in, size_t n_in, const 
     return WEDM_OK;
 }
 
+// Every block that is written against every other one (wedm_adam, wedm_minibatch_index): the first pair that shares a byte.
+static int32_t check_apart(const Entry& E, const Block* out, size_t n_out) {
+    for (const Block* a = out; a < out + n_out; ++a)
+        for (const Block* b = a + 1; b < out + n_out; ++b)
+            if (a->lo && b->lo && a->bytes && b->bytes && a->lo < b->lo + b->bytes && b->lo < a->lo + a->bytes)
+                return E.bad(b->text() + " overlaps " + a->text());
+    return WEDM_OK;
+}
+
 // The tiles of a batch of num_envs >= 1 environments, or 0 after refusing a tile range that leaves the workspace.
 static int64_t tile_range(const Entry& E, int32_t num_envs, int32_t tile_offset, int32_t n_tiles_total) {
     const int64_t tiles = ((int64_t)num_envs + WEDM_NORM_TILE - 1) / WEDM_NORM_TILE;
@@ -1876,10 +1890,7 @@ int32_t wedm_adam(const wedm_opt_desc* desc, void* stream) {
         {"info", (uintptr_t)d.info, (uintptr_t)((decide || apply) ? WEDM_OPT_INFO * 8 : 0), 8, decide || apply},
     };
     if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
-    for (const Block* a = out; a < out + std::size(out); ++a)  // every block that is written, against every other one
-        for (const Block* b = a + 1; b < out + std::size(out); ++b)
-            if (a->lo && b->lo && a->bytes && b->bytes && a->lo < b->lo + b->bytes && b->lo < a->lo + a->bytes)
-                return E.bad(b->text() + " overlaps " + a->text());
+    if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
     const hipStream_t s = (hipStream_t)stream;
     int32_t padded = 1;  // the smallest power of two >= tiles
     while (padded < tiles) padded *= 2;
@@ -1899,6 +1910,45 @@ int32_t wedm_adam(const wedm_opt_desc* desc, void* stream) {
     if (apply) {
         hipLaunchKernelGGL(wedm_adam_apply_kernel, dim3((uint32_t)tiles), dim3(WEDM_ADAM_BLOCK), 0, s, d);
         if (const int32_t rc = E.launched("apply")) return rc;
+    }
+    return WEDM_OK;
+}
+
+int32_t wedm_minibatch_index(const wedm_mb_desc* desc, void* stream) {
+    const Entry E{"wedm_minibatch_index"};
+    if (!desc) return E.bad("null descriptor");
+    const wedm_mb_desc& d = *desc;
+    const int32_t phases = WEDM_MB_COUNT | WEDM_MB_OFFSETS | WEDM_MB_SCATTER;
+    if (d.flags & ~phases) return E.bad("undefined flag bits");
+    if (d.rows < 1 || d.rows > WEDM_MB_MAX_ROWS) return E.bad("rows outside [1, " + std::to_string(WEDM_MB_MAX_ROWS) + "]");
+    if (d.n_parts < 1 || d.n_parts > std::min<int32_t>(d.rows, WEDM_MB_MAX_PARTS))
+        return E.bad("n_parts outside [1, min(rows, " + std::to_string(WEDM_MB_MAX_PARTS) + ")]");
+    const bool every = !(d.flags & phases);
+    const bool count = every || (d.flags & WEDM_MB_COUNT), offsets = every || (d.flags & WEDM_MB_OFFSETS);
+    const bool scatter = every || (d.flags & WEDM_MB_SCATTER);
+    const int32_t tiles = (d.rows + WEDM_MB_TILE - 1) / WEDM_MB_TILE;
+    const uintptr_t rows = (uintptr_t)d.rows, ws = (uintptr_t)tiles * 4;
+    const Block in[] = {{"valid", (uintptr_t)d.valid, (count || scatter) ? rows : 0, 1, false}};
+    const Block out[] = {
+        {"index", (uintptr_t)d.index, scatter ? rows * 8 : 0, 8, scatter},
+        {"count", (uintptr_t)d.count, (uintptr_t)((offsets || scatter) ? 16 : 0), 8, offsets || scatter},
+        {"tile_counts", (uintptr_t)d.tile_counts, (count || offsets) ? ws : 0, 4, count || offsets},
+        {"tile_base", (uintptr_t)d.tile_base, (offsets || scatter) ? ws : 0, 4, offsets || scatter},
+    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
+    if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    if (count) {
+        hipLaunchKernelGGL(wedm_mb_count_kernel, dim3((uint32_t)tiles), dim3(WEDM_MB_BLOCK), 0, s, d);
+        if (const int32_t rc = E.launched("count")) return rc;
+    }
+    if (offsets) {
+        hipLaunchKernelGGL(wedm_mb_offsets_kernel, dim3(1), dim3(WEDM_MB_SCAN_BLOCK), 0, s, d, tiles);
+        if (const int32_t rc = E.launched("offsets")) return rc;
+    }
+    if (scatter) {
+        hipLaunchKernelGGL(wedm_mb_scatter_kernel, dim3((uint32_t)tiles), dim3(WEDM_MB_BLOCK), 0, s, d);
+        if (const int32_t rc = E.launched("scatter")) return rc;
     }
     return WEDM_OK;
 }

@@ -260,13 +260,22 @@ class RolloutBuffer:
         TN = self.num_steps * self.num_envs
         return {k: v.view((TN,) + tuple(v.shape[2:])) for k, v in {**self.stored, **self._results()}.items()}
 
-    def minibatches(self, n: int, generator: Optional[torch.Generator] = None) -> Iterator[Dict[str, torch.Tensor]]:
+    def minibatches(self, n: int, generator: Optional[torch.Generator] = None, sampler=None) -> Iterator[Dict[str, torch.Tensor]]:
         """``n`` disjoint index-selected parts of `flat` that together cover the rollout, in the order of a device
         ``randperm`` (``generator`` must live on the buffer's device when given).  Skipped steps are among them: weigh the
-        loss by ``valid``."""
+        loss by ``valid``.  With ``sampler``, a `MinibatchSampler` of this buffer with ``n`` parts, the parts are those of
+        its next `draw` instead: a seeded permutation a checkpoint carries, the valid steps spread evenly and first in
+        every part."""
         flat = self.flat()
-        perm = torch.randperm(self.num_steps * self.num_envs, device=self.device, generator=generator)
-        for idx in torch.tensor_split(perm, int(n)):
+        if sampler is not None:
+            if sampler.buf is not self or int(n) != sampler.n_parts or generator is not None:
+                raise ValueError(f"minibatches: the sampler must be this buffer's, n ({n}) its n_parts ({sampler.n_parts}), and "
+                                 "no generator given")
+            parts = sampler.draw()
+        else:
+            perm = torch.randperm(self.num_steps * self.num_envs, device=self.device, generator=generator)
+            parts = torch.tensor_split(perm, int(n))
+        for idx in parts:
             yield {k: v[idx] for k, v in flat.items()}
 
     def reset(self) -> None:
