@@ -29,7 +29,7 @@
 #include <cstdint>
 
 #include "../../include/wedm_hip.h"
-#include "wedm_device.h"
+#include "wedm_portable.h"
 
 // Column e of the 14 rows from (h, di, mi), or the refusal.  The whole derivation, once: the kernel below and
 // wedm_draw_episode_kernel (wedm_randomize.h), which draws h, di and mi itself, both end here.

@@ -32,7 +32,7 @@
 #include <cstdint>
 
 #include "../../include/wedm_hip.h"
-#include "wedm_device.h"
+#include "wedm_portable.h"
 
 #define WEDM_HEAD_BLOCK 256
 

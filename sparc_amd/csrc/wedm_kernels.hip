@@ -4,7 +4,10 @@
 //
 // Device code, by file (DESIGN.md section 4 has the table with what binds each kernel):
 //   wedm_device.h         per-lane physics of one microsecond: Env, prelude (quiet / general), epilogue (monitor + motion),
-//                         Philox, the portable exp / log / cube, stencil_cell
+//                         stencil_cell
+//   wedm_portable.h       what of it is pure arithmetic: the portable exp / log / cube, CPython's float `//`, Philox and its
+//                         variates; wedm_device.h includes it, and so do the families outside the registry that need nothing
+//                         else of the physics (wedm_head.h, wedm_geometry.h, wedm_randomize.h, wedm_minibatch.h)
 //   wedm_env_rows.h       which Env member holds which state row, when it is final, whether a step reads it and whether a
 //                         reference-semantics reset keeps it: the lists load_env / store_env / the trace are expanded from
 //   wedm_common.h         build switches, WalkTable, KArgs, trace point, wire accessors, the LDS images' slot maps (ChunkSlot,
@@ -65,7 +68,8 @@
 //                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_minibatch_index,
 //                         wedm_episode_log); check_apart: every written block against every other one (wedm_adam,
 //                         wedm_minibatch_index)
-//   tile_range, fold_per  the tile range inside the workspace and its tile count; the tiles per lane of a 256-lane fold
+//   tile_range, fold_per, fold_padded   the tile range inside the workspace and its tile count; the tiles per lane of a
+//                         256-lane fold; the leaves of a pairwise tree over the tiles
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
 //                         (wedm_policy_head, wedm_ppo_loss)
 // The wire block is quad-interleaved, T[seg >> 2][env][seg & 3] (include/wedm_hip.h, ABI v4): a lane that owns a run of
@@ -122,7 +126,7 @@ using namespace wedm;
 // ------------------------------------------------------------ the registry of instantiations
 // Every instantiation of a step kernel, written once as data: per family its lane counts and its forms.  They are 317
 // (wedm_debug_registry counts them), which take hipcc minutes in one translation unit, so __graft_entry__.build_hip() compiles this file six times in
-// parallel: -DWEDM_PART=N defines registry_partN(), which instantiates what it lists (1: the packed kernel, 2: the fused
+// parallel (__graft_entry__.BUILD_UNITS lists the six): -DWEDM_PART=N defines registry_partN(), which instantiates what it lists (1: the packed kernel, 2: the fused
 // kernel, 3: the served kernels and kernel 2's float32 forms, 4: the float64-typed forms of kernels 2, 6, 7 and 8 and the
 // PULSE forms of 7 and 8, 5: the SIG forms of kernels 1 and 2, 0: the rest); -DWEDM_PART=0 also holds the host code and the
 // reset and debug kernels, and registry() there joins the six slices.  The six objects link into the one shared library.  Without -DWEDM_PART the file
@@ -1463,6 +1467,13 @@ static int32_t fold_per(int64_t n) {
     return per;
 }
 
+// The leaves of a pairwise tree over `tiles` tiles: the smallest power of two >= tiles.
+static int32_t fold_padded(int64_t tiles) {
+    int32_t padded = 1;
+    while (padded < tiles) padded *= 2;
+    return padded;
+}
+
 static bool finite_f64(double x) { return x - x == 0.0; }
 
 // What wedm_policy_head and wedm_ppo_loss ask of a head's parameters, in two parts, since the loss checks its coefficients
@@ -1780,9 +1791,7 @@ int32_t wedm_ppo_loss(const wedm_ppo_desc* desc, void* stream) {
         if (const int32_t rc = E.launched("main")) return rc;
     }
     if (fold) {
-        int32_t padded = 1;  // the smallest power of two >= tiles
-        while (padded < tiles) padded *= 2;
-        hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, padded, fold_per(tiles));
+        hipLaunchKernelGGL(wedm_ppo_fold_kernel, dim3(1), dim3(256), 0, s, d, (int32_t)tiles, fold_padded(tiles), fold_per(tiles));
         if (const int32_t rc = E.launched("fold")) return rc;
     }
     return WEDM_OK;
@@ -1847,10 +1856,8 @@ int32_t wedm_policy_net(const wedm_net_desc* desc, void* stream) {
     if (bwd)
         if (const int32_t rc = launch(std::true_type{}, B, dim3((uint32_t)tiles), "main")) return rc;
     if (fold) {
-        int32_t padded = 1;  // the smallest power of two >= tiles
-        while (padded < tiles) padded *= 2;
         hipLaunchKernelGGL(wedm_net_fold_kernel, dim3((uint32_t)((F.n_theta + WEDM_NET_FOLD_PARAMS - 1) / WEDM_NET_FOLD_PARAMS)), dim3(256), 0, s, d,
-                           (int32_t)F.n_theta, (int32_t)tiles, std::max(padded / 8, 1), (int32_t)((d.flags & WEDM_NET_ACCUMULATE) != 0));
+                           (int32_t)F.n_theta, (int32_t)tiles, std::max(fold_padded(tiles) / 8, 1), (int32_t)((d.flags & WEDM_NET_ACCUMULATE) != 0));
         if (const int32_t rc = E.launched("fold")) return rc;
     }
     return WEDM_OK;
@@ -1892,8 +1899,7 @@ int32_t wedm_adam(const wedm_opt_desc* desc, void* stream) {
     if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
     if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
     const hipStream_t s = (hipStream_t)stream;
-    int32_t padded = 1;  // the smallest power of two >= tiles
-    while (padded < tiles) padded *= 2;
+    const int32_t padded = fold_padded(tiles);
     if (all && d.n <= WEDM_OPT_ONE_BLOCK_MAX) {
         const uint32_t lanes = (uint32_t)std::min<int64_t>(tiles * WEDM_ADAM_BLOCK, WEDM_ADAM_ONE_BLOCK);
         hipLaunchKernelGGL(wedm_adam_one_kernel, dim3(1), dim3(lanes), 0, s, d, (int32_t)tiles, padded);

@@ -33,6 +33,7 @@
 #include <cstdint>
 
 #include "../../include/wedm_hip.h"
+#include "wedm_portable.h"  // philox4
 
 #define WEDM_MB_BLOCK 256          // lanes of a COUNT / SCATTER block: a tile of WEDM_MB_TILE rows, four per lane
 #define WEDM_MB_SCAN_BLOCK 1024    // lanes of the OFFSETS block: tile counts per pass
@@ -154,8 +155,8 @@ __global__ void __launch_bounds__(WEDM_MB_BLOCK) wedm_mb_scatter_kernel(const we
     c.mask_hi = (1u << (b - c.hl)) - 1u;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        const W4 k = philox4((uint32_t)d.seed, (uint32_t)(d.seed >> 32), (uint32_t)d.draw, (uint32_t)(d.draw >> 32), 0u,
-                             WEDM_MB_STREAM0 + (uint32_t)q);
+        const wedm::W4 k = wedm::philox4((uint32_t)d.seed, (uint32_t)(d.seed >> 32), (uint32_t)d.draw, (uint32_t)(d.draw >> 32),
+                                         0u, WEDM_MB_STREAM0 + (uint32_t)q);
         c.key[4 * q] = k.x;
         c.key[4 * q + 1] = k.y;
         c.key[4 * q + 2] = k.z;

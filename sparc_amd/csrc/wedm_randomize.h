@@ -18,7 +18,7 @@
 #include <cstdint>
 
 #include "../../include/wedm_hip.h"
-#include "wedm_device.h"
+#include "wedm_portable.h"
 #include "wedm_geometry.h"
 
 namespace wedm {

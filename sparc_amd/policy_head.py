@@ -37,7 +37,7 @@ _M32 = np.uint64(0xFFFFFFFF)
 
 # ------------------------------------------------------------------------------------------------ portable math, normals
 def portable_exp(x) -> np.ndarray:
-    """`portable_exp` of the kernels (csrc/wedm_device.h) and the CPU oracle, element-wise on float64, bit for bit."""
+    """`portable_exp` of the kernels (csrc/wedm_portable.h) and the CPU oracle, element-wise on float64, bit for bit."""
     x = np.asarray(x, dtype=np.float64)
     ln2hi, ln2lo, invln2 = 6.93147180369123816490e-01, 1.90821492927058770002e-10, 1.44269504088896338700e+00
     P1, P2, P3 = 1.66666666666666019037e-01, -2.77777777770155933842e-03, 6.61375632143793436117e-05

@@ -33,7 +33,7 @@ _OMEGA_N = envp.INDEX["omega_n"]
 
 def philox4x32_10(counter, key) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
     """Philox4x32-10 of ``counter`` (four uint32 arrays or scalars, broadcast against each other) under ``key`` (two):
-    the four output words as uint32 arrays -- `philox4` of the kernels (csrc/wedm_device.h)."""
+    the four output words as uint32 arrays -- `philox4` of the kernels (csrc/wedm_portable.h)."""
     c0, c1, c2, c3 = np.broadcast_arrays(*(np.asarray(c, dtype=np.uint64) & _M32 for c in counter))
     k0, k1 = (np.uint64(int(k) & 0xFFFFFFFF) for k in key)
     m0, m1, s32 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57), np.uint64(32)

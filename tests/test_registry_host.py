@@ -133,3 +133,14 @@ def test_recipes_are_distinct_and_their_launch_plans_hold_what_the_scenario_says
             if r.n_envs != cat.N_ENVS:   # the batches of more than 65 536 lanes
                 assert r.n_envs * r.lanes > cat.WIDE_AUTO_MAX_LANES >= (r.n_envs - 1) * r.lanes
                 assert 9 <= r.n_seg <= 16 and sum(us for us, *_ in r.launches()) <= 20
+
+
+def test_every_source_of_the_kernel_directory_is_built_and_hashed():
+    """Every *.hip of csrc/ is the source of a build unit, and every file of csrc/ is among the sources the build id hashes
+    and the build watches: a translation unit or a header added there cannot stay out of the library or of its fingerprint."""
+    import __graft_entry__ as g
+
+    csrc = ROOT / "sparc_amd" / "csrc"
+    assert {src for src, _, _ in g.BUILD_UNITS} == set(csrc.glob("*.hip"))
+    assert len({obj for _, _, obj in g.BUILD_UNITS}) == len(g.BUILD_UNITS)
+    assert {f for f in csrc.iterdir() if f.is_file()} <= set(g.KERNEL_SOURCES)

@@ -105,3 +105,22 @@ def test_the_shared_refusals_keep_their_code_and_their_text(export):
     if tiled:
         for outside in (dict(tile_offset=1), dict(tile_offset=-1), dict(n_tiles_total=0), dict(n_tiles_total=4097)):
             assert answer(export, make(**outside)) == (_abi.ERR_BAD_ARG, f"{export}: {TILES}")
+
+
+def test_create_and_the_stateless_calls_write_one_text_per_thread():
+    """`wedm_create` and the stateless entry points refuse into one thread-local text, whichever wrote last: a
+    stateless refusal, `wedm_create`'s, a stateless refusal again, each read back through `wedm_last_error(NULL)` right after
+    it; a thread that made no call reads an empty text.  `wedm_create` returns on its null check before any HIP call."""
+    import threading
+
+    L = _lib.load()
+    texts = [answer("wedm_normalize", None)[1]]
+    assert L.wedm_create(None, 1, 1, None) == _abi.ERR_BAD_ARG
+    texts.append((L.wedm_last_error(None) or b"").decode())
+    texts.append(answer("wedm_gae", None)[1])
+    assert texts == ["wedm_normalize: null descriptor", "wedm_create: null pointer or non-positive size", "wedm_gae: null descriptor"]
+    elsewhere = []
+    t = threading.Thread(target=lambda: elsewhere.append(L.wedm_last_error(None)))
+    t.start()
+    t.join()
+    assert elsewhere == [b""] and L.wedm_last_error(None) == b"wedm_gae: null descriptor"

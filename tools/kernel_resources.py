@@ -1,12 +1,13 @@
 #!/usr/bin/env python
 """Per-kernel register / scratch / LDS usage of the gfx950 build (hipcc -Rpass-analysis=kernel-resource-usage), compiled as
-the build compiles it: the six WEDM_PART translation units, in parallel.
+the build compiles it: the units of __graft_entry__.BUILD_UNITS, in parallel.
 
     python tools/kernel_resources.py [--tsv] [--out DIR] [extra hipcc flags...]
 
 --tsv      one line per instantiation, tab-separated and sorted by name: the mangled name, the demangled name and the eight
            columns.  Nothing is truncated, so two builds compare with a plain `diff`.
---out DIR  keep the objects there, in DIR/part0 ... part5 (with -save-temps=obj among the extra flags: the gfx950 assembly too)
+--out DIR  keep the objects there, one directory per unit named after its object: DIR/wedm_kernels.part0 ... part5
+           (with -save-temps=obj among the extra flags: the gfx950 assembly too)
 """
 import re
 import shutil
@@ -33,16 +34,14 @@ else:
     out_dir = Path(tempfile.mkdtemp(prefix="wedm_resources_"))
 
 
-def compile_part(part):
-    d = out_dir / f"part{part}"  # a directory per part: -save-temps names its files after the source
+def compile_unit(unit):
+    d = out_dir / unit[2][:-len(".o")]  # a directory per unit: -save-temps names its files after the source
     d.mkdir(exist_ok=True)
-    flags = [f for f in g.HIPCC_FLAGS if f != "-shared"]
-    cmd = ["hipcc", *flags, "-Rpass-analysis=kernel-resource-usage", f"-DWEDM_PART={part}", *args, "-c",
-           "-o", str(d / "wedm_kernels.o"), str(g.HIP_SRC)]
-    return subprocess.Popen(cmd, cwd=str(g.HIP_SRC.parent), stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
+    flags = [f for f in g.HIPCC_FLAGS if f != "-shared"] + ["-Rpass-analysis=kernel-resource-usage", *args]
+    return g.start_unit(unit, d / unit[2], flags, "hipcc", stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True)
 
 
-procs = [compile_part(part) for part in (1, 2, 0, 3, 4, 5)]
+procs = [compile_unit(unit) for unit in g.BUILD_UNITS]
 rows, cur, failed = [], None, None
 for p in procs:
     err = p.communicate()[1]
