@@ -1475,6 +1475,81 @@ typedef struct wedm_elog_desc {
  * terminated, truncated, mask).                                                                                          */
 int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream);
 
+/* ------------------------------------------------- the shaped reward: ten weighted terms of one control step, one call
+ * One call per control step, after the step's launch: every environment's reward as a weighted sum of ten TERMS read from
+ * the state blocks as the launch left them, and (optionally) the ten weighted terms themselves.
+ *
+ * THE ACCUMULATORS, NOT THE PUBLICATIONS.  A launch of one control interval (1000 us) BEGINS with the control sample: that
+ * sample publishes the *_ACC rows of the pulse and signal blocks into the *_LAST rows and restarts them, so when the launch
+ * ends the *_LAST rows (and observation columns 8 ...) describe the interval BEFORE this action, and what this action caused
+ * lies in the *_ACC rows: after the second of two such launches SPARK_ACC holds this launch's sparks and SPARK_LAST the
+ * previous launch's; SAMPLES_ACC is 999 and SAMPLES_LAST 1001.  The terms therefore read *_ACC.  The control sample itself
+ * belongs to the previous publication, so a launch of one control interval contributes the 999 samples after its control step;
+ * an environment that ended inside the launch contributes what it had when it froze.
+ *
+ * TERMS.  x_k of environment e, in this order (enum wedm_reward_term):
+ *   0 PROGRESS     f64[WEDM_F_WORKPIECE_POS][e] - p0,  p0 = (restart != NULL && restart[e] != 0) ? pos_restart : pos_before[e]
+ *   1 STEP         1.0
+ *   2 WIRE_BREAK   i8[WEDM_B_WIRE_BROKEN][e] != 0 ? 1.0 : 0.0
+ *   3 TARGET       i8[WEDM_B_TARGET_REACHED][e] != 0 ? 1.0 : 0.0
+ *   4 SPARKS       (double) pulse[WEDM_P_SPARK_ACC][e]
+ *   5 SHORTS       (double) pulse[WEDM_P_SHORT_ACC][e]
+ *   6 SHORT_STEPS  (double) pulse[WEDM_P_SHORT_STEPS_ACC][e]
+ *   7 ENERGY       sig[WEDM_SG_ENERGY_ACC][e]
+ *   8 GAP_BELOW    (sig[WEDM_SG_SAMPLES_ACC][e] > 0 && gap_floor > sig[WEDM_SG_GAP_MIN_ACC][e])
+ *                      ? gap_floor - sig[WEDM_SG_GAP_MIN_ACC][e] : 0.0
+ *   9 TMAX_ABOVE   (sig[WEDM_SG_SAMPLES_ACC][e] > 0 && sig[WEDM_SG_TMAX_PEAK_ACC][e] > tmax_ceiling)
+ *                      ? sig[WEDM_SG_TMAX_PEAK_ACC][e] - tmax_ceiling : 0.0
+ *   The two hinge terms guard on SAMPLES_ACC > 0 because the identities of GAP_MIN_ACC and TMAX_PEAK_ACC are +inf and -inf;
+ *   a NaN source fails both comparisons and gives 0.0.  `restart` names the environments that the launch itself restarted
+ *   (the in-kernel autoreset): their progress counts from pos_restart, the position a reset leaves.
+ * PER ENVIRONMENT e of [0, num_envs), live(e) = mask == NULL || mask[e] != 0:
+ *   not live:  reward_out[e] = +0.0f and terms_out[k][e] = +0.0 for every k (a frozen environment earns nothing).
+ *   live:      for k ascending  t_k = (weight[k] == 0.0) ? +0.0 : weight[k] * x_k   -- the product rounded to float64, nothing
+ *              fused; with a zero weight x_k is NOT READ and its block may be NULL, so 0 * inf cannot occur;
+ *              r = +0.0, then r = r + t_k for the k with a nonzero weight, in ascending k, each sum rounded to float64;
+ *              reward_out[e] = (float) r, the single rounding to float32;  terms_out[k][e] = t_k where terms_out != NULL.
+ *   A NaN is stored as 0x7FF8000000000000 in terms_out and as 0x7FC00000 in reward_out (r is summed from the t_k as they are).
+ *   Never written: columns [num_envs, stride) of any block, any input.
+ * BLOCKS.  f64 [WEDM_F64_COUNT][stride], i8 [WEDM_I8_COUNT][stride], pulse [WEDM_PULSE_COUNT][stride] and sig
+ *   [WEDM_SIG_COUNT][stride] are an environment's state blocks (one stride, in elements); only the rows named above are read,
+ *   and only those of terms whose weight is not zero: f64 and pos_before for PROGRESS, i8 for WIRE_BREAK / TARGET, pulse
+ *   for SPARKS / SHORTS / SHORT_STEPS, sig for ENERGY / GAP_BELOW / TMAX_ABOVE.  A shard passes its blocks advanced by
+ *   its first environment: the call is elementwise.                                                                      */
+enum wedm_reward_term {
+    WEDM_RW_PROGRESS = 0, WEDM_RW_STEP, WEDM_RW_WIRE_BREAK, WEDM_RW_TARGET, WEDM_RW_SPARKS, WEDM_RW_SHORTS, WEDM_RW_SHORT_STEPS,
+    WEDM_RW_ENERGY, WEDM_RW_GAP_BELOW, WEDM_RW_TMAX_ABOVE, WEDM_RW_COUNT
+};
+typedef struct wedm_reward_desc {
+    const double* f64;             /* [WEDM_F64_COUNT][stride] or NULL (weight[PROGRESS] == 0) */
+    const int8_t* i8;              /* [WEDM_I8_COUNT][stride] or NULL (weights of WIRE_BREAK and TARGET zero) */
+    const int32_t* pulse;          /* [WEDM_PULSE_COUNT][stride] or NULL (weights of SPARKS, SHORTS, SHORT_STEPS zero) */
+    const double* sig;             /* [WEDM_SIG_COUNT][stride] or NULL (weights of ENERGY, GAP_BELOW, TMAX_ABOVE zero) */
+    const double* pos_before;      /* [num_envs]: the workpiece position before the launch; NULL as f64 */
+    const uint8_t* restart;        /* [num_envs] or NULL: nobody was restarted by the launch */
+    const uint8_t* mask;           /* [num_envs] or NULL: every environment is live */
+    float* reward_out;             /* [num_envs] */
+    double* terms_out;             /* [WEDM_RW_COUNT][terms_stride] or NULL */
+    int64_t stride;                /* >= num_envs, in elements: the four state blocks' */
+    int64_t terms_stride;          /* >= num_envs where terms_out != NULL */
+    double weight[WEDM_RW_COUNT];  /* finite; 0.0: the term is off */
+    double pos_restart;            /* finite */
+    double gap_floor;              /* finite [um] */
+    double tmax_ceiling;           /* finite */
+    int32_t num_envs;
+    int32_t reserved;
+} wedm_reward_desc;
+
+/* One launch on `stream`: one lane per environment, no LDS, no atomic.  Stateless like wedm_episode_log: no wedm_ctx, the
+ * current device, caller-owned memory.  `desc` is HOST memory, read before the call returns; everything it names is device
+ * memory.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; num_envs < 1; stride < num_envs; terms_stride <
+ * num_envs with terms_out given; a weight, pos_restart, gap_floor or tmax_ceiling that is not finite; a block that a nonzero
+ * weight needs being NULL; reward_out NULL; a pointer not aligned to its element (f64, sig, pos_before, terms_out: 8; pulse,
+ * reward_out: 4; i8, restart, mask: any address); an output block (reward_out, terms_out: first to last byte that the call
+ * may write) overlapping an input block (the rows that the call may read, pos_before, restart, mask) or the other output.  */
+int32_t wedm_reward(const wedm_reward_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

@@ -561,6 +561,36 @@ class ElogDesc(C.Structure):
     ]
 
 
+class RW(enum.IntEnum):
+    """``enum wedm_reward_term``: the ten terms of `wedm_reward`, in the order of their addition."""
+
+    PROGRESS = 0
+    STEP = 1
+    WIRE_BREAK = 2
+    TARGET = 3
+    SPARKS = 4
+    SHORTS = 5
+    SHORT_STEPS = 6
+    ENERGY = 7
+    GAP_BELOW = 8
+    TMAX_ABOVE = 9
+
+
+RW_COUNT = 10  # WEDM_RW_COUNT
+
+
+class RewardDesc(C.Structure):
+    """``struct wedm_reward_desc``: what `wedm_reward` reads and where it writes (strides in elements)."""
+
+    _fields_ = [
+        ("f64", C.c_void_p), ("i8", C.c_void_p), ("pulse", C.c_void_p), ("sig", C.c_void_p), ("pos_before", C.c_void_p),
+        ("restart", C.c_void_p), ("mask", C.c_void_p), ("reward_out", C.c_void_p), ("terms_out", C.c_void_p),
+        ("stride", C.c_int64), ("terms_stride", C.c_int64),
+        ("weight", C.c_double * RW_COUNT), ("pos_restart", C.c_double), ("gap_floor", C.c_double), ("tmax_ceiling", C.c_double),
+        ("num_envs", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

@@ -68,6 +68,7 @@ _SIGNATURES = {
     "wedm_adam": (_i32, _to(_abi.OptDesc), _p),
     "wedm_minibatch_index": (_i32, _to(_abi.MbDesc), _p),
     "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
+    "wedm_reward": (_i32, _to(_abi.RewardDesc), _p),
     "wedm_build_id": (C.c_char_p,),
 }
 EXPORTS = tuple(_SIGNATURES)
@@ -293,6 +294,10 @@ class HipBackend:
     def episode_log(self, desc: "_abi.ElogDesc") -> None:
         """`wedm_episode_log` on this backend's device and torch's current stream (at most three launches, no synchronisation)."""
         call_stateless(self._L.wedm_episode_log, self.device, C.byref(desc))
+
+    def reward(self, desc: "_abi.RewardDesc") -> None:
+        """`wedm_reward` on this backend's device and torch's current stream (one launch, no synchronisation)."""
+        call_stateless(self._L.wedm_reward, self.device, C.byref(desc))
 
     def trace_samples(self) -> int:
         return int(self._L.wedm_trace_samples(self._ctx))

@@ -61,13 +61,15 @@
 //                         bijection of the live rows' ranks, dead rows last in every part; not step kernels, not in the registry
 //   wedm_eplog.h          wedm_elog_count / _scatter / _commit_kernel: the finished episodes of a control step appended to a ring
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
-// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the twelve stateless entry
-// points (wedm_copy_columns ... wedm_episode_log) behind what they share, each written once above wedm_copy_columns:
+//   wedm_reward.h         wedm_reward_kernel: a control step's shaped reward, ten weighted terms of the state blocks (the *_ACC
+//                         rows) summed in a fixed order, one lane per environment; not a step kernel, not in the registry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the thirteen stateless entry
+// points (wedm_copy_columns ... wedm_reward) behind what they share, each written once above wedm_copy_columns:
 //   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
 //   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
 //                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_minibatch_index,
-//                         wedm_episode_log); check_apart: every written block against every other one (wedm_adam,
-//                         wedm_minibatch_index)
+//                         wedm_episode_log, wedm_reward); check_apart: every written block against every other one
+//                         (wedm_adam, wedm_minibatch_index, wedm_reward)
 //   tile_range, fold_per, fold_padded   the tile range inside the workspace and its tile count; the tiles per lane of a
 //                         256-lane fold; the leaves of a pairwise tree over the tiles
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
@@ -121,6 +123,7 @@ using namespace wedm;
 #include "wedm_adam.h"
 #include "wedm_minibatch.h"
 #include "wedm_eplog.h"
+#include "wedm_reward.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -2015,6 +2018,46 @@ int32_t wedm_episode_log(const wedm_elog_desc* desc, void* stream) {
         if (const int32_t rc = E.launched("commit")) return rc;
     }
     return WEDM_OK;
+}
+
+int32_t wedm_reward(const wedm_reward_desc* desc, void* stream) {
+    const Entry E{"wedm_reward"};
+    if (!desc) return E.bad("null descriptor");
+    const wedm_reward_desc& d = *desc;
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.stride < d.num_envs) return E.bad("stride smaller than num_envs");
+    if (d.terms_out && d.terms_stride < d.num_envs) return E.bad("terms_stride smaller than num_envs");
+    for (int k = 0; k < WEDM_RW_COUNT; ++k)
+        if (!finite_f64(d.weight[k])) return E.bad("weight " + std::to_string(k) + " is not finite");
+    if (!finite_f64(d.pos_restart) || !finite_f64(d.gap_floor) || !finite_f64(d.tmax_ceiling))
+        return E.bad("pos_restart, gap_floor or tmax_ceiling is not finite");
+    const auto on = [&d](int k) { return d.weight[k] != 0.0; };
+    const bool progress = on(WEDM_RW_PROGRESS), flags = on(WEDM_RW_WIRE_BREAK) || on(WEDM_RW_TARGET);
+    const bool pulse = on(WEDM_RW_SPARKS) || on(WEDM_RW_SHORTS) || on(WEDM_RW_SHORT_STEPS);
+    const bool sig = on(WEDM_RW_ENERGY) || on(WEDM_RW_GAP_BELOW) || on(WEDM_RW_TMAX_ABOVE);
+    const uintptr_t n = (uintptr_t)d.num_envs, S = (uintptr_t)d.stride;
+    // rows [first, last] of a state block of `elem`-byte elements: from the first row's first byte to the last row's column n
+    const auto rows = [n, S](const char* name, const void* base, int first, int last, uintptr_t elem, bool needed) {
+        return Block{name, base ? (uintptr_t)base + (uintptr_t)first * S * elem : 0, ((uintptr_t)(last - first) * S + n) * elem, elem, needed};
+    };
+    const Block in[] = {
+        rows("f64", d.f64, WEDM_F_WORKPIECE_POS, WEDM_F_WORKPIECE_POS, 8, progress),
+        rows("i8", d.i8, WEDM_B_WIRE_BROKEN, WEDM_B_TARGET_REACHED, 1, flags),
+        rows("pulse", d.pulse, WEDM_P_SPARK_ACC, WEDM_P_SHORT_STEPS_ACC, 4, pulse),
+        rows("sig", d.sig, WEDM_SG_SAMPLES_ACC, WEDM_SG_TMAX_PEAK_ACC, 8, sig),
+        {"pos_before", (uintptr_t)d.pos_before, n * 8, 8, progress},
+        {"restart", (uintptr_t)d.restart, n, 1, false},
+        {"mask", (uintptr_t)d.mask, n, 1, false},
+    };
+    const Block out[] = {
+        {"reward_out", (uintptr_t)d.reward_out, n * 4, 4, true},
+        {"terms_out", (uintptr_t)d.terms_out, ((uintptr_t)(WEDM_RW_COUNT - 1) * (uintptr_t)d.terms_stride + n) * 8, 8, false},
+    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
+    if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
+    hipLaunchKernelGGL(wedm_reward_kernel, dim3((uint32_t)((d.num_envs + WEDM_RW_BLOCK - 1) / WEDM_RW_BLOCK)), dim3(WEDM_RW_BLOCK), 0,
+                       (hipStream_t)stream, d);
+    return E.launched();
 }
 
 // why a descriptor cannot be followed (wedm_derive_geometry, and wedm_draw_episode for its `geom`), or NULL

@@ -131,7 +131,9 @@ class EpisodeLog:
     an `EpisodeSampler`: ``draw``, the environment's draw count -- ``sampler.expected(records["env"], records["draw"] - 1)``
     is the physics every logged episode ran with.  With ``wire_material=[...]``: ``material``.  With ``dynamic_geometry``:
     ``height``, ``diameter_index``.  With ``pulse_stats=True``: the sums ``sparks``, ``shorts``, ``short_steps``; with
-    ``signal_stats=True``: ``samples``, ``current``, ``energy``.
+    ``signal_stats=True``: ``samples``, ``current``, ``energy``.  With a `ShapedReward`: ``rw_progress`` ... ``rw_tmax_above``,
+    the per-episode sum of each weighted reward term in float64 (they add up to ``reward_sum`` to within the float32 rounding
+    of each step's reward).
 
     `read` is the one host synchronisation, taken when the user chooses; nothing else here reads the device."""
 
@@ -192,6 +194,9 @@ class EpisodeLog:
             P.append(_Plane(("sparks", "shorts", "short_steps"), SUM_I32, row(st.pulse, _abi.PULSE.SPARK_LAST, 3), torch.int32))
         if st.signal is not None:
             P.append(_Plane(("samples", "current", "energy"), SUM_F64, row(st.signal, _abi.SIG.SAMPLES_LAST, 3), torch.float64))
+        shaped = getattr(vec, "_shaped", None)
+        if shaped is not None:
+            P.append(_Plane(tuple(f"rw_{name}" for name in shaped.term_names), SUM_F64, shaped.terms, torch.float64))
         assert len(P) <= _abi.ELOG_MAX_PLANES and sum(len(p.names) for p in P) <= _abi.ELOG_MAX_ROWS
         kw = dict(device=self.device)
         for p in P:
@@ -323,7 +328,8 @@ class EpisodeLog:
     def summary(self, records: Dict[str, Any]) -> Dict[str, Any]:
         """On the host, in NumPy: the number of ``episodes``; the shares ``terminated``, ``truncated``, ``wire_broken``,
         ``target_reached``; ``mean_time_us``; ``mean_progress`` (micrometres cut: ``workpiece_position`` minus the
-        configuration's initial gap); ``mean_speed`` (progress per microsecond, over episodes that took time); and, where
+        configuration's initial gap); ``mean_speed`` (progress per microsecond, over episodes that took time); with a `ShapedReward`
+        ``mean_rw_<term>``, the mean of each reward term's per-episode sum; and, where
         there is a ``material`` column, the same ``per_material`` by material name."""
         self._bound()
 
@@ -337,6 +343,9 @@ class EpisodeLog:
             progress = records["workpiece_position"][sel] - self._initial_gap
             out["mean_time_us"], out["mean_progress"] = mean(t), mean(progress)
             out["mean_speed"] = mean(progress[t > 0] / t[t > 0])
+            for key in records:
+                if key.startswith("rw_"):
+                    out[f"mean_{key}"] = mean(records[key][sel])
             return out
 
         everyone = np.ones(records["env"].shape[0], dtype=bool)

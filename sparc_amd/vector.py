@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .envs.wire_edm import WireEDMEnv
+from .reward import ShapedReward
 
 
 def progress_reward(env: WireEDMEnv, prev: Dict[str, torch.Tensor]) -> torch.Tensor:
@@ -101,7 +102,14 @@ class WireEDMVectorEnv:
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
         it); a callable ``f(env, prev) -> float32[N]`` receives the environment after the control
-        interval and ``prev = {"workpiece_position": ...}`` snapshotted before it (all on the device).
+        interval and ``prev = {"workpiece_position": ...}`` snapshotted before it (all on the device); a
+        `sparc_amd.reward.ShapedReward` is a weighted sum of ten terms of the step -- progress, a cost per step, wire break,
+        target, the step's sparks, shorts and short-circuit samples, its energy, the gap below a floor, the peak temperature
+        above a ceiling -- formed by one `wedm_reward` call after the launch (one copy of a row before it; no host
+        synchronisation, no allocation after the first step) from the accumulator rows, which hold what this step's action
+        caused; ``info["reward_terms"]`` is the float64 ``[10, N]`` block of the weighted terms, valid until the next step,
+        the normaliser and the episode log take the shaped reward as the raw reward, and the environment's own reward row is
+        ignored.
         ``param_sampler``: domain randomisation -- ``f(env, reset_mask) -> {name: float64[N] device tensor}`` is called at
         every `step()` before the launch (and at `reset()` with every environment marked); the values are applied
         (`WireEDMEnv.set_env_params`) only where ``reset_mask`` is set, so each new episode starts with freshly drawn
@@ -162,6 +170,9 @@ class WireEDMVectorEnv:
                              "the adapter cannot switch that off")
         if reward == "progress" and getattr(env, "reward_kind", None) == "progress":
             reward = None  # the kernel writes it
+        self._shaped = reward if isinstance(reward, ShapedReward) else None
+        if self._shaped is not None:
+            reward = None
         self._reward_fn = progress_reward if reward == "progress" else reward
         if self._reward_fn is not None and not callable(self._reward_fn):
             raise ValueError("reward must be None, 'progress' or a callable")
@@ -181,6 +192,8 @@ class WireEDMVectorEnv:
                 raise ValueError("episode_sampler replaces param_sampler / material_sampler / geometry_sampler: give either")
             episode_sampler.bind(env)
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
+        if self._shaped is not None:
+            self._shaped.bind(self)
         self.normalizer = normalizer
         if normalizer is not None:
             normalizer.bind(self.obs_names, self.num_envs, env.device, getattr(env, "_backend", None))
@@ -265,13 +278,20 @@ class WireEDMVectorEnv:
                 self.env.reset(options={"mask": self._need_reset})  # same key, next episode stream
             self.episode_count += self._need_reset.to(torch.int64)
         # environments this step leaves frozen take no part in the normaliser's statistics or in the episode log
-        live = None if (self.normalizer is None and self.episode_log is None) or self.autoreset else ~self._need_reset
+        shaped = self._shaped
+        live = None if (self.normalizer is None and self.episode_log is None and shaped is None) or self.autoreset \
+            else ~self._need_reset
+        if shaped is not None:
+            shaped.before_launch()
+            restarted = self._need_reset if self._in_kernel_reset else None  # whom the launch itself restarts
         prev = {"workpiece_position": self.env.state.workpiece_position.clone()} if self._reward_fn is not None else None
         if prev is not None and self._in_kernel_reset:  # what the kernel's reset will make of the marked environments
             prev["workpiece_position"] = torch.where(self._need_reset, torch.full_like(
                 prev["workpiece_position"], float(self.env.config.initial_gap)), prev["workpiece_position"])
         obs, reward, terminated, truncated, info = self.env.step_control(action)
-        if self._reward_fn is not None:
+        if shaped is not None:
+            reward = shaped.after_launch(restarted, live).clone()
+        elif self._reward_fn is not None:
             reward = self._reward_fn(self.env, prev)
         else:
             reward = reward.clone()
@@ -283,6 +303,8 @@ class WireEDMVectorEnv:
         self._need_reset = terminated | truncated
         info = dict(info)  # (StepInfo: the copy composes the exact int64 clock)
         info["episode"] = self.episode_count
+        if shaped is not None:
+            info["reward_terms"] = shaped.terms
         if self.normalizer is not None:
             norm = self.normalizer
             reward = reward.contiguous()
@@ -314,6 +336,8 @@ class WireEDMVectorEnv:
 
     # ---- checkpoints ----
     def _reward_kind(self) -> str:
+        if self._shaped is not None:
+            return "shaped"
         return "kernel" if self._reward_fn is None else "progress" if self._reward_fn is progress_reward else "callable"
 
     def _sampler_kinds(self) -> Tuple[str, ...]:
@@ -323,15 +347,19 @@ class WireEDMVectorEnv:
 
     def _settings(self) -> Dict[str, Any]:
         """What changes what a step does, as plain values."""
-        return {"num_envs": self.num_envs, "autoreset": self.autoreset, "max_episode_steps": self.max_episode_steps,
-                "wire_profile_bins": self.wire_profile_bins, "obs_names": tuple(self.obs_names), "reward": self._reward_kind(),
-                "samplers": self._sampler_kinds()}
+        out = {"num_envs": self.num_envs, "autoreset": self.autoreset, "max_episode_steps": self.max_episode_steps,
+               "wire_profile_bins": self.wire_profile_bins, "obs_names": tuple(self.obs_names), "reward": self._reward_kind(),
+               "samplers": self._sampler_kinds()}
+        if self._shaped is not None:  # (a ShapedReward keeps nothing across steps: its settings are all there is)
+            out.update({f"reward_{key}": value for key, value in self._shaped.settings().items()})
+        return out
 
     def state_dict(self) -> Dict[str, Any]:
         """Everything a bit-identical continuation of the adapter needs: which environments start a new episode at the next
         `step()` (``need_reset``) and their ``episode_count``, the settings that change what a step does (batch size,
         ``autoreset``, ``max_episode_steps``, ``wire_profile_bins``, ``obs_names``, the kind of reward -- ``"kernel"``,
-        ``"progress"`` or ``"callable"`` -- and the kinds of samplers present), and under ``"env"``, ``"episode_sampler"`` and
+        ``"progress"``, ``"callable"`` or ``"shaped"``, the last with the `ShapedReward`'s ``reward_weights``,
+        ``reward_gap_floor`` and ``reward_tmax_ceiling`` -- and the kinds of samplers present), and under ``"env"``, ``"episode_sampler"`` and
         ``"normalizer"`` and ``"episode_log"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
         tuples and lists only: loads with ``weights_only=True``.
         Not in it: ``param_sampler`` / ``material_sampler`` / ``geometry_sampler`` draw from a ``torch.Generator`` the caller
