@@ -1550,6 +1550,93 @@ typedef struct wedm_reward_desc {
  * may write) overlapping an input block (the rows that the call may read, pos_before, restart, mask) or the other output.  */
 int32_t wedm_reward(const wedm_reward_desc* desc, void* stream);
 
+/* ------------------------------------------------- the sensor model: noise, calibration error and latency, one call
+ * One call per control step (and per reset), between the environment's observation and everything downstream: C_out
+ * measured CHANNELS, each of one SOURCE column out of the C_in rows of up to two source planes (the environment's observation
+ * block and the wire-profile rows, as wedm_normalize takes them), delayed by a whole number of calls, scaled and shifted by
+ * a calibration error that is fixed for the episode, disturbed by fresh Gaussian noise, quantised to the ADC's step and
+ * saturated at its range.  The output is struct-of-arrays, out[C_out][out_stride]: wedm_normalize reads it as its plane 0.
+ *
+ * THE CHANNEL TABLE lies in device memory and the host does not read it: float64 chan[WEDM_SENSOR_FIELDS][C_out] (enum
+ * wedm_sensor_field: SIGMA, GAIN_SPREAD, OFFSET_SPREAD, LSB, LO, HI) and int32 route[WEDM_SENSOR_ROUTES][C_out] (SOURCE,
+ * MAX_DELAY).  Before either forms an address the kernel clamps SOURCE into [0, C_in) and MAX_DELAY into [0, L - 1]; the
+ * float64 settings are used as they are (the Python class validates them before it uploads them).
+ * STATE, the caller's memory, carried from call to call: ring[L][C_in][ring_stride] float32, the last L samples of every
+ * source column (NULL and never touched when L == 1), and int32 pos[num_envs], age[num_envs]: the ring slot of the newest
+ * sample and the number of samples the episode has behind it, at most L - 1.
+ *
+ * PER ENVIRONMENT e of [0, num_envs) with mask == NULL || mask[e] != 0 (for any other e nothing is read and nothing is
+ * written: its output, ring, pos and age stay), g = (env_id_offset + e) mod 2^32, k = episode ? (uint64) episode[e] : 0,
+ * key = {seed & 0xffffffff, seed >> 32}; all arithmetic float64, every operation rounded on its own, nothing fused:
+ *  1. first == NULL || first[e] != 0:  age = 0, pos = 0  (the old values are not used: uninitialised state is harmless);
+ *     otherwise  age = min(clamp(age_old, 0, L - 1) + 1, L - 1),  pos = (clamp(pos_old, 0, L - 1) + 1) mod L  (the clamps
+ *     change nothing of a state this call wrote; they keep a foreign one from overflowing).
+ *  2. L > 1:  ring[pos][s][e] = src[s][e] for every source column s (the bits are copied).
+ *  3. for every channel c, s = clamp(SOURCE_c), md = clamp(MAX_DELAY_c):
+ *     calibration words, only if GAIN_SPREAD_c != 0 || OFFSET_SPREAD_c != 0 || md != 0:
+ *         W  = Philox4x32-10(key, counter {k lo, k hi, g, WEDM_SENSOR_STREAM0 + 0x100000 + c})
+ *         ua = ((double) W.x + 0.5) * 2^-32,  ub = ((double) W.y + 0.5) * 2^-32,
+ *         d  = (uint32) (((uint64) W.z * (uint64) (md + 1)) >> 32)                  (d = 0 without the words)
+ *       -- gain error, offset and delay are a function of (seed, g, k, c): fixed for the episode.
+ *     sample:  d_eff = min(d, age) (a delay never reaches into the episode before);
+ *         x = d_eff == 0 ? src[s][e] : ring[(pos + L - d_eff) mod L][s][e];   y = (double) x
+ *     if GAIN_SPREAD_c != 0 || OFFSET_SPREAD_c != 0:
+ *         gain = 1.0 + GAIN_SPREAD_c * (2.0 * ua - 1.0);  off = OFFSET_SPREAD_c * (2.0 * ub - 1.0);  y = (y * gain) + off
+ *     if SIGMA_c != 0:   y = y + SIGMA_c * n,  n the step kernels' polar method (Marsaglia on 53-bit pairs, the first of 64
+ *         attempts j inside the unit circle, else 0.0) on the counters {t lo, t hi, g, WEDM_SENSOR_STREAM0 + 64 c + j}
+ *       -- fresh for every call: a function of (seed, g, t, c).
+ *     if LSB_c > 0:      y = LSB_c * rint(y / LSB_c), round half to even
+ *     if y < LO_c: y = LO_c.   if y > HI_c: y = HI_c.   (a NaN falls through both comparisons)
+ *     out[c][e] = (float) y, one rounding; a NaN is stored as 0x7FC00000 (the sign of a NaN made by an operation differs
+ *     between x86 and gfx950).
+ *   A channel with the settings 0, 0, 0, 0, -inf, +inf and MAX_DELAY 0 is therefore a copy of the source's bits, -0.0,
+ *   subnormals and infinities included (a NaN in its canonical form): that is how clean columns pass through.
+ * STREAMS.  WEDM_SENSOR_STREAM0 = 0xA0000000.  The noise of channel c uses WEDM_SENSOR_STREAM0 + 64 c + j, j < 64, c <= 158:
+ *   64 * 159 = 10 176 streams, [0xA0000000, 0xA00027C0); the calibration words use WEDM_SENSOR_STREAM0 + 0x100000 + c,
+ *   [0xA0100000, 0xA010009F).  The two ranges stay clear of each other and of the physics' streams 0 .. 64, of
+ *   wedm_draw_episode's 0x80000000 + q, of the head's from 0xC0000000 and of the minibatch index's 0xE0000000.
+ * Never written: columns [num_envs, stride) of any block, the ring slots other than pos, any input.  A shard passes every
+ * per-environment pointer advanced by its first environment and env_id_offset moved with it: the call is elementwise.   */
+#define WEDM_SENSOR_MAX_DELAY 7          /* L <= WEDM_SENSOR_MAX_DELAY + 1 */
+#define WEDM_SENSOR_STREAM0 0xA0000000u
+enum wedm_sensor_field {
+    WEDM_SN_SIGMA = 0, WEDM_SN_GAIN_SPREAD, WEDM_SN_OFFSET_SPREAD, WEDM_SN_LSB, WEDM_SN_LO, WEDM_SN_HI, WEDM_SENSOR_FIELDS
+};
+enum wedm_sensor_route { WEDM_SN_SOURCE = 0, WEDM_SN_MAX_DELAY, WEDM_SENSOR_ROUTES };
+typedef struct wedm_sensor_desc {
+    wedm_norm_plane plane[2];      /* the sources: C_in = plane[0].n_rows + plane[1].n_rows, in [1, WEDM_NORM_MAX_COLUMNS - 1] */
+    const double* chan;            /* [WEDM_SENSOR_FIELDS][n_out], device memory */
+    const int32_t* route;          /* [WEDM_SENSOR_ROUTES][n_out], device memory */
+    const uint8_t* first;          /* [num_envs] or NULL: every environment starts an episode */
+    const uint8_t* mask;           /* [num_envs] or NULL: every environment takes part */
+    const int64_t* episode;        /* [num_envs] or NULL: episode number 0 */
+    float* out;                    /* [n_out][out_stride] */
+    float* ring;                   /* [ring_len][C_in][ring_stride]; not read and not written when ring_len == 1 */
+    int32_t* pos;                  /* [num_envs] */
+    int32_t* age;                  /* [num_envs] */
+    int64_t out_stride;            /* >= num_envs, in elements */
+    int64_t ring_stride;           /* >= num_envs where ring_len > 1 */
+    uint64_t seed;
+    uint64_t t;                    /* the caller's call number */
+    uint32_t env_id_offset;        /* global id of environment 0 */
+    int32_t num_envs;
+    int32_t n_out;                 /* C_out, in [1, WEDM_NORM_MAX_COLUMNS - 1] */
+    int32_t ring_len;              /* L, in [1, WEDM_SENSOR_MAX_DELAY + 1] */
+    int32_t flags;                 /* none is defined: 0 */
+    int32_t reserved;
+} wedm_sensor_desc;
+
+/* One launch on `stream`: one lane per environment, the channel table through uniform loads, no LDS, no atomic.  Stateless
+ * like wedm_reward: no wedm_ctx, the current device, caller-owned memory.  `desc` is HOST memory, read before the call
+ * returns; everything it names is device memory.
+ * WEDM_ERR_BAD_ARG (text: wedm_last_error(NULL)), nothing launched: desc NULL; flag bits that are not defined; num_envs < 1;
+ * a negative n_rows or C_in outside [1, WEDM_NORM_MAX_COLUMNS - 1]; n_out outside the same range; ring_len outside
+ * [1, WEDM_SENSOR_MAX_DELAY + 1]; ring NULL with ring_len > 1; a stride (of a plane that has rows, out_stride, ring_stride
+ * with ring_len > 1) below num_envs; a needed block NULL or not aligned to its element (chan: 8; the planes' rows, route,
+ * out, ring, pos, age: 4; episode: 8; first, mask: any address); out, ring, pos or age (first to last byte that the call may
+ * touch) overlapping each other or an input (the planes' rows, chan, route, first, mask, episode).                       */
+int32_t wedm_sensor(const wedm_sensor_desc* desc, void* stream);
+
 /* TEST HOOK: evaluates one of the device math primitives the physics relies on,
  * element-wise on device arrays, so tests can compare them bit for bit with the CPU.
  * kind: 0 exp, 1 log, 2 correctly-rounded cube, 3 sqrt, 4 Python floor-division

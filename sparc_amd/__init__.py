@@ -36,6 +36,7 @@ from .ppo import PPOLoss
 from .randomize import EpisodeSampler
 from .reward import ShapedReward, reward_definition
 from .rollout import RolloutBuffer
+from .sensor import MEASURABLE_OBS_NAMES, Channel, Sensor, sensor_reference
 from .snapshot import EnvSnapshot
 from .trace import DeviceTrace
 from .utils.logger import LoggerConfig, SimulationLogger
@@ -47,7 +48,7 @@ __version__ = "0.1.0"
 
 __all__ = [
     "EDMState", "BatchedEDMState", "EnvironmentConfig", "MaterialDatabase", "WireMaterial", "get_material_db",
-    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss", "Adam", "MinibatchSampler", "ShapedReward", "reward_definition",
+    "WireEDMEnv", "DeviceAction", "WireEDMVectorEnv", "uniform_param_sampler", "uniform_material_sampler", "uniform_geometry_sampler", "GapController", "VoltageController", "run_controlled", "DeviceTrace", "EnvSnapshot", "EpisodeSampler", "EpisodeLog", "Normalizer", "RolloutBuffer", "PolicyHead", "PolicyNet", "PPOLoss", "Adam", "MinibatchSampler", "ShapedReward", "reward_definition", "Sensor", "Channel", "sensor_reference", "MEASURABLE_OBS_NAMES",
     "SimulationLogger", "LoggerConfig",
     "IgnitionModule", "WireModule", "MaterialRemovalModule", "DielectricModule", "MechanicsModule",
     "get_gap", "is_short_circuited",

@@ -591,6 +591,36 @@ class RewardDesc(C.Structure):
     ]
 
 
+class SN(enum.IntEnum):
+    """``enum wedm_sensor_field``: the rows of `wedm_sensor`'s float64 channel table."""
+
+    SIGMA = 0
+    GAIN_SPREAD = 1
+    OFFSET_SPREAD = 2
+    LSB = 3
+    LO = 4
+    HI = 5
+
+
+SENSOR_FIELDS = 6               # WEDM_SENSOR_FIELDS
+SN_SOURCE, SN_MAX_DELAY = 0, 1  # enum wedm_sensor_route
+SENSOR_ROUTES = 2               # WEDM_SENSOR_ROUTES
+SENSOR_MAX_DELAY = 7            # WEDM_SENSOR_MAX_DELAY
+SENSOR_STREAM0 = 0xA0000000     # WEDM_SENSOR_STREAM0
+
+
+class SensorDesc(C.Structure):
+    """``struct wedm_sensor_desc``: what `wedm_sensor` reads, its state and where it writes (strides in elements)."""
+
+    _fields_ = [
+        ("plane", NormPlane * 2), ("chan", C.c_void_p), ("route", C.c_void_p), ("first", C.c_void_p), ("mask", C.c_void_p),
+        ("episode", C.c_void_p), ("out", C.c_void_p), ("ring", C.c_void_p), ("pos", C.c_void_p), ("age", C.c_void_p),
+        ("out_stride", C.c_int64), ("ring_stride", C.c_int64), ("seed", C.c_uint64), ("t", C.c_uint64),
+        ("env_id_offset", C.c_uint32), ("num_envs", C.c_int32), ("n_out", C.c_int32), ("ring_len", C.c_int32),
+        ("flags", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class GEOMC(enum.IntEnum):
     """``enum wedm_geomc_field``: one row of the (material, diameter) combination table `wedm_derive_geometry` reads -- what
     `derive_geometry` derives from the diameter and the material alone, and ``PI_R = math.pi * (diameter / 2)``."""

@@ -69,6 +69,7 @@ _SIGNATURES = {
     "wedm_minibatch_index": (_i32, _to(_abi.MbDesc), _p),
     "wedm_episode_log": (_i32, _to(_abi.ElogDesc), _p),
     "wedm_reward": (_i32, _to(_abi.RewardDesc), _p),
+    "wedm_sensor": (_i32, _to(_abi.SensorDesc), _p),
     "wedm_build_id": (C.c_char_p,),
 }
 EXPORTS = tuple(_SIGNATURES)
@@ -298,6 +299,10 @@ class HipBackend:
     def reward(self, desc: "_abi.RewardDesc") -> None:
         """`wedm_reward` on this backend's device and torch's current stream (one launch, no synchronisation)."""
         call_stateless(self._L.wedm_reward, self.device, C.byref(desc))
+
+    def sensor(self, desc: "_abi.SensorDesc") -> None:
+        """`wedm_sensor` on this backend's device and torch's current stream (one launch, no synchronisation)."""
+        call_stateless(self._L.wedm_sensor, self.device, C.byref(desc))
 
     def trace_samples(self) -> int:
         return int(self._L.wedm_trace_samples(self._ctx))

@@ -63,13 +63,16 @@
 //                         in the order of the global environment index, per-episode sums; not step kernels, not in the registry
 //   wedm_reward.h         wedm_reward_kernel: a control step's shaped reward, ten weighted terms of the state blocks (the *_ACC
 //                         rows) summed in a fixed order, one lane per environment; not a step kernel, not in the registry
-// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the thirteen stateless entry
-// points (wedm_copy_columns ... wedm_reward) behind what they share, each written once above wedm_copy_columns:
+//   wedm_sensor.h         wedm_sensor_kernel: what a machine measures of the observation -- per channel a delayed source column,
+//                         the episode's gain and offset error, fresh noise, quantisation, saturation --, one lane per
+//                         environment, includes wedm_portable.h alone; not a step kernel, not in the registry
+// Host code, in this file's part 0: the launch plan and the entry points that take a handle, then the fourteen stateless entry
+// points (wedm_copy_columns ... wedm_sensor) behind what they share, each written once above wedm_copy_columns:
 //   Entry                 the entry point's name: bad(msg) refuses with "<name>: <msg>", launched([what]) reports a launch
 //   Block, check_blocks   a call's memory by name, inputs and outputs: null or misaligned, then an output on an input
 //                         (wedm_gae, wedm_policy_head, wedm_ppo_loss, wedm_policy_net, wedm_adam, wedm_minibatch_index,
-//                         wedm_episode_log, wedm_reward); check_apart: every written block against every other one
-//                         (wedm_adam, wedm_minibatch_index, wedm_reward)
+//                         wedm_episode_log, wedm_reward, wedm_sensor); check_apart: every written block against every other
+//                         one (wedm_adam, wedm_minibatch_index, wedm_reward, wedm_sensor)
 //   tile_range, fold_per, fold_padded   the tile range inside the workspace and its tile count; the tiles per lane of a
 //                         256-lane fold; the leaves of a pairwise tree over the tiles
 //   check_head_params, StagedRows   n_modes, strides and bounds of a head; which rows go through LDS and the LDS for it
@@ -124,6 +127,7 @@ using namespace wedm;
 #include "wedm_minibatch.h"
 #include "wedm_eplog.h"
 #include "wedm_reward.h"
+#include "wedm_sensor.h"
 #endif
 
 // ------------------------------------------------------------ the registry of instantiations
@@ -2057,6 +2061,54 @@ int32_t wedm_reward(const wedm_reward_desc* desc, void* stream) {
     if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
     hipLaunchKernelGGL(wedm_reward_kernel, dim3((uint32_t)((d.num_envs + WEDM_RW_BLOCK - 1) / WEDM_RW_BLOCK)), dim3(WEDM_RW_BLOCK), 0,
                        (hipStream_t)stream, d);
+    return E.launched();
+}
+
+int32_t wedm_sensor(const wedm_sensor_desc* desc, void* stream) {
+    const Entry E{"wedm_sensor"};
+    if (!desc) return E.bad("null descriptor");
+    const wedm_sensor_desc& d = *desc;
+    if (d.flags != 0) return E.bad("undefined flag bits");
+    if (d.num_envs < 1) return E.bad("num_envs must be positive");
+    if (d.plane[0].n_rows < 0 || d.plane[1].n_rows < 0) return E.bad("negative n_rows");
+    const int64_t C_in = (int64_t)d.plane[0].n_rows + d.plane[1].n_rows, C_out = d.n_out;
+    const std::string columns = " outside [1, " + std::to_string(WEDM_NORM_MAX_COLUMNS - 1) + "]";
+    if (C_in < 1 || C_in > WEDM_NORM_MAX_COLUMNS - 1) return E.bad("C_in" + columns);
+    if (C_out < 1 || C_out > WEDM_NORM_MAX_COLUMNS - 1) return E.bad("n_out" + columns);
+    const int64_t L = d.ring_len;
+    if (L < 1 || L > WEDM_SENSOR_MAX_DELAY + 1) return E.bad("ring_len outside [1, " + std::to_string(WEDM_SENSOR_MAX_DELAY + 1) + "]");
+    const bool ringed = L > 1;
+    if (ringed && !d.ring) return E.bad("ring is null though ring_len > 1");
+    for (int k = 0; k < 2; ++k)
+        if (d.plane[k].n_rows > 0 && d.plane[k].stride < d.num_envs) return E.bad("plane " + std::to_string(k) + ": stride smaller than num_envs");
+    if (d.out_stride < d.num_envs) return E.bad("out_stride smaller than num_envs");
+    if (ringed && d.ring_stride < d.num_envs) return E.bad("ring_stride smaller than num_envs");
+    const uintptr_t n = (uintptr_t)d.num_envs;
+    // a struct-of-arrays block of `rows` float32 rows: from its first byte to column n of its last row
+    const auto soa = [n](uintptr_t rows, int64_t stride) { return rows ? ((rows - 1) * (uintptr_t)stride + n) * 4 : (uintptr_t)0; };
+    const auto plane = [&](int k) {
+        const wedm_norm_plane& p = d.plane[k];
+        const bool used = p.n_rows > 0;
+        return Block{" rows", used ? (uintptr_t)p.rows : 0, used ? soa((uintptr_t)p.n_rows, p.stride) : 0, 4, used, false, k};
+    };
+    const Block in[] = {
+        plane(0), plane(1),
+        {"chan", (uintptr_t)d.chan, (uintptr_t)(WEDM_SENSOR_FIELDS * C_out * 8), 8, true},
+        {"route", (uintptr_t)d.route, (uintptr_t)(WEDM_SENSOR_ROUTES * C_out * 4), 4, true},
+        {"first", (uintptr_t)d.first, n, 1, false},
+        {"mask", (uintptr_t)d.mask, n, 1, false},
+        {"episode", (uintptr_t)d.episode, n * 8, 8, false},
+    };
+    const Block out[] = {
+        {"out", (uintptr_t)d.out, soa((uintptr_t)C_out, d.out_stride), 4, true},
+        {"ring", ringed ? (uintptr_t)d.ring : 0, ringed ? soa((uintptr_t)(L * C_in), d.ring_stride) : 0, 4, false},
+        {"pos", (uintptr_t)d.pos, n * 4, 4, true},
+        {"age", (uintptr_t)d.age, n * 4, 4, true},
+    };
+    if (const int32_t rc = check_blocks(E, in, std::size(in), out, std::size(out))) return rc;
+    if (const int32_t rc = check_apart(E, out, std::size(out))) return rc;
+    hipLaunchKernelGGL(wedm_sensor_kernel, dim3((uint32_t)((d.num_envs + WEDM_SN_BLOCK - 1) / WEDM_SN_BLOCK)), dim3(WEDM_SN_BLOCK), 0,
+                       (hipStream_t)stream, d, d.chan, d.route);
     return E.launched();
 }
 

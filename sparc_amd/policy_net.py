@@ -229,6 +229,7 @@ class _Net(torch.autograd.Function):
     @staticmethod
     def forward(ctx, theta, net, obs, index):
         ctx.net, ctx.obs, ctx.index = net, obs, index
+        ctx.set_materialize_grads(False)  # an output without a gradient arrives as None: `_backward` has cached zeros for it
         return net._forward(obs, index)
 
     @staticmethod
@@ -243,7 +244,9 @@ class PolicyNet:
 
     ``theta`` is one flat float32 leaf with ``requires_grad`` (``W1, b1, W2, b2, W3, b3`` are views of it), drawn on the
     host from a seeded CPU generator, so it holds the same bits wherever the network lives.  ``forward(obs)`` returns
-    ``(params [N, P], value [N])`` without a graph; ``net(obs)`` and ``net(rollout=buf, index=idx)`` return the same with a
+    ``(params [N, P], value [N])`` without a graph (``obs`` may be wider than ``obs_dim``: the leading ``obs_dim`` columns are
+    read in place through the row stride, which is how an actor on the measured columns of a `Sensor` shares the critic's
+    store); ``net(obs)`` and ``net(rollout=buf, index=idx)`` return the same with a
     graph whose backward writes ``theta.grad`` (adding to it where it exists).  The outputs are the network's own buffers,
     rewritten by its next call.  On a CPU device every call runs `policy_net_reference`.  After the first call of each
     shape nothing is allocated and nothing synchronises with the host."""
@@ -272,6 +275,7 @@ class PolicyNet:
         self._value = torch.zeros(0, dtype=torch.float32, device=self.device)
         self._partials = torch.zeros((0, self.n_theta), dtype=torch.float32, device=self.device)
         self._zero_gv = torch.zeros(0, dtype=torch.float32, device=self.device)
+        self._zero_gp = torch.zeros((0, self.param_dim), dtype=torch.float32, device=self.device)
         self._keep = None  # the inputs of the launches in flight
 
     def __getattr__(self, name: str) -> torch.Tensor:
@@ -290,12 +294,12 @@ class PolicyNet:
             obs = rollout.flat()["obs"]
         elif index is not None:
             raise ValueError("index= goes with rollout=")
-        if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.ndim != 2 or obs.shape[1] != self.obs_dim or obs.shape[0] < 1:
-            raise ValueError(f"obs must be a float32 tensor [rows, {self.obs_dim}], got {getattr(obs, 'dtype', type(obs).__name__)} "
+        if not torch.is_tensor(obs) or obs.dtype != torch.float32 or obs.ndim != 2 or obs.shape[1] < self.obs_dim or obs.shape[0] < 1:
+            raise ValueError(f"obs must be a float32 tensor [rows, >= {self.obs_dim}], got {getattr(obs, 'dtype', type(obs).__name__)} "
                              f"{list(getattr(obs, 'shape', []))}")
         if obs.device.type != self.device.type or (self.device.index is not None and obs.device.index != self.device.index):
             raise ValueError(f"obs lies on {obs.device}, the network on {self.device}")
-        obs = obs.detach()
+        obs = obs.detach()[:, : self.obs_dim]  # a wider store: the leading columns, read in place through the row stride
         if obs.stride(1) != 1 or obs.stride(0) < self.obs_dim:
             obs = obs.contiguous()
         if index is not None:
@@ -337,8 +341,10 @@ class PolicyNet:
             if self._zero_gv.shape[0] < rows:
                 self._zero_gv = torch.zeros(rows, dtype=torch.float32, device=self.device)
             gv = self._zero_gv[:rows]
-        if gp is None:
-            gp = torch.zeros((rows, P), dtype=torch.float32, device=self.device)
+        if gp is None:  # (only the value has a gradient: a critic)
+            if self._zero_gp.shape[0] < rows:
+                self._zero_gp = torch.zeros((rows, P), dtype=torch.float32, device=self.device)
+            gp = self._zero_gp[:rows]
         gp, gv = gp.detach(), gv.detach().contiguous()
         if gp.stride(1) != 1 or gp.stride(0) < P:
             gp = gp.contiguous()

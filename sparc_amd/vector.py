@@ -97,7 +97,7 @@ class WireEDMVectorEnv:
     def __init__(self, env: WireEDMEnv, *, max_episode_steps: Optional[int] = None, autoreset: bool = True,
                  reward=None, param_sampler: Optional[Callable] = None, material_sampler: Optional[Callable] = None,
                  wire_profile_bins: Optional[int] = None, geometry_sampler: Optional[Callable] = None,
-                 episode_sampler=None, normalizer=None, episode_log=None):
+                 episode_sampler=None, normalizer=None, episode_log=None, sensor=None):
         """``reward``: None keeps the environment's own reward (the reference's constant 0.0, or the
         in-kernel progress reward if the environment was built with ``reward="progress"``);
         ``"progress"`` selects `progress_reward` (computed in the kernel when the environment supports
@@ -145,7 +145,13 @@ class WireEDMVectorEnv:
         more launches, no host synchronisation, no allocation after binding) that appends a record for every environment
         whose episode ended in the step, in the order of the global environment index, and adds the step to the per-episode
         sums; ``episode_log.read()`` hands the records out when the user chooses.  A frozen environment (done, with
-        ``autoreset=False``) is logged once; `reset` zeroes the sums of the environments it resets and logs nothing."""
+        ``autoreset=False``) is logged once; `reset` zeroes the sums of the environments it resets and logs nothing.
+        ``sensor``: a `sparc_amd.sensor.Sensor` -- what `reset()` and `step()` hand out (and what the normaliser reads) is the
+        sensor's plane instead of the raw columns: per output channel a raw column delayed, miscalibrated per episode, with
+        fresh noise, quantised and saturated, then clean ``priv.<name>`` copies, by one `wedm_sensor` call (no host
+        synchronisation, no allocation after binding).  `obs_names`, the observation spaces and ``actor_obs_dim`` (the
+        leading measured columns: ``PolicyNet(vec.actor_obs_dim, head)`` reads them in place) become the sensor's;
+        ``info["raw_observation"]`` stays the clean full observation.  A frozen environment keeps its last reading."""
         self.env = env
         self.num_envs = env.num_envs
         self.single_action_space = env.single_action_space
@@ -194,10 +200,21 @@ class WireEDMVectorEnv:
         self._need_reset = torch.zeros(self.num_envs, dtype=torch.bool, device=env.device)
         if self._shaped is not None:
             self._shaped.bind(self)
+        self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
+        self.sensor = sensor
+        self.raw_obs_names = self.obs_names
+        self.actor_obs_dim = len(self.obs_names)
+        if sensor is not None:
+            from .envs.wire_edm import Box
+
+            sensor.bind(self)  # (against the raw columns, the wire profile's included)
+            self.obs_names = tuple(sensor.obs_names)
+            self.actor_obs_dim = sensor.actor_dim
+            self.single_observation_space = Box(-np.inf, np.inf, (len(self.obs_names),), np.float32)
+            self.observation_space = self.single_observation_space
         self.normalizer = normalizer
         if normalizer is not None:
             normalizer.bind(self.obs_names, self.num_envs, env.device, getattr(env, "_backend", None))
-        self.episode_count = torch.zeros(self.num_envs, dtype=torch.int64, device=env.device)
         self.episode_log = episode_log
         if episode_log is not None:
             episode_log.bind(self)
@@ -228,11 +245,26 @@ class WireEDMVectorEnv:
                 mask = torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
             self.normalizer.reset_rows(mask)
             planes = self._planes()
-            out, _ = self.normalizer.normalize(planes, mask=mask)
+            out, _ = self.normalizer.normalize(self._sensed(planes, None, mask), mask=mask)
             info = dict(info)
             info["raw_observation"] = self._raw(obs, planes)
             return out, info
+        if self.sensor is not None:
+            mask = (options or {}).get("mask")
+            if mask is not None:
+                mask = torch.as_tensor(mask, device=self.env.device).reshape(-1).to(torch.bool)
+            planes = self._planes()
+            info = dict(info)
+            info["raw_observation"] = self._raw(obs, planes)
+            return self._sensed(planes, None, mask)[0].t().contiguous(), info
         return self._observation(obs), info
+
+    def _sensed(self, planes, first, mask):
+        """The planes in front of the normaliser: the sensor's output plane where there is a sensor (one `wedm_sensor` call
+        with the episode numbers as they stand), else ``planes`` themselves."""
+        if self.sensor is None:
+            return planes
+        return [self.sensor.apply(planes, first=first, mask=mask, episode=self.episode_count)]
 
     def _planes(self):
         """The blocks `wedm_normalize` reads, as they lie: the environment's observation and the wire profile's rows."""
@@ -279,8 +311,9 @@ class WireEDMVectorEnv:
             self.episode_count += self._need_reset.to(torch.int64)
         # environments this step leaves frozen take no part in the normaliser's statistics or in the episode log
         shaped = self._shaped
-        live = None if (self.normalizer is None and self.episode_log is None and shaped is None) or self.autoreset \
-            else ~self._need_reset
+        live = None if (self.normalizer is None and self.episode_log is None and shaped is None and self.sensor is None) \
+            or self.autoreset else ~self._need_reset
+        began = self._need_reset  # who begins an episode in this step: the sensor's `first`
         if shaped is not None:
             shaped.before_launch()
             restarted = self._need_reset if self._in_kernel_reset else None  # whom the launch itself restarts
@@ -309,7 +342,8 @@ class WireEDMVectorEnv:
             norm = self.normalizer
             reward = reward.contiguous()
             planes = self._planes()
-            out, scaled = norm.normalize(planes, reward=reward, terminated=terminated, truncated=truncated, mask=live)
+            out, scaled = norm.normalize(self._sensed(planes, began, live), reward=reward, terminated=terminated,
+                                         truncated=truncated, mask=live)
             info["episode_stats"] = norm.episode_stats
             info["raw_observation"] = self._raw(obs, planes)
             info["raw_reward"] = reward
@@ -319,6 +353,10 @@ class WireEDMVectorEnv:
         if self.episode_log is not None:
             reward = reward.contiguous()
             self.episode_log.append(reward, terminated, truncated, mask=live)
+        if self.sensor is not None:
+            planes = self._planes()
+            info["raw_observation"] = self._raw(obs, planes)
+            return self._sensed(planes, began, live)[0].t().contiguous(), reward, terminated, truncated, info
         return self._observation(obs), reward, terminated, truncated, info
 
     def fork(self, src, dst) -> None:
@@ -333,6 +371,8 @@ class WireEDMVectorEnv:
             self.normalizer.fork(src, dst)
         if self.episode_log is not None:
             self.episode_log.fork(src, dst)
+        if self.sensor is not None:
+            self.sensor.fork(src, dst)
 
     # ---- checkpoints ----
     def _reward_kind(self) -> str:
@@ -352,6 +392,8 @@ class WireEDMVectorEnv:
                "samplers": self._sampler_kinds()}
         if self._shaped is not None:  # (a ShapedReward keeps nothing across steps: its settings are all there is)
             out.update({f"reward_{key}": value for key, value in self._shaped.settings().items()})
+        if self.sensor is not None:  # (the channel set; what the sensor carries across steps is in its own state dict)
+            out.update({f"sensor_{key}": value for key, value in self.sensor.settings().items()})
         return out
 
     def state_dict(self) -> Dict[str, Any]:
@@ -360,7 +402,7 @@ class WireEDMVectorEnv:
         ``autoreset``, ``max_episode_steps``, ``wire_profile_bins``, ``obs_names``, the kind of reward -- ``"kernel"``,
         ``"progress"``, ``"callable"`` or ``"shaped"``, the last with the `ShapedReward`'s ``reward_weights``,
         ``reward_gap_floor`` and ``reward_tmax_ceiling`` -- and the kinds of samplers present), and under ``"env"``, ``"episode_sampler"`` and
-        ``"normalizer"`` and ``"episode_log"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
+        ``"normalizer"``, ``"episode_log"`` and ``"sensor"`` the state dicts of what the adapter owns, each only where it has one.  CPU tensors, ints, strings,
         tuples and lists only: loads with ``weights_only=True``.
         Not in it: ``param_sampler`` / ``material_sampler`` / ``geometry_sampler`` draw from a ``torch.Generator`` the caller
         owns, and a callable reward may hold state of its own -- the caller saves those (``generator.get_state()``)."""
@@ -374,6 +416,8 @@ class WireEDMVectorEnv:
             sd["normalizer"] = self.normalizer.state_dict()
         if self.episode_log is not None:
             sd["episode_log"] = self.episode_log.state_dict()
+        if self.sensor is not None:
+            sd["sensor"] = self.sensor.state_dict()
         return sd
 
     def load_state_dict(self, sd: Dict[str, Any]) -> None:
@@ -392,7 +436,7 @@ class WireEDMVectorEnv:
             if there != here:
                 raise ValueError(f"the checkpoint was taken with {key}={sd[key]!r}, this adapter has {key}={here!r}")
         for key, mine_has in (("episode_sampler", self._episode_sampler is not None), ("normalizer", self.normalizer is not None),
-                              ("episode_log", self.episode_log is not None)):
+                              ("episode_log", self.episode_log is not None), ("sensor", self.sensor is not None)):
             if (key in sd) != mine_has:
                 raise ValueError(f"the checkpoint was taken {'with' if key in sd else 'without'} a {key}, this adapter has "
                                  f"{'one' if mine_has else 'none'}")
@@ -415,6 +459,8 @@ class WireEDMVectorEnv:
                 raise ValueError(f"the state dict holds {nsd['num_envs']} environments, this Normalizer {norm.num_envs}")
         if self.episode_log is not None:
             self.episode_log.check_state_dict(sd["episode_log"])
+        if self.sensor is not None:
+            self.sensor.check_state_dict(sd["sensor"])
         self.env.load_state_dict(sd["env"])  # (raises before it writes)
         if s is not None:
             s.load_state_dict(sd["episode_sampler"])
@@ -422,6 +468,8 @@ class WireEDMVectorEnv:
             norm.load_state_dict(sd["normalizer"])
         if self.episode_log is not None:
             self.episode_log.load_state_dict(sd["episode_log"])
+        if self.sensor is not None:
+            self.sensor.load_state_dict(sd["sensor"])
         self._need_reset = sd["need_reset"].to(device=self.env.device, dtype=torch.bool).clone()
         self.episode_count.copy_(sd["episode_count"])
 
