@@ -1,6 +1,7 @@
-"""What tests/test_policy_net_host.py (CPU oracle backends, the NumPy definition) and tests/test_policy_net.py (MI355X, the
-kernels) share: synthetic calls of `wedm_policy_net` with their expected blocks, and the training stacks of
-tests/_resume_common.py with a `PolicyNet` as the network.  TEST SEAM ONLY."""
+"""What tests/test_policy_net_host.py (CPU oracle backends, the NumPy definition), tests/test_policy_net.py and
+tests/test_policy_net_shapes.py (MI355X, the kernels) share: synthetic calls of `wedm_policy_net` with their expected blocks,
+a mirror of the kernels' LDS plan, and the training stacks of tests/_resume_common.py with a `PolicyNet` as the network
+(DESIGN.md section 4.22).  TEST SEAM ONLY."""
 from __future__ import annotations
 
 from typing import List, Optional
@@ -46,6 +47,18 @@ def define(call: dict, activation: str) -> dict:
     D = call["D"]
     return policy_net_reference(call["theta"], np.ascontiguousarray(call["obs"][:, :D]), hidden=call["hidden"], n_modes=call["M"],
                                 activation=activation, index=call["index"], grad_params=call["grad_params"], grad_value=call["grad_value"])
+
+
+def lds_plan(D: int, H1: int, H2: int, O: int, backward: bool):
+    """`net_make_shape` of sparc_amd/csrc/wedm_policy_net.h, in floats against its 160 KiB: (the parked node lies in LDS,
+    ``theta`` is staged in LDS).  The forward parks nothing."""
+    limit = 160 * 1024 // 4
+    at = 2 * 128 + 128 * (H1 + 4) + 128 * (H2 + 4) + (128 * 36 if backward else 0)   # src, act1, act2, go
+    n_theta = (D + 1) * H1 + (H1 + 1) * H2 + (H2 + 1) * O
+    park = backward and at + n_theta <= limit
+    at += n_theta if park else 0
+    staged = (D + 1) * (H1 + 4) + (H1 + 1) * (H2 + 4) + (H2 + 1) * (O + 4)   # rows of N + 4
+    return bool(park), at + staged <= limit
 
 
 # ------------------------------------------------------------------------------------------------ the stack

@@ -1,9 +1,11 @@
 """The actor-critic network on the MI355X (sparc_amd/csrc/wedm_policy_net.h, sparc_amd/policy_net.py, DESIGN.md section
 4.22): `wedm_policy_net` against `policy_net_reference` on every byte of everything it may write -- the head's rows with
-their padding columns, the values, the tile partials, the gradient, each between guard bands -- at the chunk, pass and tile
-edges, at every padding of the MFMA's k-step, through an index with repeats and entries outside the store; hostile values;
-the phases apart, repeats and `ACCUMULATE`; `PolicyNet` under `PPOLoss` without a host synchronisation or an allocation; the
-call on a side stream behind a gate; and a whole training run on the GPU against the same run on the oracle backend."""
+their padding columns, the values, the tile partials, the gradient, each between guard bands -- at samples of the chunk,
+pass and tile edges and of the paddings of the MFMA's k-step (D % 4 in {0, 1, 3}, O % 4 in {0, 2}), through an index with
+repeats and entries outside the store; hostile values; the phases apart, repeats and `ACCUMULATE`; `PolicyNet` under `PPOLoss`
+without a host synchronisation or an allocation; the call on a side stream behind a gate; and a whole training run on the
+GPU against the same run on the oracle backend.  The sweeps -- every pair of hidden widths, every mode count and k-padding,
+every LDS placement, the remaining pass edges and the fold past eight tiles -- are in tests/test_policy_net_shapes.py."""
 from __future__ import annotations
 
 import ctypes as C

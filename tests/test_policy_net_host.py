@@ -115,6 +115,44 @@ def test_bad_arguments_are_refused_before_anything_is_launched():
     refused(desc(params=at["theta"] - (99 * 20 + 17) * 4 + 4), "params' last element on theta")
 
 
+# (D, M, hidden) -> theta in LDS in the forward, the parked node in LDS, theta in LDS in the backward: `net_make_shape` of
+# csrc/wedm_policy_net.h worked by hand.  In floats against 40 960: src 256, the activations 128 (H1 + 4) + 128 (H2 + 4), in
+# the backward go 4 608, then the park (n_theta) where it fits, then the staged theta (rows of N + 4) where it fits.
+LDS_PLANS = (
+    (13, 9, (16, 16), True, True, True),       # backward 9 984 + 802 + 994
+    (13, 9, (32, 128), True, True, False),     # backward 26 368 + 6 994 = 33 362, + 7 698 = 41 060; forward 21 760 + 7 698
+    (13, 9, (64, 128), True, False, False),    # backward 30 464 + 11 538 = 42 002; forward 25 856 + 12 370 = 38 226
+    (13, 9, (80, 128), False, False, False),   # forward 27 904 + 14 706 = 42 610
+    (17, 9, (128, 32), True, True, False),     # backward 26 368 + 7 026 = 33 394, + 7 746 = 41 140
+    (16, 19, (128, 128), False, False, False),  # forward 34 048 + 23 400
+    (160, 19, (16, 128), True, True, False),   # backward 24 320 + 8 364 = 32 684, + 9 592 = 42 276
+    (160, 19, (48, 112), True, False, False),  # backward 26 368 + 16 380 = 42 748; forward 21 760 + 17 672 = 39 432
+    (160, 19, (48, 128), False, False, False),  # forward 23 808 + 18 968 = 42 776
+    (1, 1, (48, 128), True, True, False),      # backward 28 416 + 7 658 = 36 074, + 8 378 = 44 452; forward 23 808 + 8 378
+    (1, 1, (80, 128), True, False, False),     # backward 32 512 + 11 818 = 44 330; forward 27 904 + 12 666 = 40 570
+    (1, 1, (96, 128), False, False, False),    # forward 29 952 + 14 810 = 44 762
+)
+
+
+@pytest.mark.parametrize("D,M,hidden,forward_theta,park,backward_theta", LDS_PLANS)
+def test_the_mirror_of_net_make_shape_gives_the_rows_worked_by_hand(D, M, hidden, forward_theta, park, backward_theta):
+    O = 9 + M
+    assert pc.lds_plan(D, *hidden, O, False) == (False, forward_theta)
+    assert pc.lds_plan(D, *hidden, O, True) == (park, backward_theta)
+
+
+def test_the_mirror_of_net_make_shape_never_stages_theta_beside_a_park_in_partials():
+    """The staged copy has rows of N + 4, so it is larger than n_theta: where the park does not fit, it does not either.
+    `net_make_shape` sizes the workspace from the same dims as `layout`."""
+    for D in (1, 6, 13, 160):
+        for M in (1, 8, 19):
+            for H1 in range(16, 129, 16):
+                for H2 in range(16, 129, 16):
+                    park, theta = pc.lds_plan(D, H1, H2, 9 + M, True)
+                    assert park or not theta, (D, M, H1, H2)
+                    assert theta <= pc.lds_plan(D, H1, H2, 9 + M, False)[1]   # the forward has go's 4 608 floats more room
+
+
 # ------------------------------------------------------------------------------------------------ 2. the float32 fma
 def _fmaf():
     libm = C.CDLL(ctypes.util.find_library("m") or "libm.so.6")
@@ -210,11 +248,13 @@ def test_every_product_against_float64_under_the_bound_of_an_fma_chain(activatio
         assert (np.abs(f64(got) - want) <= _chain_bound(64 + depth, mag)).all(), f"d{name}"
 
 
-@pytest.mark.parametrize("M", (1, 9, 19))
+# the last: an odd number of column tiles in both hidden layers, O % 4 == 1 and D % 4 == 2
+@pytest.mark.parametrize("M,D,hidden", ((1, 13, (32, 48)), (9, 13, (32, 48)), (19, 13, (32, 48)), (8, 6, (48, 80))),
+                         ids=("1", "9", "19", "8-D6-48x80"))
 @pytest.mark.parametrize("activation", ("relu", "tanh"))
-def test_the_definition_against_torch_float64_autograd(M, activation):
+def test_the_definition_against_torch_float64_autograd(M, D, hidden, activation):
     rng = np.random.default_rng(100 + M)
-    rows, D, hidden, P = 4096, 13, (32, 48), 8 + M
+    rows, P = 4096, 8 + M
     lay = layout(D, hidden, M)
     th = (rng.standard_normal(lay["n_theta"][0]) * 0.3).astype(np.float32)
     obs = rng.standard_normal((rows, D)).astype(np.float32)
