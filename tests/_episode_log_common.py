@@ -192,6 +192,34 @@ def differences(p: Problem, got: np.ndarray, want: np.ndarray) -> List[str]:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ a shard in a large workspace
+SHARD_N = 300                                      # two tiles, the second short
+WORKSPACES = (64, 65, 256, 257, 1000, 4096)        # tiles: either side of COMMIT's pass of 64 and of SCATTER's of 256, and the cap
+WHERE, DRAWS, CAPS = ("first", "middle", "last"), ("sparse", "full"), ("seven", "total")
+
+
+def shard_case(ntt: int, where: str, draw: str, cap: str):
+    """The inputs of one case of a shard of `SHARD_N` environments inside a workspace of ``ntt`` tiles, from a seed of its own:
+    the tile offset; ``tile_counts`` as the other shards left them (0..2 each, or 128..256 with half of them full, which
+    brings a call's total to about 0.9 * 256 * ntt); the flags of two calls ("all", then "few", masked); the capacity (7,
+    or the larger call's total plus 5); per call (records of the shard that the rule ``k >= n - capacity`` stores, records of
+    the shard that finish); and the calls' totals."""
+    rng = np.random.default_rng([ntt, WHERE.index(where), DRAWS.index(draw), CAPS.index(cap)])
+    offset = {"first": 0, "middle": ntt // 2 - 1, "last": ntt - 2}[where]
+    others = (rng.integers(0, 3, ntt) if draw == "sparse" else np.minimum(256, rng.integers(128, 512, ntt))).astype(np.int32)
+    calls = []
+    for how in ("all", "few"):
+        mask = (rng.random(SHARD_N) < 0.8).astype(np.uint8)
+        calls.append(flags_from(rng, finishing(rng, SHARD_N, how), mask) + (mask,))
+    own = [(mask != 0) & ((term | trunc) != 0) for term, trunc, mask in calls]
+    rest = int(others.sum()) - int(others[offset: offset + 2].sum())
+    totals = [rest + int(o.sum()) for o in own]
+    capacity = 7 if cap == "seven" else max(totals) + 5
+    below = int(others[:offset].sum())
+    stored = [(int((o & (below + np.cumsum(o) - o >= n - capacity)).sum()), int(o.sum())) for o, n in zip(own, totals)]
+    return offset, others, calls, capacity, stored, totals
+
+
 # ------------------------------------------------------------------------------------------------ whole stacks
 def full_stack(device: str, capacity: int, n: int = 70, max_episode_steps: int = 5000, seed: int = 5):
     """An adapter with every optional block -- per-environment parameters, four materials, dynamic geometry, pulse and

@@ -1,5 +1,6 @@
 """What tests/test_ppo_loss_host.py (the definition, on the host) and tests/test_ppo_loss.py (the kernels, on the MI355X)
-share: seeded minibatches whose rows reach every branch of the loss, and the definition's keywords.  TEST SEAM ONLY."""
+share: seeded minibatches whose rows reach every branch of the loss, the definition's keywords, and the tree over the
+tiles as a plain recursion with the orders of addition it must be told from.  TEST SEAM ONLY."""
 from __future__ import annotations
 
 import numpy as np
@@ -67,3 +68,94 @@ def draw_wide_minibatch(rng: np.random.Generator, rows: int, M: int, pad: int = 
 
 def definition_kw(M: int, clip_value: bool = False, **coefs):
     return dict(modes=MODES[M], **CONSTS, **{**COEFS, **coefs}, clip_value=CLIP_VALUE if clip_value else None)
+
+
+# ------------------------------------------------------------------------------------------------ the tree over the tiles
+FOLD_TILES = (256, 257, 512, 513, 1000, 1024, 1025, 2048, 2049, 3000, 4095, 4096)   # either side of every tiles-per-lane class
+_NAN64 = np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)[0]
+
+
+def padded_tiles(tiles: int) -> int:
+    """The smallest power of two that holds ``tiles``."""
+    padded = 1
+    while padded < tiles:
+        padded *= 2
+    return padded
+
+
+def stats_of_roots(S: np.ndarray, vf_coef: float = VF_COEF, ent_coef: float = ENT_COEF) -> np.ndarray:
+    """The eight ``stats`` words from the seven roots, by the header's formulas (a NaN: 0x7FF8000000000000)."""
+    with np.errstate(all="ignore"):
+        n = S[0]
+        s = 1.0 / n if n > 0 else 0.0
+        pl, vl, en = S[2] * s, S[3] * s, S[4] * s
+        stats = np.array([n, S[1], (pl + vf_coef * vl) - ent_coef * en, pl, vl, en, S[5] * s, S[6] * s])
+    return np.where(stats != stats, _NAN64, stats)
+
+
+def tile_tree(partials: np.ndarray) -> np.ndarray:
+    """The header's tree over the tile index, written as it reads and sharing nothing with `pairwise_sum`:
+    ``tree(lo, hi) = tree(lo, mid) + tree(mid, hi)`` over the padded power of two, the lower index on the left; a leaf at or
+    past ``tiles`` is +0.0 and is added like any other.  ``partials``: float64 ``[tiles, 7]``; returns the seven roots."""
+    x = np.asarray(partials, dtype=np.float64)
+    tiles, zero = x.shape[0], np.zeros(x.shape[1:])
+
+    def tree(lo: int, hi: int) -> np.ndarray:
+        if hi - lo == 1:
+            return x[lo] if lo < tiles else zero
+        mid = (lo + hi) // 2
+        return tree(lo, mid) + tree(mid, hi)
+
+    with np.errstate(all="ignore"):
+        return tree(0, padded_tiles(tiles))
+
+
+def tile_tree_stats(partials: np.ndarray, vf_coef: float = VF_COEF, ent_coef: float = ENT_COEF) -> np.ndarray:
+    return stats_of_roots(tile_tree(partials), vf_coef, ent_coef)
+
+
+def left_to_right_stats(partials: np.ndarray) -> np.ndarray:
+    """What a fold that adds the tiles in their order, one after the other, would store: not the definition."""
+    S = np.zeros(partials.shape[1])
+    with np.errstate(all="ignore"):
+        for row in np.asarray(partials, dtype=np.float64):
+            S = S + row
+    return stats_of_roots(S)
+
+
+def lane_sequential_stats(partials: np.ndarray) -> np.ndarray:
+    """What a fold whose 256 lanes each add their ``per`` consecutive tiles one after the other, and then form the tree over
+    the lanes, would store: the definition up to two tiles per lane, and not from four on."""
+    x = np.asarray(partials, dtype=np.float64)
+    tiles, padded = x.shape[0], padded_tiles(x.shape[0])
+    per = max(1, padded // 256)
+    full = np.zeros((padded,) + x.shape[1:])
+    full[:tiles] = x
+    lanes = full.reshape(padded // per, per, -1)
+    with np.errstate(all="ignore"):
+        node = lanes[:, 0]
+        for j in range(1, per):
+            node = node + lanes[:, j]
+    return tile_tree_stats(node)
+
+
+def draw_partials(rng: np.random.Generator, tiles: int) -> np.ndarray:
+    """A synthesised ``partials`` block ``[tiles, 7]``: LIVE an integer in 0..256 with every eighth tile or so empty, BAD a small
+    integer, the five sums of either sign with magnitudes 10^U(-8, 8), so that the order of the additions shows in the
+    low bits of every root."""
+    p = np.empty((tiles, 7))
+    p[:, 0] = np.where(rng.random(tiles) < 0.125, 0, rng.integers(0, 257, tiles))
+    p[:, 1] = rng.integers(0, 4, tiles)
+    p[:, 2:] = rng.choice((-1.0, 1.0), (tiles, 5)) * 10.0 ** rng.uniform(-8.0, 8.0, (tiles, 5))
+    return p
+
+
+def telling_partials(tiles: int, seed: int, tries: int = 5) -> np.ndarray:
+    """`draw_partials` at the first of ``tries`` seeds whose data tells the definition's tree from the left-to-right sum and,
+    where a lane holds four tiles or more, from the lane-sequential sum, in at least one ``stats`` word each."""
+    for k in range(tries):
+        p = draw_partials(np.random.default_rng(1000 * seed + k), tiles)
+        want = tile_tree_stats(p).tobytes()
+        if left_to_right_stats(p).tobytes() != want and (padded_tiles(tiles) < 1024 or lane_sequential_stats(p).tobytes() != want):
+            return p
+    raise AssertionError(f"{tries} draws of {tiles} tiles prove nothing: every order of the additions gives the tree's bits")

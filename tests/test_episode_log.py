@@ -1,7 +1,8 @@
 """`wedm_episode_log` on the MI355X: the call against `episode_log_definition` on every byte of an arena
 that holds all its blocks between guard bands -- the ring, the accumulators, ``tile_counts``, ``head``, padding columns, the
 inputs -- at the wave and block edges, with bases on and off 16 bytes, at the plane and row limits, the phases apart and two
-shards in turn; `EpisodeLog` through `WireEDMVectorEnv` without a host synchronisation or an allocation, against its twin
+shards in turn; a small shard in workspaces of 64 to 4096 tiles, whole batches past one pass over ``tile_counts`` and a head
+past 32 bits; `EpisodeLog` through `WireEDMVectorEnv` without a host synchronisation or an allocation, against its twin
 on the CPU oracle backend; and the call on a side stream behind a gate."""
 from __future__ import annotations
 
@@ -14,7 +15,8 @@ import torch
 from sparc_amd import EpisodeLog, Normalizer, WireEDMVectorEnv
 from sparc_amd.episode_log import COMMIT, COUNT, SCATTER, device_episode_log
 from tests import _snapshot_common as snap
-from tests._episode_log_common import SPEC_MAX, SPEC_SHARD, Problem, differences, finishing, flags_from, full_stack
+from tests._episode_log_common import (CAPS, DRAWS, SHARD_N, SPEC_MAX, SPEC_SHARD, WHERE, WORKSPACES, Problem, differences, finishing,
+                                        flags_from, full_stack, shard_case)
 from tests._stream_gate import Gate, check_control, gated, seconds_on
 
 pytestmark = pytest.mark.gpu
@@ -67,7 +69,76 @@ def test_the_call_against_the_definition_on_every_byte(N, how):
             d.check((N, how, cap, call))
 
 
-@pytest.mark.parametrize("N,cap", [(257, 7), (1000, 1005), (1000, 300)])
+# ------------------------------------------------------------------------------------------------ large workspaces
+@pytest.mark.parametrize("cap", CAPS)
+@pytest.mark.parametrize("draw", DRAWS)
+@pytest.mark.parametrize("where", WHERE)
+@pytest.mark.parametrize("ntt", WORKSPACES)
+def test_a_small_shard_in_a_large_workspace(ntt, where, draw, cap):
+    """300 environments at the start, near the middle and at the end of a workspace of 64 to 4096 tiles whose other tiles
+    hold counts that `shard_case` drew: SCATTER's and COMMIT's sums over ``tile_counts`` run one pass, two and sixteen (or
+    64), the ranks start at up to 900 000 and ``head`` moves by as much.  One call, and COUNT, SCATTER, COMMIT apart; two
+    calls each, on a ring entered two slots before its end.  tests/test_episode_log_host.py asserts the input conditions
+    over the parametrisation: records all stored, none stored, a strict part."""
+    offset, others, calls, capacity, _, totals = shard_case(ntt, where, draw, cap)
+    p = Problem(np.random.default_rng(ntt + capacity), SHARD_N, capacity, tile_offset=offset, n_tiles_total=ntt, head0=capacity - 2,
+                masked=True, pad=3, off16=where == "middle")
+    p.view(p.buf, "tile_counts")[:] = others
+    for apart in (False, True):
+        d = OnDevice(p)
+        for call, (term, trunc, mask) in enumerate(calls):
+            d.flags(term, trunc, mask)
+            for phase in (COUNT, SCATTER, COMMIT) if apart else (0,):
+                d.call(stamp=call, env_id_offset=9000, flags=phase)
+            p.define(d.want, stamp=call, env_id_offset=9000)
+            d.check((ntt, where, draw, cap, apart, call))
+        head = p.view(d.want, "head")
+        assert head[0] == capacity - 2 + sum(totals) and head[1] == totals[1]
+
+
+@pytest.mark.parametrize("N,cap", [(16_385, 300), (16_641, 300), (16_641, 16_646), (65_537, 300), (65_793, 300), (65_793, 65_798)])
+def test_whole_batches_past_one_pass_over_the_tile_counts(N, cap):
+    """65 and 66 tiles, 257 and 258: one and two more than COMMIT's 64 lanes and than SCATTER's 256 take in a pass, the last
+    tile of one environment: "few", "all", "few" with a mask, on a ring that drops most records and on one that holds them
+    all, entered two slots before its end."""
+    rng = np.random.default_rng(N + cap)
+    p = Problem(rng, N, cap, masked=True, pad=3, off16=cap == 300, head0=cap - 2)
+    assert p.tiles in (65, 66, 257, 258) and p.ntt == p.tiles
+    d = OnDevice(p)
+    for call, how in enumerate(("few", "all", "few")):
+        mask = (rng.random(N) < 0.8).astype(np.uint8)
+        if how == "all":
+            mask[-1] = 1   # the one environment of the last tile finishes: the tile past the first pass counts
+        d.flags(*flags_from(rng, finishing(rng, N, how), mask), mask)
+        d.call(stamp=call, env_id_offset=12)
+        p.define(d.want, stamp=call, env_id_offset=12)
+        d.check((N, cap, call))
+        if how == "all":
+            counts = p.view(d.want, "tile_counts")
+            assert p.view(d.want, "head")[1] > 0.7 * N and (counts[: p.tiles - 1] > 150).all() and counts[-1] == 1
+
+
+@pytest.mark.parametrize("cap", [7, 100, 256])
+@pytest.mark.parametrize("head0", [2 ** 40 + 3, 2 ** 31 - 1])
+def test_a_head_past_32_bits(head0, cap):
+    """``head[0]`` where `EpisodeLog` leaves it after 2^31 and 2^40 episodes: the slot is ``(head[0] + k) mod capacity`` in 64 bits.
+    At 257 environments and capacities 7 and 100 the slot of the sum's low 32 bits is another one (2^31 and 2^40 leave
+    remainders there; a capacity of 256 divides both, so its slots alone could not tell)."""
+    N = 257
+    rng = np.random.default_rng(cap)
+    assert cap == 256 or (head0 + 1) % cap != (np.int64(head0 + 1).astype(np.int32).item()) % cap
+    p = Problem(rng, N, cap, masked=True, pad=3, head0=head0)
+    d = OnDevice(p)
+    for call, how in enumerate(("all", "few")):
+        mask = (rng.random(N) < 0.8).astype(np.uint8)
+        d.flags(*flags_from(rng, finishing(rng, N, how), mask), mask)
+        d.call(stamp=call)
+        p.define(d.want, stamp=call)
+        d.check((head0, cap, call))
+    assert p.view(d.want, "head")[0] > head0 + 100
+
+
+@pytest.mark.parametrize("N,cap", [(257, 7), (1000, 1005), (1000, 300), (65_793, 1000)])
 def test_the_maximum_plane_and_row_counts(N, cap):
     rng = np.random.default_rng(N + cap)
     p = Problem(rng, N, cap, spec=SPEC_MAX, pad=3, off16=True, masked=True, head0=cap - 2)

@@ -19,7 +19,8 @@ from sparc_amd.core import env_params as envp
 from sparc_amd.episode_log import COMMIT, COUNT, LAST, SCATTER, SUM_F32, SUM_F64, SUM_I32
 from tests import _snapshot_common as snap
 from tests._resume_common import assert_equal, vec_everything
-from tests._episode_log_common import SPEC, SPEC_MAX, SPEC_SHARD, Problem, differences, finishing, flags_from, full_stack
+from tests._episode_log_common import (CAPS, DRAWS, SPEC, SPEC_MAX, SPEC_SHARD, WHERE, WORKSPACES, Problem, differences, finishing,
+                                        flags_from, full_stack, shard_case)
 
 ROOT = Path(__file__).resolve().parent.parent
 
@@ -540,3 +541,19 @@ def test_an_adapter_without_a_log_has_the_state_dict_keys_it_had():
     torch.save(logged.state_dict(), io.BytesIO())
     for v in (plain, normed, logged):
         v.close()
+
+
+def test_the_shard_cases_store_every_record_none_and_a_strict_part():
+    """The input conditions of tests/test_episode_log.py's shard in a large workspace, over its whole parametrisation: some call stores every finishing record of
+    the shard, some call stores none of them though some finish (the SUM planes still move), some a strict part; and the
+    largest total reaches 900 000, near the 1 048 576 that the kernels' int32 sums are said to hold."""
+    seen, largest = set(), 0
+    for ntt in WORKSPACES:
+        for where in WHERE:
+            for draw in DRAWS:
+                for cap in CAPS:
+                    offset, others, _, capacity, stored, _ = shard_case(ntt, where, draw, cap)
+                    largest = max(largest, int(others.sum()))
+                    assert 0 <= offset and offset + 2 <= ntt and all(n > 0 for _, n in stored)
+                    seen |= {"every" if s == n else ("none" if s == 0 else "part") for s, n in stored}
+    assert seen == {"every", "none", "part"} and largest > 900_000

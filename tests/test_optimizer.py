@@ -1,9 +1,9 @@
 """Adam with clipping and a KL gate on the MI355X (sparc_amd/csrc/wedm_adam.h, sparc_amd/optimizer.py, DESIGN.md section
 4.23): `wedm_adam` against `adam_reference` on every byte of one arena per block -- guard bands, the gradient and the KL
 left alone, ``partials``, ``state``, ``info`` -- at the wave, tile and block edges and on either side of the one-block
-threshold, in the one-block form, the phased form and the phases in three calls; hostile values; the gate; repeats; an
-update without a host synchronisation or an allocation; the call on a side stream behind a gate; and a whole training run
-on the GPU against the same run on the oracle backend."""
+threshold, in the one-block form, the phased form and the phases in three calls, and up to the cap of 1 048 576; hostile
+values; the gate; repeats; an update without a host synchronisation or an allocation; the call on a side stream behind a
+gate; and a whole training run on the GPU against the same run on the oracle backend."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,7 +18,7 @@ import pytest
 import torch
 
 from sparc_amd import Adam, _abi, _lib
-from sparc_amd.optimizer import APPLIED, LATCH, SCALE, SKIPPED_KL, SKIPPED_NONFINITE, SUMSQ, T
+from sparc_amd.optimizer import APPLIED, LATCH, MAX_N, SCALE, SKIPPED_KL, SKIPPED_NONFINITE, SUMSQ, T
 from tests import _optimizer_common as oc
 from tests import _resume_common as rc
 from tests._arena import FILL, Arena
@@ -31,6 +31,10 @@ DEV = "cuda:0"
 ROOT = Path(__file__).resolve().parent.parent
 ONE = _abi.OPT_ONE_BLOCK_MAX
 SIZES = (1, 63, 64, 255, 256, 257, 1025, 6418, ONE, ONE + 1, 65537)
+# 2049 tiles (half of DECIDE's tree is padding), 4096 tiles with a last tile of one element, and the cap, where the tree's
+# 4096 doubles are full to the last word; the call accepts them in the phased form and the phases in three calls
+LARGE = (524_289, 1_048_321, MAX_N)
+EVERY_BYTE = [(n, form) for form in oc.FORMS for n in SIZES + LARGE if n not in LARGE or form != "one"]
 BLOCKS = ("theta", "m", "v", "grad", "partials", "state", "info", "stats")
 
 
@@ -92,9 +96,10 @@ class Problem:
         return [name for name in BLOCKS if not np.array_equal(self.arena[name].raw.cpu().numpy(), self.image[name])]
 
 
-@pytest.mark.parametrize("form", tuple(oc.FORMS))
-@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("n,form", EVERY_BYTE)
 def test_three_steps_are_the_definition_on_every_byte(n, form):
+    """`SIZES` in every form, `LARGE` in the phased form and the phases apart; at the large sizes a fourth call whose gradient
+    is not finite in its last element -- the last tile, the last word of DECIDE's tree -- which is skipped and counted."""
     grads = oc.draw_grads(n, seed=n)
     shifts = itertools.cycle((0, 4, 12))
     for clip, decay in itertools.product((True, False), repeat=2):
@@ -107,6 +112,14 @@ def test_three_steps_are_the_definition_on_every_byte(n, form):
         assert p.host["state"][T] == 6.0 and (np.abs(p.host["m"]).sum() > 0)
         if n >= 63:   # the second gradient's norm lies over max_norm, the others' under it
             assert scales[1] < 1.0 and scales[0] == scales[2] == 1.0 if clip else scales == [1.0] * 3
+        if n in LARGE:
+            assert p.tiles == (n + 255) // 256 > 2048
+            bad = grads[0].copy()
+            bad[n - 1] = np.nan if clip else -np.inf
+            held = {k: p.host[k].copy() for k in ("theta", "m", "v")}
+            assert p.step(bad, form, clip=clip, decay=decay) == [], (n, form, clip, decay, "not finite")
+            assert all(same_bits(p.host[k], held[k]) for k in held) and p.host["info"][APPLIED] == 0.0
+            assert p.host["state"][SKIPPED_NONFINITE] == 1.0 and p.host["state"][T] == 6.0
 
 
 @pytest.mark.parametrize("form", tuple(oc.FORMS))

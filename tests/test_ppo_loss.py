@@ -2,9 +2,10 @@
 `ppo_loss_definition` on every byte of everything it may write -- the gradient blocks with their padding columns, the tile
 partials, the statistics, the count words, each between guard bands -- at the wave and block edges, through LDS and
 directly, with and without a mask, an index, value clipping and the gradient; every mode count from 1 to 19; a wide
-regime (ratios of 0 and +inf, clip = 0, advantages and returns from subnormal to 1e30); the phases apart; hostile rows;
-`PPOLoss` through `WireEDMVectorEnv`, `PolicyHead` and `RolloutBuffer` without a host synchronisation or an allocation; and the call
-on a side stream behind a gate."""
+regime (ratios of 0 and +inf, clip = 0, advantages and returns from subnormal to 1e30); the fold alone against an independent
+tile tree in every class of tiles per lane up to 4096 tiles, with signed zeros and non-finite nodes, and whole calls at the
+first row count of the larger classes; the phases apart; hostile rows; `PPOLoss` through `WireEDMVectorEnv`, `PolicyHead` and
+`RolloutBuffer` without a host synchronisation or an allocation; and the call on a side stream behind a gate."""
 from __future__ import annotations
 
 import gc
@@ -18,7 +19,8 @@ from sparc_amd.ppo import device_ppo_loss, ppo_loss_definition
 from tests._gae_common import is_subnormal
 from tests._normalize_common import same_bits
 from tests._policy_head_common import ALL_M, HI, LO, LOG_SPAN, make_hostile, random_params, zero_probability_rows
-from tests._ppo_common import CLIP_VALUE, COEFS, STORED, definition_kw, draw_minibatch, draw_wide_minibatch
+from tests._ppo_common import (CLIP_VALUE, COEFS, FOLD_TILES, STORED, definition_kw, draw_minibatch, draw_partials,
+                                draw_wide_minibatch, padded_tiles, telling_partials, tile_tree_stats)
 from tests._snapshot_common import make
 from tests._stream_gate import Gate, check_control, gated, seconds_on
 from tests.test_rollout import DEV, FILL, Banded, poisoned
@@ -217,6 +219,94 @@ def test_a_fold_lane_with_more_than_one_tile_and_a_last_tile_of_one_row():
     want = p.check("large", valid="some", index="perm", clip_value=True)
     assert want["stats"][0] == p.host["valid_some"][:rows].sum() and want["partials"][-1][0] in (0.0, 1.0)
     p.check("large, dense")
+
+
+class FoldAlone:
+    """FOLD by itself (``flags=PPO_FOLD``) over a ``partials`` block that the test wrote: ``partials``, ``stats`` and ``count``
+    lie between guard bands, and every pointer that FOLD does not read is NULL, which the entry point accepts.  `fold`
+    returns the names of the blocks and bands that differ from what the call has to leave: ``stats`` as
+    `tile_tree_stats` gives it, everything else as it was."""
+
+    def __init__(self, partials: np.ndarray):
+        self.host = {"partials": np.ascontiguousarray(partials, dtype=np.float64), "stats": poisoned((_abi.PPO_STATS,), np.float64),
+                     "count": poisoned((_abi.PPO_COUNT_WORDS,), np.int32)}
+        self.tiles = self.host["partials"].shape[0]
+        self.blocks = {name: Banded(a) for name, a in self.host.items()}
+        self.want = tile_tree_stats(self.host["partials"])
+
+    def fold(self, rows: int) -> list:
+        assert -(-rows // 256) == self.tiles
+        b = self.blocks
+        b["stats"].raw.fill_(FILL)
+        d = _abi.PpoDesc(partials=b["partials"].t.data_ptr(), stats=b["stats"].t.data_ptr(), count=b["count"].t.data_ptr(),
+                         param_stride=10, grad_stride=10, n_src=rows, n_modes=2, rows=rows, flags=_abi.PPO_FOLD, **COEFS)
+        d.lo[:], d.hi[:], d.log_span[:] = LO, HI, LOG_SPAN
+        device_ppo_loss(d, DEV)
+        torch.cuda.synchronize()
+        want = {**self.host, "stats": self.want}
+        return [name for name, blk in b.items() if not same_bits(blk.t, want[name])] + \
+            [f"band of {name}" for name, blk in b.items() if not blk.bands_intact()]
+
+
+@pytest.mark.parametrize("tiles", FOLD_TILES)
+def test_the_fold_alone_is_the_tile_tree_in_every_class_of_tiles_per_lane(tiles):
+    """256 to 4096 tiles, either side of every step of the fold's tiles per lane (1, 2, 4, 8, 16), with the last tile full
+    and holding one row.  The data (`draw_partials`) tells the tree from the left-to-right sum and from a lane that adds
+    its tiles one after the other: `telling_partials` asserts that before anything runs.  Only ``stats`` changes."""
+    f = FoldAlone(telling_partials(tiles, seed=tiles))
+    assert (f.host["partials"][:, 0] == 0).any() and np.isfinite(f.want).all() and f.want[0] > 0
+    for rows in (256 * tiles, 256 * tiles - 255):
+        assert f.fold(rows) == [], (tiles, rows)
+
+
+NEG_ZERO_BITS = 0x8000000000000000
+ODD_NAN = np.array([0xFFF4000000000123], dtype=np.uint64).view(np.float64)[0]   # signalling, signed, with a payload
+# ((column, value) pairs written into tile 0, pairs written into the last tile); columns 2..6 are the five sums
+NON_FINITE = ((((3, np.inf),), ((2, ODD_NAN),)),
+              (((4, ODD_NAN),), ((5, np.inf),)),
+              (((6, np.inf),), ((6, -np.inf),)),
+              ((), ((2, -ODD_NAN), (6, np.inf))))
+
+
+@pytest.mark.parametrize("tiles", [512, 513, 1024, 2048, 2049, 4096])
+def test_signed_zeros_and_non_finite_values_through_the_fold_alone(tiles):
+    """Five sum columns of -0.0 under a positive count: where the tiles fill the tree (512, 1024, 2048, 4096) no +0.0 is ever
+    added and the five means are -0.0; at 513 and 2049 the definition's padding makes them +0.0.  Then an odd NaN or an
+    infinity in the last tile and another in tile 0, and +inf against -inf in one column: every NaN comes out as
+    0x7FF8000000000000, whichever operand or operation made it."""
+    zeros = np.zeros((tiles, 7))
+    zeros[:, 0], zeros[:, 2:] = 3.0, -0.0
+    f = FoldAlone(zeros)
+    bits = f.want.view(np.uint64)
+    assert f.want[0] == 3.0 * tiles and all(bits[3:] == (NEG_ZERO_BITS if tiles & (tiles - 1) == 0 else 0))
+    assert f.fold(256 * tiles) == [], (tiles, "signed zeros")
+    for case, (first, last) in enumerate(NON_FINITE):
+        p = draw_partials(np.random.default_rng(10 * tiles + case), tiles)
+        for col, x in first:
+            p[0, col] = x
+        for col, x in last:
+            p[-1, col] = x
+        f = FoldAlone(p)
+        hit = sorted({col for col, _ in first + last})
+        assert np.isfinite(f.want[:2]).all() and not np.isfinite(f.want[[c + 1 for c in hit]]).any() and np.isnan(f.want).any()
+        assert all(w == 0x7FF8000000000000 for w in f.want.view(np.uint64)[np.isnan(f.want)])
+        assert f.fold(256 * tiles - 255) == [], (tiles, "non-finite", case)
+
+
+@pytest.mark.parametrize("dense", [False, True])
+@pytest.mark.parametrize("rows", [131_073, 262_145, 524_289])
+def test_whole_calls_at_the_first_row_count_of_four_eight_and_sixteen_tiles_per_fold_lane(rows, dense):
+    """COUNT, MAIN and FOLD in one call at 513, 1025 and 2049 tiles (a last tile of one row, a tree half padding): with a
+    mask, a permutation and value clipping, and dense."""
+    p = Problem(rows, 2, seed=rows % 1000)
+    assert p.tiles == rows // 256 + 1 and padded_tiles(p.tiles) == 2 * (p.tiles - 1)
+    if dense:
+        want = p.check("large, dense")
+        assert want["stats"][0] == rows
+    else:
+        want = p.check("large", valid="some", index="perm", clip_value=True)
+        assert want["stats"][0] == p.host["valid_some"][:rows].sum() and want["partials"][-1][0] in (0.0, 1.0)
+    assert same_bits(tile_tree_stats(want["partials"]), want["stats"])
 
 
 def test_the_phases_apart_equal_the_one_call_and_a_second_call_the_first():

@@ -19,7 +19,8 @@ from sparc_amd.ppo import MAX_ROWS, STAT_NAMES, PPOStats, pairwise_sum, ppo_loss
 from tests._normalize_common import same_bits
 from tests._policy_head_common import ALL_M, CONSTS, HI, LO, LOG_SPAN, MODES, random_params, zero_probability_rows
 from tests._ppo_common import (CLIP, CLIP_VALUE, ENT_COEF, STORED, VALUE_KINDS, VF_COEF, definition_kw, draw_minibatch,
-                                draw_wide_minibatch)
+                                draw_partials, draw_wide_minibatch, lane_sequential_stats, left_to_right_stats, telling_partials, tile_tree,
+                                tile_tree_stats)
 from tests._snapshot_common import make
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -426,6 +427,32 @@ def test_the_sums_are_the_pairwise_tree_over_the_row_number():
     leaves = np.zeros((2048, 7))
     leaves[:1100] = out["summands"]
     assert same_bits(pairwise_sum(out["summands"])[1], tree(leaves))
+
+
+@pytest.mark.parametrize("tiles", [3, 257, 513, 1025, 2049, 4096])
+def test_the_recursive_tile_tree_equals_the_definitions(tiles):
+    """`tests._ppo_common.tile_tree` (what tests/test_ppo_loss.py holds the fold kernel to where it runs alone) is the tree of
+    `pairwise_sum` and of `ppo_loss_definition` in every class of tiles per fold lane: on the tile nodes of a minibatch
+    whose last tile holds one row, and on a synthesised block of wide magnitudes laid out one leaf per tile.  The sums that
+    add in another order are told apart from it by that block."""
+    rows, M = 256 * (tiles - 1) + 1, 2
+    mb = draw_minibatch(np.random.default_rng(tiles), rows, M)
+    out = ppo_loss_definition(**mb, **definition_kw(M, True))
+    nodes, root = pairwise_sum(out["summands"])
+    assert nodes.shape == (tiles, 7) and same_bits(out["partials"], nodes) and np.isfinite(nodes).all()
+    assert same_bits(tile_tree(nodes), root) and same_bits(tile_tree_stats(nodes), out["stats"])
+    assert out["stats"][0] == out["count"][0] > 0 and out["partials"][-1][0] in (0.0, 1.0)
+    if tiles == 3:   # ((a + b) + c) and ((a + b) + (c + 0)) are the same bits: no data tells them apart
+        wide = draw_partials(np.random.default_rng(tiles), tiles)
+        assert same_bits(tile_tree(wide), (wide[0] + wide[1]) + wide[2])
+        return
+    wide = telling_partials(tiles, seed=tiles)
+    leaves = np.zeros((256 * tiles, 7))
+    leaves[::256] = wide
+    nodes, root = pairwise_sum(leaves)
+    assert same_bits(nodes, wide) and same_bits(tile_tree(wide), root)
+    assert not same_bits(left_to_right_stats(wide), tile_tree_stats(wide))
+    assert same_bits(lane_sequential_stats(wide), tile_tree_stats(wide)) == (tiles <= 512), "two tiles per lane are one addition"
 
 
 # ------------------------------------------------------------------------------------------------ 5. PPOLoss
